@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark: structures/s of GNN polarizability evaluation on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 3|2]
+    python bench.py --gpus N --steps K --warmup W [--config 3|2] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path -- ``PotGNN.calc_polarizabilities`` on synthetic MD
 frames already resident in HBM -- plus, for N > 1, the single all-gather of the per-frame
 polarizabilities (RCCL).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline rate and the
+roofline figures read from HIP events of those same steps.  ``--full`` adds what takes runs of its
+own: the host-boundary rates, the exact-fp32 comparison run, the documented widths, the TiO2
+workload and the CPU baseline.  ``--dump-outputs DIR`` writes the polarizabilities of the last
+timed step (float64 [frames, 3, 3], the whole trajectory) to ``DIR/polarizabilities.npy``.
 
 ``--config 3`` (default, BASELINE.json configs[2], the north star's workload): 256-atom
 rocksalt cell (cutoff 3.2 A: E = 4608 directed edges, T = 78336 triplets), ONE 10 000-frame
@@ -500,10 +506,17 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=100,
                     help="frames for the CPU baseline (100 = one reference sub-batch)")
     ap.add_argument("--cpu-reps", type=int, default=3)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the extras and the CPU baseline (runs of their own: "
+                         "host-boundary rates, exact-fp32 comparison run, documented widths, the reference's "
+                         "published TiO2 workload); a plain run times the steps only")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the N = 1 extras: pipelined host-buffer rate, exact-fp32 comparison run, documented "
-                         "widths, the reference's published TiO2 workload (profiling passes: the timed steps only)")
+                    help="with --full: skip the extras: host-boundary rates, exact-fp32 comparison run, documented "
+                         "widths, the reference's published TiO2 workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the polarizabilities of the last timed step (all frames, float64) to "
+                         "DIR/polarizabilities.npy")
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="time the steps without the HIP-event pairs around the EdgeBlock / NodeBlock launches "
@@ -513,6 +526,9 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    extras = args.full and not args.no_extras
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -591,11 +607,20 @@ def main():
         elapsed = float(t.item())
     times = model.kernel_times()
     model.set_profiling(0)
+    # what the timed path returned in its last step, written before any extra run reuses `out`
+    if args.dump_outputs is not None and rank == 0:
+        if world > 1:  # drop the padding rows of the shorter blocks
+            blocks = [shard_bounds(total, world, r) if strong else (r * per, (r + 1) * per, per) for r in range(world)]
+            alpha = torch.cat([gathered[r * per:r * per + hi_r - lo_r] for r, (lo_r, hi_r, _) in enumerate(blocks)])
+        else:
+            alpha = out[:mine]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "polarizabilities.npy"), alpha.cpu().numpy())
     # informational, N > 1: the same step from the caller's HOST array (what `calc_polarizabilities_sharded` does: every rank
     # uploads its block through the pipelined staging entry, results stay in HBM for the all-gather) -- the rate a
     # `Trajectory.get_raman_spectrum` across ranks sees, beside the HBM-resident `value`
     host_inclusive = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and extras:
         host_steps = max(1, min(args.steps, 5))
 
         def host_step():
@@ -617,7 +642,7 @@ def main():
     # informational: the host-buffer entry point (adds PCIe H2D/D2H); never the headline value
     host_rate = None
     host_api = None
-    if rank == 0 and mine and not args.no_extras:
+    if rank == 0 and mine and extras:
         host_rate = host_pipelined_rate(model, wl["positions"])
         if world == 1:
             host_api = host_boundary(model, wl["positions"])
@@ -627,7 +652,7 @@ def main():
     # against a run that makes no use of f16 at all
     exact = None
     if world == 1 and mine and model.config_flags()["split_f16_mfma"] and model.config_flags()["fused_edge_block"] \
-            and "RN_POTGNN_MFMA" not in os.environ and not args.no_extras:
+            and "RN_POTGNN_MFMA" not in os.environ and extras:
         os.environ["RN_POTGNN_MFMA"] = "f32"
         try:
             model32 = wl["model"](device=local, max_chunk_structures=args.chunk)
@@ -765,7 +790,7 @@ def main():
             "host_inclusive_structures_per_s": host_inclusive,
             "exact_fp32_mfma": exact,
         }
-        if world == 1 and not args.no_extras and args.config == 3 and args.hparams == "perf" and not args.frames \
+        if world == 1 and extras and args.config == 3 and args.hparams == "perf" and not args.frames \
                 and not args.cells:
             # (b) the documented widths on the same cell and trajectory, and the one workload the reference
             # publishes a rate for (506.79 configs/s, machine-learning.ipynb:401)
@@ -785,7 +810,7 @@ def main():
             result["reference_published_workload"] = pub
         if args.profile_all:
             result["kernel_ms"] = {k: round(v[0], 3) for k, v in times.items()}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline(wl, min(args.cpu_sample, mine), args.cpu_reps)
         for key in ("roofline_nodeblock", "roofline_projection"):
             if result.get(key) is None:

@@ -1479,24 +1479,24 @@ def test_bench_two_ranks_contract(tmp_path):
     env = dict(os.environ, RN_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "2", "--frames", "96", "--no-cpu"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "2", "--frames", "96", "--no-cpu", "--full"]
     result = _bench_line(cmd, env, root)
     assert result["n_gpus"] == 2 and result["steps"] == 2 and result["scaling"] == "weak"
     assert result["value"] == pytest.approx(2 * 96 * 2 / (result["ms_per_step"] * 2e-3), rel=1e-6)
     assert result["roofline"]["launches"] > 0 and result["unit"] == "structures/s"
     assert "128 atoms" in result["config"]["workload"]
-    # N > 1 extra: the same step from the caller's host array (every rank uploads its block through the staging entry)
+    # N > 1 extra (--full): the same step from the caller's host array (every rank uploads its block through the staging entry)
     assert result["host_inclusive_structures_per_s"] > 0
 
 
 def test_bench_single_gpu_line_contract():
-    """``python bench.py`` at N = 1 (a short trajectory and a 4-frame CPU sample instead of the defaults):
+    """``python bench.py --full`` at N = 1 (a short trajectory and a 4-frame CPU sample instead of the defaults):
     one JSON line with every key of the bench contract, the roofline object (algorithmic figure,
     committed traffic / issue records only when they match the workload) and the CPU baseline."""
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "60",
-           "--cpu-sample", "4", "--cpu-reps", "1"]
+           "--cpu-sample", "4", "--cpu-reps", "1", "--full"]
     result = _bench_line(cmd, dict(os.environ), root)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -1519,24 +1519,55 @@ def test_bench_single_gpu_line_contract():
     assert exact["structures_per_s"] > 0 and exact["max_rel_diff_of_alpha"] < 1e-5
 
 
-def test_bench_starts_its_own_ranks():
+def test_bench_plain_run_times_the_steps_and_dumps_them(tmp_path):
+    """``python bench.py`` without ``--full``: the headline, its roofline and nothing that takes a run of its own; with
+    ``--dump-outputs DIR`` the polarizabilities of the last timed step are what the host entry computes on the same
+    frames, and a second run writes the same file bit for bit."""
+    import sys
+    from bench import make_workload
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--frames", "60",
+               "--dump-outputs", str(tmp_path / str(run))]
+        result = _bench_line(cmd, dict(os.environ), root)
+        assert result["steps"] == 3 and result["warmup"] == 1 and result["unit"] == "structures/s"
+        assert result["value"] == pytest.approx(60 * 3 / (result["ms_per_step"] * 3e-3), rel=1e-6)
+        assert result["roofline"]["launches"] > 0
+        assert "cpu_baseline" not in result and "documented_hparams" not in result
+        assert result["host_boundary"] is None and result["exact_fp32_mfma"] is None
+        dumps.append(np.load(tmp_path / str(run) / "polarizabilities.npy"))
+    assert dumps[0].shape == (60, 3, 3) and dumps[0].dtype == np.float64
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+    wl = make_workload((4, 4, 2), 60, "perf", seed=33)  # bench.CONFIGS[3]
+    want = wl["model"]().calc_polarizabilities(wl["positions"])
+    np.testing.assert_allclose(dumps[0], want, rtol=0, atol=1e-6 * np.abs(want).max())
+
+
+def test_bench_starts_its_own_ranks(tmp_path):
     """``python bench.py --gpus 2`` with no launcher: the process starts the two ranks itself
     (before touching the GPU) and rank 0 prints the one JSON line.  Default workload = BASELINE
     config 3: the 256-atom cell, ONE trajectory sharded over the ranks (here 97 frames: blocks of
-    49 and 48, so the padded all-gather is exercised), strong scaling.  A ``--gpus`` that
-    contradicts WORLD_SIZE is refused."""
+    49 and 48, so the padded all-gather is exercised), strong scaling; the dumped outputs are the
+    97 frames without the padding row.  A ``--gpus`` that contradicts WORLD_SIZE is refused."""
     import subprocess
     import sys
+    from bench import make_workload
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["RN_BENCH_SHARE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--frames", "97", "--no-cpu"]
+           "--frames", "97", "--no-cpu", "--dump-outputs", str(tmp_path)]
     result = _bench_line(cmd, env, root)
     assert result["n_gpus"] == 2 and result["scaling"] == "strong"
     assert "256 atoms" in result["config"]["workload"] and result["config"]["total_frames"] == 97
     assert result["config"]["frames_per_gpu"] == 49 and "sharded x2" in result["config"]["parallelism"]
     assert result["value"] == pytest.approx(97 * 2 / (result["ms_per_step"] * 2e-3), rel=1e-6)
+    got = np.load(tmp_path / "polarizabilities.npy")
+    wl = make_workload((4, 4, 2), 97, "perf", seed=33)
+    want = wl["model"]().calc_polarizabilities(wl["positions"])
+    assert got.shape == (97, 3, 3)
+    np.testing.assert_allclose(got, want, rtol=0, atol=1e-6 * np.abs(want).max())
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--no-cpu"],
                          env=dict(env, WORLD_SIZE="1", RANK="0"), cwd=root, capture_output=True, text=True,
                          timeout=300)
