@@ -123,9 +123,16 @@ int rn_potgnn_calc_polarizabilities(rn_potgnn *h, const double *positions, int64
  * f64[S*9].  The positions are cast to float32 while they are staged into page-locked memory -- the reference casts them
  * before any arithmetic (_gnn.py:709), so the results are bit-identical to a float64 upload at half the PCIe bytes -- and
  * go through one work chunk at a time, cast / copy / kernels of consecutive chunks overlapped (rn_potgnn_calc_polarizabilities
- * does the same and then copies the result down).  Returns once everything is enqueued; `stream` (a hipStream_t, NULL = the null stream) is
- * made to wait for the evaluation, so work the caller enqueues on it afterwards -- the all-gather of a sharded run,
- * dynamics/_trajectory.py:71-90 across ranks -- sees the finished d_alpha.  `positions` may be reused on return.
+ * does the same and then copies the result down).  Returns once everything is enqueued.  Ordering, with `stream` a
+ * hipStream_t (NULL = the null stream):
+ *   - work queued on `stream` before the call completes before d_alpha is written (an earlier reader of the same buffer:
+ *     the previous all-gather on it, the last user of a recycled allocation);
+ *   - `stream` is made to wait for the evaluation, so work the caller enqueues on it afterwards -- the all-gather of a
+ *     sharded run, dynamics/_trajectory.py:71-90 across ranks -- sees the finished d_alpha;
+ *   - a later call on the handle, through any entry point, needs no synchronisation in between: its float32 kernels queue
+ *     behind this call's on the handle's streams, the float32 positions this call still reads sit in a device buffer of
+ *     their own, and the weight updates of a training step (taped forward, rn_potgnn_adam_step) wait for this call.
+ * `positions` may be reused on return.
  */
 int rn_potgnn_calc_polarizabilities_to_device(rn_potgnn *h, const double *positions, int64_t S, double *d_alpha,
                                               void *stream);

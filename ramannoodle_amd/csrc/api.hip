@@ -214,6 +214,11 @@ struct rn_potgnn {
     size_t elems = 0;  // floats per buffer
     hipEvent_t copied[2] = {nullptr, nullptr};
     hipEvent_t done = nullptr;
+    // The float32 positions on the device.  Only staged_forward writes them (behind `done`): a to-device call returns
+    // with kernels that still read them, and the other host entries fill io_pos from the null stream, which does not
+    // wait for the handle's non-blocking streams.
+    DeviceBuf pos;
+    hipEvent_t caller = nullptr;  // the to-device entry: the caller's stream up to the call
     char *out_pin = nullptr;  // the result (+ the EdgeBlock's time-out word) of the synchronous host entry
     size_t out_bytes = 0;
   } hstage;
@@ -1671,6 +1676,14 @@ ChunkRun<T> train_forward_core(rn_potgnn *h, int S) {
   HIP_TRY(hipGetLastError());
   return c;
 }
+// The kernels that rewrite the float32 weights on the device run on lane 0.  An evaluation that returned unfinished (the
+// to-device entry, a device entry without synchronisation) may still read them on lane 1, whose last kernels of a lane pair
+// are ordered behind nothing on lane 0: `st` waits for the other lanes' last evaluation first.
+inline void after_other_lanes(rn_potgnn *h, hipStream_t st) {
+  for (auto &ln : h->f32.lanes)
+    if (ln.stream && ln.stream != st && ln.done) HIP_TRY(hipStreamWaitEvent(st, ln.done, 0));
+}
+
 // running statistics where the weights live (torch: momentum 0.1, unbiased variance) and everything derived from them
 inline void train_running_stats(rn_potgnn *h, hipStream_t st) {
   Precision<float> &P = h->f32;
@@ -1679,6 +1692,7 @@ inline void train_running_stats(rn_potgnn *h, hipStream_t st) {
   const int HP = std::max(d.FeP, 32);
   float *Wd = P.weights.as<float>();
   const double rows = h->bn_count;
+  after_other_lanes(h, st);
   launch_bn_running(Wd + L.bn_rm, Wd + L.bn_rv, P.mv.as<float>(), P.mv.as<float>() + HP, d.Fe, 0.1,
                     rows / std::max(rows - 1.0, 1.0), st);
   launch_setup<float>(Wd + L.emb, Wd + L.W2, Wd + L.b2, Wd + L.W4, Wd + L.b4, h->cfg.num_atom_types, h->d,
@@ -2594,6 +2608,7 @@ void rn_potgnn_destroy(rn_potgnn *h) {
     if (h->hstage.copied[b]) (void)hipEventDestroy(h->hstage.copied[b]);
   }
   if (h->hstage.done) (void)hipEventDestroy(h->hstage.done);
+  if (h->hstage.caller) (void)hipEventDestroy(h->hstage.caller);
   if (h->hstage.out_pin) (void)hipHostFree(h->hstage.out_pin);
   delete h;
 }
@@ -2656,8 +2671,10 @@ static void staged_forward(rn_potgnn *h, const double *positions, int64_t S, dou
     }
     hs.elems = (size_t)piece * per_frame;
   }
-  h->io_pos.ensure((size_t)S * per_frame * sizeof(float));
-  float *d_pos32 = h->io_pos.as<float>();
+  const size_t pos_bytes = (size_t)S * per_frame * sizeof(float);
+  if (hs.pos.bytes < pos_bytes && hs.done) HIP_TRY(hipEventSynchronize(hs.done));  // (growing frees what it may still read)
+  hs.pos.ensure(pos_bytes);
+  float *d_pos32 = hs.pos.as<float>();
   int b = 0;
   int64_t first = 0;
   static const bool timing = getenv("RN_POTGNN_HOST_TIMING") && atoi(getenv("RN_POTGNN_HOST_TIMING")) != 0;
@@ -2773,9 +2790,16 @@ int rn_potgnn_calc_polarizabilities_to_device(rn_potgnn *h, const double *positi
   }
   if (S == 0) return RN_OK;
   return guarded(h, [&]() {
+    // The evaluation starts behind what the caller queued on `stream` before the call: an earlier reader of d_alpha (the
+    // previous all-gather on the same tensor, the last user of a block torch's caching allocator handed out again).
+    auto &hs = h->hstage;
+    if (!h->exec_stream) HIP_TRY(hipStreamCreateWithFlags(&h->exec_stream, hipStreamNonBlocking));
+    if (!hs.caller) HIP_TRY(hipEventCreateWithFlags(&hs.caller, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(hs.caller, (hipStream_t)stream));
+    HIP_TRY(hipStreamWaitEvent(h->exec_stream, hs.caller, 0));
     staged_forward(h, positions, S, d_alpha, false);
     // the caller's stream continues behind the evaluation (e.g. the RCCL all-gather of ramannoodle_amd.parallel)
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, h->hstage.done, 0));
+    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, hs.done, 0));
   });
 }
 
@@ -3267,6 +3291,7 @@ int rn_potgnn_adam_step(rn_potgnn *h, double lr, double beta1, double beta2, dou
       h->num_derived_ops = (int)ops.size();
     }
     float *w = P.weights.as<float>();
+    after_other_lanes(h, st);
     launch_adam(w, P.grad.as<float>(), h->adam_m.as<float>(), h->adam_v.as<float>(),
                 h->trainable_mask.as<unsigned char>(), n, lr, beta1, beta2, eps, weight_decay, step, st,
                 (h->use_ps && h->ps_fail.p) ? h->ps_fail.as<int>() : nullptr);

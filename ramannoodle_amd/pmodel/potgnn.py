@@ -57,6 +57,21 @@ def _ptr(array) -> C.c_void_p:
     return C.c_void_p(array.ctypes.data)
 
 
+def _check_out(out, s: int, device_index: int) -> None:
+    """A caller's result tensor for the device entries, which write ``s * 9`` float64 values through its pointer: checked
+    before anything reaches the library (a leading slice ``out[:s]`` of a larger tensor is contiguous and passes)."""
+    if not isinstance(out, torch.Tensor):
+        raise ValueError(f"out must be a torch.Tensor, not {type(out).__name__}")
+    if not out.is_cuda or out.device.index != device_index:
+        raise ValueError(f"out lives on {out.device}, the evaluation writes on cuda:{device_index}")
+    if out.dtype != torch.float64:
+        raise ValueError(f"out must be float64, not {out.dtype}")
+    if tuple(out.shape) != (s, 3, 3):
+        raise ValueError(f"out has shape {tuple(out.shape)}, the evaluation writes ({s}, 3, 3)")
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+
+
 class _Activation(torch.nn.Module):
     """Placeholder for the reference's parameter-free ``ShiftedSoftplus`` entries of its ``Sequential`` containers
     (``_gnn.py:508-514, 532-539``): keeps the children's indices -- and with them the ``state_dict`` keys -- the
@@ -429,12 +444,16 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         """``calc_polarizabilities`` with the result left in HBM (``rn_potgnn_calc_polarizabilities_to_device``): host
         ``float64[S,N,3]`` in, device ``float64[S,3,3]`` out, float32 arithmetic.  The upload is pipelined with the
         kernels (positions cast to float32 while staged: bit-identical results, half the PCIe bytes); torch's current
-        stream is ordered behind the evaluation, so the tensor can go straight into a collective."""
+        stream is ordered behind the evaluation, so the tensor can go straight into a collective, and the evaluation
+        behind what was queued on that stream before the call (an earlier reader of ``out``).  ``out``, when given, must
+        be a contiguous ``float64[S,3,3]`` tensor on the model's device."""
         pos = self._check_positions(positions_batch)
         self.eval()
         device = torch.device("cuda", self.device_index)
         if out is None:
             out = torch.empty((pos.shape[0], 3, 3), dtype=torch.float64, device=device)
+        else:
+            _check_out(out, pos.shape[0], self.device_index)
         handle = self._ensure_handle()
         stream = torch.cuda.current_stream(device).cuda_stream
         rc = _lib.load().rn_potgnn_calc_polarizabilities_to_device(handle, _ptr(pos), pos.shape[0],
@@ -457,6 +476,8 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         s = positions.shape[0]
         if out is None:
             out = torch.empty((s, 3, 3), dtype=torch.float64, device=positions.device)
+        else:
+            _check_out(out, s, positions.device.index)
         handle = self._ensure_handle()
         stream = torch.cuda.current_stream(positions.device).cuda_stream
         if _wants_float64(dtype):

@@ -116,6 +116,20 @@ def test_wrong_positions_shape_is_value_error_before_any_device_work():
         model.calc_polarizabilities([[1.0]])
 
 
+def test_to_device_refuses_a_host_out_tensor_before_any_device_work():
+    """``calc_polarizabilities_to_device`` hands ``out``'s pointer to the library, which writes ``S * 9`` doubles through it
+    on the device: a CPU tensor is refused with ``ValueError`` before the handle is created (so on any machine, with or
+    without a GPU), and is left untouched."""
+    g = load_golden("triclinic20")
+    model = product_model_from_golden(g)
+    pos = g["pos_batch"][:3]
+    out = torch.full((3, 3, 3), -7.0, dtype=torch.float64)
+    with pytest.raises(ValueError, match="out lives on cpu"):
+        model.calc_polarizabilities_to_device(pos, out=out)
+    assert model._handle is None
+    assert bool((out == -7.0).all())
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_no_device_fails_loudly():
     model = product_model_from_golden(load_golden("triclinic20"))
