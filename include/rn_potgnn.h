@@ -326,6 +326,32 @@ int rn_potgnn_train_backward_device(rn_potgnn *h, const float *dvec6);
 int rn_potgnn_train_forward_samples_device(rn_potgnn *h, const float *d_lattices, const int32_t *d_atom_types,
                                            const double *d_positions, int64_t S, float *d_vec6, void *stream);
 int rn_potgnn_train_backward_samples_device(rn_potgnn *h, const float *d_dvec6, void *stream);
+
+/*
+ * Input gradients of the forward: vector-Jacobian products of the standardised 6-vectors with respect to the fractional
+ * positions and to the lattice.  All pointers are DEVICE memory.
+ *
+ * rn_potgnn_forward_vjp_device (evaluation mode, running-statistics BatchNorm): d_lattices f64[S][9] (row i = lattice
+ * vector i) or NULL (the reference structure's), d_atom_types int32[S][N] atom types or NULL (validated by the caller),
+ * d_positions f64[S][N][3], d_dvec6 f64[S][6] one cotangent per frame -> d_dpos f64[S][N][3] and / or d_dlat f64[S][9]
+ * (either may be NULL, not both), every entry written.  The forward is recomputed with its tape on lane 0, a work chunk
+ * at a time (bounded memory for any S), in float32 or, with use_float64, in the kernels instantiated for double; the
+ * taped forward runs on different kernels from the fast evaluation, so float32 gradients belong to the evaluated
+ * function up to float32 rounding.  A pending train_forward is discarded (its tape is reused).  Work is ordered after
+ * `stream`, `stream` waits for it and is synchronised once at the end.
+ *
+ * rn_potgnn_train_backward_inputs / _inputs_device: rn_potgnn_train_backward / _samples_device with the input gradients
+ * of the pending float32 train_forward written by the same reverse pass (batch-statistics BatchNorm): dpos f64[S][N][3]
+ * and / or dlat f64[S][9] (host memory for the first, device memory for the second; the lattice is the one the forward
+ * ran on).  The parameter gradients are bit-identical to those of the entries without inputs.  In the host entry
+ * grads == NULL leaves them on the device, as rn_potgnn_train_backward_device does.
+ */
+int rn_potgnn_forward_vjp_device(rn_potgnn *h, const double *d_lattices, const int32_t *d_atom_types,
+                                 const double *d_positions, int64_t S, const double *d_dvec6, int use_float64,
+                                 double *d_dpos, double *d_dlat, void *stream);
+int rn_potgnn_train_backward_inputs(rn_potgnn *h, const float *dvec6, float *grads, double *dpos, double *dlat);
+int rn_potgnn_train_backward_inputs_device(rn_potgnn *h, const float *d_dvec6, double *d_dpos, double *d_dlat,
+                                           void *stream);
 int rn_potgnn_gradient_buffer(rn_potgnn *h, void **device_ptr, size_t *count);
 int rn_potgnn_adam_step(rn_potgnn *h, double lr, double beta1, double beta2, double eps,
                         double weight_decay, int64_t step);

@@ -152,6 +152,7 @@ struct Precision {
   hipEvent_t ev_side[3] = {nullptr, nullptr, nullptr};
   DeviceBuf tn_arena;  // partial sums of the weight-gradient products (reverse_pass)
   DeviceBuf tape_z1, bn_stats, grad, seeds, mv, type_sums;  // training: pre-BatchNorm activations, batch sums, gradient blob
+  DeviceBuf in_dcart, in_lat, in_grads;  // input gradients: per-edge Cartesian cotangents, a chunk's lattices, host-path outputs
   bool tape_on = false;
 };
 
@@ -1285,9 +1286,11 @@ void forward_device(rn_potgnn *h, const double *d_pos, int64_t S, double *d_alph
 
 // Reverse pass over a taped forward of S frames with B cotangents per frame.
 //   d_dout6   device [S*B, 6]  cotangents of the standardised 6-vectors
-//   d_dpos    device f64 [S*B, N, 3] or null   -> d / d(fractional positions)
+//   d_dpos    device f64 [S*B, N, 3] or null   -> d / d(fractional positions), ACCUMULATED (geom_bwd_kernel, the Jacobian)
 //   grad      device packed-layout gradient blob or null -> parameter gradients (training)
 //   train_bn  readout BatchNorm used batch statistics (z1 / bn_stats hold the taped values)
+//   in_dpos / in_dlat  device f64 [S*B, N, 3] / [S*B, 9] or null -> input gradients of forward, WRITTEN (geom_input_bwd_kernel,
+//             with the frame's own lattice); computed from the cotangents the pass leaves anyway, so they change nothing else
 template <typename T>
 struct Reverse {
   int S, B;
@@ -1295,6 +1298,8 @@ struct Reverse {
   double *d_dpos;
   T *grad;
   bool train_bn;
+  double *in_dpos = nullptr;
+  double *in_dlat = nullptr;
 };
 
 enum { DE0, DE1, DN0, DN1, DNX, DPQ, DNP3, DC2, DPROD, DBC1, DNPC1, DPOL, DUNIT, DH, POL, DOUT, DPROD2, BWN };
@@ -1484,6 +1489,12 @@ void reverse_pass(rn_potgnn *h, ChunkRun<T> &c, const Reverse<T> &rv) {
   if (rv.d_dpos)
     launch_geom_bwd<T>(b[DE0 + cur], b[DUNIT], unit4, P.lattice.template as<T>(), P.offsets,
                        (T)h->cfg.gauss_coefficient, C, B, g, d, rv.d_dpos, st);
+  if (rv.in_dpos || rv.in_dlat) {
+    P.in_dcart.ensure((size_t)C * E * 3 * sizeof(double));
+    launch_geom_input_bwd<T>(b[DE0 + cur], b[DUNIT], unit4, c.d_pos, c.d_lat ? c.d_lat : P.lattice.template as<T>(),
+                             c.d_lat ? 9 : 0, P.offsets, (T)h->cfg.gauss_coefficient, C, B, g, d,
+                             P.in_dcart.template as<double>(), rv.in_dpos, rv.in_dlat, st);
+  }
   HIP_TRY(hipGetLastError());
 }
 
@@ -1555,6 +1566,57 @@ void jacobian(rn_potgnn *h, const double *host_pos, double *host_jac /*[6][N*3]*
   check_ps_fail(h);
   HIP_TRY(hipMemcpy(host_jac, dposbuf.p, (size_t)6 * N * 3 * sizeof(double), hipMemcpyDeviceToHost));
   (void)P;
+}
+
+// Frames per taped chunk of the input-gradient entry: the handle's work chunk, further bounded so that the tape, lane 0's
+// full-width buffers and the reverse pass's workspace of one chunk stay within kTapeBudget bytes (38 MB per frame of
+// config 3's shape -- 256 atoms, 4608 edges, Fn = Fe = 64, four passes -- in float32: 111 frames a chunk).
+constexpr size_t kTapeBudget = (size_t)4 << 30;
+template <typename T>
+int tape_frames(const rn_potgnn *h) {
+  const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges, NP = h->cfg.num_message_passes;
+  const size_t FnP = h->d.FnP, FeP = h->d.FeP, HP = std::max<size_t>(FeP, 32);
+  const size_t tape = (NP + 1) * (N * FnP + 2 * E * FeP);
+  const size_t bw = E * (2 * FeP + 4 * FeP + std::max(2 * FeP, HP) + FnP + 2 * FnP + 32 + 4 + HP + 32) +
+                    N * (3 * FnP + 6 * FeP + 2 * FnP);
+  const size_t per = (tape + per_structure_elems(h, false) + bw) * sizeof(T) + E * 3 * sizeof(double);
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk_frames<T>(h), kTapeBudget / std::max<size_t>(per, 1)));
+}
+
+// Input gradients of the evaluation-mode forward (rn_potgnn_forward_vjp_device): per chunk of frames, the taped forward on
+// lane 0 and one reverse pass with one cotangent per frame, in precision T.  Ordered after `user`; `user` waits for the
+// work and is synchronised once at the end (the EdgeBlock's time-out word is read there).
+template <typename T>
+void forward_vjp(rn_potgnn *h, const double *d_lat /* [S][9] or null */, const int32_t *d_types /* [S][N] or null */,
+                 const double *d_pos, int64_t S, const double *d_dvec6, double *d_dpos, double *d_dlat, hipStream_t user) {
+  ensure_precision<T>(h);
+  Precision<T> &P = prec<T>(h);
+  const int N = h->g.N;
+  h->train_S = 0;  // the tape and lane 0 are reused: a pending train_forward is void
+  hipStream_t st = P.lanes[0].stream;
+  HIP_TRY(hipEventRecord(h->ev_start, user));
+  HIP_TRY(hipStreamWaitEvent(st, h->ev_start, 0));
+  const int chunk = tape_frames<T>(h);
+  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+    const int s = (int)std::min<int64_t>(chunk, S - s0);
+    const T *lat = nullptr;
+    if (d_lat) {  // in the arithmetic of the run, as the forward casts them
+      P.in_lat.ensure((size_t)s * 9 * sizeof(T));
+      launch_cast_from_f64<T>(d_lat + s0 * 9, P.in_lat.template as<T>(), (int64_t)s * 9, st);
+      lat = P.in_lat.template as<T>();
+    }
+    ChunkRun<T> c = taped_forward<T>(h, d_pos + s0 * N * 3, s, lat, d_types ? d_types + s0 * N : nullptr);
+    P.seeds.ensure((size_t)s * 6 * sizeof(T));
+    launch_cast_from_f64<T>(d_dvec6 + s0 * 6, P.seeds.template as<T>(), (int64_t)s * 6, st);
+    Reverse<T> rv{s, 1, P.seeds.template as<T>(), nullptr, nullptr, false};
+    rv.in_dpos = d_dpos ? d_dpos + s0 * N * 3 : nullptr;
+    rv.in_dlat = d_dlat ? d_dlat + s0 * 9 : nullptr;
+    reverse_pass<T>(h, c, rv);
+  }
+  HIP_TRY(hipEventRecord(P.lanes[0].done, st));
+  HIP_TRY(hipStreamWaitEvent(user, P.lanes[0].done, 0));
+  HIP_TRY(hipStreamSynchronize(user));
+  check_ps_fail(h);
 }
 
 // ---- device-resident optimisation step: which entries of the packed blob are parameters, which are
@@ -1793,7 +1855,8 @@ template <typename T>
 void unpack_grads(const rn_potgnn *h, const T *gp, T *out, bool buffers);
 
 template <typename T>
-void train_backward(rn_potgnn *h, const T *dvec6, T *grads /* null: leave the gradients on the device */) {
+void train_backward(rn_potgnn *h, const T *dvec6, T *grads /* null: leave the gradients on the device */,
+                    double *host_dpos = nullptr /* [S][N][3] or null */, double *host_dlat = nullptr /* [S][9] or null */) {
   Precision<T> &P = prec<T>(h);
   const int S = h->train_S;
   if (S <= 0 || h->train_prec != (int)sizeof(T))
@@ -1808,10 +1871,18 @@ void train_backward(rn_potgnn *h, const T *dvec6, T *grads /* null: leave the gr
   P.grad.ensure(h->lay.total * sizeof(T));
   HIP_TRY(hipMemsetAsync(P.grad.p, 0, h->lay.total * sizeof(T), st));
   Reverse<T> rv{S, 1, seeds.template as<T>(), nullptr, P.grad.template as<T>(), true};
+  const size_t npos = (size_t)S * h->g.N * 3;
+  if (host_dpos || host_dlat) {  // input gradients from the same reverse pass (device scratch, copied out below)
+    P.in_grads.ensure((npos + (size_t)S * 9) * sizeof(double));
+    rv.in_dpos = host_dpos ? P.in_grads.template as<double>() : nullptr;
+    rv.in_dlat = host_dlat ? P.in_grads.template as<double>() + npos : nullptr;
+  }
   reverse_pass<T>(h, c, rv);
   HIP_TRY(hipStreamSynchronize(st));
   h->train_S = 0;  // (the pending forward is consumed whether or not the check below throws)
   check_ps_fail(h);
+  if (host_dpos) HIP_TRY(hipMemcpy(host_dpos, rv.in_dpos, npos * sizeof(double), hipMemcpyDeviceToHost));
+  if (host_dlat) HIP_TRY(hipMemcpy(host_dlat, rv.in_dlat, (size_t)S * 9 * sizeof(double), hipMemcpyDeviceToHost));
   if (sizeof(T) == 4) h->grads_on_device = true;
   if (!grads) return;
   std::vector<T> gp(h->lay.total);
@@ -1821,7 +1892,8 @@ void train_backward(rn_potgnn *h, const T *dvec6, T *grads /* null: leave the gr
 
 // Reverse pass of a pending train_forward(_device) with the cotangents [S][6] in a DEVICE buffer; the gradients stay in HBM
 // (device-resident training), nothing is synchronised: `user` waits for the lane, the Adam step runs on the lane's stream.
-inline void train_backward_device(rn_potgnn *h, const float *d_dvec6, hipStream_t user) {
+inline void train_backward_device(rn_potgnn *h, const float *d_dvec6, hipStream_t user, double *d_dpos = nullptr,
+                                  double *d_dlat = nullptr) {
   Precision<float> &P = h->f32;
   const int S = h->train_S;
   if (S <= 0 || h->train_prec != 4)
@@ -1837,6 +1909,8 @@ inline void train_backward_device(rn_potgnn *h, const float *d_dvec6, hipStream_
   P.grad.ensure(h->lay.total * sizeof(float));
   HIP_TRY(hipMemsetAsync(P.grad.p, 0, h->lay.total * sizeof(float), st));
   Reverse<float> rv{S, 1, P.seeds.as<float>(), nullptr, P.grad.as<float>(), true};
+  rv.in_dpos = d_dpos;  // (input gradients, when asked for, from the same reverse pass)
+  rv.in_dlat = d_dlat;
   reverse_pass<float>(h, c, rv);
   HIP_TRY(hipEventRecord(P.lanes[0].done, st));
   HIP_TRY(hipStreamWaitEvent(user, P.lanes[0].done, 0));
@@ -3197,6 +3271,53 @@ int rn_potgnn_forward_samples_device(rn_potgnn *h, const float *d_lattices, cons
     forward_device<float>(h, d_positions, S, nullptr, d_vec6, nullptr, (hipStream_t)stream, synchronize != 0, d_lattices,
                           d_atom_types);
   });
+}
+
+int rn_potgnn_forward_vjp_device(rn_potgnn *h, const double *d_lattices, const int32_t *d_atom_types,
+                                 const double *d_positions, int64_t S, const double *d_dvec6, int use_float64,
+                                 double *d_dpos, double *d_dlat, void *stream) {
+  if (!h) return RN_ERR_INVALID_ARGUMENT;
+  if (S < 0 || (S > 0 && (!d_positions || !d_dvec6)) || (!d_dpos && !d_dlat)) {
+    set_error(h, "invalid arguments to forward_vjp_device (positions, cotangents, S, or neither dpos nor dlat)");
+    return RN_ERR_INVALID_ARGUMENT;
+  }
+  if (S == 0) return RN_OK;
+  return guarded(h, [&]() {
+    if (use_float64) {
+      sync_host(h);
+      forward_vjp<double>(h, d_lattices, d_atom_types, d_positions, S, d_dvec6, d_dpos, d_dlat, (hipStream_t)stream);
+    } else {
+      forward_vjp<float>(h, d_lattices, d_atom_types, d_positions, S, d_dvec6, d_dpos, d_dlat, (hipStream_t)stream);
+    }
+  });
+}
+
+int rn_potgnn_train_backward_inputs(rn_potgnn *h, const float *dvec6, float *grads, double *dpos, double *dlat) {
+  if (!h || !dvec6 || (!dpos && !dlat)) {
+    set_error(h, "invalid arguments to train_backward_inputs");
+    return RN_ERR_INVALID_ARGUMENT;
+  }
+  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
+  if (h->train_S <= 0 || h->train_prec != 4) {
+    set_error(h, "train_backward_inputs needs a preceding train_forward (an evaluation or Jacobian call in "
+                 "between discards its tape)");
+    return RN_ERR_INVALID_ARGUMENT;
+  }
+  return guarded(h, [&]() { train_backward<float>(h, dvec6, grads, dpos, dlat); });
+}
+
+int rn_potgnn_train_backward_inputs_device(rn_potgnn *h, const float *d_dvec6, double *d_dpos, double *d_dlat,
+                                           void *stream) {
+  if (!h || !d_dvec6 || (!d_dpos && !d_dlat)) {
+    set_error(h, "invalid arguments to train_backward_inputs_device");
+    return RN_ERR_INVALID_ARGUMENT;
+  }
+  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
+  if (!h->device_training || h->train_S <= 0 || h->train_prec != 4) {
+    set_error(h, "train_backward_inputs_device needs device-resident training and a preceding float32 train_forward");
+    return RN_ERR_INVALID_ARGUMENT;
+  }
+  return guarded(h, [&]() { train_backward_device(h, d_dvec6, (hipStream_t)stream, d_dpos, d_dlat); });
 }
 
 int rn_potgnn_train_forward_f64(rn_potgnn *h, const double *positions, int64_t S, double *vec6,

@@ -96,6 +96,15 @@ __device__ __forceinline__ double ssp(double x) {
   return sp - 0.6931471805599453;
 }
 
+// Minimum-image fractional displacement of one coordinate (_gnn.py:603-606): the forward geometry kernel
+// (kernels_agg.hip) and the input-gradient reverse (kernels_bwd.hip) share this expression.
+template <typename T>
+__device__ __forceinline__ T wrap_min_image(T d) {
+  T m = fmod(d, (T)1);            // torch "%" == python remainder:
+  if (m != 0 && m < 0) m += 1;    //   fmod, then shift negatives by the divisor
+  return (m > (T)0.5) ? m - 1 : m;
+}
+
 // ---------------------------------------------------------------- row fragments
 // Four consecutive columns of a row, held by one lane.
 template <typename T>

@@ -268,6 +268,16 @@ void launch_node_embed_bwd(const T *dnode0, int S, const Graph &g, Dims d, int K
 template <typename T>
 void launch_geom_bwd(const T *dedge0, const T *dunit, const T *unit4, const T *lat, const T *offs,
                      T coef, int C, int B, const Graph &g, Dims d, double *dpos, hipStream_t st);
+// Input gradients of the forward (kernels_bwd.hip: geom_input_bwd_kernel): d(edge0), d(unit) -> dpos float64 [C][N][3]
+// (fractional positions) and / or dlat float64 [C][9] (the frame's lattice, row i = lattice vector i), each written
+// once per entry; either may be null.  `pos` float64 [S][N][3] and `lat` ([9] with lat_stride 0, [S][9] with 9) are
+// what the taped forward ran on; `dcart`: scratch of C * E * 3 doubles.
+template <typename T>
+void launch_geom_input_bwd(const T *dedge0, const T *dunit, const T *unit4, const double *pos, const T *lat,
+                           int lat_stride, const T *offs, T coef, int C, int B, const Graph &g, Dims d, double *dcart,
+                           double *dpos, double *dlat, hipStream_t st);
+template <typename T>
+void launch_cast_from_f64(const double *src, T *dst, int64_t n, hipStream_t st);
 
 // Fused EdgeBlock (kernels_fused.hip): projections + triplet aggregation in one launch.
 // Fused EdgeBlock (kernels_fused.hip): float32, FnP == FeP == 64.  Two workgroups per CU

@@ -91,13 +91,7 @@ template void launch_setup<double>(const double *, const double *, const double 
 //   cart = d @ lattice;  dist = |cart|;  unit = cart/|cart|   (_gnn.py:610-611, _utils.py:78-84)
 // computed from the edge list only (O(S*E), not the reference's O(S*N^2)), followed by the
 // Gaussian radial basis exp(coef*(dist - mu_f)^2) (_gnn.py:81-82) written as padded rows.
-template <typename T>
-__device__ __forceinline__ T wrap_min_image(T d) {
-  T m = fmod(d, (T)1);            // torch "%" == python remainder:
-  if (m != 0 && m < 0) m += 1;    //   fmod, then shift negatives by the divisor
-  return (m > (T)0.5) ? m - 1 : m;
-}
-
+// (wrap_min_image: device_utils.hpp, shared with the input-gradient reverse in kernels_bwd.hip)
 // PT: the type the positions arrive in.  float32 evaluations cast them to float before any arithmetic (_gnn.py:709), so
 // positions that were cast on the host while staging (rn_potgnn_calc_polarizabilities: half the PCIe bytes) give
 // bit-identical rows.

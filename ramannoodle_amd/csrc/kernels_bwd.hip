@@ -1389,6 +1389,121 @@ template void launch_geom_bwd<double>(const double *, const double *, const doub
                                       const double *, double, int, int, const Graph &, Dims,
                                       double *, hipStream_t);
 
+// Input gradients of PotGNN.forward (positions AND lattice), one workgroup per cotangent row c (frame s = c / B):
+//   phase 1, per edge e (thread-strided): the Cartesian cotangent dc(e) from d edge0 (RBF derivative) and d unit, as
+//            geom_bwd_kernel builds it, stored as float64 [3] in `dcart`; and the lattice term f(e) (x) dc(e), f the
+//            wrapped fractional displacement recomputed with geom_rbf_kernel's expression in its precision, summed per
+//            thread in float64.
+//   phase 2, per atom n (thread-strided): dpos[c][n] = L_s (sum_{e in in(n)} dc(e) - sum_{e in out(n)} dc(e)), the two
+//            segments walked in CSR order -- every entry written exactly once: no atomics, no memset.
+//   phase 3: the 9 lattice sums of the 256 threads reduced in LDS by a fixed tree: dlat[c][i][k] = sum_e f_i(e) dc_k(e).
+// Fixed orders throughout: two launches on the same cotangents give the same bits.
+constexpr int kGeomInputThreads = 256;
+template <typename T>
+__global__ __launch_bounds__(kGeomInputThreads) void geom_input_bwd_kernel(
+    const T *__restrict__ dedge0, const T *__restrict__ dunit, const T *__restrict__ unit4,
+    const double *__restrict__ pos, const T *__restrict__ lat_base, int lat_stride, const T *__restrict__ offs, T coef,
+    int B, Graph g, Dims d, double *__restrict__ dcart, double *__restrict__ dpos, double *__restrict__ dlat) {
+  __shared__ double red[9][kGeomInputThreads];
+  const int c = blockIdx.x, s = c / B, tid = threadIdx.x;
+  const T *lat = lat_base + (int64_t)s * lat_stride;  // the frame's own lattice, as the forward used it
+  double *dc_row = dcart + (int64_t)c * g.E * 3;
+  double acc[9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) acc[j] = 0.0;
+  for (int e = tid; e < g.E; e += kGeomInputThreads) {
+    const int64_t idx = (int64_t)c * g.E + e, frow = (int64_t)s * g.E + e;
+    const T ux = unit4[frow * 4], uy = unit4[frow * 4 + 1], uz = unit4[frow * 4 + 2], dist = unit4[frow * 4 + 3];
+    T ddist = 0;
+    const T *de = dedge0 + idx * d.FeP;
+    for (int f = 0; f < d.Fe; ++f) {
+      const T x = dist - offs[f];
+      ddist += de[f] * exp(coef * x * x) * ((T)2 * coef * x);
+    }
+    const T dux = dunit[idx * 4], duy = dunit[idx * 4 + 1], duz = dunit[idx * 4 + 2];
+    const T proj = dux * ux + duy * uy + duz * uz;
+    const T dc[3] = {ddist * ux + (dux - proj * ux) / dist, ddist * uy + (duy - proj * uy) / dist,
+                     ddist * uz + (duz - proj * uz) / dist};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dc_row[(int64_t)e * 3 + k] = (double)dc[k];
+    if (dlat) {
+      const int a = g.edge_a[e], b = g.edge_b[e];
+      const double *pa = pos + ((int64_t)s * g.N + a) * 3, *pb = pos + ((int64_t)s * g.N + b) * 3;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double fi = (double)wrap_min_image((T)pb[i] - (T)pa[i]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) acc[3 * i + k] += fi * (double)dc[k];
+      }
+    }
+  }
+  __syncthreads();  // (the workgroup's dcart rows are complete and visible to all of its threads)
+  if (dpos) {
+    double L[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) L[j] = (double)lat[j];
+    for (int n = tid; n < g.N; n += kGeomInputThreads) {
+      double sx = 0.0, sy = 0.0, sz = 0.0;
+      for (int j = g.in_ptr[n]; j < g.in_ptr[n + 1]; ++j) {  // n is the destination b: + dc
+        const double *v = dc_row + (int64_t)g.in_edge[j] * 3;
+        sx += v[0];
+        sy += v[1];
+        sz += v[2];
+      }
+      for (int e = g.out_ptr[n]; e < g.out_ptr[n + 1]; ++e) {  // n is the source a: - dc
+        const double *v = dc_row + (int64_t)e * 3;
+        sx -= v[0];
+        sy -= v[1];
+        sz -= v[2];
+      }
+      double *out = dpos + ((int64_t)c * g.N + n) * 3;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) out[i] = L[3 * i] * sx + L[3 * i + 1] * sy + L[3 * i + 2] * sz;  // cart_k = sum_i f_i L[i][k]
+    }
+  }
+  if (dlat) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) red[j][tid] = acc[j];
+    __syncthreads();
+    for (int half = kGeomInputThreads / 2; half > 0; half >>= 1) {
+      if (tid < half) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) red[j][tid] += red[j][tid + half];
+      }
+      __syncthreads();
+    }
+    if (tid < 9) dlat[(int64_t)c * 9 + tid] = red[tid][0];
+  }
+}
+template <typename T>
+void launch_geom_input_bwd(const T *dedge0, const T *dunit, const T *unit4, const double *pos, const T *lat,
+                           int lat_stride, const T *offs, T coef, int C, int B, const Graph &g, Dims d, double *dcart,
+                           double *dpos, double *dlat, hipStream_t st) {
+  if (C == 0 || (!dpos && !dlat)) return;
+  geom_input_bwd_kernel<T><<<(unsigned)C, kGeomInputThreads, 0, st>>>(dedge0, dunit, unit4, pos, lat, lat_stride, offs,
+                                                                       coef, B, g, d, dcart, dpos, dlat);
+}
+template void launch_geom_input_bwd<float>(const float *, const float *, const float *, const double *, const float *,
+                                           int, const float *, float, int, int, const Graph &, Dims, double *, double *,
+                                           double *, hipStream_t);
+template void launch_geom_input_bwd<double>(const double *, const double *, const double *, const double *,
+                                            const double *, int, const double *, double, int, int, const Graph &, Dims,
+                                            double *, double *, double *, hipStream_t);
+
+// float64 -> T, element-wise (cotangents and lattices handed to the input-gradient entry in float64)
+template <typename T>
+__global__ void cast_from_f64_kernel(const double *__restrict__ src, T *__restrict__ dst, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = (T)src[i];
+}
+template <typename T>
+void launch_cast_from_f64(const double *src, T *dst, int64_t n, hipStream_t st) {
+  if (n <= 0) return;
+  cast_from_f64_kernel<T><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(src, dst, n);
+}
+template void launch_cast_from_f64<float>(const double *, float *, int64_t, hipStream_t);
+template void launch_cast_from_f64<double>(const double *, double *, int64_t, hipStream_t);
+
 // =========================================================================== launchers
 #define RN_LG_SWITCH(FP, CALL)   \
   switch ((FP) / 4) {            \

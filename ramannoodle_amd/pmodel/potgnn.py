@@ -15,6 +15,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 from numpy.typing import NDArray
+from torch.autograd.function import once_differentiable
 
 from ramannoodle_amd import _lib
 from ramannoodle_amd.abstract import PolarizabilityModel
@@ -515,7 +516,28 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         The result lives where the inputs live, as the reference's does (``_train.py:51-75`` moves a batch to the
         device and takes the loss there; ``test/tests/torch/test_gnn.py:130-160``): CUDA tensors are evaluated in
         place in HBM (``rn_potgnn_forward_samples_device``: no copy through the host) and a CUDA tensor comes back;
-        host tensors / arrays give a host tensor."""
+        host tensors / arrays give a host tensor.
+
+        Input gradients: with grad mode on and ``positions`` and / or ``lattice`` requiring grad, the result's backward
+        fills ``positions.grad`` ``[S,N,3]`` (with respect to the FRACTIONAL positions, as ``alpha_jacobian``) and
+        ``lattice.grad`` ``[S,3,3]`` (row i = lattice vector i; a lattice given as ``L.expand(S,3,3)`` gets the sum through
+        torch's expand), in the dtype and on the device of each input (CUDA inputs: the work is ordered on torch's current
+        stream at backward time; host inputs: host gradients).  ``atomic_numbers`` gets none.  Double backward raises
+        ``RuntimeError``.
+        * EVALUATION mode: the forward value is the one computed without gradients, bit for bit; ``backward`` recomputes
+          the forward with its tape, a work chunk at a time (bounded memory for any S), and runs one reverse pass with
+          one cotangent per frame (``rn_potgnn_forward_vjp_device``), in the dtype of the parameters (float32 kernels, or
+          those instantiated for ``double`` for a float64 model).  The taped forward runs on different kernels from the
+          fast evaluation, so a float32 gradient is that of the same function up to float32 rounding.  Like any
+          evaluation, the backward reuses the device workspace and tape of lane 0: a training step whose forward ran
+          before it and whose backward has not yet run raises ``ValueError`` afterwards.
+        * TRAINING mode: the step's own reverse pass (batch-statistics BatchNorm, so one sample's gradient depends on the
+          whole batch) writes the input gradients too (``rn_potgnn_train_backward_inputs(_device)``); the parameter
+          gradients are bit-identical to those of a step whose inputs require no grad.
+        With no input requiring grad, or under ``torch.no_grad()``, nothing of this runs: same entries, same bits, no
+        tape."""
+        if not self.training and torch.is_grad_enabled() and (_requires_grad(positions) or _requires_grad(lattice)):
+            return _EvalInputGrad.apply(self, lattice, atomic_numbers, positions)
         pos_t, lat_t, zs_t = torch.as_tensor(positions), torch.as_tensor(lattice), torch.as_tensor(atomic_numbers)
         s = pos_t.shape[0] if pos_t.dim() == 3 else -1
         if pos_t.dim() != 3 or tuple(pos_t.shape[1:]) != (self.num_atoms, 3):
@@ -547,10 +569,10 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
                                  "model has no atom type for")
         if self.training:
             extra = (None if same_lattice else lat, types)
-            if self._device_training:  # gradients stay in HBM: nothing for autograd to route
-                out = _TrainStep.apply(self, pos, extra, self._device_anchor)
+            if self._device_training:  # parameter gradients stay in HBM: nothing for autograd to route but the inputs'
+                out = _TrainStep.apply(self, pos, extra, pos_t, lat_t, self._device_anchor)
             else:
-                out = _TrainStep.apply(self, pos, extra, *self.parameters())
+                out = _TrainStep.apply(self, pos, extra, pos_t, lat_t, *self.parameters())
             return out.to(out_device) if out_device is not None else out
         handle = self._ensure_handle()
         if model_f64:  # the model's parameters are float64: evaluate in double, as the reference does
@@ -638,12 +660,49 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         self._device_ahead = True
         return out
 
-    def _train_backward_on_device(self, grad_out: torch.Tensor) -> None:
+    def _train_backward_on_device(self, grad_out: torch.Tensor, want_pos: bool = False, want_lat: bool = False):
+        """Reverse pass of the pending device-resident step; with ``want_pos`` / ``want_lat`` the same pass also writes the
+        input gradients, returned as device float64 ``([S,N,3] or None, [S,9] or None)``."""
         dvec6 = grad_out.detach().to(dtype=torch.float32).contiguous()
         stream = torch.cuda.current_stream(dvec6.device).cuda_stream
-        rc = _lib.load().rn_potgnn_train_backward_samples_device(self._handle, C.c_void_p(dvec6.data_ptr()),
-                                                                 C.c_void_p(stream))
-        _lib.check(rc, self._handle, "rn_potgnn_train_backward_samples_device")
+        if not (want_pos or want_lat):
+            rc = _lib.load().rn_potgnn_train_backward_samples_device(self._handle, C.c_void_p(dvec6.data_ptr()),
+                                                                     C.c_void_p(stream))
+            _lib.check(rc, self._handle, "rn_potgnn_train_backward_samples_device")
+            return None, None
+        s = dvec6.shape[0]
+        dpos = torch.empty((s, self.num_atoms, 3), dtype=torch.float64, device=dvec6.device) if want_pos else None
+        dlat = torch.empty((s, 9), dtype=torch.float64, device=dvec6.device) if want_lat else None
+        rc = _lib.load().rn_potgnn_train_backward_inputs_device(
+            self._handle, C.c_void_p(dvec6.data_ptr()), None if dpos is None else C.c_void_p(dpos.data_ptr()),
+            None if dlat is None else C.c_void_p(dlat.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, self._handle, "rn_potgnn_train_backward_inputs_device")
+        return dpos, dlat
+
+    def _input_gradients(self, lat_t: torch.Tensor, zs, pos_t: torch.Tensor, grad_out: torch.Tensor, want_pos: bool,
+                         want_lat: bool):
+        """Evaluation-mode input gradients (``rn_potgnn_forward_vjp_device``): device float64 ``([S,N,3] or None,
+        [S,9] or None)`` on the inputs' GPU (the model's for host inputs), ordered on torch's current stream there."""
+        zs_t = torch.as_tensor(zs)
+        home = next((t.device for t in (pos_t, lat_t, zs_t) if t.is_cuda), None)
+        device = home if home is not None else torch.device("cuda", self.device_index)
+        device, s, pos, _, types = self._device_inputs(lat_t.detach().to(device), zs_t.to(device), pos_t.detach().to(device))
+        dpos = torch.zeros((s, self.num_atoms, 3), dtype=torch.float64, device=device) if want_pos else None
+        dlat = torch.zeros((s, 9), dtype=torch.float64, device=device) if want_lat else None
+        if s == 0 or not (want_pos or want_lat):
+            return dpos, dlat
+        lat64 = lat_t.detach().to(device=device, dtype=torch.float64).reshape(s, 9).contiguous()
+        dvec6 = grad_out.detach().to(device=device, dtype=torch.float64).contiguous()
+        model_f64 = next(self.parameters()).dtype == torch.float64  # the precision forward evaluated in
+        handle = self._ensure_handle()
+        stream = torch.cuda.current_stream(device).cuda_stream
+        rc = _lib.load().rn_potgnn_forward_vjp_device(
+            handle, C.c_void_p(lat64.data_ptr()), None if types is None else C.c_void_p(types.data_ptr()),
+            C.c_void_p(pos.data_ptr()), s, C.c_void_p(dvec6.data_ptr()), int(model_f64),
+            None if dpos is None else C.c_void_p(dpos.data_ptr()), None if dlat is None else C.c_void_p(dlat.data_ptr()),
+            C.c_void_p(stream))
+        _lib.check(rc, handle, "rn_potgnn_forward_vjp_device")
+        return dpos, dlat
 
     # -- training step pieces used by _TrainStep ------------------------------------------
     def enable_data_parallel(self, group=None) -> None:
@@ -719,13 +778,18 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         self._uploaded_version = None  # buffers changed: re-upload before the next evaluation
         return out
 
-    def _train_backward(self, dvec6: np.ndarray):
+    def _train_backward(self, dvec6: np.ndarray, dpos: np.ndarray | None = None, dlat: np.ndarray | None = None):
         handle = self._handle
         lib = _lib.load()
         blob = np.empty(sum(v.numel() for v in self._state.values() if v.is_floating_point()),
                         dtype=np.float32)
-        rc = lib.rn_potgnn_train_backward(handle, _ptr(dvec6), _ptr(blob))
-        _lib.check(rc, handle, "rn_potgnn_train_backward")
+        if dpos is None and dlat is None:
+            rc = lib.rn_potgnn_train_backward(handle, _ptr(dvec6), _ptr(blob))
+            _lib.check(rc, handle, "rn_potgnn_train_backward")
+        else:  # the same reverse pass, writing the input gradients too
+            rc = lib.rn_potgnn_train_backward_inputs(handle, _ptr(dvec6), _ptr(blob), None if dpos is None else _ptr(dpos),
+                                                     None if dlat is None else _ptr(dlat))
+            _lib.check(rc, handle, "rn_potgnn_train_backward_inputs")
         grads, offset = [], 0
         for key, value in self._state.items():
             if not value.is_floating_point():
@@ -751,9 +815,16 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         self._device_batches_tracked = int(
             self._state_store["_to_polarizability_embedding.1.num_batches_tracked"])
 
-    def _train_backward_device(self, dvec6: np.ndarray) -> None:
-        rc = _lib.load().rn_potgnn_train_backward_device(self._handle, _ptr(dvec6))
-        _lib.check(rc, self._handle, "rn_potgnn_train_backward_device")
+    def _train_backward_device(self, dvec6: np.ndarray, dpos: np.ndarray | None = None,
+                               dlat: np.ndarray | None = None) -> None:
+        if dpos is None and dlat is None:
+            rc = _lib.load().rn_potgnn_train_backward_device(self._handle, _ptr(dvec6))
+            _lib.check(rc, self._handle, "rn_potgnn_train_backward_device")
+            return
+        rc = _lib.load().rn_potgnn_train_backward_inputs(self._handle, _ptr(dvec6), None,
+                                                         None if dpos is None else _ptr(dpos),
+                                                         None if dlat is None else _ptr(dlat))
+        _lib.check(rc, self._handle, "rn_potgnn_train_backward_inputs")
 
     def device_gradients(self) -> torch.Tensor:
         """The float32 gradient buffer of the last device backward, as a CUDA tensor that
@@ -934,25 +1005,74 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         return {names[i].decode(): (ms[i], launches[i]) for i in range(max(n, 0))}
 
 
+def _requires_grad(value) -> bool:
+    return isinstance(value, torch.Tensor) and value.requires_grad
+
+
+def _as_input_grad(grad, like: torch.Tensor):
+    """A float64 gradient in the shape, dtype and on the device of the input it belongs to."""
+    if grad is None:
+        return None
+    return grad.reshape(like.shape).to(device=like.device, dtype=like.dtype)
+
+
+class _EvalInputGrad(torch.autograd.Function):
+    """``PotGNN.forward`` in evaluation mode with positions and / or lattice requiring grad: the value is the plain
+    evaluation's (``forward`` under no grad), the backward is ``rn_potgnn_forward_vjp_device``."""
+
+    @staticmethod
+    def forward(ctx, model, lattice, atomic_numbers, positions):  # pylint: disable=arguments-differ
+        ctx.model = model
+        ctx.atomic_numbers = atomic_numbers
+        # (the inputs themselves: their gradients go back in their dtype, on their device)
+        lat_t = lattice if isinstance(lattice, torch.Tensor) else torch.as_tensor(lattice)
+        pos_t = positions if isinstance(positions, torch.Tensor) else torch.as_tensor(positions)
+        ctx.save_for_backward(lat_t, pos_t)
+        return model.forward(lattice, atomic_numbers, positions)  # (grad mode is off in here: the plain path)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):  # pylint: disable=arguments-differ
+        lat_t, pos_t = ctx.saved_tensors
+        want_lat, want_pos = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        dpos, dlat = ctx.model._input_gradients(lat_t, ctx.atomic_numbers, pos_t, grad_out, want_pos, want_lat)
+        return (None, _as_input_grad(dlat, lat_t) if want_lat else None, None,
+                _as_input_grad(dpos, pos_t) if want_pos else None)
+
+
 class _TrainStep(torch.autograd.Function):
     """``PotGNN.forward`` in training mode: forward and backward both run on the device
     (``rn_potgnn_train_forward`` / ``rn_potgnn_train_backward``); autograd only routes the
-    parameter gradients."""
+    parameter gradients and, when the position / lattice tensors ``pos_t`` / ``lat_t`` require grad, theirs
+    (``rn_potgnn_train_backward_inputs``: the same reverse pass)."""
 
     @staticmethod
-    def forward(ctx, model, pos, extra, *params):  # pylint: disable=arguments-differ
+    def forward(ctx, model, pos, extra, pos_t, lat_t, *params):  # pylint: disable=arguments-differ
         ctx.model = model
+        ctx.inputs = (pos_t.detach(), lat_t.detach())  # (shape, dtype and device of their gradients)
         return torch.from_numpy(model._train_forward(pos, *extra))
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_out):  # pylint: disable=arguments-differ
         dvec6 = np.ascontiguousarray(grad_out.detach().cpu().numpy(), dtype=np.float32)
+        want_pos, want_lat = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        s = dvec6.shape[0]
+        dpos = np.empty((s, ctx.model.num_atoms, 3), dtype=np.float64) if want_pos else None
+        dlat = np.empty((s, 9), dtype=np.float64) if want_lat else None
         if ctx.model._device_training:
-            ctx.model._train_backward_device(dvec6)
-            return (None, None, None, None)
-        grads = ctx.model._train_backward(dvec6)
-        params = [p for _, p in torch.nn.Module.named_parameters(ctx.model)]
-        return (None, None, None, *[g.to(device=p.device, dtype=p.dtype) for g, p in zip(grads, params)])
+            ctx.model._train_backward_device(dvec6, dpos, dlat)
+            params = []
+        else:
+            grads = ctx.model._train_backward(dvec6, dpos, dlat)
+            params = [g.to(device=p.device, dtype=p.dtype)
+                      for g, p in zip(grads, [p for _, p in torch.nn.Module.named_parameters(ctx.model)])]
+        pos_t, lat_t = ctx.inputs
+        din = (_as_input_grad(None if dpos is None else torch.from_numpy(dpos), pos_t),
+               _as_input_grad(None if dlat is None else torch.from_numpy(dlat), lat_t))
+        if ctx.model._device_training:
+            return (None, None, None, *din, None)  # (the anchor)
+        return (None, None, None, *din, *params)
 
 
 class _TrainStepOnDevice(torch.autograd.Function):
@@ -963,12 +1083,16 @@ class _TrainStepOnDevice(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, lat_t, zs_t, pos_t, anchor):  # pylint: disable=arguments-differ,unused-argument
         ctx.model = model
+        ctx.inputs = (pos_t.detach(), lat_t.detach())  # (shape, dtype and device of their gradients)
         return model._train_forward_on_device(lat_t, zs_t, pos_t)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_out):  # pylint: disable=arguments-differ
-        ctx.model._train_backward_on_device(grad_out)
-        return (None, None, None, None, None)
+        want_lat, want_pos = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        dpos, dlat = ctx.model._train_backward_on_device(grad_out, want_pos, want_lat)
+        pos_t, lat_t = ctx.inputs
+        return (None, _as_input_grad(dlat, lat_t), None, _as_input_grad(dpos, pos_t), None)
 
 
 class _DeviceSpan:  # pylint: disable=too-few-public-methods
