@@ -406,6 +406,38 @@ int rn_md_raman_intensities(const double *alpha, int64_t S, int device, double *
 int rn_md_raman_intensities_device(const double *d_alpha, int64_t S, int device, double *intensities,
                                    int64_t num_bins, void *stream);
 
+/*
+ * Polarized / oriented MD Raman spectra of K configurations (MDRamanSpectrum.measure_polarized before
+ * the laser / Bose-Einstein corrections).  With da(t) = alpha(t+1) - alpha(t) and its symmetric part
+ * d(t) = (xx, yy, zz, xy, yz, xz) (component order 0..5; the off-diagonal ones are (a_ij + a_ji) / 2),
+ * configuration k's intensities are
+ *   I_k(f) = sum_{j<=l} weights[k][p(j,l)] C_jl(f),   f = bins 1..num_bins of fftfreq(S-1),
+ * where C_jl is calc_signal_spectrum's transform (real part of the length-(S-1) FFT of the positive
+ * lags) of the symmetrised cross-correlation (r_jl(t) + r_lj(t)) / 2, r_jl(t) = sum_n d_j(n+t) d_l(n).
+ * The 21 pairs are packed row-major over the upper triangle, p = (0,0) (0,1) .. (0,5) (1,1) .. (1,5)
+ * (2,2) .. (5,5); the weights of a symmetric 6x6 form M_k are M_k[j][j] on the diagonal and
+ * 2 M_k[j][l] off it.  For the signal s_k = w_k . d (e_s . R da R^T . e_i), M_k = w_k w_k^T, and I_k is
+ * calc_signal_spectrum(s_k) without the zero bin.  The device computes the 21 basis spectra once
+ * (6 + 2 * 21 FFTs whatever K is) and contracts them with the weights; it never sees geometry.
+ * alpha: host float64[S][3][3]; weights: host float64[K][21]; intensities: host float64[K][num_bins],
+ * num_bins = ceil((S-1)/2) - 1 as for rn_md_raman_intensities (same argument checks and codes,
+ * RN_ERR_UNSUPPORTED without hipFFT).  workspace_limit (bytes, 0 = 4 GiB) bounds the device memory of
+ * the call besides the staged copy of alpha: the pairs go through the FFTs in groups of at most 21,
+ * as many as fit, and the intensities reach the host in blocks of configurations; a limit that not even
+ * one pair and one configuration fit in returns RN_ERR_OUT_OF_MEMORY.  hipFFT plans and work buffers
+ * are cached per (device, S, group size), apart from rn_md_raman_intensities' cache.  The work runs on
+ * the null stream and the call returns when the intensities are on the host.
+ */
+int rn_md_raman_polarized(const double *alpha, int64_t S, const double *weights, int64_t K, int device,
+                          size_t workspace_limit, double *intensities, int64_t num_bins);
+/*
+ * The same for a time series already in HBM (d_alpha: device float64[S][3][3], produced on `stream`):
+ * the call synchronises `stream` before it reads d_alpha, then runs on the null stream; only the
+ * K * num_bins intensities travel to the host.
+ */
+int rn_md_raman_polarized_device(const double *d_alpha, int64_t S, const double *weights, int64_t K, int device,
+                                 size_t workspace_limit, double *intensities, int64_t num_bins, void *stream);
+
 /* Introspection: bit 0 = the fused EdgeBlock kernel is in use (float32, Fn and Fe padded to
  * 64); bit 1 = every pass takes the folded-LayerNorm-scale triplet loop; bit 2 = the fused
  * kernels' matrix products run as split-f16 MFMA (default; RN_POTGNN_MFMA=f32 at create time

@@ -13,7 +13,7 @@ from numpy.typing import NDArray
 
 from ramannoodle_amd.abstract import RamanSpectrum
 from ramannoodle_amd.constants import BOLTZMANN_CONSTANT
-from ramannoodle_amd.exceptions import get_type_error, verify_ndarray_shape
+from ramannoodle_amd.exceptions import get_type_error, shape_string, verify_ndarray_shape
 
 _CM1_TO_HZ = 29979245800.0
 _PLANCK_EV_S = 4.1357e-15  # value used by the reference (spectrum/_raman.py:37)
@@ -61,6 +61,152 @@ def _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelen
 def _require_polycrystalline(orientation) -> None:
     if not (isinstance(orientation, str) and orientation == "polycrystalline"):
         raise NotImplementedError("only polycrystalline spectra are supported for now")
+
+
+# ----------------------------------------------------------------------------- polarized spectra
+# The six components of a symmetric tensor, in the order the device entry uses, and the 21 pairs
+# (j <= l) of them, packed row-major over the upper triangle (include/rn_potgnn.h).
+_COMPONENTS = ((0, 0), (1, 1), (2, 2), (0, 1), (1, 2), (0, 2))
+_PAIRS = tuple((j, l) for j in range(6) for l in range(j, 6))
+_PAIR_J = np.array([j for j, _ in _PAIRS])
+_PAIR_L = np.array([l for _, l in _PAIRS])
+_PAIR_SCALE = np.where(_PAIR_J == _PAIR_L, 1.0, 2.0)  # off-diagonal entries of M appear twice
+# quadratic forms over the components: a^2 = ((xx+yy+zz)/3)^2 and the anisotropy gamma^2 of measure()
+_ISO_FORM = np.zeros((6, 6))
+_ISO_FORM[:3, :3] = 1.0 / 9.0
+_ANISO_FORM = np.diag([1.0, 1.0, 1.0, 3.0, 3.0, 3.0])
+_ANISO_FORM[:3, :3] -= 0.5 * (1.0 - np.eye(3))
+
+
+def _symmetric_components(tensors: NDArray[np.float64]) -> NDArray[np.float64]:
+    """``(..., 3, 3)`` -> ``(..., 6)``: (xx, yy, zz, xy, yz, xz) of the symmetric part."""
+    return np.stack([0.5 * (tensors[..., a, b] + tensors[..., b, a]) for a, b in _COMPONENTS], axis=-1)
+
+
+def _polarization_vectors(name: str, value) -> NDArray[np.float64]:
+    if value is None or isinstance(value, (str, bytes)):
+        raise get_type_error(name, value, "ndarray")
+    try:
+        array = np.asarray(value)
+    except (TypeError, ValueError) as exc:
+        raise get_type_error(name, value, "ndarray") from exc
+    if array.dtype.kind not in "iuf":
+        raise get_type_error(name, value, "ndarray of real numbers")
+    array = array.astype(np.float64)
+    if array.ndim not in (1, 2) or array.shape[-1] != 3:
+        raise ValueError(f"{name} has wrong shape: {shape_string(array.shape)} != (3,) or (_,3)")
+    if not np.all(np.isfinite(array)):
+        raise ValueError(f"{name} is not finite")
+    norms = np.linalg.norm(array, axis=-1)
+    if np.any(norms == 0):
+        raise ValueError(f"{name} holds a zero vector")
+    return array / norms[..., None]
+
+
+def _orientations(orientation):
+    """``None`` -> identity, ``"polycrystalline"`` -> that string, else validated rotations."""
+    if orientation is None:
+        return np.eye(3)
+    if isinstance(orientation, str):
+        if orientation != "polycrystalline":
+            raise ValueError(f"unknown orientation: {orientation!r}")
+        return orientation
+    try:
+        array = np.asarray(orientation)
+    except (TypeError, ValueError) as exc:
+        raise get_type_error("orientation", orientation, "ndarray or str") from exc
+    if array.dtype.kind not in "iuf":
+        raise get_type_error("orientation", orientation, "ndarray or str")
+    array = array.astype(np.float64)
+    if array.ndim not in (2, 3) or array.shape[-2:] != (3, 3):
+        raise ValueError(f"orientation has wrong shape: {shape_string(array.shape)} != (3,3) or (_,3,3)")
+    if not np.all(np.isfinite(array)):
+        raise ValueError("orientation is not finite")
+    deviation = np.linalg.norm(array @ np.swapaxes(array, -1, -2) - np.eye(3), axis=(-2, -1))
+    if np.any(deviation > 1e-8) or np.any(np.linalg.det(array) < 0):
+        raise ValueError("orientation is not a proper rotation")
+    return array
+
+
+def polarized_weights(incident, scattered, orientation=None) -> tuple[NDArray[np.float64], bool]:
+    """The packed weights ``W[K][21]`` of ``measure_polarized`` and whether the result is squeezed.
+
+    Configuration k's intensity is ``sum_p W[k,p] C_p`` over the 21 component pairs ``p = (j,l)``,
+    ``j <= l``, of (xx, yy, zz, xy, yz, xz) (``include/rn_potgnn.h``), where ``C_p`` is the spectrum of
+    the symmetrised cross-correlation of components j and l (phonons: the product ``T_j T_l``); ``W`` packs
+    a symmetric 6x6 form ``M`` with its off-diagonal entries doubled.  For one orientation R, ``M = w w^T``
+    with ``w = (v0 u0, v1 u1, v2 u2, v0 u1 + v1 u0, v1 u2 + v2 u1, v0 u2 + v2 u0)``, ``u = R^T e_i``,
+    ``v = R^T e_s``; for ``"polycrystalline"`` it is the isotropic average
+    ``c^2 a^2 + (3 + c^2) gamma^2 / 45``, ``c = e_i . e_s``.  Every class builds its weights here.
+    """
+    e_i = _polarization_vectors("incident", incident)
+    e_s = _polarization_vectors("scattered", scattered)
+    rotations = _orientations(orientation)
+    counts = [a.shape[0] for a in (e_i, e_s) if a.ndim == 2]
+    if not isinstance(rotations, str) and rotations.ndim == 3:
+        counts.append(rotations.shape[0])
+    if len(set(counts)) > 1:
+        raise ValueError(f"incident, scattered and orientation disagree on the number of configurations: {counts}")
+    k = counts[0] if counts else 1
+    e_i = np.broadcast_to(e_i, (k, 3))
+    e_s = np.broadcast_to(e_s, (k, 3))
+    if isinstance(rotations, str):
+        c2 = np.einsum("ka,ka->k", e_i, e_s) ** 2
+        forms = c2[:, None, None] * _ISO_FORM + ((3.0 + c2) / 45.0)[:, None, None] * _ANISO_FORM
+        weights = forms[:, _PAIR_J, _PAIR_L] * _PAIR_SCALE
+    else:
+        rotations = np.broadcast_to(rotations, (k, 3, 3))
+        u = np.einsum("kab,ka->kb", rotations, e_i)  # R^T e_i: crystal-frame components
+        v = np.einsum("kab,ka->kb", rotations, e_s)
+        outer = v[:, :, None] * u[:, None, :]
+        w = _symmetric_components(outer) * np.array([1.0, 1.0, 1.0, 2.0, 2.0, 2.0])
+        weights = w[:, _PAIR_J] * w[:, _PAIR_L] * _PAIR_SCALE
+    return np.ascontiguousarray(weights, dtype=np.float64), not counts
+
+
+def _md_basis_spectra(polarizability_ts: NDArray[np.float64], timestep: float):
+    """(wavenumbers, ``C[21][bins]``) on the host: calc_signal_spectrum's transform of the symmetrised
+    cross-correlation of each component pair of the symmetric part of d(alpha)/dt, zero bin dropped."""
+    d = _symmetric_components(np.diff(polarizability_ts, axis=0))
+    n = d.shape[0]
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    keep = np.flatnonzero(wavenumbers >= 0)[1:]
+    basis = np.empty((len(_PAIRS), len(keep)))
+    for p, (j, l) in enumerate(_PAIRS):
+        full = scipy.signal.correlate(d[:, j], d[:, l], "full")
+        lags = 0.5 * (full[n - 1:] + full[n - 1::-1])
+        basis[p] = np.real(scipy.fftpack.fft(lags))[keep]
+    return wavenumbers[keep], basis
+
+
+def _md_polarized_on_device(alpha, timestep: float, weights, device: int, stream=None,
+                            workspace_limit: int = 0):
+    """(wavenumbers, uncorrected ``I[K][bins]``) from ``rn_md_raman_polarized`` (host alpha) or, with a
+    torch CUDA tensor, ``rn_md_raman_polarized_device`` ordered after ``stream``."""
+    import ctypes as C
+
+    from ramannoodle_amd import _lib
+    n = alpha.shape[0] - 1
+    if n < 2:
+        raise ValueError("the device reduction needs at least three time steps")
+    bins = (n + 1) // 2 - 1
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    intensities = np.empty((weights.shape[0], bins), dtype=np.float64)
+    lib = _lib.load()
+    if stream is None:
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+        rc = lib.rn_md_raman_polarized(C.c_void_p(alpha.ctypes.data), alpha.shape[0],
+                                       C.c_void_p(weights.ctypes.data), weights.shape[0], device, workspace_limit,
+                                       C.c_void_p(intensities.ctypes.data), bins)
+        _lib.check(rc, None, "rn_md_raman_polarized")
+    else:
+        rc = lib.rn_md_raman_polarized_device(C.c_void_p(alpha.data_ptr()), alpha.shape[0],
+                                              C.c_void_p(weights.ctypes.data), weights.shape[0], device,
+                                              workspace_limit, C.c_void_p(intensities.ctypes.data), bins,
+                                              C.c_void_p(stream))
+        _lib.check(rc, None, "rn_md_raman_polarized_device")
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    return wavenumbers[1:bins + 1], intensities
 
 
 def calc_signal_spectrum(signal: NDArray[np.float64],
@@ -174,6 +320,28 @@ class PhononRamanSpectrum(RamanSpectrum):
                                          laser_wavelength, bose_einstein_correction, temperature)
         return self._phonon_wavenumbers, intensities
 
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False,
+                          laser_wavelength=522, bose_einstein_correction=False, temperature=300, device=None):
+        """Intensities ``(e_s . R T_m R^T . e_i)^2`` of each mode for set polarizations (an addition).
+
+        ``incident`` / ``scattered``: lab-frame vectors ``(3,)`` or ``(K,3)``, normalised here (a zero
+        vector is a ``ValueError``); ``orientation``: ``None`` (identity), a proper rotation ``(3,3)`` or
+        ``(K,3,3)`` taking crystal-frame components to the lab frame, or ``"polycrystalline"`` (the
+        isotropic average, ``c^2 a^2 + (3 + c^2) gamma^2 / 45`` with ``c = e_i . e_s``; so
+        ``45 (I_parallel + I_perpendicular)`` is ``measure()``).  ``K`` broadcasts across the three.
+        The symmetric part of each Raman tensor is used.  Returns ``(wavenumbers, intensities)`` with
+        intensities ``(K, M)``, or ``(M,)`` when no argument has a ``K`` axis; the corrections apply to
+        each row as in ``measure``.  ``device`` is accepted for a signature common to all spectra; the
+        reduction of at most 3N modes always runs on the host.
+        """
+        del device
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        d = _symmetric_components(np.asarray(self._raman_tensors, dtype=np.float64))
+        intensities = weights @ (d[:, _PAIR_J] * d[:, _PAIR_L]).T
+        intensities = _apply_corrections(self._phonon_wavenumbers, intensities, laser_correction,
+                                         laser_wavelength, bose_einstein_correction, temperature)
+        return self._phonon_wavenumbers, intensities[0] if squeeze else intensities
+
 
 class MDRamanSpectrum(RamanSpectrum):
     """Spectrum from a polarizability time series ``(S,3,3)`` and a timestep in fs
@@ -226,6 +394,34 @@ class MDRamanSpectrum(RamanSpectrum):
                                          laser_wavelength, bose_einstein_correction, temperature)
         return wavenumbers, intensities
 
+    def _polarized_on_device(self, weights, device: int):
+        return _md_polarized_on_device(self._polarizability_ts, self._timestep, weights, device)
+
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False,
+                          laser_wavelength=522, bose_einstein_correction=False, temperature=300, device=None):
+        """Spectra for set incident / scattered polarizations and crystal orientations (an addition).
+
+        Configuration k's spectrum is ``calc_signal_spectrum(s_k, timestep)`` without the zero bin, on
+        ``measure``'s wavenumbers, for ``s_k(t) = e_s . R da(t) R^T . e_i`` with
+        ``da(t) = alpha(t+1) - alpha(t)``; the symmetric part of ``da`` is used (every model output is
+        exactly symmetric).  Arguments as ``PhononRamanSpectrum.measure_polarized``; under
+        ``"polycrystalline"`` the invariant spectra take the place of ``a^2`` and ``gamma^2``, so
+        ``45 (I_parallel + I_perpendicular)`` is ``measure()``.  Intensities are ``(K, bins)``, or
+        ``(bins,)`` when no argument has a ``K`` axis.  The 21 cross-spectra of the tensor components are
+        computed once and contracted with each configuration's weights (``polarized_weights``);
+        ``device`` (an int) does that on the GPU (``rn_md_raman_polarized``).
+        """
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        if device is not None:
+            wavenumbers, intensities = self._polarized_on_device(weights, int(device))
+        else:
+            wavenumbers, basis = _md_basis_spectra(np.asarray(self._polarizability_ts, dtype=np.float64),
+                                                   self._timestep)
+            intensities = weights @ basis
+        intensities = _apply_corrections(wavenumbers, intensities, laser_correction,
+                                         laser_wavelength, bose_einstein_correction, temperature)
+        return wavenumbers, intensities[0] if squeeze else intensities
+
 
 class DeviceMDRamanSpectrum(MDRamanSpectrum):
     """``MDRamanSpectrum`` whose polarizability time series stays where the evaluator wrote it
@@ -266,3 +462,20 @@ class DeviceMDRamanSpectrum(MDRamanSpectrum):
             device = self._device_ts.device.index or 0
         return super().measure(orientation, laser_correction, laser_wavelength, bose_einstein_correction,
                                temperature, device=None if host else device)
+
+    def _polarized_on_device(self, weights, device: int):
+        import torch
+        if device != (self._device_ts.device.index or 0):
+            return _md_polarized_on_device(self.polarizability_ts, self._timestep, weights, device)
+        stream = torch.cuda.current_stream(self._device_ts.device).cuda_stream
+        return _md_polarized_on_device(self._device_ts, self._timestep, weights, device, stream=stream)
+
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False,
+                          laser_wavelength=522, bose_einstein_correction=False, temperature=300, device=None,
+                          host=False):
+        """As ``MDRamanSpectrum.measure_polarized``; reduces on the tensor's GPU unless ``host=True``
+        (``rn_md_raman_polarized_device``: only the intensities leave HBM)."""
+        if device is None and not host:
+            device = self._device_ts.device.index or 0
+        return super().measure_polarized(incident, scattered, orientation, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature, device=None if host else device)
