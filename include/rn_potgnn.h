@@ -349,6 +349,33 @@ int rn_potgnn_train_backward_samples_device(rn_potgnn *h, const float *d_dvec6, 
 int rn_potgnn_forward_vjp_device(rn_potgnn *h, const double *d_lattices, const int32_t *d_atom_types,
                                  const double *d_positions, int64_t S, const double *d_dvec6, int use_float64,
                                  double *d_dpos, double *d_dlat, void *stream);
+/*
+ * Atom-group decomposition (PartialMDRamanSpectrum / PartialPhononRamanSpectrum).  J_i(x) = d alpha / d x_i is the derivative
+ * of the de-standardised polarizability (sigma applied, mu drops out) with respect to atom i's fractional coordinates, in
+ * evaluation mode; labels host int32[N] put atom i in group labels[i], 1 <= G <= 16, every group non-empty (else
+ * RN_ERR_INVALID_ARGUMENT).  The atoms are bucketed by group as a CSR permutation, rebuilt on the handle when the labels
+ * change, and each group is summed in a fixed order without atomics.  The Jacobian rows come from the existing reverse
+ * pass, whose EdgeBlock backward accumulates cotangents with atomics: repeated calls and different chunkings agree to
+ * round-off, not bit for bit.
+ *
+ * rn_potgnn_group_increments_device: d_positions device f64[S][N][3] (fractional, wrapped), S >= 2 -> d_out device
+ * f64[S-1][G][9], the trapezoid increments
+ *   d_out[t][g] = sum_{i in g} 1/2 (J_i(x_t) + J_i(x_{t+1})) . dx_{t,i},   dx_t = x_{t+1} - x_t - round(x_{t+1} - x_t),
+ * so that sum_g d_out[t][g] = alpha(x_{t+1}) - alpha(x_t) + O(|dx|^3).  The Jacobian rows of a chunk of frames come from
+ * the taped forward on lane 0 and one reverse pass with six one-hot cotangents per frame, in float32 or, with use_float64,
+ * in the kernels instantiated for double; chunks of frames overlap by one frame (its rows are carried over).  The tape,
+ * the reverse pass and the rows of one chunk stay within workspace_limit bytes (0 = 4 GiB); a limit that not one step
+ * fits in returns RN_ERR_OUT_OF_MEMORY.  A pending train_forward is discarded.  Work is ordered after `stream`, `stream`
+ * waits for it and is synchronised once at the end.
+ *
+ * rn_potgnn_partial_raman_tensors: host pointers ref_positions f64[N*3], displacements f64[M][N][3] -> raman
+ * f64[M][G][9], R[m][g] = 2 sum_{i in g} J_i(ref) . d_{m,i} (the factor 2 of rn_potgnn_raman_tensors_analytic, so that
+ * sum_g R[m][g] is that entry's tensor): one float64 Jacobian at the reference positions, then the same contraction kernel.
+ */
+int rn_potgnn_group_increments_device(rn_potgnn *h, const double *d_positions, int64_t S, const int32_t *labels, int G,
+                                      int use_float64, size_t workspace_limit, double *d_out, void *stream);
+int rn_potgnn_partial_raman_tensors(rn_potgnn *h, const double *ref_positions, const double *displacements, int64_t M,
+                                    const int32_t *labels, int G, double *raman);
 int rn_potgnn_train_backward_inputs(rn_potgnn *h, const float *dvec6, float *grads, double *dpos, double *dlat);
 int rn_potgnn_train_backward_inputs_device(rn_potgnn *h, const float *d_dvec6, double *d_dpos, double *d_dlat,
                                            void *stream);
@@ -437,6 +464,29 @@ int rn_md_raman_polarized(const double *alpha, int64_t S, const double *weights,
  */
 int rn_md_raman_polarized_device(const double *d_alpha, int64_t S, const double *weights, int64_t K, int device,
                                  size_t workspace_limit, double *intensities, int64_t num_bins, void *stream);
+
+/*
+ * Partial (atom-group) MD Raman spectra of K configurations from per-group increments: increments host
+ * float64[N][G][9] (N = S - 1 steps, N >= 2; group g's da(t), e.g. from rn_potgnn_group_increments_device), 1 <= G <= 16,
+ * weights host float64[K][21] as for rn_md_raman_polarized.  With d_g(t) the six components of the symmetric part of
+ * group g's increment and M_k the symmetric 6x6 form of configuration k's weights,
+ *   I_k[g][h](f) = sum_{c,c'} M_k[c][c'] C(d_{g,c}, d_{h,c'})(f),   f = bins 1..num_bins of fftfreq(N),
+ * C(a, b) as C_jl of rn_md_raman_polarized (calc_signal_spectrum's transform of the symmetrised cross-correlation): so
+ * sum_{g,h} I_k[g][h] is rn_md_raman_polarized of the summed increments and I_k[g][g] that of group g alone.
+ * intensities: host float64[K][G(G+1)/2][num_bins], the pairs g <= h packed row-major over the upper triangle
+ * ((0,0) (0,1) .. (0,G-1) (1,1) ..), num_bins = ceil(N/2) - 1.  The device runs 6G forward FFTs in one batched launch,
+ * then per block of rows (k, g <= h) a contraction kernel, an inverse FFT and a length-N FFT.  workspace_limit (bytes,
+ * 0 = 4 GiB) bounds the device memory besides the staged increments: a limit that the components and one row do not fit
+ * in returns RN_ERR_OUT_OF_MEMORY.  hipFFT plans and buffers are cached per (device, N, G, rows per block), apart from
+ * the caches of rn_md_raman_intensities and rn_md_raman_polarized.  Work runs on the null stream; the call returns when
+ * the intensities are on the host (RN_ERR_UNSUPPORTED without hipFFT).
+ */
+int rn_md_raman_partial(const double *increments, int64_t N, int G, const double *weights, int64_t K, int device,
+                        size_t workspace_limit, double *intensities, int64_t num_bins);
+/* The same for increments already in HBM (d_increments: device float64[N][G][9], produced on `stream`): the call
+ * synchronises `stream` before it reads them; only the intensities travel to the host. */
+int rn_md_raman_partial_device(const double *d_increments, int64_t N, int G, const double *weights, int64_t K,
+                               int device, size_t workspace_limit, double *intensities, int64_t num_bins, void *stream);
 
 /* Introspection: bit 0 = the fused EdgeBlock kernel is in use (float32, Fn and Fe padded to
  * 64); bit 1 = every pass takes the folded-LayerNorm-scale triplet loop; bit 2 = the fused

@@ -80,6 +80,8 @@ SIGNATURES = {
     "rn_potgnn_train_backward_samples_device": (C.c_int, [_P, _P, _P]),
     "rn_potgnn_train_backward_f64": (C.c_int, [_P, _P, _P]),
     "rn_potgnn_forward_vjp_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int, _P, _P, _P]),
+    "rn_potgnn_group_increments_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_size_t, _P, _P]),
+    "rn_potgnn_partial_raman_tensors": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, _P]),
     "rn_potgnn_train_backward_inputs": (C.c_int, [_P, _P, _P, _P, _P]),
     "rn_potgnn_train_backward_inputs_device": (C.c_int, [_P, _P, _P, _P, _P]),
     "rn_potgnn_num_triplets": (C.c_int64, [_P]),
@@ -97,6 +99,9 @@ SIGNATURES = {
     "rn_md_raman_polarized": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_size_t, _P, C.c_int64]),
     "rn_md_raman_polarized_device": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_size_t, _P, C.c_int64,
                                                _P]),
+    "rn_md_raman_partial": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_size_t, _P, C.c_int64]),
+    "rn_md_raman_partial_device": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_size_t, _P,
+                                             C.c_int64, _P]),
     # include/rn_ingest.h (host-only trajectory reader)
     "rn_xdatcar_open": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "rn_xdatcar_close": (None, [_P]),

@@ -153,6 +153,8 @@ struct Precision {
   DeviceBuf tn_arena;  // partial sums of the weight-gradient products (reverse_pass)
   DeviceBuf tape_z1, bn_stats, grad, seeds, mv, type_sums;  // training: pre-BatchNorm activations, batch sums, gradient blob
   DeviceBuf in_dcart, in_lat, in_grads;  // input gradients: per-edge Cartesian cotangents, a chunk's lattices, host-path outputs
+  DeviceBuf eye_seeds;  // atom-group increments: one-hot cotangents [frames][6][6], filled once per size
+  int eye_frames = 0;
   bool tape_on = false;
 };
 
@@ -249,6 +251,10 @@ struct rn_potgnn {
   hipEvent_t ev_start = nullptr;
   hipEvent_t ev_g[2] = {nullptr, nullptr};  // "projection stage done" per lane (run_pair)
   bool interleave = true;
+  // atom-group contractions: the CSR permutation of the last labels (perm [N] | gptr [G+1]), Jacobian rows, staging
+  std::vector<int32_t> grp_labels;
+  int grp_G = 0;
+  DeviceBuf grp_csr, grp_jac, grp_disp, grp_out;
 };
 
 namespace {
@@ -1619,6 +1625,106 @@ void forward_vjp(rn_potgnn *h, const double *d_lat /* [S][9] or null */, const i
   check_ps_fail(h);
 }
 
+// ---- atom-group contractions (rn_potgnn_group_increments_device, rn_potgnn_partial_raman_tensors)
+constexpr int kMaxGroups = 16;
+
+// labels host int32[N] in [0, G), every group used: the atoms bucketed by group (ascending atom index within a group) as a
+// CSR permutation in h->grp_csr; rebuilt only when the labels change.  false on a label out of range or an empty group.
+bool set_group_labels(rn_potgnn *h, const int32_t *labels, int G) {
+  const int N = h->g.N;
+  std::vector<int32_t> ptr(G + 1, 0);
+  for (int i = 0; i < N; ++i) {
+    if (labels[i] < 0 || labels[i] >= G) return false;
+    ++ptr[labels[i] + 1];
+  }
+  for (int g = 0; g < G; ++g) {
+    if (ptr[g + 1] == 0) return false;
+    ptr[g + 1] += ptr[g];
+  }
+  if (h->grp_G == G && h->grp_labels.size() == (size_t)N && std::equal(labels, labels + N, h->grp_labels.begin()))
+    return true;
+  std::vector<int32_t> csr(N + G + 1);
+  std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+  for (int i = 0; i < N; ++i) csr[fill[labels[i]]++] = i;
+  std::copy(ptr.begin(), ptr.end(), csr.begin() + N);
+  h->grp_csr.ensure(csr.size() * sizeof(int32_t));
+  HIP_TRY(hipMemcpy(h->grp_csr.p, csr.data(), csr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  h->grp_labels.assign(labels, labels + N);
+  h->grp_G = G;
+  return true;
+}
+
+// Frames per taped chunk of the group entries in precision T: the tape, lane 0's buffers and the reverse pass of six
+// cotangent rows per frame (their per-edge Cartesian cotangents and Jacobian rows included) of F frames, plus one frame of
+// Jacobian rows carried over, within `limit` bytes; 0 when not even one frame fits.
+template <typename T>
+int group_frames(const rn_potgnn *h, size_t limit) {
+  const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges, NP = h->cfg.num_message_passes;
+  const size_t FnP = h->d.FnP, FeP = h->d.FeP, HP = std::max<size_t>(FeP, 32);
+  const size_t tape = (NP + 1) * (N * FnP + 2 * E * FeP);
+  const size_t bw = E * (2 * FeP + 4 * FeP + std::max(2 * FeP, HP) + FnP + 2 * FnP + 32 + 4 + HP + 32) +
+                    N * (3 * FnP + 6 * FeP + 2 * FnP);
+  const size_t rows = 6 * N * 3 * sizeof(double);
+  const size_t per = (tape + per_structure_elems(h, false) + 6 * bw + 36) * sizeof(T) + 6 * E * 3 * sizeof(double) + rows;
+  if (limit < per + rows) return 0;
+  return (int)std::min<size_t>((size_t)chunk_frames<T>(h), (limit - rows) / per);
+}
+
+// d vec6_c / d x of s frames (device float64 [s][N][3]) -> d_jac device float64 [s][6][N][3]: the taped forward on lane 0
+// and one reverse pass with six one-hot cotangent rows per frame (geom_input_bwd_kernel: every entry written, no atomics)
+template <typename T>
+void jacobian_rows(rn_potgnn *h, const double *d_pos, int s, double *d_jac) {
+  Precision<T> &P = prec<T>(h);
+  if (P.eye_frames < s) {
+    std::vector<T> eye((size_t)s * 36, (T)0);
+    for (int f = 0; f < s; ++f)
+      for (int k = 0; k < 6; ++k) eye[(size_t)f * 36 + k * 6 + k] = (T)1;
+    HIP_TRY(hipStreamSynchronize(P.lanes[0].stream));  // (an earlier chunk may still read the old seeds)
+    P.eye_seeds.ensure(eye.size() * sizeof(T));
+    HIP_TRY(hipMemcpy(P.eye_seeds.p, eye.data(), eye.size() * sizeof(T), hipMemcpyHostToDevice));
+    P.eye_frames = s;
+  }
+  ChunkRun<T> c = taped_forward<T>(h, d_pos, s);
+  Reverse<T> rv{s, 6, P.eye_seeds.template as<T>(), nullptr, nullptr, false};
+  rv.in_dpos = d_jac;
+  reverse_pass<T>(h, c, rv);
+}
+
+// Trapezoid increments of the S frames d_pos (device float64 [S][N][3]) per atom group -> d_out [S-1][G][9], in chunks
+// of F steps whose Jacobian rows overlap by one frame (the last frame's rows are carried into the next chunk).  Ordered
+// after `user`; `user` waits for the work and is synchronised once at the end.
+template <typename T>
+void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_t limit, double *d_out,
+                      hipStream_t user) {
+  ensure_precision<T>(h);
+  Precision<T> &P = prec<T>(h);
+  const int N = h->g.N;
+  const int F = group_frames<T>(h, limit);
+  if (F < 1) throw HipError{hipErrorOutOfMemory, "group_increments: one step does not fit the workspace limit"};
+  h->train_S = 0;  // the tape and lane 0 are reused: a pending train_forward is void
+  hipStream_t st = P.lanes[0].stream;
+  HIP_TRY(hipEventRecord(h->ev_start, user));
+  HIP_TRY(hipStreamWaitEvent(st, h->ev_start, 0));
+  const int64_t rows = (int64_t)6 * N * 3;
+  h->grp_jac.ensure((size_t)(F + 1) * rows * sizeof(double));
+  double *jac = h->grp_jac.as<double>();
+  const int *perm = h->grp_csr.as<int>(), *gptr = perm + N;
+  const double *sigma = h->d_mean_std.as<double>() + 9;
+  jacobian_rows<T>(h, d_pos, 1, jac);
+  for (int64_t t0 = 0; t0 < S - 1; t0 += F) {
+    const int f = (int)std::min<int64_t>(F, S - 1 - t0);
+    if (t0 > 0) HIP_TRY(hipMemcpyAsync(jac, jac + (int64_t)F * rows, rows * sizeof(double), hipMemcpyDeviceToDevice, st));
+    jacobian_rows<T>(h, d_pos + (t0 + 1) * N * 3, f, jac + rows);
+    launch_group_increments(jac, rows, d_pos + t0 * N * 3, nullptr, 0.0, f, N, perm, gptr, G, sigma,
+                            d_out + t0 * G * 9, st);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(P.lanes[0].done, st));
+  HIP_TRY(hipStreamWaitEvent(user, P.lanes[0].done, 0));
+  HIP_TRY(hipStreamSynchronize(user));
+  check_ps_fail(h);
+}
+
 // ---- device-resident optimisation step: which entries of the packed blob are parameters, which are
 // functions of parameters (and how to recompute them on the device)
 
@@ -1999,6 +2105,8 @@ void unpack_grads(const rn_potgnn *h, const T *gp, T *out, bool buffers /* true:
 // Every entry point that touches a handle runs inside guarded(): calls on ONE handle are serialised by the handle's own
 // lock (they share its workspaces, streams and tape), so a handle may be used from several threads; distinct handles are
 // independent.  No exception leaves the C ABI.
+struct RnInvalid {};  // an argument found invalid inside guarded() (the error text is already set)
+
 int guarded(rn_potgnn *h, const std::function<void()> &fn) {
   std::unique_lock<std::recursive_mutex> lock;
   if (h) lock = std::unique_lock<std::recursive_mutex>(h->lock);
@@ -2006,6 +2114,8 @@ int guarded(rn_potgnn *h, const std::function<void()> &fn) {
     if (h) HIP_TRY(hipSetDevice(h->cfg.device));
     fn();
     return RN_OK;
+  } catch (const RnInvalid &) {
+    return RN_ERR_INVALID_ARGUMENT;
   } catch (const HipError &e) {
     set_error(h, "HIP error %d (%s) in %s", (int)e.code, hipGetErrorString(e.code), e.what);
     return e.code == hipErrorOutOfMemory ? RN_ERR_OUT_OF_MEMORY : RN_ERR_HIP;
@@ -3289,6 +3399,66 @@ int rn_potgnn_forward_vjp_device(rn_potgnn *h, const double *d_lattices, const i
     } else {
       forward_vjp<float>(h, d_lattices, d_atom_types, d_positions, S, d_dvec6, d_dpos, d_dlat, (hipStream_t)stream);
     }
+  });
+}
+
+int rn_potgnn_group_increments_device(rn_potgnn *h, const double *d_positions, int64_t S, const int32_t *labels, int G,
+                                      int use_float64, size_t workspace_limit, double *d_out, void *stream) {
+  if (!h) return RN_ERR_INVALID_ARGUMENT;
+  if (S < 2 || !d_positions || !labels || !d_out || G < 1 || G > kMaxGroups) {
+    set_error(h, "invalid arguments to group_increments_device (S < 2, G outside 1..%d or a null pointer)", kMaxGroups);
+    return RN_ERR_INVALID_ARGUMENT;
+  }
+  return guarded(h, [&]() {
+    if (!set_group_labels(h, labels, G)) {
+      set_error(h, "group_increments_device: a label outside [0, G) or an empty group");
+      throw RnInvalid{};
+    }
+    const size_t limit = workspace_limit ? workspace_limit : kTapeBudget;
+    if (use_float64) {
+      sync_host(h);
+      group_increments<double>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream);
+    } else {
+      group_increments<float>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream);
+    }
+  });
+}
+
+int rn_potgnn_partial_raman_tensors(rn_potgnn *h, const double *ref_positions, const double *displacements, int64_t M,
+                                    const int32_t *labels, int G, double *raman) {
+  if (!h) return RN_ERR_INVALID_ARGUMENT;
+  if (M < 0 || !ref_positions || !labels || G < 1 || G > kMaxGroups || (M > 0 && (!displacements || !raman))) {
+    set_error(h, "invalid arguments to partial_raman_tensors (G outside 1..%d or a null pointer)", kMaxGroups);
+    return RN_ERR_INVALID_ARGUMENT;
+  }
+  return guarded(h, [&]() {
+    if (!set_group_labels(h, labels, G)) {
+      set_error(h, "partial_raman_tensors: a label outside [0, G) or an empty group");
+      throw RnInvalid{};
+    }
+    if (M == 0) return;
+    sync_host(h);  // (device-resident training may have moved the weights ahead of the float64 copy)
+    ensure_precision<double>(h);
+    h->train_S = 0;  // the tape and lane 0 are reused: a pending train_forward is void
+    const int N = h->g.N;
+    const size_t n3 = (size_t)N * 3;
+    hipStream_t st = h->f64.lanes[0].stream;
+    HIP_TRY(hipStreamSynchronize(st));  // (io_pos and the staging below are filled from the null stream)
+    h->io_pos.ensure(n3 * sizeof(double));
+    h->grp_disp.ensure((size_t)M * n3 * sizeof(double));
+    h->grp_out.ensure((size_t)M * G * 9 * sizeof(double));
+    h->grp_jac.ensure(6 * n3 * sizeof(double));
+    HIP_TRY(hipMemcpy(h->io_pos.p, ref_positions, n3 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->grp_disp.p, displacements, (size_t)M * n3 * sizeof(double), hipMemcpyHostToDevice));
+    jacobian_rows<double>(h, h->io_pos.as<double>(), 1, h->grp_jac.as<double>());
+    // R[m][g] = 2 sigma (.) sum_{i in g} J_i . d_{m,i}: the kernel's 1/2 (J + J) . (2 d)
+    const int *perm = h->grp_csr.as<int>();
+    launch_group_increments(h->grp_jac.as<double>(), 0, nullptr, h->grp_disp.as<double>(), 2.0, M, N, perm, perm + N, G,
+                            h->d_mean_std.as<double>() + 9, h->grp_out.as<double>(), st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    check_ps_fail(h);
+    HIP_TRY(hipMemcpy(raman, h->grp_out.p, (size_t)M * G * 9 * sizeof(double), hipMemcpyDeviceToHost));
   });
 }
 

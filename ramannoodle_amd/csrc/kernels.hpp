@@ -278,6 +278,14 @@ void launch_geom_input_bwd(const T *dedge0, const T *dunit, const T *unit4, cons
                            double *dpos, double *dlat, hipStream_t st);
 template <typename T>
 void launch_cast_from_f64(const double *src, T *dst, int64_t n, hipStream_t st);
+// Atom-group contraction (kernels_group.hip: group_increment_kernel): for steps t < `steps` and groups g < G,
+// out[t][g][9] = sigma (.) sum_{i in g} 1/2 (J(t)_i + J(t+1)_i) . dx_{t,i}, J float64 [.][6][N][3] frames `jac_stride`
+// doubles apart (0: one Jacobian for every t); dx = the minimum image of pos[t+1] - pos[t] (pos float64 [steps+1][N][3])
+// or, with `disp` float64 [steps][N][3], disp_scale * disp[t].  perm [N] / gptr [G+1]: the atoms of group g are
+// perm[gptr[g] .. gptr[g+1]).  Written once per entry, no atomics.
+void launch_group_increments(const double *jac, int64_t jac_stride, const double *pos, const double *disp,
+                             double disp_scale, int64_t steps, int N, const int *perm, const int *gptr, int G,
+                             const double *sigma, double *out, hipStream_t st);
 
 // Fused EdgeBlock (kernels_fused.hip): projections + triplet aggregation in one launch.
 // Fused EdgeBlock (kernels_fused.hip): float32, FnP == FeP == 64.  Two workgroups per CU

@@ -935,6 +935,76 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         _lib.check(rc, handle, "rn_potgnn_alpha_jacobian")
         return out
 
+    # ------------------------------------------------------------------ atom-group decomposition
+    def _group_labels(self, groups):
+        from ramannoodle_amd.spectrum import group_labels
+        return group_labels(groups, self._ref_structure.atomic_numbers)
+
+    def calc_group_increments_device(self, positions: torch.Tensor, groups, float64: bool = True,
+                                     out: torch.Tensor | None = None, workspace_limit: int = 0) -> torch.Tensor:
+        """Per-group trapezoid increments of the polarizability along a trajectory
+        (``rn_potgnn_group_increments_device``): a contiguous float64 CUDA tensor ``(S,N,3)`` of fractional, wrapped
+        positions in, a float64 CUDA tensor ``(S-1,G,3,3)`` out,
+        ``out[t,g] = 1/2 sum_{i in g} (J_i(x_t) + J_i(x_{t+1})) . dx_{t,i}`` with ``J_i = d alpha / d x_i`` (evaluation
+        mode, ``float64`` or float32 arithmetic) and ``dx`` the minimum image of ``x_{t+1} - x_t``.  ``sum_g out[t]`` is
+        ``alpha(x_{t+1}) - alpha(x_t)`` up to the trapezoid error.  ``groups``: ``spectrum.group_labels``.  Ordered on
+        torch's current stream.  ``out``, when given, must be a contiguous float64 ``(S-1,G,3,3)`` tensor on the
+        positions' device."""
+        if not (isinstance(positions, torch.Tensor) and positions.is_cuda and positions.dtype == torch.float64
+                and positions.is_contiguous()):
+            raise ValueError("positions must be a contiguous float64 device tensor")
+        if positions.dim() != 3 or tuple(positions.shape[1:]) != (self.num_atoms, 3):
+            raise ValueError(f"positions has wrong shape: {tuple(positions.shape)} != (_,{self.num_atoms},3)")
+        s = positions.shape[0]
+        if s < 2:
+            raise ValueError(f"group increments need at least two frames, not {s}")
+        labels, num_groups = self._group_labels(groups)
+        shape = (s - 1, num_groups, 3, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=positions.device)
+        else:
+            if not isinstance(out, torch.Tensor):
+                raise ValueError(f"out must be a torch.Tensor, not {type(out).__name__}")
+            if not out.is_cuda or out.device.index != positions.device.index:
+                raise ValueError(f"out lives on {out.device}, the increments are written on {positions.device}")
+            if out.dtype != torch.float64:
+                raise ValueError(f"out must be float64, not {out.dtype}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out has shape {tuple(out.shape)}, the increments are {shape}")
+            if not out.is_contiguous():
+                raise ValueError("out must be contiguous")
+        self.eval()
+        handle = self._ensure_handle()
+        stream = torch.cuda.current_stream(positions.device).cuda_stream
+        rc = _lib.load().rn_potgnn_group_increments_device(
+            handle, C.c_void_p(positions.data_ptr()), s, _ptr(labels), num_groups, int(float64), int(workspace_limit),
+            C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, handle, "rn_potgnn_group_increments_device")
+        return out
+
+    def calc_group_increments(self, positions_ts, groups, float64: bool = True) -> NDArray[np.float64]:
+        """``calc_group_increments_device`` for host arrays: fractional positions ``(S,N,3)`` in, float64
+        ``(S-1,G,3,3)`` out."""
+        verify_ndarray_shape("positions_ts", positions_ts, (None, self.num_atoms, 3))
+        positions = torch.tensor(np.asarray(positions_ts, dtype=np.float64), device=f"cuda:{self.device_index}")
+        return self.calc_group_increments_device(positions, groups, float64=float64).cpu().numpy()
+
+    def calc_partial_raman_tensors(self, ref_positions, displacements, groups) -> NDArray[np.float64]:
+        """Raman tensors split by atom group, ``(M,G,3,3)``: ``R[m,g] = 2 sum_{i in g} J_i(ref) . d_{m,i}``
+        (``rn_potgnn_partial_raman_tensors``: one float64 Jacobian, then the device contraction), so that
+        ``sum_g R[m,g]`` is ``calc_raman_tensors(method="analytic")``."""
+        self._check_raman_arguments(ref_positions, displacements, method="analytic")
+        labels, num_groups = self._group_labels(groups)
+        ref = np.ascontiguousarray(ref_positions, dtype=np.float64)
+        disp = np.ascontiguousarray(displacements, dtype=np.float64)
+        out = np.empty((disp.shape[0], num_groups, 3, 3), dtype=np.float64)
+        self.eval()
+        handle = self._ensure_handle()
+        rc = _lib.load().rn_potgnn_partial_raman_tensors(handle, _ptr(ref), _ptr(disp), disp.shape[0], _ptr(labels),
+                                                         num_groups, _ptr(out))
+        _lib.check(rc, handle, "rn_potgnn_partial_raman_tensors")
+        return out
+
     # ------------------------------------------------------------------ introspection
     @property
     def num_triplets(self) -> int:

@@ -479,3 +479,243 @@ class DeviceMDRamanSpectrum(MDRamanSpectrum):
             device = self._device_ts.device.index or 0
         return super().measure_polarized(incident, scattered, orientation, laser_correction, laser_wavelength,
                                          bose_einstein_correction, temperature, device=None if host else device)
+
+
+# ----------------------------------------------------------------------------- atom-group (partial) spectra
+MAX_GROUPS = 16
+
+
+def group_labels(groups, atomic_numbers) -> tuple[NDArray[np.int32], int]:
+    """Resolve ``groups`` for a structure with ``atomic_numbers`` ``(N,)`` into ``(labels int32[N], G)``.
+
+    ``groups`` is an integer array ``(N,)`` of labels in ``[0, G)``, every label used, ``1 <= G <= 16``; or
+    ``"species"``: one group per distinct atomic number, in ascending atomic number.  Anything else (a wrong length, a
+    negative or non-integer label, an empty group, ``G > 16``, another string) is a ``ValueError``.  Every partial
+    spectrum path resolves its groups here."""
+    numbers = np.asarray(atomic_numbers)
+    n = numbers.shape[0]
+    if isinstance(groups, str):
+        if groups != "species":
+            raise ValueError(f"unknown groups: {groups!r} (an integer array (N,) or 'species')")
+        species, labels = np.unique(numbers, return_inverse=True)
+        labels = labels.reshape(-1)
+        count = len(species)
+    else:
+        if groups is None or isinstance(groups, bytes):
+            raise ValueError("groups must be an integer array (N,) or 'species'")
+        labels = np.asarray(groups)
+        if labels.dtype.kind not in "iu":
+            raise ValueError(f"groups must hold integer labels, not {labels.dtype}")
+        if labels.shape != (n,):
+            raise ValueError(f"groups has wrong shape: {shape_string(labels.shape)} != ({n},)")
+        if n and labels.min() < 0:
+            raise ValueError("groups holds a negative label")
+        count = int(labels.max()) + 1 if n else 0
+        used = np.bincount(labels.astype(np.int64), minlength=count)
+        if count and np.any(used == 0):
+            raise ValueError(f"groups leaves group(s) {np.flatnonzero(used == 0).tolist()} empty")
+    if count < 1:
+        raise ValueError("groups defines no group")
+    if count > MAX_GROUPS:
+        raise ValueError(f"groups defines {count} groups, more than {MAX_GROUPS}")
+    return np.ascontiguousarray(labels, dtype=np.int32), count
+
+
+def _weight_forms(weights: NDArray[np.float64]) -> NDArray[np.float64]:
+    """``W[K][21]`` -> the symmetric 6x6 forms ``M[K]`` (off-diagonal entries halved back)."""
+    forms = np.zeros((weights.shape[0], 6, 6))
+    forms[:, _PAIR_J, _PAIR_L] = weights / _PAIR_SCALE
+    forms[:, _PAIR_L, _PAIR_J] = weights / _PAIR_SCALE
+    return forms
+
+
+def _measure_weights() -> NDArray[np.float64]:
+    """The weights of ``measure()`` (``45 a^2 + 7 gamma^2``): 45 (parallel + perpendicular) of the powder average."""
+    weights, _ = polarized_weights([1.0, 0.0, 0.0], [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]], "polycrystalline")
+    return 45.0 * weights.sum(axis=0, keepdims=True)
+
+
+def _unpack_pairs(packed: NDArray[np.float64], num_groups: int) -> NDArray[np.float64]:
+    """``[K][G(G+1)/2][bins]`` (pairs g <= h, row-major) -> the symmetric ``[K,G,G,bins]``."""
+    rows, cols = np.triu_indices(num_groups)
+    out = np.empty((packed.shape[0], num_groups, num_groups, packed.shape[-1]))
+    out[:, rows, cols] = packed
+    out[:, cols, rows] = packed
+    return out
+
+
+def _md_partial_host(increments: NDArray[np.float64], timestep: float, weights: NDArray[np.float64]):
+    """(wavenumbers, ``I[K,G,G,bins]``) on the host: for each pair of groups, calc_signal_spectrum's transform of the
+    symmetrised cross-correlation of their component series, contracted with each configuration's form, zero bin
+    dropped (``include/rn_potgnn.h``, ``rn_md_raman_partial``)."""
+    d = _symmetric_components(np.asarray(increments, dtype=np.float64))  # (N, G, 6)
+    n, num_groups = d.shape[:2]
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    keep = np.flatnonzero(wavenumbers >= 0)[1:]
+    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    spectra = np.fft.rfft(d, n=length, axis=0)  # (length / 2 + 1, G, 6)
+    forms = _weight_forms(weights)
+    out = np.empty((weights.shape[0], num_groups, num_groups, len(keep)))
+    for g in range(num_groups):
+        for h in range(g, num_groups):
+            cross = np.real(spectra[:, g, :, None] * np.conj(spectra[:, h, None, :]))
+            power = np.einsum("kce,fce->kf", forms, cross)
+            lags = np.fft.irfft(power, n=length, axis=-1)[:, :n]
+            out[:, g, h] = out[:, h, g] = np.real(scipy.fftpack.fft(lags, axis=-1))[:, keep]
+    return wavenumbers[keep], out
+
+
+def _md_partial_on_device(increments, timestep: float, weights, device: int, stream=None, workspace_limit: int = 0):
+    """(wavenumbers, uncorrected ``I[K,G,G,bins]``) from ``rn_md_raman_partial`` (host increments) or, with a torch CUDA
+    tensor, ``rn_md_raman_partial_device`` ordered after ``stream``."""
+    import ctypes as C
+
+    from ramannoodle_amd import _lib
+    n, num_groups = increments.shape[0], increments.shape[1]
+    if n < 2:
+        raise ValueError("the device reduction needs at least two increments")
+    bins = (n + 1) // 2 - 1
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    packed = np.empty((weights.shape[0], num_groups * (num_groups + 1) // 2, bins), dtype=np.float64)
+    lib = _lib.load()
+    if stream is None:
+        increments = np.ascontiguousarray(increments, dtype=np.float64)
+        rc = lib.rn_md_raman_partial(C.c_void_p(increments.ctypes.data), n, num_groups, C.c_void_p(weights.ctypes.data),
+                                     weights.shape[0], device, workspace_limit, C.c_void_p(packed.ctypes.data), bins)
+        _lib.check(rc, None, "rn_md_raman_partial")
+    else:
+        rc = lib.rn_md_raman_partial_device(C.c_void_p(increments.data_ptr()), n, num_groups,
+                                            C.c_void_p(weights.ctypes.data), weights.shape[0], device, workspace_limit,
+                                            C.c_void_p(packed.ctypes.data), bins, C.c_void_p(stream))
+        _lib.check(rc, None, "rn_md_raman_partial_device")
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    return wavenumbers[1:bins + 1], _unpack_pairs(packed, num_groups)
+
+
+class _PartialSpectrum:
+    """``measure`` / ``measure_polarized`` of the partial spectra: ``_partial(weights, device)`` returns the uncorrected
+    ``(wavenumbers, I[K,G,G,bins])``; the corrections apply to every ``(g, h)`` row."""
+
+    def _partial(self, weights, device):
+        raise NotImplementedError
+
+    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
+                bose_einstein_correction=False, temperature=300, device=None):
+        """``(wavenumbers, I[G,G,bins])``: ``I[g,h]`` is the symmetric bilinear form of ``measure()``'s
+        ``45 a^2 + 7 gamma^2`` between groups g and h, so ``I.sum((0, 1))`` is the whole spectrum and ``I[g,g]`` the
+        spectrum of group g alone."""
+        _require_polycrystalline(orientation)
+        wavenumbers, intensities = self._partial(_measure_weights(), device)
+        intensities = _apply_corrections(wavenumbers, intensities[0], laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities
+
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False, laser_wavelength=522,
+                          bose_einstein_correction=False, temperature=300, device=None):
+        """``(wavenumbers, I[K,G,G,bins])`` for the configurations of ``polarized_weights``; ``[G,G,bins]`` when no
+        argument has a ``K`` axis, as ``measure_polarized`` squeezes."""
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        wavenumbers, intensities = self._partial(weights, device)
+        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities[0] if squeeze else intensities
+
+
+class PartialPhononRamanSpectrum(_PartialSpectrum):
+    """Atom-group decomposition of a phonon spectrum: wavenumbers ``(M,)`` and partial Raman tensors ``(M,G,3,3)``
+    (``R[m,g] = 2 sum_{i in g} J_i . d_{m,i}``, ``PotGNN.calc_partial_raman_tensors``).  ``I[g,h](m)`` is the bilinear
+    form of the chosen intensity between ``R[m,g]`` and ``R[m,h]``: ``sum_{g,h}`` is the spectrum of ``sum_g R[m,g]``, and
+    ``I[g,g]`` that of group g's tensors alone (the reference's masking of the other atoms' displacements)."""
+
+    def __init__(self, phonon_wavenumbers, partial_raman_tensors) -> None:
+        verify_ndarray_shape("phonon_wavenumbers", phonon_wavenumbers, (None,))
+        verify_ndarray_shape("partial_raman_tensors", partial_raman_tensors, (len(phonon_wavenumbers), None, 3, 3))
+        self._phonon_wavenumbers = phonon_wavenumbers
+        self._partial_raman_tensors = partial_raman_tensors
+
+    @property
+    def phonon_wavenumbers(self):
+        return self._phonon_wavenumbers.copy()
+
+    @property
+    def partial_raman_tensors(self):
+        return self._partial_raman_tensors.copy()
+
+    def _partial(self, weights, device):
+        del device  # (at most 3N modes: always the host)
+        d = _symmetric_components(np.asarray(self._partial_raman_tensors, dtype=np.float64))  # (M, G, 6)
+        intensities = np.einsum("kce,mgc,mhe->kghm", _weight_forms(weights), d, d)
+        rows, cols = np.triu_indices(d.shape[1], 1)
+        intensities[:, cols, rows] = intensities[:, rows, cols]  # (exactly symmetric)
+        return self._phonon_wavenumbers, intensities
+
+
+class PartialMDRamanSpectrum(_PartialSpectrum):
+    """Atom-group decomposition of an MD spectrum: per-group polarizability increments ``(S-1,G,3,3)``
+    (``PotGNN.calc_group_increments``) and a timestep in fs.  ``I[g,h]`` is the transform of the symmetrised
+    cross-correlation of groups g and h, so ``I[g,g]`` is ``MDRamanSpectrum(cumsum of group g's increments).measure()`` and
+    ``sum_{g,h} I`` that of the summed increments.  ``device`` (an int) reduces on that GPU (``rn_md_raman_partial``)."""
+
+    def __init__(self, increments, timestep: float):
+        verify_ndarray_shape("increments", increments, (None, None, 3, 3))
+        self._increments = increments
+        self._timestep = timestep
+
+    @property
+    def increments(self):
+        return self._increments
+
+    @property
+    def timestep(self) -> float:
+        return self._timestep
+
+    def _partial(self, weights, device):
+        if device is not None:
+            return _md_partial_on_device(self.increments, self._timestep, weights, int(device))
+        return _md_partial_host(self.increments, self._timestep, weights)
+
+
+class DevicePartialMDRamanSpectrum(PartialMDRamanSpectrum):
+    """``PartialMDRamanSpectrum`` whose increments stay in HBM (a contiguous float64 CUDA tensor ``(S-1,G,3,3)``):
+    ``measure`` / ``measure_polarized`` reduce them on that GPU (``rn_md_raman_partial_device``, ordered after torch's
+    current stream) unless ``host=True``; ``increments`` copies them to the host on first use."""
+
+    def __init__(self, increments_device, timestep: float):  # pylint: disable=super-init-not-called
+        shape = tuple(increments_device.shape)
+        if len(shape) != 4 or shape[2:] != (3, 3):
+            raise ValueError(f"increments has wrong shape: {shape} != (_,_,3,3)")
+        if not (increments_device.is_cuda and increments_device.is_contiguous()
+                and str(increments_device.dtype) == "torch.float64"):
+            raise ValueError("increments must be a contiguous float64 CUDA tensor")
+        self._device_increments = increments_device
+        self._host_increments = None
+        self._timestep = timestep
+
+    @property
+    def increments(self):
+        if self._host_increments is None:
+            self._host_increments = self._device_increments.cpu().numpy()
+        return self._host_increments
+
+    def _partial(self, weights, device):
+        import torch
+        if device is None or device != (self._device_increments.device.index or 0):
+            return super()._partial(weights, device)
+        stream = torch.cuda.current_stream(self._device_increments.device).cuda_stream
+        return _md_partial_on_device(self._device_increments, self._timestep, weights, device, stream=stream)
+
+    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
+                bose_einstein_correction=False, temperature=300, device=None, host=False):
+        """As ``PartialMDRamanSpectrum.measure``; reduces on the tensor's GPU unless ``host=True``."""
+        if device is None and not host:
+            device = self._device_increments.device.index or 0
+        return super().measure(orientation, laser_correction, laser_wavelength, bose_einstein_correction, temperature,
+                               device=None if host else device)
+
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False, laser_wavelength=522,
+                          bose_einstein_correction=False, temperature=300, device=None, host=False):
+        """As ``PartialMDRamanSpectrum.measure_polarized``; reduces on the tensor's GPU unless ``host=True``."""
+        if device is None and not host:
+            device = self._device_increments.device.index or 0
+        return super().measure_polarized(incident, scattered, orientation, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature, device=None if host else device)
