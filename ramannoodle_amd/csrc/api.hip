@@ -1625,8 +1625,7 @@ void forward_vjp(rn_potgnn *h, const double *d_lat /* [S][9] or null */, const i
   check_ps_fail(h);
 }
 
-// ---- atom-group contractions (rn_potgnn_group_increments_device, rn_potgnn_partial_raman_tensors)
-constexpr int kMaxGroups = 16;
+// ---- atom-group contractions (rn_potgnn_group_increments_device, rn_potgnn_partial_raman_tensors); G <= kMaxGroups (kernels.hpp)
 
 // labels host int32[N] in [0, G), every group used: the atoms bucketed by group (ascending atom index within a group) as a
 // CSR permutation in h->grp_csr; rebuilt only when the labels change.  false on a label out of range or an empty group.

@@ -278,6 +278,9 @@ void launch_geom_input_bwd(const T *dedge0, const T *dunit, const T *unit4, cons
                            double *dpos, double *dlat, hipStream_t st);
 template <typename T>
 void launch_cast_from_f64(const double *src, T *dst, int64_t n, hipStream_t st);
+// The most atom groups a call may name (the group entries of api.hip and rn_md_raman_partial; MAX_GROUPS in spectrum.py).
+constexpr int kMaxGroups = 16;
+
 // Atom-group contraction (kernels_group.hip: group_increment_kernel): for steps t < `steps` and groups g < G,
 // out[t][g][9] = sigma (.) sum_{i in g} 1/2 (J(t)_i + J(t+1)_i) . dx_{t,i}, J float64 [.][6][N][3] frames `jac_stride`
 // doubles apart (0: one Jacobian for every t); dx = the minimum image of pos[t+1] - pos[t] (pos float64 [steps+1][N][3])

@@ -179,34 +179,49 @@ def _md_basis_spectra(polarizability_ts: NDArray[np.float64], timestep: float):
     return wavenumbers[keep], basis
 
 
+def _call_md_reducer(entry: str, source, n: int, too_short: str, timestep: float, device: int, stream,
+                     out_shape, args_before=(), args_after=()):
+    """What every device reduction shares.  ``source`` is a host array (entry ``entry``) or, with ``stream`` set, a
+    contiguous float64 CUDA tensor (entry ``entry + "_device"``, ordered after ``stream``); ``n`` is the number of
+    differences of the series.  The call is ``entry(source, *args_before, device, *args_after, out, bins[, stream])``
+    with ``out`` a new float64 array ``(*out_shape, bins)``.  Returns ``(wavenumbers, out)``."""
+    import ctypes as C
+
+    from ramannoodle_amd import _lib
+    if n < 2:
+        raise ValueError(too_short)
+    bins = (n + 1) // 2 - 1
+    out = np.empty((*out_shape, bins), dtype=np.float64)
+    if stream is None:
+        source = np.ascontiguousarray(source, dtype=np.float64)
+        pointer, tail = source.ctypes.data, ()
+    else:
+        entry += "_device"
+        pointer, tail = source.data_ptr(), (C.c_void_p(stream),)
+    rc = getattr(_lib.load(), entry)(C.c_void_p(pointer), *args_before, device, *args_after,
+                                     C.c_void_p(out.ctypes.data), bins, *tail)
+    _lib.check(rc, None, entry)
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    return wavenumbers[1:bins + 1], out
+
+
+def _weights_arguments(weights):
+    """``(contiguous float64 weights, their (pointer, K) arguments)``."""
+    import ctypes as C
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    return weights, (C.c_void_p(weights.ctypes.data), weights.shape[0])
+
+
+_TOO_FEW_STEPS = "the device reduction needs at least three time steps"
+
+
 def _md_polarized_on_device(alpha, timestep: float, weights, device: int, stream=None,
                             workspace_limit: int = 0):
     """(wavenumbers, uncorrected ``I[K][bins]``) from ``rn_md_raman_polarized`` (host alpha) or, with a
     torch CUDA tensor, ``rn_md_raman_polarized_device`` ordered after ``stream``."""
-    import ctypes as C
-
-    from ramannoodle_amd import _lib
-    n = alpha.shape[0] - 1
-    if n < 2:
-        raise ValueError("the device reduction needs at least three time steps")
-    bins = (n + 1) // 2 - 1
-    weights = np.ascontiguousarray(weights, dtype=np.float64)
-    intensities = np.empty((weights.shape[0], bins), dtype=np.float64)
-    lib = _lib.load()
-    if stream is None:
-        alpha = np.ascontiguousarray(alpha, dtype=np.float64)
-        rc = lib.rn_md_raman_polarized(C.c_void_p(alpha.ctypes.data), alpha.shape[0],
-                                       C.c_void_p(weights.ctypes.data), weights.shape[0], device, workspace_limit,
-                                       C.c_void_p(intensities.ctypes.data), bins)
-        _lib.check(rc, None, "rn_md_raman_polarized")
-    else:
-        rc = lib.rn_md_raman_polarized_device(C.c_void_p(alpha.data_ptr()), alpha.shape[0],
-                                              C.c_void_p(weights.ctypes.data), weights.shape[0], device,
-                                              workspace_limit, C.c_void_p(intensities.ctypes.data), bins,
-                                              C.c_void_p(stream))
-        _lib.check(rc, None, "rn_md_raman_polarized_device")
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    return wavenumbers[1:bins + 1], intensities
+    weights, weight_args = _weights_arguments(weights)
+    return _call_md_reducer("rn_md_raman_polarized", alpha, alpha.shape[0] - 1, _TOO_FEW_STEPS, timestep, device,
+                            stream, (weights.shape[0],), (alpha.shape[0], *weight_args), (workspace_limit,))
 
 
 def calc_signal_spectrum(signal: NDArray[np.float64],
@@ -246,45 +261,13 @@ def convolve_spectrum(wavenumbers, intensities, function: str = "gaussian", widt
     return out_wavenumbers, (kernel * np.asarray(intensities)[:, None]).sum(axis=0)
 
 
-def _md_intensities_on_device(polarizability_ts: NDArray[np.float64], timestep: float, device: int):
-    """(wavenumbers, uncorrected intensities) of ``MDRamanSpectrum.measure`` from the device path."""
-    import ctypes as C
-
-    from ramannoodle_amd import _lib
-    alpha = np.ascontiguousarray(polarizability_ts, dtype=np.float64)
-    n = alpha.shape[0] - 1
-    if n < 2:
-        raise ValueError("the device reduction needs at least three time steps")
-    bins = (n + 1) // 2 - 1
-    intensities = np.empty(bins, dtype=np.float64)
-    rc = _lib.load().rn_md_raman_intensities(C.c_void_p(alpha.ctypes.data), alpha.shape[0], device,
-                                             C.c_void_p(intensities.ctypes.data), bins)
-    _lib.check(rc, None, "rn_md_raman_intensities")
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    return wavenumbers[1:bins + 1], intensities
-
-
-def _md_intensities_device_resident(alpha_device, timestep: float):
-    """The same reduction for a time series that already lives in HBM (a torch CUDA tensor
-    ``float64[S,3,3]``): ``rn_md_raman_intensities_device`` -- only the intensities reach the host."""
-    import ctypes as C
-
-    import torch
-
-    from ramannoodle_amd import _lib
-    n = alpha_device.shape[0] - 1
-    if n < 2:
-        raise ValueError("the device reduction needs at least three time steps")
-    bins = (n + 1) // 2 - 1
-    intensities = np.empty(bins, dtype=np.float64)
-    device = alpha_device.device.index if alpha_device.device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(alpha_device.device).cuda_stream
-    rc = _lib.load().rn_md_raman_intensities_device(C.c_void_p(alpha_device.data_ptr()), alpha_device.shape[0],
-                                                    device, C.c_void_p(intensities.ctypes.data), bins,
-                                                    C.c_void_p(stream))
-    _lib.check(rc, None, "rn_md_raman_intensities_device")
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    return wavenumbers[1:bins + 1], intensities
+def _md_intensities_on_device(polarizability_ts, timestep: float, device: int, stream=None):
+    """(wavenumbers, uncorrected intensities) of ``MDRamanSpectrum.measure`` from ``rn_md_raman_intensities`` (a host
+    series) or, with a torch CUDA tensor ``float64[S,3,3]``, ``rn_md_raman_intensities_device`` ordered after ``stream``:
+    then only the intensities reach the host."""
+    steps = polarizability_ts.shape[0]
+    return _call_md_reducer("rn_md_raman_intensities", polarizability_ts, steps - 1, _TOO_FEW_STEPS, timestep, device,
+                            stream, (), (steps,))
 
 
 class PhononRamanSpectrum(RamanSpectrum):
@@ -423,66 +406,91 @@ class MDRamanSpectrum(RamanSpectrum):
         return wavenumbers, intensities[0] if squeeze else intensities
 
 
-class DeviceMDRamanSpectrum(MDRamanSpectrum):
+class _DeviceResident:
+    """Mixin for a spectrum whose input stays in HBM as a contiguous float64 CUDA tensor: ``measure`` /
+    ``measure_polarized`` reduce it on the tensor's GPU unless ``host=True``; another ``device`` gets the host copy,
+    which is made on first use."""
+
+    def _set_tensor(self, name: str, tensor, ndim: int, pattern: str) -> None:
+        shape = tuple(tensor.shape)
+        if len(shape) != ndim or shape[-2:] != (3, 3):
+            raise ValueError(f"{name} has wrong shape: {shape} != {pattern}")
+        if not (tensor.is_cuda and tensor.is_contiguous() and str(tensor.dtype) == "torch.float64"):
+            raise ValueError(f"{name} must be a contiguous float64 CUDA tensor")
+        self._tensor = tensor
+        self._host_copy = None
+
+    def _host(self):
+        if self._host_copy is None:
+            self._host_copy = self._tensor.cpu().numpy()
+        return self._host_copy
+
+    def _device_index(self) -> int:
+        return self._tensor.device.index or 0
+
+    def _source(self, device: int):
+        """``(source, stream)`` of a reduction on ``device``: the tensor and the current stream of its GPU, or the
+        host copy and ``None`` when ``device`` is another GPU."""
+        import torch
+        if device != self._device_index():
+            return self._host(), None
+        return self._tensor, torch.cuda.current_stream(self._tensor.device).cuda_stream
+
+    def _device_or_host(self, device, host: bool):
+        """The base classes' ``device=`` argument for this class's ``device=`` / ``host=``."""
+        if host:
+            return None
+        return self._device_index() if device is None else device
+
+    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
+                bose_einstein_correction=False, temperature=300, device=None, host=False):
+        """As the base class's ``measure``; reduces on the tensor's GPU unless ``host=True``."""
+        return super().measure(orientation, laser_correction, laser_wavelength, bose_einstein_correction,
+                               temperature, device=self._device_or_host(device, host))
+
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False,
+                          laser_wavelength=522, bose_einstein_correction=False, temperature=300, device=None,
+                          host=False):
+        """As the base class's ``measure_polarized``; reduces on the tensor's GPU unless ``host=True`` (the
+        ``_device`` entries: only the intensities leave HBM)."""
+        return super().measure_polarized(incident, scattered, orientation, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature,
+                                         device=self._device_or_host(device, host))
+
+
+class DeviceMDRamanSpectrum(_DeviceResident, MDRamanSpectrum):
     """``MDRamanSpectrum`` whose polarizability time series stays where the evaluator wrote it
     (HBM, a contiguous torch CUDA tensor ``float64[S,3,3]``): ``measure`` reduces it on that GPU
     and only the intensities travel to the host.  ``polarizability_ts``
     copies the series to the host on first use, for callers that want the numbers themselves."""
 
     def __init__(self, polarizability_ts_device, timestep: float):  # pylint: disable=super-init-not-called
-        shape = tuple(polarizability_ts_device.shape)
-        if len(shape) != 3 or shape[1:] != (3, 3):
-            raise ValueError(f"polarizability_ts has wrong shape: {shape} != (_,3,3)")
-        if not (polarizability_ts_device.is_cuda and polarizability_ts_device.is_contiguous()
-                and str(polarizability_ts_device.dtype) == "torch.float64"):
-            raise ValueError("polarizability_ts must be a contiguous float64 CUDA tensor")
-        self._device_ts = polarizability_ts_device
-        self._host_ts = None
+        self._set_tensor("polarizability_ts", polarizability_ts_device, 3, "(_,3,3)")
         self._timestep = timestep
 
     @property
+    def _device_ts(self):
+        return self._tensor
+
+    @property
     def polarizability_ts(self):
-        if self._host_ts is None:
-            self._host_ts = self._device_ts.cpu().numpy()
-        return self._host_ts
+        return self._host()
 
     @property
     def _polarizability_ts(self):  # what the host path of MDRamanSpectrum.measure reads
-        return self.polarizability_ts
+        return self._host()
 
     def _measure_on_device(self, device: int):
-        if device != (self._device_ts.device.index or 0):
-            return _md_intensities_on_device(self.polarizability_ts, self._timestep, device)
-        return _md_intensities_device_resident(self._device_ts, self._timestep)
-
-    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
-                bose_einstein_correction=False, temperature=300, device=None, host=False):
-        """As ``MDRamanSpectrum.measure``; reduces on the tensor's GPU unless ``host=True``."""
-        if device is None and not host:
-            device = self._device_ts.device.index or 0
-        return super().measure(orientation, laser_correction, laser_wavelength, bose_einstein_correction,
-                               temperature, device=None if host else device)
+        source, stream = self._source(device)
+        return _md_intensities_on_device(source, self._timestep, device, stream)
 
     def _polarized_on_device(self, weights, device: int):
-        import torch
-        if device != (self._device_ts.device.index or 0):
-            return _md_polarized_on_device(self.polarizability_ts, self._timestep, weights, device)
-        stream = torch.cuda.current_stream(self._device_ts.device).cuda_stream
-        return _md_polarized_on_device(self._device_ts, self._timestep, weights, device, stream=stream)
-
-    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False,
-                          laser_wavelength=522, bose_einstein_correction=False, temperature=300, device=None,
-                          host=False):
-        """As ``MDRamanSpectrum.measure_polarized``; reduces on the tensor's GPU unless ``host=True``
-        (``rn_md_raman_polarized_device``: only the intensities leave HBM)."""
-        if device is None and not host:
-            device = self._device_ts.device.index or 0
-        return super().measure_polarized(incident, scattered, orientation, laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature, device=None if host else device)
+        source, stream = self._source(device)
+        return _md_polarized_on_device(source, self._timestep, weights, device, stream=stream)
 
 
 # ----------------------------------------------------------------------------- atom-group (partial) spectra
-MAX_GROUPS = 16
+MAX_GROUPS = 16  # kMaxGroups of csrc/kernels.hpp
 
 
 def group_labels(groups, atomic_numbers) -> tuple[NDArray[np.int32], int]:
@@ -568,28 +576,12 @@ def _md_partial_host(increments: NDArray[np.float64], timestep: float, weights: 
 def _md_partial_on_device(increments, timestep: float, weights, device: int, stream=None, workspace_limit: int = 0):
     """(wavenumbers, uncorrected ``I[K,G,G,bins]``) from ``rn_md_raman_partial`` (host increments) or, with a torch CUDA
     tensor, ``rn_md_raman_partial_device`` ordered after ``stream``."""
-    import ctypes as C
-
-    from ramannoodle_amd import _lib
     n, num_groups = increments.shape[0], increments.shape[1]
-    if n < 2:
-        raise ValueError("the device reduction needs at least two increments")
-    bins = (n + 1) // 2 - 1
-    weights = np.ascontiguousarray(weights, dtype=np.float64)
-    packed = np.empty((weights.shape[0], num_groups * (num_groups + 1) // 2, bins), dtype=np.float64)
-    lib = _lib.load()
-    if stream is None:
-        increments = np.ascontiguousarray(increments, dtype=np.float64)
-        rc = lib.rn_md_raman_partial(C.c_void_p(increments.ctypes.data), n, num_groups, C.c_void_p(weights.ctypes.data),
-                                     weights.shape[0], device, workspace_limit, C.c_void_p(packed.ctypes.data), bins)
-        _lib.check(rc, None, "rn_md_raman_partial")
-    else:
-        rc = lib.rn_md_raman_partial_device(C.c_void_p(increments.data_ptr()), n, num_groups,
-                                            C.c_void_p(weights.ctypes.data), weights.shape[0], device, workspace_limit,
-                                            C.c_void_p(packed.ctypes.data), bins, C.c_void_p(stream))
-        _lib.check(rc, None, "rn_md_raman_partial_device")
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    return wavenumbers[1:bins + 1], _unpack_pairs(packed, num_groups)
+    weights, weight_args = _weights_arguments(weights)
+    wavenumbers, packed = _call_md_reducer(
+        "rn_md_raman_partial", increments, n, "the device reduction needs at least two increments", timestep, device,
+        stream, (weights.shape[0], num_groups * (num_groups + 1) // 2), (n, num_groups, *weight_args), (workspace_limit,))
+    return wavenumbers, _unpack_pairs(packed, num_groups)
 
 
 class _PartialSpectrum:
@@ -675,47 +667,21 @@ class PartialMDRamanSpectrum(_PartialSpectrum):
         return _md_partial_host(self.increments, self._timestep, weights)
 
 
-class DevicePartialMDRamanSpectrum(PartialMDRamanSpectrum):
+class DevicePartialMDRamanSpectrum(_DeviceResident, PartialMDRamanSpectrum):
     """``PartialMDRamanSpectrum`` whose increments stay in HBM (a contiguous float64 CUDA tensor ``(S-1,G,3,3)``):
     ``measure`` / ``measure_polarized`` reduce them on that GPU (``rn_md_raman_partial_device``, ordered after torch's
     current stream) unless ``host=True``; ``increments`` copies them to the host on first use."""
 
     def __init__(self, increments_device, timestep: float):  # pylint: disable=super-init-not-called
-        shape = tuple(increments_device.shape)
-        if len(shape) != 4 or shape[2:] != (3, 3):
-            raise ValueError(f"increments has wrong shape: {shape} != (_,_,3,3)")
-        if not (increments_device.is_cuda and increments_device.is_contiguous()
-                and str(increments_device.dtype) == "torch.float64"):
-            raise ValueError("increments must be a contiguous float64 CUDA tensor")
-        self._device_increments = increments_device
-        self._host_increments = None
+        self._set_tensor("increments", increments_device, 4, "(_,_,3,3)")
         self._timestep = timestep
 
     @property
     def increments(self):
-        if self._host_increments is None:
-            self._host_increments = self._device_increments.cpu().numpy()
-        return self._host_increments
+        return self._host()
 
     def _partial(self, weights, device):
-        import torch
-        if device is None or device != (self._device_increments.device.index or 0):
-            return super()._partial(weights, device)
-        stream = torch.cuda.current_stream(self._device_increments.device).cuda_stream
-        return _md_partial_on_device(self._device_increments, self._timestep, weights, device, stream=stream)
-
-    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
-                bose_einstein_correction=False, temperature=300, device=None, host=False):
-        """As ``PartialMDRamanSpectrum.measure``; reduces on the tensor's GPU unless ``host=True``."""
-        if device is None and not host:
-            device = self._device_increments.device.index or 0
-        return super().measure(orientation, laser_correction, laser_wavelength, bose_einstein_correction, temperature,
-                               device=None if host else device)
-
-    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False, laser_wavelength=522,
-                          bose_einstein_correction=False, temperature=300, device=None, host=False):
-        """As ``PartialMDRamanSpectrum.measure_polarized``; reduces on the tensor's GPU unless ``host=True``."""
-        if device is None and not host:
-            device = self._device_increments.device.index or 0
-        return super().measure_polarized(incident, scattered, orientation, laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature, device=None if host else device)
+        if device is None:
+            return super()._partial(weights, None)
+        source, stream = self._source(int(device))
+        return _md_partial_on_device(source, self._timestep, weights, int(device), stream=stream)
