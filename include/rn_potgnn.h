@@ -522,6 +522,23 @@ int rn_potgnn_config_flags(const rn_potgnn *h);
 int rn_potgnn_debug_ps_schedule(const int32_t *rb, const int32_t *re, int32_t num_destinations, int32_t back,
                                 int32_t ring_tiles, int32_t *window);
 
+/*
+ * Host-only (no device is touched, none is needed): the plan rn_potgnn_create would make for this graph on a device with
+ * num_cus compute units, under the RN_POTGNN_* knobs of the environment.  The arguments are validated as rn_potgnn_create
+ * validates them (same status codes and texts through rn_potgnn_last_error(NULL)).  The plan is written as int32 values:
+ *   FnP, FeP                                   padded widths
+ *   five partitions, in the order EdgeBlock (Graph::tile_begin), NodeBlock (nt_), twelve-wave EdgeBlock (et_, experiment
+ *   builds), reverse EdgeBlock (bt_), role-specialised EdgeBlock (pt_); each as
+ *     L, begin[0 .. L), max_out_rows, max_in_rows, max_nodes      (L = tiles + 1, or 0: no such partition)
+ *   nt_narrow, na_num, na_max_deg, pt_back, pt_gram, T
+ *   use_fused, use_edge2, use_edge3, use_ps, use_narrow, use_node_fused, use_readout_fused, num_lanes
+ *   out_ptr[N+1], in_ptr[N+1], in_edge[E], in_pos[E], rev_edge[E], trip_off[E+1]
+ * *count = the number of values; when out is NULL or capacity < *count nothing is written and the call returns
+ * RN_ERR_INVALID_ARGUMENT with *count set.
+ */
+int rn_potgnn_debug_plan(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
+                         const int32_t *atom_types, int32_t num_cus, int32_t *out, size_t capacity, size_t *count);
+
 /* Number of edge triplets T of the frozen graph. */
 int64_t rn_potgnn_num_triplets(const rn_potgnn *h);
 

@@ -1,5 +1,7 @@
 // Host orchestration + C ABI (include/rn_potgnn.h) for the gfx950 PotGNN evaluator.
 //
+// Planning -- validation of the create arguments, the CSRs, the atom tiles of every kernel family and the choice of the
+// family -- is host-only code in graph_plan.hip (rn_potgnn_debug_plan runs it without a device); this file uploads the plan.
 // A handle owns: the frozen graph (CSR both ways, node tiles, triplet offsets), the
 // weights re-laid-out for the kernels (transposed, [filter|core] halves padded to a
 // power-of-two width, concatenated Linear layers split into per-operand blocks), and
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "../../include/rn_potgnn.h"
+#include "graph_plan.hpp"
 #include "kernels.hpp"
 
 using namespace rn;
@@ -32,29 +35,6 @@ using namespace rn;
 namespace {
 
 std::string g_create_error;
-
-int pad_pow2(int f) {
-  int p = 16;
-  while (p < f) p *= 2;
-  return p;
-}
-
-// Which padded widths a model runs at.  Fe padded to 64 with a narrower Fn (e.g. Fn = 32 / Fe = 64, Fn = 20 / Fe = 48): padding
-// Fn to 64 as well puts the model on the fused MFMA kernels (their masked LayerNorms handle F < FP) instead of the unfused
-// per-stage chain (round 3: 15.4 -> 12.4 us per 128-atom structure).  Since round 5 the same holds for Fe in 17..32 (below).
-// RN_POTGNN_WIDEN=0: minimal power-of-two padding everywhere; =1: round 4's policy; =3: experiment.
-void widen_for_fused(rn::Dims &d) {
-  static const int widen = getenv("RN_POTGNN_WIDEN") ? atoi(getenv("RN_POTGNN_WIDEN")) : 2;
-  if (widen == 0) return;
-  if (d.FeP == 64 && d.FnP < 64) d.FnP = 64;
-  // round 5: with the role-specialised EdgeBlock at 3.2 us per structure and pass the 64-wide fused kernels (7.8 us per
-  // 128-atom structure whatever the real widths) are level with or ahead of the unfused chain for every Fe in 17..32 (7.5-7.9 us
-  // at Fn <= 32, 9.1 at Fn in 33..64: profiles/r05/width_sweep.txt), so those pad to 64 x 64 as well: one kernel family
-  // for every edge width in 17..64.  Fe <= 16 with a wide Fn stays unfused (6.0 us).  RN_POTGNN_WIDEN=1 keeps round 4's
-  // policy (only Fe in 33..64 widens Fn).
-  if (widen >= 2 && d.FeP == 32 && d.FnP >= 32 && d.FnP <= 64) d.FnP = d.FeP = 64;  // Fe in 17..32, Fn in 17..64 (Fn <= 16: 6.8 unfused against 7.7)
-  if (widen >= 3 && d.FeP <= 16 && d.FnP >= 32 && d.FnP <= 64) d.FnP = d.FeP = 64;  // (experiment) Fe <= 16 with Fn in 17..64
-}
 
 struct HipError {
   hipError_t code;
@@ -171,23 +151,14 @@ struct rn_potgnn {
   Dims d{};
   int chunk = 1;
   size_t f64_budget = 0;  // workspace bytes the float64 lanes may take (0: what the float32 lanes were given)
-  int num_lanes = 2;
   bool keep_stages = false;
   bool debug_sync = false;  // RN_POTGNN_DEBUG_SYNC=1: synchronise + check after every kernel
-  // graph
-  std::vector<int> edge_a, edge_b, out_ptr, in_ptr, in_edge, atom_type, tile_begin, trip_off, rev_edge, nt_begin, et_begin, bt_begin, pt_begin, in_pos;
-  bool use_fused = false;
-  bool use_edge2 = false;  // fused EdgeBlock in its frame-pipelined form (edge_block2_kernel + edge_c2_kernel)
+  GraphPlan plan;  // the graph's host arrays, its atom tiles, the kernel family and the lanes (graph_plan.hpp); `g` is its device image
   bool split_projections = true;  // RN_POTGNN_SPLIT_PROJ=0: the forward's stand-alone projections on the exact-f32 MFMA kernel
-  bool use_edge3 = false;  // fused EdgeBlock on twelve waves, one workgroup per CU (edge_block3_kernel + edge_c2_kernel)
-  bool use_ps = false;     // role-specialised fused EdgeBlock (kernels_edge_ps.hip) on its own atom tiles (Graph::pt_*)
-  bool use_node_fused = false;  // fused NodeBlock (only together with the fused EdgeBlock)
   bool want_pair_rows = true;   // RN_POTGNN_PAIR_ROWS at create time (ForwardRun::pair_rows decides per run)
   DeviceBuf step_seg, step_stage;  // segments / staging of the one download after a device-resident Adam step
   float *step_host = nullptr;      // its pinned host image
   bool tape_ps = true;          // RN_POTGNN_TAPE_PS: taped float32 runs on the role-specialised EdgeBlock / atom-owning NodeBlock
-  bool use_readout_fused = false;  // readout MLP in one launch (same condition)
-  bool use_narrow = false;  // narrow-width kernels (kernels_narrow.hip): Fn, Fe <= 16, one lane per row
   bool mfma_f16 = true;  // fused kernels: split-f16 MFMA products are in use (requested and inside the safe range)
   bool mfma_f16_requested = true;   // RN_POTGNN_MFMA=f32 at create time: exact-f32 MFMA everywhere
   bool mfma_range_fallback = false; // split-f16 was requested but the range guard (mfma_f16_range_ok) refused it
@@ -277,10 +248,6 @@ void set_error(rn_potgnn *h, const char *fmt, ...) {
 // Column of the padded [filter | core] layout for original output row r of a Linear /
 // LayerNorm of logical width 2F (first F rows = filter, last F = core; _gnn.py:143).
 inline int gated_col(int r, int F, int FP) { return r < F ? r : FP + (r - F); }
-
-// Largest out-degree the tiled kernels take: the rows of one atom's outgoing edges, 2 FeP float64
-// values (+ an index) each, have to fit a 150 KB LDS tile.  590 for FeP = 16, 149 for 64, 74 for 128.
-inline size_t max_out_degree(int FeP) { return (size_t)150 * 1024 / ((size_t)2 * FeP * sizeof(double) + 4); }
 
 // The weight blocks that enter a split-f16 matrix product and where their (s, 1/s) pair lives.
 struct MfmaScaleOp {
@@ -611,7 +578,7 @@ void reduce_over_ranks(rn_potgnn *h, double *dev, size_t n, hipStream_t st) {
 // the [S*E, 32] readout output (bufA) is left.  Taped runs (training, Jacobian) size the full-width buffers
 // for their own, much smaller, batch (ensure_tape).
 bool lean_workspace(const rn_potgnn *h) {
-  return (h->use_fused && h->use_node_fused && h->use_readout_fused) || h->use_narrow;
+  return (h->plan.use_fused && h->plan.use_node_fused && h->plan.use_readout_fused) || h->plan.use_narrow;
 }
 size_t bufA_width(const rn_potgnn *h, bool lean) {
   return lean ? 32 : std::max<size_t>(std::max(2 * h->d.FnP, 2 * h->d.FeP), 32);
@@ -620,7 +587,7 @@ size_t per_structure_elems(const rn_potgnn *h, bool lean) {
   const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges;
   const size_t FnP = h->d.FnP, FeP = h->d.FeP;
   return E * 4 + 2 * N * FnP + 2 * E * FeP + N * 2 * FnP + N * 6 * FeP + E * bufA_width(h, lean) +
-         (lean ? 0 : E * 4 * FeP) + ((h->use_edge2 || h->use_edge3) ? E * FeP : 0);
+         (lean ? 0 : E * 4 * FeP) + ((h->plan.use_edge2 || h->plan.use_edge3) ? E * FeP : 0);
 }
 
 // May the fused kernels run their matrix products as split-f16 MFMAs (device_utils.hpp)?
@@ -692,7 +659,7 @@ void refresh_pass_flags(rn_potgnn *h) {
     // bit 0: fused EdgeBlock kernel; bit 1: unfused edge_agg_kernel -- there only with a
     // single lane: its 170 registers per lane shut the other lane's projection workgroups
     // out of the CU (150 do not), which costs more than the shorter loop gains
-    P.pass[p].c3_fast = ok ? (h->num_lanes == 1 ? 3 : 1) : 0;
+    P.pass[p].c3_fast = ok ? (h->plan.num_lanes == 1 ? 3 : 1) : 0;
   }
 }
 
@@ -769,7 +736,7 @@ void ensure_precision(rn_potgnn *h) {
   const size_t FnP = h->d.FnP, FeP = h->d.FeP;
   const bool lean = sizeof(T) == 4 && lean_workspace(h);
   const size_t bufA = bufA_width(h, lean);
-  for (int l = 0; l < h->num_lanes; ++l) {
+  for (int l = 0; l < h->plan.num_lanes; ++l) {
     Lane<T> &ln = P.lanes[l];
     HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
@@ -782,7 +749,7 @@ void ensure_precision(rn_potgnn *h) {
     ln.np3.ensure(S * N * 6 * FeP * sizeof(T));
     ln.bufA.ensure(S * E * bufA * sizeof(T));
     if (!lean) ln.bufB.ensure(S * E * 4 * FeP * sizeof(T));
-    if (sizeof(T) == 4 && (h->use_edge2 || h->use_edge3)) ln.c2.ensure(S * E * FeP * sizeof(T));
+    if (sizeof(T) == 4 && (h->plan.use_edge2 || h->plan.use_edge3)) ln.c2.ensure(S * E * FeP * sizeof(T));
   }
   if (h->keep_stages) {
     const int np = h->cfg.num_message_passes + 1;
@@ -960,7 +927,7 @@ struct ChunkRun {
     }
     bool node_fused = false;
     if constexpr (sizeof(T) == 4) {
-      if (fused() && h->use_node_fused) {  // c1 edge projection + aggregation in one launch
+      if (fused() && h->plan.use_node_fused) {  // c1 edge projection + aggregation in one launch
         Timer t(h, st(), K_NODE_AGG);
         if (node_centred() && g.na_num > 0) launch_node_atom(edge[cur], node[cur], npc1, node[nxt], S, g, d, w, st(), pair_rows());
         else launch_node_fused(edge[cur], node[cur], npc1, node[nxt], S, g, d, w, h->mfma_f16, node_centred(), st());
@@ -984,7 +951,7 @@ struct ChunkRun {
     }
     if constexpr (sizeof(T) == 4) {
 #if RN_EXPERIMENTS
-      if (fused() && (h->use_edge2 || (h->use_edge3 && edge3_applicable(w, h->mfma_f16)))) {  // c2 branch of the EdgeBlock, one finished row per edge
+      if (fused() && (h->plan.use_edge2 || (h->plan.use_edge3 && edge3_applicable(w, h->mfma_f16)))) {  // c2 branch of the EdgeBlock, one finished row per edge
         Timer t(h, st(), K_PROJ_C2);
         launch_edge_c2(node[nxt], c2, S, g, d, w, h->mfma_f16, st());
       }
@@ -1011,9 +978,9 @@ struct ChunkRun {
       if constexpr (sizeof(T) == 4) {
         if (narrow()) launch_edge_narrow(edge[cur], edge[nxt], node[nxt], S, h->g, h->d, w, st());
 #if RN_EXPERIMENTS
-        else if (fused() && h->use_edge3 && edge3_applicable(w, h->mfma_f16))
+        else if (fused() && h->plan.use_edge3 && edge3_applicable(w, h->mfma_f16))
           launch_edge3(edge[cur], edge[nxt], np3, c2, tape_agg(p), S, h->g, h->d, w, st());
-        else if (fused() && h->use_edge2)
+        else if (fused() && h->plan.use_edge2)
           launch_edge2(edge[cur], edge[nxt], np3, c2, tape_agg(p), S, h->g, h->d, w, h->mfma_f16, st());
 #endif
         else if (role_split(w)) launch_edge_ps(edge[cur], edge[nxt], node[nxt], np3, tape_agg(p), S, h->g, h->d, w, h->ps_fail.as<int>(), st(), pair_rows(), h->mfma_f16);
@@ -1086,7 +1053,7 @@ struct ChunkRun {
       const int HP = std::max(d.FeP, 32);
       bool done = false;
       if constexpr (sizeof(T) == 4) {
-        if (fused() && h->use_readout_fused) {  // the three layers in one launch; whole 64-byte rows of the 16 columns it writes
+        if (fused() && h->plan.use_readout_fused) {  // the three layers in one launch; whole 64-byte rows of the 16 columns it writes
           pol_stride = h->keep_stages ? 32 : 16;  // (the stage snapshots read the unfused chain's 32-column layout)
           launch_readout_fused(edge[cur], ME, P.ro, bufA, h->mfma_f16, st(), pair_rows(), pol_stride);
           done = true;
@@ -1109,12 +1076,12 @@ struct ChunkRun {
   }
   // (the fused kernels also serve taped float32 runs: the EdgeBlock kernel records the one extra
   //  array the reverse pass needs; RN_POTGNN_TAPE_FUSED=0 keeps those runs on the unfused kernels)
-  bool fused() const { return sizeof(T) == 4 && h->use_fused && (!prec<T>(h).tape_on || h->tape_fused); }
-  bool narrow() const { return sizeof(T) == 4 && h->use_narrow && !prec<T>(h).tape_on; }
+  bool fused() const { return sizeof(T) == 4 && h->plan.use_fused && (!prec<T>(h).tape_on || h->tape_fused); }
+  bool narrow() const { return sizeof(T) == 4 && h->plan.use_narrow && !prec<T>(h).tape_on; }
   // the fused NodeBlock on the centred copy of c1_linear (evaluation runs, split-f16 products)
   bool node_centred() const {
     static const bool on = !(getenv("RN_POTGNN_NODE_CENTRED") && atoi(getenv("RN_POTGNN_NODE_CENTRED")) == 0);
-    return sizeof(T) == 4 && on && fused() && h->use_node_fused && h->mfma_f16 && (!prec<T>(h).tape_on || h->tape_ps);
+    return sizeof(T) == 4 && on && fused() && h->plan.use_node_fused && h->mfma_f16 && (!prec<T>(h).tape_on || h->tape_ps);
   }
   // the role-specialised EdgeBlock (kernels_edge_ps.hip): split-f16 products and the folded gate scale only.  Taped runs
   // take it too (round 4: it records the pre-LayerNorm sums like the per-frame kernel, and the reverse pass recomputes
@@ -1122,13 +1089,13 @@ struct ChunkRun {
   // them on the per-frame kernel and the row-ordered NodeBlock
   bool role_split(const PassW<T> &w) const {
     // (round 5: also with exact-f32 products -- RN_POTGNN_MFMA=f32, the range guard's fallback -- on the kernel's F16 = false form)
-    return sizeof(T) == 4 && fused() && h->use_ps && (w.c3_fast & 1) != 0 && (!prec<T>(h).tape_on || h->tape_ps);
+    return sizeof(T) == 4 && fused() && h->plan.use_ps && (w.c3_fast & 1) != 0 && (!prec<T>(h).tape_on || h->tape_ps);
   }
   // Edge rows as split-f16 pairs (kernels.hpp: launch_geom_rbf_pairs): when EVERY kernel that touches them in this run is one
   // that speaks the format -- the role-specialised EdgeBlock in every pass, the atom-owning NodeBlock, the fused readout --
   // and nothing else looks at them (no tape, no stage snapshots).  RN_POTGNN_PAIR_ROWS=0 keeps plain float32 rows.
   bool pair_rows() const {
-    if (sizeof(T) != 4 || !h->want_pair_rows || h->keep_stages || prec<T>(h).tape_on || !node_centred() || h->g.na_num <= 0 || !h->use_readout_fused) return false;
+    if (sizeof(T) != 4 || !h->want_pair_rows || h->keep_stages || prec<T>(h).tape_on || !node_centred() || h->g.na_num <= 0 || !h->plan.use_readout_fused) return false;
     for (const auto &w : prec<T>(h).pass)
       if (!role_split(w)) return false;
     return true;
@@ -1186,7 +1153,7 @@ void run_pair(rn_potgnn *h, ChunkRun<T> &a, ChunkRun<T> &b) {
 // the call it happened in (or the first synchronising call behind it), never by an unrelated later one.  Entry points that do
 // not synchronise (device buffers with synchronize = 0) hand back NaN rows in that case.
 void check_ps_fail(rn_potgnn *h) {
-  if (!h->use_ps || !h->ps_fail.p) return;
+  if (!h->plan.use_ps || !h->ps_fail.p) return;
   int fail = 0;
   HIP_TRY(hipMemcpy(&fail, h->ps_fail.p, sizeof(int), hipMemcpyDeviceToHost));
 #ifdef RN_PS_TIMING
@@ -1239,7 +1206,7 @@ void forward_device(rn_potgnn *h, const double *d_pos, int64_t S, double *d_alph
   Precision<T> &P = prec<T>(h);
   const int N = h->cfg.num_atoms;
   HIP_TRY(hipEventRecord(h->ev_start, user));
-  const int lanes = h->num_lanes;
+  const int lanes = h->plan.num_lanes;
   for (int l = 0; l < lanes; ++l) HIP_TRY(hipStreamWaitEvent(P.lanes[l].stream, h->ev_start, 0));
   auto make = [&](int lane, int64_t first, int s) {
     ChunkRun<T> c(h, P.lanes[lane], d_pos ? d_pos + first * N * 3 : nullptr, s,
@@ -2151,68 +2118,77 @@ const char *rn_potgnn_last_error(const rn_potgnn *h) {
   return h ? h->error.c_str() : g_create_error.c_str();
 }
 
+// Packs the plan's int arrays into one device allocation (each padded to 16 bytes) and points a Graph at them.
+static Graph upload(const GraphPlan &plan, DeviceBuf &buf) {
+  std::vector<int> ints;
+  auto push = [&](const std::vector<int> &v) {
+    size_t o = ints.size();
+    ints.insert(ints.end(), v.begin(), v.end());
+    while (ints.size() % 4) ints.push_back(0);
+    return o;
+  };
+  const size_t o_a = push(plan.edge_a), o_b = push(plan.edge_b), o_op = push(plan.out_ptr),
+               o_ip = push(plan.in_ptr), o_ie = push(plan.in_edge), o_at = push(plan.atom_type),
+               o_tb = push(plan.tile.begin), o_to = push(plan.trip_off), o_rv = push(plan.rev_edge),
+               o_nt = push(plan.nt.begin), o_et = push(plan.et.begin), o_bt = push(plan.bt.begin), o_pt = push(plan.pt.begin), o_ipos = push(plan.in_pos);
+  buf.ensure(ints.size() * sizeof(int));
+  HIP_TRY(hipMemcpy(buf.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
+  const int *base = buf.as<int>();
+  Graph g = plan.scalars();
+  g.edge_a = base + o_a;
+  g.edge_b = base + o_b;
+  g.out_ptr = base + o_op;
+  g.in_ptr = base + o_ip;
+  g.in_edge = base + o_ie;
+  g.in_pos = base + o_ipos;
+  g.atom_type = base + o_at;
+  g.rev_edge = base + o_rv;
+  g.tile_begin = base + o_tb;
+  g.trip_off = base + o_to;
+  g.nt_begin = base + o_nt;
+  g.et_begin = base + o_et;
+  g.pt_begin = base + o_pt;
+  g.bt_begin = base + o_bt;
+  return g;
+}
+
+// Chunk size.  Throughput rises monotonically with the frames per launch
+// (profiles/r01_chunk_sweep.txt, profiles/r01/overlap_experiments.txt section 7) and the
+// Infinity Cache does not reward small chunks.  The fused kernels take a whole CU each, so a
+// second lane has nothing to overlap with: ONE lane with an 8 GiB workspace (of 288 GB HBM)
+// beats two lanes of 1.5 GiB (63.7 k vs 62.1 k structures/s at 4000 frames).  The unfused
+// pipeline keeps two alternating lanes of 1.5 GiB (GraphPlan::num_lanes).
+static void size_chunk(rn_potgnn *h) {
+  int chunk = h->cfg.max_chunk_structures;
+  if (const char *e = getenv("RN_POTGNN_CHUNK")) chunk = atoi(e);
+  if (chunk <= 0) {
+    const size_t per = per_structure_elems(h, lean_workspace(h)) * sizeof(float);
+    size_t budget = (h->plan.use_fused || h->plan.use_narrow) ? ((size_t)8192 << 20) : ((size_t)1536 << 20);
+    size_t free_b = 0, total_b = 0;  // on a shared GPU: at most 1/8 of what is free right now
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
+      budget = std::min(budget, std::max<size_t>(free_b / 8 / (size_t)h->plan.num_lanes, (size_t)64 << 20));
+    chunk = (int)std::max<size_t>(1, budget / std::max<size_t>(per, 1));
+    chunk = std::min(chunk, 4096);
+    // the float64 lanes (created on first use) get their own allowance against the same "an eighth of what is free"
+    // rule: up to 24 GiB of the full-width float64 layout (1270 frames at 256 atoms, Fn = Fe = 64), so that the phonon
+    // finite differences of config 4 -- 1536 cells -- still run in two launches (chunk_frames<double>)
+    h->f64_budget = (size_t)24 << 30;
+    if (free_b > 0) h->f64_budget = std::min(h->f64_budget, std::max<size_t>(free_b / 8 / (size_t)h->plan.num_lanes, (size_t)64 << 20));
+  }
+  h->chunk = chunk;
+}
+
 int rn_potgnn_create(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
                      const int32_t *atom_types, const double *lattice, const float *weights,
                      size_t num_weights, const double *mean, const double *stddev,
                      rn_potgnn **out) {
   if (!out) return RN_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (!cfg || !atom_types || !lattice || !weights || !mean || !stddev ||
-      (cfg->num_edges > 0 && (!edge_a || !edge_b))) {
-    set_error(nullptr, "null argument");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  const int N = cfg->num_atoms, E = cfg->num_edges;
-  if (N <= 0 || E < 0 || cfg->num_atom_types <= 0 || cfg->size_node_embedding <= 0 ||
-      cfg->size_edge_embedding <= 0 || cfg->num_message_passes <= 0) {
-    set_error(nullptr, "invalid configuration (non-positive size)");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (E == 0) {
-    set_error(nullptr, "reference graph has no edges: the per-structure mean over edges "
-                       "(_gnn.py:662-664) is undefined");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (cfg->size_node_embedding > 128 || cfg->size_edge_embedding > 128) {
-    set_error(nullptr, "embedding sizes above 128 are not supported (Fn=%d, Fe=%d)",
-              cfg->size_node_embedding, cfg->size_edge_embedding);
-    return RN_ERR_UNSUPPORTED;
-  }
-  if (num_weights != rn_potgnn_weight_count(cfg)) {
-    set_error(nullptr, "weights has %zu floats, expected %zu", num_weights,
-              rn_potgnn_weight_count(cfg));
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  for (int e = 0; e < E; ++e) {
-    if (edge_a[e] < 0 || edge_a[e] >= N || edge_b[e] < 0 || edge_b[e] >= N ||
-        edge_a[e] == edge_b[e]) {
-      set_error(nullptr, "edge %d = (%d,%d) is out of range or a self loop", e, edge_a[e],
-                edge_b[e]);
-      return RN_ERR_INVALID_ARGUMENT;
-    }
-    if (e > 0 && (edge_a[e] < edge_a[e - 1] ||
-                  (edge_a[e] == edge_a[e - 1] && edge_b[e] <= edge_b[e - 1]))) {
-      set_error(nullptr, "edges must be strictly sorted by (a, b); violated at edge %d", e);
-      return RN_ERR_INVALID_ARGUMENT;
-    }
-  }
-  for (int n = 0; n < N; ++n)
-    if (atom_types[n] < 0 || atom_types[n] >= cfg->num_atom_types) {
-      set_error(nullptr, "atom %d has type %d outside [0,%d)", n, atom_types[n],
-                cfg->num_atom_types);
-      return RN_ERR_INVALID_ARGUMENT;
-    }
-
-  {  // an atom's outgoing-edge rows (in float64) must fit one workgroup's LDS tile
-    const size_t cap = max_out_degree(pad_pow2(cfg->size_edge_embedding));
-    std::vector<int> deg(N, 0);
-    for (int e = 0; e < E; ++e) deg[edge_a[e]]++;
-    for (int n = 0; n < N; ++n)
-      if ((size_t)deg[n] > cap) {
-        set_error(nullptr, "atom %d has %d outgoing edges; more than %zu per atom is unsupported "
-                           "for size_edge_embedding=%d", n, deg[n], cap, cfg->size_edge_embedding);
-        return RN_ERR_UNSUPPORTED;
-      }
+  std::string invalid;
+  int rc = validate_create_args(cfg, edge_a, edge_b, atom_types, !lattice || !weights || !mean || !stddev, &num_weights, invalid);
+  if (rc != RN_OK) {
+    set_error(nullptr, "%s", invalid.c_str());
+    return rc;
   }
 
   int ndev = 0;
@@ -2221,542 +2197,79 @@ int rn_potgnn_create(const rn_potgnn_config *cfg, const int32_t *edge_a, const i
     set_error(nullptr, "no usable HIP device (count=%d, requested=%d)", ndev, cfg->device);
     return RN_ERR_NO_DEVICE;
   }
+  int cus = 256;
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+  }
 
   std::unique_ptr<rn_potgnn> h(new rn_potgnn());
   h->cfg = *cfg;
-  h->d = {cfg->size_node_embedding, cfg->size_edge_embedding, pad_pow2(cfg->size_node_embedding),
-          pad_pow2(cfg->size_edge_embedding)};
-  widen_for_fused(h->d);
   std::memcpy(h->lattice, lattice, sizeof(h->lattice));
   std::memcpy(h->mean, mean, sizeof(h->mean));
   std::memcpy(h->stdv, stddev, sizeof(h->stdv));
   h->keep_stages = getenv("RN_POTGNN_KEEP_STAGES") && atoi(getenv("RN_POTGNN_KEEP_STAGES")) != 0;
   h->debug_sync = getenv("RN_POTGNN_DEBUG_SYNC") && atoi(getenv("RN_POTGNN_DEBUG_SYNC")) != 0;
   if (const char *e = getenv("RN_POTGNN_INTERLEAVE")) h->interleave = atoi(e) != 0;
-  if (const char *e = getenv("RN_POTGNN_LANES")) h->num_lanes = std::max(1, std::min(2, atoi(e)));
   if (const char *e = getenv("RN_POTGNN_MFMA")) h->mfma_f16_requested = !(e[0] == 'f' && e[1] == '3');
   h->mfma_f16 = h->mfma_f16_requested;
   if (const char *e = getenv("RN_POTGNN_TAPE_FUSED")) h->tape_fused = atoi(e) != 0;
   if (const char *e = getenv("RN_POTGNN_TAPE_PS")) h->tape_ps = atoi(e) != 0;
+  h->split_projections = getenv("RN_POTGNN_SPLIT_PROJ") ? atoi(getenv("RN_POTGNN_SPLIT_PROJ")) != 0 : true;
+  h->want_pair_rows = !(getenv("RN_POTGNN_PAIR_ROWS") && atoi(getenv("RN_POTGNN_PAIR_ROWS")) == 0);
 
-  // ---- graph: CSR over a (edges are already grouped), CSR over b, tiles, triplet offsets
-  h->edge_a.assign(edge_a, edge_a + E);
-  h->edge_b.assign(edge_b, edge_b + E);
-  h->atom_type.assign(atom_types, atom_types + N);
-  h->out_ptr.assign(N + 1, 0);
-  h->in_ptr.assign(N + 1, 0);
-  for (int e = 0; e < E; ++e) {
-    h->out_ptr[edge_a[e] + 1]++;
-    h->in_ptr[edge_b[e] + 1]++;
-  }
-  for (int n = 0; n < N; ++n) {
-    h->out_ptr[n + 1] += h->out_ptr[n];
-    h->in_ptr[n + 1] += h->in_ptr[n];
-  }
-  h->in_edge.assign(E, 0);
-  {
-    std::vector<int> fill(h->in_ptr.begin(), h->in_ptr.end() - 1);
-    for (int e = 0; e < E; ++e) h->in_edge[fill[edge_b[e]]++] = e;  // ascending edge id per b
-  }
-  const Dims d = h->d;
-  // node tiles: consecutive atoms whose outgoing-edge rows fit an LDS budget (counted in
-  // float32 rows; the float64 path uses twice the bytes for the same tiles).  A workgroup
-  // serves its tile's destination edges G at a time (G lane groups), so the budget is chosen
-  // to waste as few lane groups in the last round as possible (18 in-edges per atom and
-  // G = 16: 4 atoms per tile idle 10 % of the groups, 6 atoms 4 %).
-  const size_t row_bytes = (size_t)2 * d.FeP * sizeof(float);  // (the out-degree cap was checked before the device probe)
-  auto build_tiles = [&](size_t budget_rows, std::vector<int> &tb) {
-    tb.assign(1, 0);
-    int rows = 0, max_rows = 0;
-    for (int n = 0; n < N; ++n) {
-      const int deg = h->out_ptr[n + 1] - h->out_ptr[n];
-      if (rows > 0 && (size_t)(rows + deg) > budget_rows) {
-        tb.push_back(n);
-        rows = 0;
-      }
-      rows += deg;
-      max_rows = std::max(max_rows, rows);
-    }
-    tb.push_back(N);
-    return max_rows;
-  };
-  const bool vpl8 = getenv("RN_POTGNN_VPL") && atoi(getenv("RN_POTGNN_VPL")) == 8;
-  // fused EdgeBlock (kernels_fused.hip): its LDS footprint bounds the tile instead
-  const bool want_fused = getenv("RN_POTGNN_FUSED") ? atoi(getenv("RN_POTGNN_FUSED")) != 0 : true;
-  const bool fused_mode = want_fused && d.FnP == 64 && d.FeP == 64;
-  // Experiment builds (-DRN_EXPERIMENTS=1) only -- RN_POTGNN_EDGE2=1: the frame-pipelined form of the fused EdgeBlock
-  // (edge_block2_kernel + edge_c2_kernel), measured level with the per-frame form (profiles/r03/edge2_experiment.txt).
-#if RN_EXPERIMENTS
-  const bool want_edge2 = getenv("RN_POTGNN_EDGE2") ? atoi(getenv("RN_POTGNN_EDGE2")) != 0 : false;
-#else
-  const bool want_edge2 = false;
-  (void)want_edge2;
-#endif
-  // narrow-width kernels (kernels_narrow.hip): one lane per destination edge, so a tile should bring
-  // about one workgroup's worth (256) of destination edges and keep its LDS rows within ~40 KiB
-  const bool want_narrow = getenv("RN_POTGNN_NARROW") ? atoi(getenv("RN_POTGNN_NARROW")) != 0 : true;
-  const bool narrow_mode = want_narrow && narrow_supported(d);
-  int max_rows = 0;
-  if (narrow_mode && !getenv("RN_POTGNN_TILE_KB")) {
-    const size_t per_row = edge_narrow_lds_bytes(d.Fn, d.Fe, 1024, 1024) / 1024 + 1;
-    // 128 rows = one two-wave workgroup per tile (kernels_narrow.hip launch_edge_cfg); an atom with more out-edges gets a
-    // tile of its own and the four-wave form
-    size_t budget = std::min<size_t>(128, (size_t)40 * 1024 / per_row);
-    if (const char *e = getenv("RN_POTGNN_NARROW_TILE_ROWS")) budget = (size_t)std::max(1, atoi(e));  // experiment knob
-    max_rows = build_tiles(std::max<size_t>(1, budget), h->tile_begin);
-    // The greedy partition fills every tile but the last (256 atoms of degree 18: eighteen tiles of 14 atoms and one
-    // of 4).  The same NUMBER of tiles with boundaries at equal shares of the edge list (14, 13, 14, 13, ...) costs
-    // the same lane slots and keeps the workgroups of a frame in step, as long as no tile exceeds the budget.
-    if (h->tile_begin.size() > 2) {
-      const int T = (int)h->tile_begin.size() - 1;
-      std::vector<int> tb(1, 0);
-      for (int t = 1; t < T; ++t) {
-        const int64_t want = ((int64_t)E * t + T - 1) / T;
-        int n = tb.back();
-        while (n < N && h->out_ptr[n] < want) ++n;
-        tb.push_back(std::max(n, tb.back()));
-      }
-      tb.push_back(N);
-      int worst_out = 0, worst_in = 0, greedy_in = 0;
-      bool ok = true;
-      for (int t = 0; t < T; ++t) {
-        ok = ok && tb[t + 1] > tb[t];
-        worst_out = std::max(worst_out, h->out_ptr[tb[t + 1]] - h->out_ptr[tb[t]]);
-        worst_in = std::max(worst_in, h->in_ptr[tb[t + 1]] - h->in_ptr[tb[t]]);
-        greedy_in = std::max(greedy_in, h->in_ptr[h->tile_begin[t + 1]] - h->in_ptr[h->tile_begin[t]]);
-      }
-      if (ok && (size_t)worst_out <= budget && worst_in <= std::max(greedy_in, (int)budget)) {
-        h->tile_begin = tb;
-        max_rows = worst_out;
-      }
-    }
-  } else if (getenv("RN_POTGNN_TILE_KB") || vpl8) {
-    const size_t tile_kb = getenv("RN_POTGNN_TILE_KB") ? (size_t)atoi(getenv("RN_POTGNN_TILE_KB")) : 64;
-    max_rows = build_tiles(std::max<size_t>(1, tile_kb * 1024 / row_bytes), h->tile_begin);
-  } else {
-    // relative cost of one frame = (rounds of the slowest tile) x (tiles sharing the chip),
-    // among budgets whose whole LDS footprint stays within 64 KiB (measured: beyond that
-    // only one workgroup per CU runs)
-    const int G = 256 / std::max(1, d.FeP / 4);
-    double best = 0;
-    std::vector<int> tb;
-    for (size_t kb = 8; kb <= 62; kb += 2) {
-      const int mr = build_tiles(std::max<size_t>(1, kb * 1024 / row_bytes), tb);
-      int rounds = 1, max_in = 0, max_nodes = 0;
-      for (size_t t = 0; t + 1 < tb.size(); ++t) {
-        const int din = h->in_ptr[tb[t + 1]] - h->in_ptr[tb[t]];
-        rounds = std::max(rounds, (din + G - 1) / G);
-        max_in = std::max(max_in, din);
-        max_nodes = std::max(max_nodes, tb[t + 1] - tb[t]);
-      }
-#if RN_EXPERIMENTS
-      const size_t fused_lds_need = want_edge2 ? edge2_lds_bytes(mr, max_in, max_nodes) : edge_fused_lds_bytes(mr, max_in, max_nodes);
-#else
-      const size_t fused_lds_need = edge_fused_lds_bytes(mr, max_in, max_nodes);
-#endif
-      const size_t lds = fused_mode ? fused_lds_need
-                                    : (size_t)mr * (row_bytes + 4) + (size_t)max_nodes * row_bytes +
-                                          (size_t)12 * d.FeP * 4 + (size_t)mr * 4 + (size_t)max_in * 24 + 96;
-      // unfused: two aggregation workgroups + one projection workgroup (34 KiB) share a CU
-      const size_t lds_cap = fused_mode ? kFusedLdsBudget : (size_t)63 * 1024;
-      if (lds > lds_cap && !h->tile_begin.empty()) break;
-      const double cost = (double)rounds * (double)(tb.size() - 1);
-      if (h->tile_begin.empty() || cost < best * 0.995) {
-        best = cost;
-        h->tile_begin = tb;
-        max_rows = mr;
-      }
-    }
-  }
-  // node tiles of the twelve-wave EdgeBlock (edge_block3_kernel): one 768-thread workgroup per CU with the CU's LDS,
-  // 48 destinations per round -> as few rounds as possible in total; among equals the larger tiles (fewer per-tile phases)
-  int et_max_rows = 0, et_max_in = 0, et_max_nodes = 0;
-#if RN_EXPERIMENTS
-  const bool want_edge3 = getenv("RN_POTGNN_EDGE3") ? atoi(getenv("RN_POTGNN_EDGE3")) != 0 : false;
-  if (fused_mode && want_edge3) {
-    double best = 0;
-    std::vector<int> tb;
-    const int forced = getenv("RN_POTGNN_EDGE3_TILE_ROWS") ? atoi(getenv("RN_POTGNN_EDGE3_TILE_ROWS")) : 0;  // experiment knob
-    for (size_t budget = forced > 0 ? forced : 16; budget <= (size_t)(forced > 0 ? forced : 300); budget += 2) {
-      const int mr = build_tiles(budget, tb);
-      int max_in = 0, max_nodes = 0;
-      double cost = 0;
-      for (size_t t = 0; t + 1 < tb.size(); ++t) {
-        const int din = h->in_ptr[tb[t + 1]] - h->in_ptr[tb[t]];
-        cost += (double)((din + edge3_dests_per_round() - 1) / edge3_dests_per_round());
-        max_in = std::max(max_in, din);
-        max_nodes = std::max(max_nodes, tb[t + 1] - tb[t]);
-      }
-      if (edge3_lds_bytes(mr, max_in, max_nodes) > kEdge3LdsBudget) {
-        if (!h->et_begin.empty()) break;
-        continue;
-      }
-      if (h->et_begin.empty() || cost <= best) {
-        best = cost;
-        h->et_begin = tb;
-        et_max_rows = mr;
-        et_max_in = max_in;
-        et_max_nodes = max_nodes;
-      }
-    }
-  }
-#else
-  const bool want_edge3 = false;
-#endif
-  // node tiles of the EdgeBlock reverse kernel: the largest whose float32 LDS footprint leaves room for two workgroups
-  // per CU (RN_POTGNN_BWD_TILES=0: the forward kernel's tiles, one 512-thread workgroup per CU)
-  int bt_max_rows = 0, bt_max_in = 0, bt_max_nodes = 0;
-  if (!(getenv("RN_POTGNN_BWD_TILES") && atoi(getenv("RN_POTGNN_BWD_TILES")) == 0)) {
-    std::vector<int> tb;
-    for (size_t budget = 1; budget <= 512; ++budget) {
-      const int mr = build_tiles(budget, tb);
-      int max_in = 0, max_nodes = 0;
-      for (size_t t = 0; t + 1 < tb.size(); ++t) {
-        max_in = std::max(max_in, h->in_ptr[tb[t + 1]] - h->in_ptr[tb[t]]);
-        max_nodes = std::max(max_nodes, tb[t + 1] - tb[t]);
-      }
-      if (edge_bwd_tile2_lds_bytes(mr, max_in, max_nodes, d.FeP, sizeof(float)) > (size_t)78 * 1024) {
-        if (!h->bt_begin.empty()) break;
-        continue;
-      }
-      if (h->bt_begin.empty() || mr > bt_max_rows) {
-        h->bt_begin = tb;
-        bt_max_rows = mr;
-        bt_max_in = max_in;
-        bt_max_nodes = max_nodes;
-      }
-    }
-  }
-  // node tiles of the fused NodeBlock kernel: consecutive atoms by IN-edges; four workgroups per CU
-  // (40 KiB of LDS each), as few rounds x tiles as possible
-  int nt_max_in = 0, nt_max_nodes = 0;
-  bool nt_narrow = false;
-  if (narrow_mode) {
-    // node_tiled_kernel (kernels_narrow.hip): ONE WAVE per tile -- at most 64 atoms (one lane each in its last pass)
-    // whose in-edge rows are streamed 64 at a time: the partition that fills those chunks best, within 12 KiB of LDS
-    // (thirteen waves per CU and more); among equals the larger tiles (fewer frame starts per row)
-    double best = -1;
-    const int max_budget = getenv("RN_POTGNN_NODE_TILE_ROWS") ? std::max(1, atoi(getenv("RN_POTGNN_NODE_TILE_ROWS"))) : 256;
-    const int lds_kb = getenv("RN_POTGNN_NODE_TILE_KB") ? std::max(1, atoi(getenv("RN_POTGNN_NODE_TILE_KB"))) : 12;
-    for (int budget = 32; budget <= std::max(max_budget, 32); budget += 2) {
-      std::vector<int> tb(1, 0);
-      int rows_in = 0, max_in = 0, max_nodes = 0, first = 0;
-      double work = 0;  // chunk slots the partition pays for
-      auto close = [&](int n) {
-        max_nodes = std::max(max_nodes, n - first);
-        work += (double)std::max((rows_in + 63) / 64, 1) * 64.0;
-      };
-      for (int n = 0; n < N; ++n) {
-        const int deg = h->in_ptr[n + 1] - h->in_ptr[n];
-        if (n > first && (rows_in + deg > budget || n - first >= 64)) {
-          close(n);
-          tb.push_back(n);
-          first = n;
-          rows_in = 0;
-        }
-        rows_in += deg;
-        max_in = std::max(max_in, rows_in);
-      }
-      close(N);
-      tb.push_back(N);
-      // (a single atom with more in-edges than the budget still gets its tile: the LDS check below decides)
-      if (node_tiled_lds_bytes(d.Fn, d.Fe, max_in, max_nodes) > (size_t)(h->nt_begin.empty() ? 64 : lds_kb) * 1024) {
-        if (!h->nt_begin.empty()) break;
-        continue;
-      }
-      const double fill = (double)E / std::max(work, 1.0);
-      if (fill >= best * 0.999) {
-        best = std::max(best, fill);
-        h->nt_begin = tb;
-        nt_max_in = max_in;
-        nt_max_nodes = max_nodes;
-      }
-    }
-    nt_narrow = !h->nt_begin.empty();
-  }
-  if (!nt_narrow) {
-    double best = 0;
-#if RN_EXPERIMENTS
-    const bool node_wave = node_fused_wave_tiles() && d.FnP == 64 && d.FeP == 64;
-#else
-    const bool node_wave = false;
-#endif
-    const int forced = getenv("RN_POTGNN_NODE_TILE_ROWS") ? atoi(getenv("RN_POTGNN_NODE_TILE_ROWS")) : 0;  // experiment knob
-    for (int budget = forced > 0 ? forced : 16; budget <= (forced > 0 ? forced : 256); budget += 8) {
-      std::vector<int> tb(1, 0);
-      int rows_in = 0, max_in = 0, max_nodes = 0, first = 0;
-      for (int n = 0; n < N; ++n) {
-        const int deg = h->in_ptr[n + 1] - h->in_ptr[n];
-        if (n > first && rows_in + deg > budget) {
-          max_nodes = std::max(max_nodes, n - first);
-          tb.push_back(n);
-          first = n;
-          rows_in = 0;
-        }
-        rows_in += deg;
-        max_in = std::max(max_in, rows_in);
-      }
-      max_nodes = std::max(max_nodes, N - first);
-      tb.push_back(N);
-      double cost;
-      if (node_wave) {
-        // wave-autonomous kernel: a workgroup's four waves take the tile's 16-row pieces four at a time;
-        // two workgroups per CU (register-bound), so up to 72 KiB of LDS each
-#if RN_EXPERIMENTS
-        if (node_wave_lds_bytes(max_in, max_nodes) > (size_t)72 * 1024 && !h->nt_begin.empty()) break;
-#endif
-        cost = 0;
-        for (size_t t = 0; t + 1 < tb.size(); ++t) {
-          const int rows_t = h->in_ptr[tb[t + 1]] - h->in_ptr[tb[t]];
-          cost += (double)(((rows_t + 15) / 16 + 3) / 4);
-        }
-      } else {
-        if (node_fused_lds_bytes(max_in, max_nodes) > (size_t)40 * 1024 && !h->nt_begin.empty()) break;
-        cost = (double)((max_in + 15) / 16) * (double)(tb.size() - 1);
-      }
-      if (h->nt_begin.empty() || cost < best * 0.995) {
-        best = cost;
-        h->nt_begin = tb;
-        nt_max_in = max_in;
-        nt_max_nodes = max_nodes;
-      }
-    }
-  }
-  h->trip_off.assign(E + 1, 0);
-  for (int e = 0; e < E; ++e) {
-    const int bd = edge_b[e], ad = edge_a[e];
-    int cnt = 0;
-    for (int o = h->out_ptr[bd]; o < h->out_ptr[bd + 1]; ++o) cnt += edge_b[o] != ad;
-    h->trip_off[e + 1] = h->trip_off[e] + cnt;
-  }
-
-  h->in_pos.assign(E, 0);
-  for (int i = 0; i < E; ++i) h->in_pos[h->in_edge[i]] = i;  // position of edge e in the (b, a) order
-  h->rev_edge.assign(E, -1);
-  for (int e = 0; e < E; ++e) {  // reverse edge (b -> a): binary search in b's sorted out-list
-    const int bd = edge_b[e], ad = edge_a[e];
-    const int *lo = edge_b + h->out_ptr[bd], *hi = edge_b + h->out_ptr[bd + 1];
-    const int *it = std::lower_bound(lo, hi, ad);
-    if (it != hi && *it == ad) h->rev_edge[e] = (int)(it - edge_b);
-  }
+  const PlanKnobs knobs = read_plan_knobs();
+  h->d = plan_dims(*cfg, knobs);
+  h->plan = plan_graph(*cfg, h->d, edge_a, edge_b, atom_types, cus, knobs);
 
   rn_potgnn *hp = h.get();
-  int rc = guarded(nullptr, [&]() {
+  rc = guarded(nullptr, [&]() {
     HIP_TRY(hipSetDevice(cfg->device));
     HIP_TRY(hipEventCreateWithFlags(&hp->ev_start, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&hp->ev_g[0], hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&hp->ev_g[1], hipEventDisableTiming));
-    // node tiles of the role-specialised EdgeBlock (kernels_edge_ps.hip): ONE twelve-wave workgroup per CU, 16 destinations
-    // per round.  A launch runs floor(CUs / tiles) frame groups side by side, so the cost of a partition is (rounds of its
-    // slowest tile) / (frame groups); a partition is admissible when every tile passes the producers' schedule check and
-    // the kernel's LDS footprint fits the CU.
-    int pt_max_rows = 0, pt_max_in = 0, pt_back = 2, pt_gram = 0;
-    const bool want_ps = getenv("RN_POTGNN_EDGE_PS") ? atoi(getenv("RN_POTGNN_EDGE_PS")) != 0 : true;
-    if (fused_mode && want_ps) {
-      int cus = 256;
-      {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-      }
-      double best = 0;
-      std::vector<int> tb, rb, re;
-      const int forced = getenv("RN_POTGNN_PS_TILE_ROWS") ? atoi(getenv("RN_POTGNN_PS_TILE_ROWS")) : 0;  // experiment knob
-      const bool want_back3 = !(getenv("RN_POTGNN_PS_BACK") && atoi(getenv("RN_POTGNN_PS_BACK")) == 2);
-      // GRAM is opt-in (RN_POTGNN_PS_GRAM=1): parity-green, but the producers' Gram phase costs them more than the consumers' loop
-      // gains while the producers are the slower role with it (profiles/r05/edge_ps_experiments.txt: 7.38 against 7.01 ms per launch)
-      const bool want_gram = getenv("RN_POTGNN_PS_GRAM") && atoi(getenv("RN_POTGNN_PS_GRAM")) != 0;
-      // One variant of the kernel for a partition: {gram, back}.  GRAM (the LayerNorm cross terms on the matrix pipe) has a ring
-      // of 7 tiles and needs every round's window to span <= 3 of them, every destination <= 32 source rows, and its tables
-      // inside the CU's LDS; back = 3 (the producers three rounds ahead of the slower consumer set) needs the room in the ring.
-      // (back = 4: with eight destinations per consumer wave four rounds are in flight at a time -- the eight-lane form of
-      //  the kernel --, and a step that may only rewrite the ring behind round g - 4 would stall the producers)
-      struct Variant { bool gram; int back; double factor; };
-      const int max_back = getenv("RN_POTGNN_PS_BACK") ? atoi(getenv("RN_POTGNN_PS_BACK")) : 5;
-      const Variant variants[6] = {{true, 3, 0.88}, {true, 2, 0.94}, {false, 5, 0.94}, {false, 4, 0.96}, {false, 3, 1.0}, {false, 2, 1.07}};
-      for (size_t budget = forced > 0 ? forced : 8; budget <= (size_t)(forced > 0 ? forced : 1024); budget += 2) {
-        const int mr = build_tiles(budget, tb);
-        const int ntiles = (int)tb.size() - 1;
-        for (const Variant &v : variants) {
-          if ((v.gram && !want_gram) || (v.back == 3 && !want_back3) || v.back > max_back) continue;
-          int max_in = 0, max_rounds = 1;
-          bool ok = true;
-          for (int t = 0; t < ntiles && ok; ++t) {
-            const int eo0 = hp->out_ptr[tb[t]];
-            rb.clear();
-            re.clear();
-            int longest = 0;
-            for (int i = hp->in_ptr[tb[t]]; i < hp->in_ptr[tb[t + 1]]; ++i) {
-              const int bd = edge_b[hp->in_edge[i]];
-              rb.push_back(hp->out_ptr[bd] - eo0);
-              re.push_back(hp->out_ptr[bd + 1] - eo0);
-              longest = std::max(longest, re.back() - rb.back());
-            }
-            const int din = (int)rb.size();
-            max_in = std::max(max_in, din);
-            max_rounds = std::max(max_rounds, (din + 15) / 16);
-            int window = 0;
-            ok = edge_ps_tile_ok(rb.data(), re.data(), din, v.back, edge_ps_ring_tiles(v.gram), &window);
-            if (v.gram) ok = ok && window <= edge_ps_gram_window() && longest <= 32;
-          }
-          if (!ok || edge_ps_lds_bytes(mr, max_in, v.gram) > (size_t)160 * 1024) continue;
-          const double groups = ntiles <= cus ? (double)(cus / ntiles) : 1.0 / (double)((ntiles + cus - 1) / cus);
-          const double cost = (double)max_rounds / groups * v.factor;
-          if (hp->pt_begin.empty() || cost < best * 0.999) {
-            best = cost;
-            hp->pt_begin = tb;
-            pt_max_rows = mr;
-            pt_max_in = max_in;
-            pt_back = v.back;
-            pt_gram = v.gram ? 1 : 0;
-          }
-          break;  // (the variants are ordered by their factor: the first admissible one is this partition's)
-        }
-        if (mr >= E) break;  // one tile holds everything: larger budgets change nothing
-      }
-    }
-    // upload all int arrays in one allocation
-    std::vector<int> ints;
-    auto push = [&](const std::vector<int> &v) {
-      size_t o = ints.size();
-      ints.insert(ints.end(), v.begin(), v.end());
-      while (ints.size() % 4) ints.push_back(0);
-      return o;
-    };
-    const size_t o_a = push(hp->edge_a), o_b = push(hp->edge_b), o_op = push(hp->out_ptr),
-                 o_ip = push(hp->in_ptr), o_ie = push(hp->in_edge), o_at = push(hp->atom_type),
-                 o_tb = push(hp->tile_begin), o_to = push(hp->trip_off), o_rv = push(hp->rev_edge),
-                 o_nt = push(hp->nt_begin), o_et = push(hp->et_begin), o_bt = push(hp->bt_begin), o_pt = push(hp->pt_begin), o_ipos = push(hp->in_pos);
-    hp->g_ints.ensure(ints.size() * sizeof(int));
-    HIP_TRY(hipMemcpy(hp->g_ints.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
-    const int *base = hp->g_ints.as<int>();
-    Graph &g = hp->g;
-    g.N = N;
-    g.E = E;
-    g.edge_a = base + o_a;
-    g.edge_b = base + o_b;
-    g.out_ptr = base + o_op;
-    g.in_ptr = base + o_ip;
-    g.in_edge = base + o_ie;
-    g.in_pos = base + o_ipos;
-    g.atom_type = base + o_at;
-    g.rev_edge = base + o_rv;
-    g.num_tiles = (int)hp->tile_begin.size() - 1;
-    g.tile_begin = base + o_tb;
-    g.max_tile_out_rows = max_rows;
-    g.max_tile_in_rows = 0;
-    g.max_tile_nodes = 0;
-    for (size_t t = 0; t + 1 < hp->tile_begin.size(); ++t) {
-      g.max_tile_in_rows = std::max(g.max_tile_in_rows,
-                                    hp->in_ptr[hp->tile_begin[t + 1]] - hp->in_ptr[hp->tile_begin[t]]);
-      g.max_tile_nodes = std::max(g.max_tile_nodes, hp->tile_begin[t + 1] - hp->tile_begin[t]);
-    }
-    g.trip_off = base + o_to;
-    g.T = hp->trip_off[E];
-    g.nt_num = (int)hp->nt_begin.size() - 1;
-    g.nt_begin = base + o_nt;
-    g.nt_max_in_rows = nt_max_in;
-    g.nt_max_nodes = nt_max_nodes;
-    g.nt_narrow = nt_narrow ? 1 : 0;
-    {
-      // the atom-owning NodeBlock pays max-in-degree rounds per 16-atom tile; the row-ordered one ceil(rows / 16) per tile of
-      // its own partition.  A round of the former is ~25 % cheaper (one barrier, no LDS pass per row): take it unless the
-      // in-degrees are so uneven that it runs > 1.2x the rounds.  RN_POTGNN_NODE_ATOM=0 / 1 forces.
-      int max_deg = 0;
-      long rounds_atom = 0, rounds_row = 0;
-      for (int n0 = 0; n0 < N; n0 += 16) {
-        int m = 0;
-        for (int n = n0; n < std::min(N, n0 + 16); ++n) m = std::max(m, hp->in_ptr[n + 1] - hp->in_ptr[n]);
-        rounds_atom += m;
-        max_deg = std::max(max_deg, m);
-      }
-      for (size_t t = 0; t + 1 < hp->nt_begin.size(); ++t)
-        rounds_row += (hp->in_ptr[hp->nt_begin[t + 1]] - hp->in_ptr[hp->nt_begin[t]] + 15) / 16;
-      bool ok = !nt_narrow && hp->d.FnP == 64 && hp->d.FeP == 64 && node_atom_lds_bytes(max_deg) <= (size_t)40 * 1024 &&
-                (double)rounds_atom <= 1.2 * (double)rounds_row;
-      if (const char *e = getenv("RN_POTGNN_NODE_ATOM"))
-        ok = atoi(e) != 0 && hp->d.FnP == 64 && hp->d.FeP == 64 && node_atom_lds_bytes(max_deg) <= (size_t)64 * 1024;
-      g.na_num = ok ? (N + 15) / 16 : 0;
-      g.na_max_deg = max_deg;
-    }
-    g.et_num = hp->et_begin.empty() ? 0 : (int)hp->et_begin.size() - 1;
-    g.et_begin = base + o_et;
-    g.et_max_out_rows = et_max_rows;
-    g.et_max_in_rows = et_max_in;
-    g.et_max_nodes = et_max_nodes;
-    g.pt_num = hp->pt_begin.empty() ? 0 : (int)hp->pt_begin.size() - 1;
-    g.pt_begin = base + o_pt;
-    g.pt_max_out_rows = pt_max_rows;
-    g.pt_max_in_rows = pt_max_in;
-    g.pt_back = pt_back;
-    g.pt_gram = pt_gram;
-    g.bt_num = hp->bt_begin.empty() ? 0 : (int)hp->bt_begin.size() - 1;
-    g.bt_begin = base + o_bt;
-    g.bt_max_out_rows = bt_max_rows;
-    g.bt_max_in_rows = bt_max_in;
-    g.bt_max_nodes = bt_max_nodes;
+    hp->g = upload(hp->plan, hp->g_ints);
     double ms[18];
     std::memcpy(ms, hp->mean, sizeof(hp->mean));
     std::memcpy(ms + 9, hp->stdv, sizeof(hp->stdv));
     hp->d_mean_std.ensure(sizeof(ms));
     HIP_TRY(hipMemcpy(hp->d_mean_std.p, ms, sizeof(ms), hipMemcpyHostToDevice));
-
     pack_weights(hp, weights);
     refresh_mfma_mode(hp);
-    // The fused kernels (kernels_fused.hip) are the default where they apply (float32, Fn and
-    // Fe padded to 64); RN_POTGNN_FUSED=0 selects projections + edge_agg_kernel.
-#if RN_EXPERIMENTS
-    hp->use_edge2 = want_fused && want_edge2 && edge2_supported(hp->g, hp->d);
-#endif
-    hp->use_fused = hp->use_edge2 || (want_fused && edge_fused_supported(hp->g, hp->d));
-#if RN_EXPERIMENTS
-    hp->use_edge3 = hp->use_fused && !hp->use_edge2 && want_edge3 && edge3_supported(hp->g, hp->d);
-#else
-    (void)want_edge3;
-#endif
-    hp->use_ps = hp->use_fused && !hp->use_edge2 && !hp->use_edge3 && hp->g.pt_num > 0;
     hp->ps_fail.ensure(2048);  // [0] the failure word; timing builds (RN_PS_TIMING) keep their cycle counters from byte 64 on
     HIP_TRY(hipMemset(hp->ps_fail.p, 0, 2048));
-    hp->split_projections = getenv("RN_POTGNN_SPLIT_PROJ") ? atoi(getenv("RN_POTGNN_SPLIT_PROJ")) != 0 : true;
-    hp->use_narrow = narrow_mode && edge_narrow_lds_bytes(hp->d.Fn, hp->d.Fe, hp->g.max_tile_out_rows,
-                                                          hp->g.max_tile_in_rows) <= (size_t)64 * 1024;
-    // Chunk size and lanes.  Throughput rises monotonically with the frames per launch
-    // (profiles/r01_chunk_sweep.txt, profiles/r01/overlap_experiments.txt section 7) and the
-    // Infinity Cache does not reward small chunks.  The fused kernels take a whole CU each, so a
-    // second lane has nothing to overlap with: ONE lane with an 8 GiB workspace (of 288 GB HBM)
-    // beats two lanes of 1.5 GiB (63.7 k vs 62.1 k structures/s at 4000 frames).  The unfused
-    // pipeline keeps two alternating lanes of 1.5 GiB.  Round 4: the role-specialised EdgeBlock is bound by SIMD issue and
-    // leaves HBM idle and ~10 KiB of LDS per CU free, so the small HBM-bound kernels of a second lane (geometry, per-atom
-    // projections, readout reduction) do run under it: RN_POTGNN_LANES=2 gives 48.9 -> 49.2 k structures/s on config 3.
-    // Not the default: kernels of two lanes wait for each other's LDS, and HIP events around a launch then time the wait
-    // too (the NodeBlock's HBM figure of the bench line reads 6 % instead of 46 %).
-    const bool want_node = getenv("RN_POTGNN_NODE_FUSED") ? atoi(getenv("RN_POTGNN_NODE_FUSED")) != 0 : true;
-    hp->use_node_fused = hp->use_fused && want_node && node_fused_lds_bytes(hp->g) <= 64 * 1024;
-    hp->want_pair_rows = !(getenv("RN_POTGNN_PAIR_ROWS") && atoi(getenv("RN_POTGNN_PAIR_ROWS")) == 0);
-    const bool want_ro = getenv("RN_POTGNN_READOUT_FUSED") ? atoi(getenv("RN_POTGNN_READOUT_FUSED")) != 0 : true;
-    hp->use_readout_fused = hp->use_fused && want_ro;
-    if (!getenv("RN_POTGNN_LANES")) hp->num_lanes = (hp->use_fused || hp->use_narrow) ? 1 : 2;
-    int chunk = cfg->max_chunk_structures;
-    if (const char *e = getenv("RN_POTGNN_CHUNK")) chunk = atoi(e);
-    if (chunk <= 0) {
-      const size_t per = per_structure_elems(hp, lean_workspace(hp)) * sizeof(float);
-      size_t budget = (hp->use_fused || hp->use_narrow) ? ((size_t)8192 << 20) : ((size_t)1536 << 20);
-      size_t free_b = 0, total_b = 0;  // on a shared GPU: at most 1/8 of what is free right now
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
-        budget = std::min(budget, std::max<size_t>(free_b / 8 / (size_t)hp->num_lanes, (size_t)64 << 20));
-      chunk = (int)std::max<size_t>(1, budget / std::max<size_t>(per, 1));
-      chunk = std::min(chunk, 4096);
-      // the float64 lanes (created on first use) get their own allowance against the same "an eighth of what is free"
-      // rule: up to 24 GiB of the full-width float64 layout (1270 frames at 256 atoms, Fn = Fe = 64), so that the phonon
-      // finite differences of config 4 -- 1536 cells -- still run in two launches (chunk_frames<double>)
-      hp->f64_budget = (size_t)24 << 30;
-      if (free_b > 0) hp->f64_budget = std::min(hp->f64_budget, std::max<size_t>(free_b / 8 / (size_t)hp->num_lanes, (size_t)64 << 20));
-    }
-    hp->chunk = chunk;
+    size_chunk(hp);
     ensure_precision<float>(hp);
   });
   if (rc != RN_OK) return rc;
   *out = h.release();
   return RN_OK;
+}
+
+int rn_potgnn_debug_plan(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
+                         const int32_t *atom_types, int32_t num_cus, int32_t *out, size_t capacity, size_t *count) {
+  if (!count || num_cus <= 0) return RN_ERR_INVALID_ARGUMENT;
+  *count = 0;
+  std::string invalid;
+  const int rc = validate_create_args(cfg, edge_a, edge_b, atom_types, false, nullptr, invalid);
+  if (rc != RN_OK) {
+    set_error(nullptr, "%s", invalid.c_str());
+    return rc;
+  }
+  try {
+    const PlanKnobs knobs = read_plan_knobs();
+    const std::vector<int32_t> flat = plan_graph(*cfg, plan_dims(*cfg, knobs), edge_a, edge_b, atom_types, num_cus, knobs).flat();
+    *count = flat.size();
+    if (!out || capacity < flat.size()) {
+      set_error(nullptr, "out holds %zu values, the plan has %zu", out ? capacity : (size_t)0, flat.size());
+      return RN_ERR_INVALID_ARGUMENT;
+    }
+    std::memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
+    return RN_OK;
+  } catch (const std::bad_alloc &) {
+    set_error(nullptr, "host allocation failed");
+    return RN_ERR_OUT_OF_MEMORY;
+  }
 }
 
 void rn_potgnn_destroy(rn_potgnn *h) {
@@ -2956,7 +2469,7 @@ int rn_potgnn_calc_polarizabilities(rn_potgnn *h, const double *positions, int64
     int *fail_pin = reinterpret_cast<int *>(hs.out_pin + out_bytes);
     *fail_pin = 0;
     HIP_TRY(hipMemcpyAsync(hs.out_pin, h->io_alpha.p, out_bytes, hipMemcpyDeviceToHost, h->exec_stream));
-    const bool watch = h->use_ps && h->ps_fail.p;
+    const bool watch = h->plan.use_ps && h->ps_fail.p;
     if (watch) HIP_TRY(hipMemcpyAsync(fail_pin, h->ps_fail.p, sizeof(int), hipMemcpyDeviceToHost, h->exec_stream));
     HIP_TRY(hipStreamSynchronize(h->exec_stream));
     resolve_timers(h);
@@ -3584,7 +3097,7 @@ int rn_potgnn_adam_step(rn_potgnn *h, double lr, double beta1, double beta2, dou
     after_other_lanes(h, st);
     launch_adam(w, P.grad.as<float>(), h->adam_m.as<float>(), h->adam_v.as<float>(),
                 h->trainable_mask.as<unsigned char>(), n, lr, beta1, beta2, eps, weight_decay, step, st,
-                (h->use_ps && h->ps_fail.p) ? h->ps_fail.as<int>() : nullptr);
+                (h->plan.use_ps && h->ps_fail.p) ? h->ps_fail.as<int>() : nullptr);
     launch_refresh_derived(w, h->derived_ops.as<DerivedOp>(), h->derived_first_stage, st);
     launch_refresh_derived(w, h->derived_ops.as<DerivedOp>() + h->derived_first_stage, h->num_derived_ops - h->derived_first_stage, st);
     launch_setup<float>(w + L.emb, w + L.W2, w + L.b2, w + L.W4, w + L.b4, h->cfg.num_atom_types, h->d,
@@ -3706,22 +3219,22 @@ int rn_potgnn_radius_graph(const double *lattice, const double *positions, int32
 int rn_potgnn_config_flags(const rn_potgnn *h) {
   if (!h) return -1;
   std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the pass flags are rewritten when weights change)
-  int flags = (h->use_fused ? 1 : 0) | ((h->use_fused && h->mfma_f16) ? 4 : 0) | (h->use_narrow ? 8 : 0) |
-              ((h->use_fused && h->mfma_range_fallback) ? 16 : 0) | (h->use_edge2 ? 32 : 0) | (h->use_edge3 ? 64 : 0) | (RN_EXPERIMENTS ? 128 : 0);
+  int flags = (h->plan.use_fused ? 1 : 0) | ((h->plan.use_fused && h->mfma_f16) ? 4 : 0) | (h->plan.use_narrow ? 8 : 0) |
+              ((h->plan.use_fused && h->mfma_range_fallback) ? 16 : 0) | (h->plan.use_edge2 ? 32 : 0) | (h->plan.use_edge3 ? 64 : 0) | (RN_EXPERIMENTS ? 128 : 0);
   {  // bit 8: every pass of a float32 evaluation takes the role-specialised EdgeBlock (kernels_edge_ps.hip)
-    bool ps = h->use_fused && h->use_ps && !h->f32.pass.empty();  // (split-f16 or exact-f32 products: the same kernel)
+    bool ps = h->plan.use_fused && h->plan.use_ps && !h->f32.pass.empty();  // (split-f16 or exact-f32 products: the same kernel)
     for (const auto &p : h->f32.pass) ps = ps && (p.c3_fast & 1);
     flags |= ps ? 256 : 0;
   }
   {  // bit 9: float32 evaluations take the atom-owning fused NodeBlock (kernels_node_atom.hip)
     static const bool centred = !(getenv("RN_POTGNN_NODE_CENTRED") && atoi(getenv("RN_POTGNN_NODE_CENTRED")) == 0);
-    const bool atom = h->use_fused && h->use_node_fused && h->mfma_f16 && centred && h->g.na_num > 0;
+    const bool atom = h->plan.use_fused && h->plan.use_node_fused && h->mfma_f16 && centred && h->g.na_num > 0;
     flags |= atom ? 512 : 0;
     // bit 10: float32 evaluations keep their edge rows as split-f16 pairs (bits 8 and 9 and the fused readout)
-    flags |= (atom && (flags & 256) && h->use_readout_fused && h->want_pair_rows && !h->keep_stages) ? 1024 : 0;
+    flags |= (atom && (flags & 256) && h->plan.use_readout_fused && h->want_pair_rows && !h->keep_stages) ? 1024 : 0;
   }
   bool fast = !h->f32.pass.empty();
-  for (const auto &p : h->f32.pass) fast = fast && !h->use_narrow && (p.c3_fast & (h->use_fused ? 1 : 2));
+  for (const auto &p : h->f32.pass) fast = fast && !h->plan.use_narrow && (p.c3_fast & (h->plan.use_fused ? 1 : 2));
   return flags | (fast ? 2 : 0);
 }
 
@@ -3791,7 +3304,7 @@ int rn_potgnn_debug_stage(rn_potgnn *h, int stage, int index, float *out, size_t
       const int E = h->g.E;
       for (int64_t s = 0; s < S; ++s)
         for (int e = 0; e < E; ++e)
-          std::memcpy(out + (s * E + e) * c, tmp.data() + (s * E + h->in_pos[e]) * c, (size_t)c * sizeof(float));
+          std::memcpy(out + (s * E + e) * c, tmp.data() + (s * E + h->plan.in_pos[e]) * c, (size_t)c * sizeof(float));
     }
     *rows = r;
     *cols = c;

@@ -12,7 +12,7 @@ bdir="build${tag:+_$tag}"
 mkdir -p "$here/$bdir"
 pids=()
 # RN_EXTRA_FLAGS=-DRN_EXPERIMENTS=1 adds the opt-in round-3 experiment kernels (experiments/ at the repository root, outside the package); the product build has none.
-hip_srcs="api kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group spectrum spectrum_polarized spectrum_partial"
+hip_srcs="api graph_plan kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group spectrum spectrum_polarized spectrum_partial"
 case " ${RN_EXTRA_FLAGS:-} " in *" -DRN_EXPERIMENTS=1 "*) hip_srcs="$hip_srcs ../../experiments/kernels_fused_experiments ../../experiments/kernels_edge_frame";; esac
 objs=()
 for f in $hip_srcs; do
@@ -20,6 +20,7 @@ for f in $hip_srcs; do
   objs+=("$o")
   if [ ! -f "$o" ] || [ "$here/$f.hip" -nt "$o" ] || [ "$here/fused_common.hpp" -nt "$o" ] || \
      [ "$here/kernels.hpp" -nt "$o" ] || [ "$here/device_utils.hpp" -nt "$o" ] || \
+     [ "$here/graph_plan.hpp" -nt "$o" ] || \
      [ "$here/spectrum_common.hpp" -nt "$o" ] || \
      [ "$here/../../include/rn_potgnn.h" -nt "$o" ]; then
     extra=""

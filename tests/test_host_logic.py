@@ -586,6 +586,210 @@ def test_role_split_schedule_check_on_the_host():
     assert lib.rn_potgnn_debug_ps_schedule(None, None, 0, 2, 8, None) < 0
 
 
+# ----------------------------------------------------------------------------- graph plans
+_PLAN_GOLDEN = os.path.join(ROOT, "tests", "golden", "graph_plans.npz")
+_PLAN_CACHE = {}
+
+
+def _plans(group, num_cus):
+    """Every case of knob group `group` through ``rn_potgnn_debug_plan`` in a child process (tests/plan_worker.py) whose
+    environment holds exactly that group's knobs: name -> (shape, edge_a, edge_b, types, flat plan)."""
+    import subprocess
+    import sys
+    import tempfile
+    from tests.helpers import PLAN_KNOBS, plan_cases
+    if (group, num_cus) not in _PLAN_CACHE:
+        env = {k: v for k, v in os.environ.items() if not k.startswith("RN_POTGNN_") or k == "RN_POTGNN_LIB"}
+        env.update({"RN_POTGNN_" + k: v for k, v in PLAN_KNOBS[group].items()})
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "plans.npz")
+            run = subprocess.run([sys.executable, "-m", "tests.plan_worker", str(group), str(num_cus), out], cwd=ROOT,
+                                 env=env, capture_output=True, text=True, timeout=600)
+            assert run.returncode == 0, run.stdout + run.stderr
+            flat = dict(np.load(out))
+        cases = plan_cases(PLAN_KNOBS[group])
+        assert sorted(flat) == sorted(c[0] for c in cases)
+        _PLAN_CACHE[(group, num_cus)] = {name: (shape, ea, eb, types, flat[name]) for name, shape, ea, eb, types in cases}
+    return _PLAN_CACHE[(group, num_cus)]
+
+
+def _parse_plan(flat, n, e):
+    """The layout documented at ``rn_potgnn_debug_plan`` in include/rn_potgnn.h."""
+    plan = {"FnP": int(flat[0]), "FeP": int(flat[1])}
+    i = 2
+    for part in ("tile", "nt", "et", "bt", "pt"):
+        length = int(flat[i])
+        plan[part] = (flat[i + 1:i + 1 + length], tuple(int(v) for v in flat[i + 1 + length:i + 4 + length]))
+        i += length + 4
+    for key in ("nt_narrow", "na_num", "na_max_deg", "pt_back", "pt_gram", "T", "use_fused", "use_edge2", "use_edge3", "use_ps",
+                "use_narrow", "use_node_fused", "use_readout_fused", "num_lanes"):
+        plan[key] = int(flat[i])
+        i += 1
+    plan["head"] = flat[:i]
+    for key, size in (("out_ptr", n + 1), ("in_ptr", n + 1), ("in_edge", e), ("in_pos", e), ("rev_edge", e), ("trip_off", e + 1)):
+        plan[key] = flat[i:i + size]
+        i += size
+    assert i == len(flat)
+    return plan
+
+
+def _all_plan_groups(num_cus):
+    from tests.helpers import PLAN_KNOBS, plan_group_name
+    for group, knobs in enumerate(PLAN_KNOBS):
+        for name, (shape, ea, eb, types, flat) in _plans(group, num_cus).items():
+            yield plan_group_name(knobs) + "/" + name, shape, ea, eb, types, _parse_plan(flat, shape[0], shape[1])
+
+
+def test_graph_plans_match_the_parent_commit():
+    """The host-only planner (csrc/graph_plan.hip) chooses, element for element, the partitions, scalars and kernel family
+    that ``rn_potgnn_create`` chose before planning moved out of it.  tests/golden/graph_plans.npz was recorded from that
+    parent commit (c6d5589), not from this code: a throw-away patch (not committed) made the parent's ``rn_potgnn_create``
+    write the array of ``rn_potgnn_debug_plan`` when it returned, over the case list of tests/helpers.py ``plan_cases`` --
+    the fixtures' graphs, the benchmark cells at eight width pairs, 24 ragged graphs, and eleven knob variants in a
+    process each.  The file was meant to be taken on an MI355X; no GPU could be had while this was written, so the patch
+    also let the parent skip its device probe and device calls and take the CU count (256, an MI355X's, and the parent's
+    own value when the query fails) from the environment: the planning code that ran is the parent's, unchanged, on a
+    CPU (profiles/plan_refactor_ab.txt: the commit, the patch, the cases, the CU count).  ``num_cus`` is the recorded one,
+    so this runs anywhere."""
+    golden = np.load(_PLAN_GOLDEN)
+    num_cus = int(golden["num_cus"])
+    seen = set()
+    for key, shape, ea, eb, types, plan in _all_plan_groups(num_cus):
+        np.testing.assert_array_equal(plan["head"], golden[key], err_msg=key)
+        seen.add(key)
+    assert seen == set(golden.files) - {"num_cus", "parent_commit"} and len(seen) >= 4 + 24 + 20 + 22
+
+
+def test_graph_plan_index_arrays_against_their_definitions():
+    """out_ptr / in_ptr are the CSRs over source and destination, in_edge lists each destination's edges ascending, in_pos
+    is its inverse, rev_edge[e] the id of (b -> a) or -1, trip_off the running count of b's out-edges other than the one
+    back to a -- recomputed here in numpy; for the fixtures T is also the reference-order triplet count."""
+    from tests.helpers import PLAN_FIXTURES
+    for key, (n, e, _, _, _), ea, eb, types, plan in _all_plan_groups(256):
+        ea64, eb64 = ea.astype(np.int64), eb.astype(np.int64)
+        deg_out = np.bincount(ea, minlength=n)
+        np.testing.assert_array_equal(plan["out_ptr"], np.concatenate([[0], np.cumsum(deg_out)]), err_msg=key)
+        np.testing.assert_array_equal(plan["in_ptr"], np.concatenate([[0], np.cumsum(np.bincount(eb, minlength=n))]), err_msg=key)
+        in_edge = np.argsort(eb, kind="stable")
+        np.testing.assert_array_equal(plan["in_edge"], in_edge, err_msg=key)
+        in_pos = np.empty(e, dtype=np.int64)
+        in_pos[in_edge] = np.arange(e)
+        np.testing.assert_array_equal(plan["in_pos"], in_pos, err_msg=key)
+        ids = {(a, b): i for i, (a, b) in enumerate(zip(ea64.tolist(), eb64.tolist()))}
+        rev = np.array([ids.get((b, a), -1) for a, b in zip(ea64.tolist(), eb64.tolist())])
+        np.testing.assert_array_equal(plan["rev_edge"], rev, err_msg=key)
+        per_edge = deg_out[eb] - (rev >= 0)
+        np.testing.assert_array_equal(plan["trip_off"], np.concatenate([[0], np.cumsum(per_edge)]), err_msg=key)
+        assert plan["T"] == per_edge.sum()
+        if key.split("/")[1] in PLAN_FIXTURES:
+            assert plan["T"] == len(G.reference_order_triplets(np.stack([ea64, eb64]), n)[2])
+
+
+def test_graph_plan_partitions_hold_their_invariants():
+    """Every partition of every case: ``begin`` runs from 0 to N and rises strictly, the three maxima are those of its tiles,
+    ``pt_back`` lies in 2 .. 5 and the producers' schedule check accepts every tile of the role-specialised EdgeBlock at
+    that lookahead and the matching ring (8 tiles; 7 with the Gram tables).  The ragged graphs are there for the planner's
+    rarer branches, and this test checks that each is taken: (1) the atom-owning NodeBlock refused because it would run more
+    than 1.2x the rounds (every even ``ragged``; the benchmark cells take it), (2) a greedy walk that gives one atom with
+    more rows than the budget a tile of its own, (3) a search of the role-specialised tiles that stops because one tile
+    holds the whole graph (E <= 1024 at 64 x 64: ``ragged04``, ``ragged20``), (4) such a search that ends without a partition
+    (``ragged07``, ``ragged11``, ``ragged23``: out-degrees near 50 do not fit the ring)."""
+    lib = _lib.load()
+    hit = {"atom_refused": [], "atom_taken": [], "single_atom_over_budget": [], "one_tile": [], "no_ps_partition": []}
+    for key, (n, e, _, _, _), ea, eb, types, plan in _all_plan_groups(256):
+        out_ptr, in_ptr, in_edge = (plan[k].astype(np.int64) for k in ("out_ptr", "in_ptr", "in_edge"))
+        for part in ("tile", "nt", "et", "bt", "pt"):
+            begin, maxima = plan[part]
+            if len(begin) == 0:
+                assert maxima == (0, 0, 0) and part in ("et", "bt", "pt"), (key, part)
+                continue
+            assert begin[0] == 0 and begin[-1] == n and np.all(np.diff(begin) > 0), (key, part)
+            rows_out, rows_in = np.diff(out_ptr[begin]), np.diff(in_ptr[begin])
+            assert maxima == (rows_out.max(), rows_in.max(), np.diff(begin).max()), (key, part)
+            # a greedy walk closes tile t because the first atom of tile t + 1 would exceed the budget, so the budget
+            # lies below rows(t) + that atom's rows for every closed tile; a one-atom tile at or above that is over it
+            by_in = part == "nt"
+            if len(begin) > 2 and not (by_in and plan["nt_narrow"]) and not (part == "tile" and plan["use_narrow"]):
+                rows, ptr = (rows_in, in_ptr) if by_in else (rows_out, out_ptr)
+                bound = (rows[:-1] + (ptr[begin[1:-1] + 1] - ptr[begin[1:-1]])).min()
+                if np.any((np.diff(begin) == 1) & (rows >= bound)):
+                    hit["single_atom_over_budget"].append(key + ":" + part)
+        assert 2 <= plan["pt_back"] <= 5, key
+        begin = plan["pt"][0]
+        for t in range(len(begin) - 1):
+            dest = eb[in_edge[in_ptr[begin[t]]:in_ptr[begin[t + 1]]]]
+            rb = (out_ptr[dest] - out_ptr[begin[t]]).astype(np.int32)
+            re_ = (out_ptr[dest + 1] - out_ptr[begin[t]]).astype(np.int32)
+            ok = lib.rn_potgnn_debug_ps_schedule(ctypes.c_void_p(rb.ctypes.data), ctypes.c_void_p(re_.ctypes.data), len(rb),
+                                                 plan["pt_back"], 7 if plan["pt_gram"] else 8, None)
+            assert ok == 1, (key, t)
+        if key.startswith("default/") and plan["FnP"] == 64 and plan["FeP"] == 64:
+            deg_in = np.diff(in_ptr)
+            rounds_atom = sum(int(deg_in[i:i + 16].max()) for i in range(0, n, 16))
+            rounds_row = int(((np.diff(in_ptr[plan["nt"][0]]) + 15) // 16).sum())
+            if rounds_atom > 1.2 * rounds_row:
+                assert plan["na_num"] == 0, key
+                hit["atom_refused"].append(key)
+            elif plan["na_num"] > 0:
+                hit["atom_taken"].append(key)
+            if e <= 1024:
+                hit["one_tile"].append(key)
+            if len(begin) == 0:
+                hit["no_ps_partition"].append(key)
+    assert all(hit.values()), hit
+
+
+def test_debug_plan_rejects_what_create_rejects():
+    """The bad inputs of ``test_create_rejects_bad_arguments_without_touching_the_gpu`` (and the documented size limits)
+    through ``rn_potgnn_debug_plan``: the same status codes and texts, from the same code."""
+    lib = _lib.load()
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    ea, eb, ty = np.array([0, 1], dtype=np.int32), np.array([1, 0], dtype=np.int32), np.zeros(4, dtype=np.int32)
+    out, count = np.zeros(64, dtype=np.int32), ctypes.c_size_t(0)
+
+    def plan(cfg, a, b, t=ty):
+        rc = lib.rn_potgnn_debug_plan(ctypes.byref(cfg), p(a), p(b), p(t), 256, p(out), out.size, ctypes.byref(count))
+        return rc, lib.rn_potgnn_last_error(None)
+
+    cfg = _lib.Config(4, 2, 1, 200, 8, 1, -1.0, 0, 0)
+    rc, text = plan(cfg, ea, eb)
+    assert rc == _lib.RN_ERR_UNSUPPORTED and text == b"embedding sizes above 128 are not supported (Fn=200, Fe=8)"
+    cfg.size_node_embedding = 8
+    rc, text = plan(cfg, ea, np.array([1, 1], dtype=np.int32))
+    assert rc == _lib.RN_ERR_INVALID_ARGUMENT and text == b"edge 1 = (1,1) is out of range or a self loop"
+    rc, text = plan(cfg, np.array([1, 0], dtype=np.int32), ea)
+    assert rc == _lib.RN_ERR_INVALID_ARGUMENT and text == b"edges must be strictly sorted by (a, b); violated at edge 1"
+    rc, text = plan(cfg, ea, eb, np.array([0, 0, 1, 0], dtype=np.int32))
+    assert rc == _lib.RN_ERR_INVALID_ARGUMENT and text == b"atom 2 has type 1 outside [0,1)"
+    assert lib.rn_potgnn_debug_plan(ctypes.byref(cfg), None, p(eb), p(ty), 256, p(out), out.size, ctypes.byref(count)) \
+        == _lib.RN_ERR_INVALID_ARGUMENT and lib.rn_potgnn_last_error(None) == b"null argument"
+    cfg.num_edges = 0
+    rc, text = plan(cfg, ea, eb)
+    assert rc == _lib.RN_ERR_INVALID_ARGUMENT and text.startswith(b"reference graph has no edges")
+    cfg.num_edges, cfg.num_atoms = 2, 0
+    assert plan(cfg, ea, eb) == (_lib.RN_ERR_INVALID_ARGUMENT, b"invalid configuration (non-positive size)")
+    # more out-edges than one LDS tile holds: 75 from one atom at Fe = 128 (74 fit)
+    many = _lib.Config(80, 75, 1, 8, 128, 1, -1.0, 0, 0)
+    star_a, star_b, star_ty = np.zeros(75, dtype=np.int32), np.arange(1, 76, dtype=np.int32), np.zeros(80, dtype=np.int32)
+    rc, text = plan(many, star_a, star_b, star_ty)
+    assert rc == _lib.RN_ERR_UNSUPPORTED
+    assert text == b"atom 0 has 75 outgoing edges; more than 74 per atom is unsupported for size_edge_embedding=128"
+    # the same texts come from rn_potgnn_create
+    h, lat = ctypes.c_void_p(), np.eye(3)
+    n = lib.rn_potgnn_weight_count(ctypes.byref(many))
+    w = np.zeros(n, dtype=np.float32)
+    rc = lib.rn_potgnn_create(ctypes.byref(many), p(star_a), p(star_b), p(star_ty), p(lat), p(w), n, p(lat), p(lat),
+                              ctypes.byref(h))
+    assert rc == _lib.RN_ERR_UNSUPPORTED and lib.rn_potgnn_last_error(None) == text
+    # a valid graph: the size query, then the plan; no device is needed
+    cfg = _lib.Config(4, 2, 1, 8, 8, 1, -1.0, 0, 0)
+    assert lib.rn_potgnn_debug_plan(ctypes.byref(cfg), p(ea), p(eb), p(ty), 256, None, 0, ctypes.byref(count)) \
+        == _lib.RN_ERR_INVALID_ARGUMENT and count.value > 0
+    assert plan(cfg, ea, eb)[0] == _lib.RN_OK and out[0] == 16 and out[1] == 16
+    assert lib.rn_potgnn_debug_plan(ctypes.byref(cfg), p(ea), p(eb), p(ty), 0, p(out), out.size, ctypes.byref(count)) \
+        == _lib.RN_ERR_INVALID_ARGUMENT
+
+
 def test_committed_profile_records_are_fresh():
     """`bench.py` prints `roofline.traffic` / `issue_frac` from PMC / SQ passes committed under profiles/rNN/ -- next to a
     FRESH timing.  Every record carries the git blob hash of the kernel source it was taken on and is refused when that file
