@@ -488,6 +488,40 @@ int rn_md_raman_partial(const double *increments, int64_t N, int G, const double
 int rn_md_raman_partial_device(const double *d_increments, int64_t N, int G, const double *weights, int64_t K,
                                int device, size_t workspace_limit, double *intensities, int64_t num_bins, void *stream);
 
+/*
+ * Segment-averaged (Welch) and time-resolved MD Raman spectra of K configurations (MDRamanSpectrum.measure_segments /
+ * measure_segments_polarized before the laser / Bose-Einstein corrections).  The series alpha[0..S-1] is cut into
+ * Q = (S - segment_steps) / hop + 1 segments of segment_steps polarizabilities, segment q starting at step q * hop; with
+ * n = segment_steps - 1 and the taper tau[0..n-1] (host float64[n], already normalised to mean(tau^2) = 1), segment q's
+ * tapered differences are
+ *   d_q[t] = tau[t] (alpha[q hop + t + 1] - alpha[q hop + t]),   t = 0..n-1,
+ * and row (q, k) is rn_md_raman_polarized's I_k(f) evaluated on d_q instead of the whole series' differences: bins
+ * 1..num_bins of fftfreq(n), num_bins = ceil(n/2) - 1, weights host float64[K][21] as there.  With tau = 1, row q is
+ * rn_md_raman_polarized of alpha[q hop .. q hop + segment_steps); with any taper, of the series (0, cumsum(d_q)).
+ * intensities: host float64[Q][K][num_bins] (average = 0), or float64[K][num_bins], the arithmetic mean of the Q rows of
+ * each configuration with no further normalisation (average = 1): magnitudes scale with the segment length as
+ * rn_md_raman_polarized's do with S.  Everything after the contracted power spectrum is linear, so the mean is taken
+ * before the inverse transform: 6 Q forward FFTs and 2 K more, against Q (6 + 2 * 21) for Q calls of
+ * rn_md_raman_polarized (fewer when K < 21 Q; beyond that the gain is the Q K rows that are neither transformed back nor
+ * copied).  When neither the K rows of the mean nor the Q segments fit the workspace in one block each, the segments are
+ * transformed again for every block of configurations.  Each (k, f) of the mean is summed by one thread in segment
+ * order, without atomics: repeated calls are bit-identical.  Checks, in this order: a null pointer, K < 1,
+ * segment_steps < 3 or > S, hop < 1, a wrong num_bins, average not 0 or 1 (RN_ERR_INVALID_ARGUMENT each); hipFFT missing
+ * (RN_ERR_UNSUPPORTED); a bad device (RN_ERR_NO_DEVICE).  workspace_limit (bytes, 0 = 4 GiB) bounds the device memory of the call besides the staged copy of
+ * alpha: the segments go through the forward FFTs in blocks, as many as fit, and the rows through the inverse and length-n
+ * FFTs in sub-blocks; a limit that one segment and one row do not fit in returns RN_ERR_OUT_OF_MEMORY.  hipFFT plans and
+ * work buffers are cached per (device, n, segments per block, rows per block), apart from the caches of the other three
+ * reducers.  The work runs on the null stream and the call returns when the intensities are on the host.
+ */
+int rn_md_raman_segments(const double *alpha, int64_t S, int64_t segment_steps, int64_t hop, const double *taper,
+                         const double *weights, int64_t K, int average, int device, size_t workspace_limit,
+                         double *intensities, int64_t num_bins);
+/* The same for a time series already in HBM (d_alpha: device float64[S][3][3], produced on `stream`): the call
+ * synchronises `stream` before it reads d_alpha, then runs on the null stream; only the intensities travel to the host. */
+int rn_md_raman_segments_device(const double *d_alpha, int64_t S, int64_t segment_steps, int64_t hop, const double *taper,
+                                const double *weights, int64_t K, int average, int device, size_t workspace_limit,
+                                double *intensities, int64_t num_bins, void *stream);
+
 /* Introspection: bit 0 = the fused EdgeBlock kernel is in use (float32, Fn and Fe padded to
  * 64); bit 1 = every pass takes the folded-LayerNorm-scale triplet loop; bit 2 = the fused
  * kernels' matrix products run as split-f16 MFMA (default; RN_POTGNN_MFMA=f32 at create time

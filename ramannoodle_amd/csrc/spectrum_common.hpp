@@ -1,16 +1,17 @@
-// What the three on-device MD spectrum reducers share (spectrum.hip, spectrum_polarized.hip, spectrum_partial.hip):
-// the hipFFT loader, the series-length arithmetic, RAII holders for plans and device buffers, the most-recently-used
-// plan cache, the argument / device check, the host-or-HBM source of a call and the two per-slot kernels of the
-// polarized and partial pipelines.  Each reducer keeps its own signal builder, power / contraction kernel, plans
-// struct, workspace arithmetic and pipeline.
+// What the four on-device MD spectrum reducers share (spectrum.hip, spectrum_polarized.hip, spectrum_partial.hip,
+// spectrum_segments.hip): the hipFFT loader, the series-length arithmetic, RAII holders for plans and device buffers, the
+// most-recently-used plan cache, the argument / device check, the host-or-HBM source of a call and the two per-slot
+// kernels of the polarized, partial and segment pipelines.  Each reducer keeps its own signal builder, power /
+// contraction kernel, plans struct, workspace arithmetic and pipeline.
 //
 // Two decisions that hold for every reducer:
-//  * Buffer sizing.  A buffer that `workspace_limit` counts (the weights, the polarized output block, and the fixed
+//  * Buffer sizing.  A buffer that `workspace_limit` counts (the weights, the taper, the polarized output block, and the fixed
 //    x / p / c / out buffers of an entry) is sized with Fit::kExact: it is reallocated whenever the size differs, so a
 //    cached entry never holds more than the limit of the call that uses it.  The staged copies of a host input
 //    (`alpha`, `incr`) are outside the accounting by rn_potgnn.h's own words and use Fit::kGrowOnly.
-//  * Shrink and retry.  The polarized reducer shrinks G (pairs per group, then balanced over ceil(21/G) groups) and the
-//    partial reducer shrinks B (rows per block, capped by the row count); they differ in the key, the balancing, the
+//  * Shrink and retry.  The polarized reducer shrinks G (pairs per group, then balanced over ceil(21/G) groups), the
+//    partial reducer shrinks B (rows per block, capped by the row count) and the segment reducer shrinks B and R
+//    (segments and rows per block) together; they differ in the key, the balancing, the
 //    per-slot cost and what the leftover bytes are used for, and share only "make, measure the work areas, drop".
 //    So each keeps its own loop over the shared cache and arithmetic below.
 #pragma once
@@ -172,7 +173,7 @@ struct DeviceBuffer {
 };
 
 // Most-recently-used cache of one reducer's plans (front = most recent), instantiated once per reducer so that the
-// three caches stay apart and each keeps kCacheEntries entries.  The caller holds `mutex` for the whole call.
+// caches stay apart and each keeps kCacheEntries entries.  The caller holds `mutex` for the whole call.
 template <class Entry>
 struct PlanCache {
   std::mutex mutex;

@@ -270,6 +270,110 @@ def _md_intensities_on_device(polarizability_ts, timestep: float, device: int, s
                             stream, (), (steps,))
 
 
+# ----------------------------------------------------------------------------- segment (Welch / time-resolved) spectra
+_TAPERS = ("boxcar", "hann", "hamming", "blackman")
+
+
+def segment_plan(steps: int, segment_steps, hop=None, taper="hann") -> tuple[int, int, NDArray[np.float64]]:
+    """Resolve the segmentation of a series of ``steps`` polarizabilities into ``(W, H, tau)``.
+
+    ``segment_steps = W`` polarizabilities per segment (an int, ``3 <= W <= steps``), ``hop = H >= 1`` steps between
+    segment starts (default ``W // 2``), ``taper``: ``"boxcar"``, ``"hann"``, ``"hamming"``, ``"blackman"`` (the symmetric
+    forms, ``scipy.signal.get_window(name, W - 1, fftbins=False)``) or a real array ``(W - 1,)``.  ``tau`` is the taper
+    over the ``W - 1`` differences of a segment, normalised to ``mean(tau^2) = 1`` (a taper whose mean square is zero,
+    such as ``"hann"`` at ``W = 3``, is a ``ValueError``).  Every segment spectrum path resolves its arguments here."""
+    if isinstance(segment_steps, (bool, np.bool_)) or not isinstance(segment_steps, (int, np.integer)):
+        raise get_type_error("segment_steps", segment_steps, "int")
+    width = int(segment_steps)
+    if width < 3:
+        raise ValueError(f"invalid segment_steps: {width} < 3")
+    if width > steps:
+        raise ValueError(f"invalid segment_steps: {width} > {steps} time steps")
+    if hop is None:
+        hop = width // 2
+    if isinstance(hop, (bool, np.bool_)) or not isinstance(hop, (int, np.integer)):
+        raise get_type_error("hop", hop, "int")
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError(f"invalid hop: {hop} < 1")
+    n = width - 1
+    if isinstance(taper, str):
+        if taper not in _TAPERS:
+            raise ValueError(f"unknown taper: {taper!r} (one of {', '.join(_TAPERS)}, or an array ({n},))")
+        tau = scipy.signal.get_window(taper, n, fftbins=False).astype(np.float64)
+    else:
+        if taper is None or isinstance(taper, bytes):
+            raise get_type_error("taper", taper, "str or ndarray")
+        try:
+            tau = np.asarray(taper)
+        except (TypeError, ValueError) as exc:
+            raise get_type_error("taper", taper, "str or ndarray") from exc
+        if tau.dtype.kind not in "iuf":
+            raise get_type_error("taper", taper, "str or ndarray of real numbers")
+        if tau.shape != (n,):
+            raise ValueError(f"taper has wrong shape: {shape_string(tau.shape)} != ({n},)")
+        tau = tau.astype(np.float64)
+        if not np.all(np.isfinite(tau)):
+            raise ValueError("taper is not finite")
+    mean_square = float(np.mean(tau * tau))
+    if not mean_square > 0.0:
+        raise ValueError(f"taper has mean(taper^2) == 0 over the {n} differences of a segment")
+    return width, hop, np.ascontiguousarray(tau / np.sqrt(mean_square))
+
+
+def _segment_starts(steps: int, width: int, hop: int) -> NDArray[np.int64]:
+    return np.arange((steps - width) // hop + 1, dtype=np.int64) * hop
+
+
+_SEGMENT_CHUNK_ELEMENTS = 1 << 23  # complex spectra held at once by the host path
+
+
+def _md_segments_host(polarizability_ts, timestep: float, weights, width: int, hop: int, tau, average: bool):
+    """(wavenumbers, ``I[K][bins]`` or ``I[Q][K][bins]``) on the host, from the definition (``include/rn_potgnn.h``,
+    ``rn_md_raman_segments``): per segment the zero-padded transforms of the six tapered difference components, the
+    contracted power spectrum of each configuration, its inverse transform, the positive lags and their length-n
+    transform; the mean over the segments is taken on the power spectra."""
+    d = _symmetric_components(np.diff(np.asarray(polarizability_ts, dtype=np.float64), axis=0))  # (S - 1, 6)
+    n = width - 1
+    starts = _segment_starts(d.shape[0] + 1, width, hop)
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    keep = np.flatnonzero(wavenumbers >= 0)[1:]
+    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    count = weights.shape[0]
+
+    def finish(power):  # (..., length / 2 + 1) -> (..., bins)
+        lags = np.fft.irfft(power, n=length, axis=-1)[..., :n]
+        return np.real(scipy.fftpack.fft(lags, axis=-1))[..., keep]
+
+    rows = None if average else np.empty((len(starts), count, len(keep)))
+    mean = np.zeros((count, length // 2 + 1))
+    chunk = max(1, _SEGMENT_CHUNK_ELEMENTS // ((length // 2 + 1) * max(count, len(_PAIRS))))
+    for first in range(0, len(starts), chunk):
+        index = starts[first:first + chunk, None] + np.arange(n)[None, :]
+        spectra = np.fft.rfft(d[index] * tau[None, :, None], n=length, axis=1)  # (q, length / 2 + 1, 6)
+        cross = np.real(spectra[:, :, _PAIR_J] * np.conj(spectra[:, :, _PAIR_L]))
+        power = np.einsum("kp,qfp->qkf", weights, cross)
+        if average:
+            mean += power.sum(axis=0)
+        else:
+            rows[first:first + chunk] = finish(power)
+    return wavenumbers[keep], finish(mean / len(starts)) if average else rows
+
+
+def _md_segments_on_device(alpha, timestep: float, weights, width: int, hop: int, tau, average: bool, device: int,
+                           stream=None, workspace_limit: int = 0):
+    """(wavenumbers, uncorrected ``I[K][bins]`` or ``I[Q][K][bins]``) from ``rn_md_raman_segments`` (host alpha) or, with
+    a torch CUDA tensor, ``rn_md_raman_segments_device`` ordered after ``stream``."""
+    import ctypes as C
+    steps = alpha.shape[0]
+    weights, weight_args = _weights_arguments(weights)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    shape = (weights.shape[0],) if average else ((steps - width) // hop + 1, weights.shape[0])
+    return _call_md_reducer("rn_md_raman_segments", alpha, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
+                            (steps, width, hop, C.c_void_p(tau.ctypes.data), *weight_args, int(bool(average))),
+                            (workspace_limit,))
+
+
 class PhononRamanSpectrum(RamanSpectrum):
     """First-order spectrum from phonon wavenumbers ``(M,)`` and Raman tensors ``(M,3,3)``
     (``spectrum/_raman.py:72-194``)."""
@@ -405,11 +509,63 @@ class MDRamanSpectrum(RamanSpectrum):
                                          laser_wavelength, bose_einstein_correction, temperature)
         return wavenumbers, intensities[0] if squeeze else intensities
 
+    def _num_steps(self) -> int:
+        return self._polarizability_ts.shape[0]
+
+    def _segments_on_device(self, weights, width, hop, tau, average, device: int):
+        return _md_segments_on_device(self._polarizability_ts, self._timestep, weights, width, hop, tau, average, device)
+
+    def _segments(self, weights, segment_steps, hop, taper, average, device):
+        """The uncorrected ``(wavenumbers, I[K][bins] or I[Q][K][bins])`` of both segment measurements."""
+        width, hop, tau = segment_plan(self._num_steps(), segment_steps, hop, taper)
+        if device is not None:
+            return self._segments_on_device(weights, width, hop, tau, bool(average), int(device))
+        return _md_segments_host(self._polarizability_ts, self._timestep, weights, width, hop, tau, bool(average))
+
+    def segment_starts(self, segment_steps, hop=None) -> NDArray[np.int64]:
+        """The first step of each of the ``Q = (S - segment_steps) // hop + 1`` segments of ``measure_segments``: the time
+        axis of a spectrogram (segment q covers steps ``starts[q] .. starts[q] + segment_steps - 1``)."""
+        width, hop, _ = segment_plan(self._num_steps(), segment_steps, hop, "boxcar")
+        return _segment_starts(self._num_steps(), width, hop)
+
+    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
+                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
+                         device=None):
+        """Segment-averaged (Welch) or time-resolved spectrum of ``measure()``'s ``45 a^2 + 7 gamma^2`` (an addition).
+
+        The series is cut into ``Q`` overlapping segments of ``segment_steps`` polarizabilities, ``hop`` steps apart
+        (default ``segment_steps // 2``), whose ``segment_steps - 1`` differences are multiplied by ``taper``
+        (``spectrum.segment_plan``; normalised to a mean square of one).  Row q is the spectrum of segment q: with
+        ``taper="boxcar"`` it is ``MDRamanSpectrum(alpha[a:a + segment_steps], timestep).measure()`` for
+        ``a = segment_starts(...)[q]``.  ``average=True`` returns ``(wavenumbers, I[bins])``, the arithmetic mean of the
+        rows, whose variance falls with ``Q`` where a single periodogram's does not fall with the length of the series;
+        ``average=False`` returns the spectrogram ``(wavenumbers, I[Q, bins])``.  No further normalisation is applied:
+        magnitudes scale with the segment length as ``measure()``'s scale with the series length, and the wavenumbers
+        are those of a ``segment_steps`` series.  The corrections apply to every row.  ``device`` (an int) reduces on
+        that GPU (``rn_md_raman_segments``: the mean is taken before the inverse transform)."""
+        _require_polycrystalline(orientation)
+        wavenumbers, intensities = self._segments(_measure_weights(), segment_steps, hop, taper, average, device)
+        intensities = _apply_corrections(wavenumbers, intensities[..., 0, :], laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities
+
+    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
+                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
+                                   bose_einstein_correction=False, temperature=300, device=None):
+        """``measure_segments`` for the configurations of ``measure_polarized`` (``polarized_weights``): intensities
+        ``(K, bins)``, or ``(Q, K, bins)`` with ``average=False``; the ``K`` axis is squeezed when no argument has one."""
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        wavenumbers, intensities = self._segments(weights, segment_steps, hop, taper, average, device)
+        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities[..., 0, :] if squeeze else intensities
+
 
 class _DeviceResident:
     """Mixin for a spectrum whose input stays in HBM as a contiguous float64 CUDA tensor: ``measure`` /
-    ``measure_polarized`` reduce it on the tensor's GPU unless ``host=True``; another ``device`` gets the host copy,
-    which is made on first use."""
+    ``measure_polarized`` (and, where the base class has them, ``measure_segments`` / ``measure_segments_polarized``)
+    reduce it on the tensor's GPU unless ``host=True``; another ``device`` gets the host copy, which is made on first
+    use."""
 
     def _set_tensor(self, name: str, tensor, ndim: int, pattern: str) -> None:
         shape = tuple(tensor.shape)
@@ -457,6 +613,24 @@ class _DeviceResident:
                                          bose_einstein_correction, temperature,
                                          device=self._device_or_host(device, host))
 
+    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
+                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
+                         device=None, host=False):
+        """As the base class's ``measure_segments``; reduces on the tensor's GPU unless ``host=True``."""
+        return super().measure_segments(segment_steps, hop, taper, average, orientation, laser_correction,
+                                        laser_wavelength, bose_einstein_correction, temperature,
+                                        device=self._device_or_host(device, host))
+
+    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
+                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
+                                   bose_einstein_correction=False, temperature=300, device=None, host=False):
+        """As the base class's ``measure_segments_polarized``; reduces on the tensor's GPU unless ``host=True``."""
+        return super().measure_segments_polarized(
+            incident, scattered, orientation, segment_steps=segment_steps, hop=hop, taper=taper, average=average,
+            laser_correction=laser_correction, laser_wavelength=laser_wavelength,
+            bose_einstein_correction=bose_einstein_correction, temperature=temperature,
+            device=self._device_or_host(device, host))
+
 
 class DeviceMDRamanSpectrum(_DeviceResident, MDRamanSpectrum):
     """``MDRamanSpectrum`` whose polarizability time series stays where the evaluator wrote it
@@ -487,6 +661,13 @@ class DeviceMDRamanSpectrum(_DeviceResident, MDRamanSpectrum):
     def _polarized_on_device(self, weights, device: int):
         source, stream = self._source(device)
         return _md_polarized_on_device(source, self._timestep, weights, device, stream=stream)
+
+    def _num_steps(self) -> int:
+        return self._tensor.shape[0]
+
+    def _segments_on_device(self, weights, width, hop, tau, average, device: int):
+        source, stream = self._source(device)
+        return _md_segments_on_device(source, self._timestep, weights, width, hop, tau, average, device, stream=stream)
 
 
 # ----------------------------------------------------------------------------- atom-group (partial) spectra
