@@ -10,6 +10,12 @@
 // The fused pipeline (kernels_fused.hip) uses one lane; the unfused one alternates chunks
 // between two lanes so that the HBM-bound projections of one chunk overlap the VALU-bound
 // aggregation of the other (run_pair).
+//
+// In file order: weight packing and upload; ForwardIO (what an evaluation reads and writes, sliced per chunk in one place)
+// and ChunkRun (one chunk's stages on one lane); forward_device and the reverse pass with their users (Jacobian, input
+// gradients, atom groups, training); then the C entries.  The entries share their argument checks (check_batch,
+// check_train_batch, check_pending, check_types), their staging (stage, stage_lattices, stage_types, lazy_stream,
+// lazy_event) and the ordering bracket around work done for a caller's stream (behind_caller / hand_back).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -663,18 +669,33 @@ void refresh_pass_flags(rn_potgnn *h) {
   }
 }
 
+// ensure + a blocking host-to-device copy
+template <typename T>
+T *stage(DeviceBuf &buf, const void *host, size_t bytes) {
+  buf.ensure(bytes);
+  HIP_TRY(hipMemcpy(buf.p, host, bytes, hipMemcpyHostToDevice));
+  return buf.as<T>();
+}
+
+template <typename T>
+T *upload_packed(rn_potgnn *h) {  // the host master copy, in T, into the precision's weight blob
+  const std::vector<T> host(h->packed.begin(), h->packed.end());
+  return stage<T>(prec<T>(h).weights, host.data(), host.size() * sizeof(T));
+}
+
+// the frame-independent device precompute (node table, folded readout BatchNorm) on the weight blob `w`
+template <typename T>
+void device_setup(rn_potgnn *h, T *w, hipStream_t st) {
+  const PackedLayout &L = h->lay;
+  launch_setup<T>(w + L.emb, w + L.W2, w + L.b2, w + L.W4, w + L.b4, h->cfg.num_atom_types, h->d,
+                  w + L.node_table, w + L.b0, w + L.bn_w, w + L.bn_b, w + L.bn_rm, w + L.bn_rv,
+                  w + L.scale0, w + L.shift0, st);
+}
+
 template <typename T>
 void upload_weights(rn_potgnn *h) {  // (re)upload the packed weights and redo the device precompute
   Precision<T> &P = prec<T>(h);
-  const PackedLayout &L = h->lay;
-  std::vector<T> host(h->packed.size());
-  for (size_t i = 0; i < host.size(); ++i) host[i] = (T)h->packed[i];
-  P.weights.ensure(host.size() * sizeof(T));
-  HIP_TRY(hipMemcpy(P.weights.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-  T *w = P.weights.template as<T>();
-  launch_setup<T>(w + L.emb, w + L.W2, w + L.b2, w + L.W4, w + L.b4, h->cfg.num_atom_types, h->d,
-                  w + L.node_table, w + L.b0, w + L.bn_w, w + L.bn_b, w + L.bn_rm, w + L.bn_rv,
-                  w + L.scale0, w + L.shift0, P.lanes[0].stream);
+  device_setup<T>(h, upload_packed<T>(h), P.lanes[0].stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(P.lanes[0].stream));
   refresh_pass_flags<T>(h);
@@ -685,15 +706,10 @@ void ensure_precision(rn_potgnn *h) {
   Precision<T> &P = prec<T>(h);
   if (P.ready) return;
   const PackedLayout &L = h->lay;
-  std::vector<T> host(h->packed.size());
-  for (size_t i = 0; i < host.size(); ++i) host[i] = (T)h->packed[i];
-  P.weights.ensure(host.size() * sizeof(T));
-  HIP_TRY(hipMemcpy(P.weights.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+  T *w = upload_packed<T>(h);
   T lat[9];
   for (int i = 0; i < 9; ++i) lat[i] = (T)h->lattice[i];
-  P.lattice.ensure(sizeof(lat));
-  HIP_TRY(hipMemcpy(P.lattice.p, lat, sizeof(lat), hipMemcpyHostToDevice));
-  T *w = P.weights.template as<T>();
+  stage<T>(P.lattice, lat, sizeof(lat));
   P.pass.resize(L.pass.size());
   for (size_t p = 0; p < L.pass.size(); ++p) {
     const auto &q = L.pass[p];
@@ -760,10 +776,7 @@ void ensure_precision(rn_potgnn *h) {
       P.snap_edge[i].ensure(S * E * FeP * sizeof(T));
     }
   }
-  // frame-independent device precompute
-  launch_setup<T>(w + L.emb, w + L.W2, w + L.b2, w + L.W4, w + L.b4, h->cfg.num_atom_types, h->d,
-                  w + L.node_table, w + L.b0, w + L.bn_w, w + L.bn_b, w + L.bn_rm, w + L.bn_rv,
-                  w + L.scale0, w + L.shift0, P.lanes[0].stream);
+  device_setup<T>(h, w, P.lanes[0].stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(P.lanes[0].stream));
   P.ready = true;
@@ -811,27 +824,43 @@ void resolve_timers(rn_potgnn *h) {
   h->timed.clear();
 }
 
+// What an evaluation of S frames reads and writes: device arrays, frame-major; a null field is absent.
+template <typename T>
+struct ForwardIO {
+  const double *pos = nullptr;     // [S][N][3] fractional positions ...
+  const float *pos32 = nullptr;    // ... or, float32 evaluations only, the same as float32 (then pos is null)
+  double *alpha = nullptr;         // [S][9] polarizabilities
+  float *vec6 = nullptr;           // [S][6] standardised 6-vectors
+  double *alpha_raw = nullptr;     // [S][9] the standardised tensor in float64
+  const T *lat = nullptr;          // [S][9] per-frame lattices, or null: the reference structure's
+  const int *types = nullptr;      // [S][N] per-frame atom types, or null: the reference structure's
+  ForwardIO at(int64_t first, int N) const {  // the frames from `first` on: the one place that knows the strides
+    auto from = [first](auto *p, int64_t stride) { return p ? p + first * stride : nullptr; };
+    ForwardIO o;
+    o.pos = from(pos, 3 * (int64_t)N);
+    o.pos32 = from(pos32, 3 * (int64_t)N);
+    o.alpha = from(alpha, 9);
+    o.vec6 = from(vec6, 6);
+    o.alpha_raw = from(alpha_raw, 9);
+    o.lat = from(lat, 9);
+    o.types = from(types, N);
+    return o;
+  }
+};
+
 // One chunk of `S` frames on one lane, split into stages so that two chunks can be
 // interleaved (see forward_device).  Mirrors PotGNN.forward (_gnn.py:641-665).
 template <typename T>
 struct ChunkRun {
   rn_potgnn *h;
   Lane<T> *ln;
-  const double *d_pos;
-  const float *d_pos32 = nullptr;  // float32 evaluations: the chunk's positions as float32 (then d_pos is null)
+  ForwardIO<T> io;  // this chunk's slice
   int S;
-  double *d_alpha;
-  float *d_vec6;
-  double *d_alpha_raw;
-  const T *d_lat = nullptr;  // per-frame lattices [S][9] of this chunk, or null: the reference structure's
-  const int *d_types = nullptr;  // per-frame atom types [S][N] of this chunk, or null: the reference structure's
   int cur = 0;
   T *node[2], *edge[2], *unit4, *npc1, *np3, *bufA, *bufB, *c2;
   int64_t MN, ME;
 
-  ChunkRun(rn_potgnn *h_, Lane<T> &l, const double *pos, int S_, double *alpha, float *vec6,
-           double *alpha_raw)
-      : h(h_), ln(&l), d_pos(pos), S(S_), d_alpha(alpha), d_vec6(vec6), d_alpha_raw(alpha_raw) {
+  ChunkRun(rn_potgnn *h_, Lane<T> &l, const ForwardIO<T> &io_, int S_) : h(h_), ln(&l), io(io_), S(S_) {
     node[0] = l.node[0].template as<T>();
     node[1] = l.node[1].template as<T>();
     edge[0] = l.edge[0].template as<T>();
@@ -870,29 +899,37 @@ struct ChunkRun {
     {
       Timer t(h, st(), K_GEOM);
       bool done = false;
+      const T *lat = io.lat ? io.lat : P.lattice.template as<T>();
+      const int lat_stride = io.lat ? 9 : 0;
+      const T gauss = (T)h->cfg.gauss_coefficient;
       if constexpr (sizeof(T) == 4) {
-        if (d_pos32) {
-          const float *lat = d_lat ? d_lat : P.lattice.template as<T>();
-          if (pair_rows()) launch_geom_rbf_pairs_pos32(d_pos32, S, h->g, lat, d_lat ? 9 : 0, P.offsets, (T)h->cfg.gauss_coefficient, h->d, unit4, edge[0], st());
-          else launch_geom_rbf_pos32(d_pos32, S, h->g, lat, d_lat ? 9 : 0, P.offsets, (T)h->cfg.gauss_coefficient, h->d, unit4, edge[0], st(), narrow());
+        if (io.pos32) {
+          if (pair_rows()) launch_geom_rbf_pairs_pos32(io.pos32, S, h->g, lat, lat_stride, P.offsets, gauss, h->d, unit4, edge[0], st());
+          else launch_geom_rbf_pos32(io.pos32, S, h->g, lat, lat_stride, P.offsets, gauss, h->d, unit4, edge[0], st(), narrow());
           done = true;
         } else if (pair_rows()) {
-          launch_geom_rbf_pairs(d_pos, S, h->g, d_lat ? d_lat : P.lattice.template as<T>(), d_lat ? 9 : 0, P.offsets,
-                                (T)h->cfg.gauss_coefficient, h->d, unit4, edge[0], st());
+          launch_geom_rbf_pairs(io.pos, S, h->g, lat, lat_stride, P.offsets, gauss, h->d, unit4, edge[0], st());
           done = true;
         }
       }
-      if (!done)
-        launch_geom_rbf<T>(d_pos, S, h->g, d_lat ? d_lat : P.lattice.template as<T>(), d_lat ? 9 : 0,
-                           P.offsets, (T)h->cfg.gauss_coefficient, h->d, unit4, edge[0], st(), narrow());
+      if (!done) launch_geom_rbf<T>(io.pos, S, h->g, lat, lat_stride, P.offsets, gauss, h->d, unit4, edge[0], st(), narrow());
       h->last_in_order = narrow();  // (kernels_narrow.hip: edge rows in (b, a) order; rn_potgnn_debug_stage undoes it)
     }
     {
       Timer t(h, st(), K_NODE_INIT);
-      launch_node_init<T>(P.node_table, S, h->g, h->d, node[0], d_types, st());
+      launch_node_init<T>(P.node_table, S, h->g, h->d, node[0], io.types, st());
     }
     cur = 0;
     snapshot(0);
+  }
+
+  // begin + every pass: what is left is finish(), or the reverse pass over the tape
+  void run_stages() {
+    begin();
+    for (int p = 0; p < h->cfg.num_message_passes; ++p) {
+      stage_project(p);
+      stage_aggregate(p);
+    }
   }
 
   // "G" stage of pass p: NodeBlock + every dense projection the EdgeBlock needs
@@ -1041,7 +1078,7 @@ struct ChunkRun {
       if (narrow()) {  // readout MLP + edge tensors + per-frame mean in one launch
         Timer t(h, st(), K_READOUT_MLP);
         const double *ms = h->d_mean_std.as<double>();
-        launch_readout_narrow(edge[cur], unit4, S, g, d, P.ro, ms, ms + 9, d_vec6, d_alpha, d_alpha_raw,
+        launch_readout_narrow(edge[cur], unit4, S, g, d, P.ro, ms, ms + 9, io.vec6, io.alpha, io.alpha_raw,
                               h->keep_stages ? bufA : nullptr, st());
         HIP_TRY(hipGetLastError());
         return;
@@ -1070,7 +1107,7 @@ struct ChunkRun {
     {
       Timer t(h, st(), K_READOUT_REDUCE);
       const double *ms = h->d_mean_std.as<double>();
-      launch_readout_reduce<T>(bufA, unit4, S, g, ms, ms + 9, d_vec6, d_alpha, d_alpha_raw, st(), pol_stride);
+      launch_readout_reduce<T>(bufA, unit4, S, g, ms, ms + 9, io.vec6, io.alpha, io.alpha_raw, st(), pol_stride);
     }
     HIP_TRY(hipGetLastError());
   }
@@ -1107,17 +1144,8 @@ struct ChunkRun {
 };
 
 template <typename T>
-void run_chunk(rn_potgnn *h, Lane<T> &ln, const double *d_pos, int S, double *d_alpha,
-               float *d_vec6, double *d_alpha_raw, const T *d_lat, const int *d_types, const float *d_pos32 = nullptr) {
-  ChunkRun<T> c(h, ln, d_pos, S, d_alpha, d_vec6, d_alpha_raw);
-  c.d_lat = d_lat;
-  c.d_types = d_types;
-  c.d_pos32 = d_pos32;
-  c.begin();
-  for (int p = 0; p < h->cfg.num_message_passes; ++p) {
-    c.stage_project(p);
-    c.stage_aggregate(p);
-  }
+void run_chunk(ChunkRun<T> c) {
+  c.run_stages();
   c.finish();
 }
 
@@ -1198,25 +1226,34 @@ void check_ps_fail(rn_potgnn *h) {
   throw HipError{hipErrorLaunchFailure, which[fail >= 0 && fail <= 6 ? fail : 0]};
 }
 
+// The bracket around work the handle's lanes do for a caller's stream.  behind_caller: the first `n` lanes start behind
+// what `user` holds so far.  hand_back: `user` continues behind what they hold now; with `sync` it is synchronised and the
+// EdgeBlock's time-out word is read (an evaluation resolves its kernel timers there too: `timers`).
 template <typename T>
-void forward_device(rn_potgnn *h, const double *d_pos, int64_t S, double *d_alpha, float *d_vec6,
-                    double *d_alpha_raw, hipStream_t user, bool sync, const T *d_lat = nullptr,
-                    const int *d_types = nullptr, const float *d_pos32 = nullptr /* instead of d_pos: float32 positions */) {
+void behind_caller(rn_potgnn *h, hipStream_t user, Lane<T> *lanes, int n) {
+  HIP_TRY(hipEventRecord(h->ev_start, user));
+  for (int l = 0; l < n; ++l) HIP_TRY(hipStreamWaitEvent(lanes[l].stream, h->ev_start, 0));
+}
+template <typename T>
+void hand_back(rn_potgnn *h, hipStream_t user, Lane<T> *lanes, int n, bool sync, bool timers = false) {
+  for (int l = 0; l < n; ++l) {
+    HIP_TRY(hipEventRecord(lanes[l].done, lanes[l].stream));
+    HIP_TRY(hipStreamWaitEvent(user, lanes[l].done, 0));
+  }
+  if (!sync) return;
+  HIP_TRY(hipStreamSynchronize(user));
+  if (timers) resolve_timers(h);
+  check_ps_fail(h);
+}
+
+template <typename T>
+void forward_device(rn_potgnn *h, const ForwardIO<T> &io, int64_t S, hipStream_t user, bool sync) {
   ensure_precision<T>(h);
   Precision<T> &P = prec<T>(h);
   const int N = h->cfg.num_atoms;
-  HIP_TRY(hipEventRecord(h->ev_start, user));
   const int lanes = h->plan.num_lanes;
-  for (int l = 0; l < lanes; ++l) HIP_TRY(hipStreamWaitEvent(P.lanes[l].stream, h->ev_start, 0));
-  auto make = [&](int lane, int64_t first, int s) {
-    ChunkRun<T> c(h, P.lanes[lane], d_pos ? d_pos + first * N * 3 : nullptr, s,
-                  d_alpha ? d_alpha + first * 9 : nullptr, d_vec6 ? d_vec6 + first * 6 : nullptr,
-                  d_alpha_raw ? d_alpha_raw + first * 9 : nullptr);
-    c.d_pos32 = d_pos32 ? d_pos32 + first * N * 3 : nullptr;
-    c.d_lat = d_lat ? d_lat + first * 9 : nullptr;
-    c.d_types = d_types ? d_types + first * N : nullptr;
-    return c;
-  };
+  behind_caller(h, user, P.lanes, lanes);
+  auto make = [&](int lane, int64_t first, int s) { return ChunkRun<T>(h, P.lanes[lane], io.at(first, N), s); };
   int64_t done = 0;
   // Work chunks of EQUAL size: as many as the workspace demands, the frames split evenly among them (10 000 frames at a
   // capacity of 2344: five launches of 2000 instead of four of 2344 and one of 624, whose persistent workgroups idle through
@@ -1237,24 +1274,13 @@ void forward_device(rn_potgnn *h, const double *d_pos, int64_t S, double *d_alph
       done += both;
     } else {
       const int s = (int)std::min<int64_t>(chunk, left);
-      run_chunk<T>(h, P.lanes[0], d_pos ? d_pos + done * N * 3 : nullptr, s, d_alpha ? d_alpha + done * 9 : nullptr,
-                   d_vec6 ? d_vec6 + done * 6 : nullptr, d_alpha_raw ? d_alpha_raw + done * 9 : nullptr,
-                   d_lat ? d_lat + done * 9 : nullptr, d_types ? d_types + done * N : nullptr,
-                   d_pos32 ? d_pos32 + done * N * 3 : nullptr);
+      run_chunk(make(0, done, s));
       h->last_chunk_structs = s;
       done += s;
     }
   }
   h->last_was_f64 = sizeof(T) == 8;
-  for (int l = 0; l < lanes; ++l) {
-    HIP_TRY(hipEventRecord(P.lanes[l].done, P.lanes[l].stream));
-    HIP_TRY(hipStreamWaitEvent(user, P.lanes[l].done, 0));
-  }
-  if (sync) {
-    HIP_TRY(hipStreamSynchronize(user));
-    resolve_timers(h);
-    check_ps_fail(h);
-  }
+  hand_back(h, user, P.lanes, lanes, sync, true);
 }
 
 // Reverse pass over a taped forward of S frames with B cotangents per frame.
@@ -1457,15 +1483,15 @@ void reverse_pass(rn_potgnn *h, ChunkRun<T> &c, const Reverse<T> &rv) {
     P.type_sums.ensure((size_t)h->cfg.num_atom_types * d.Fn * sizeof(T));
     launch_node_embed_bwd<T>(b[DN0 + cur], S, g, d, h->cfg.num_atom_types, Wd + L.emb, Wd + L.W2, Wd + L.b2,
                              Wd + L.W4, G + L.emb, G + L.W2, G + L.b2, G + L.W4, G + L.b4,
-                             P.type_sums.template as<T>(), c.d_types, st);
+                             P.type_sums.template as<T>(), c.io.types, st);
   }
   if (rv.d_dpos)
     launch_geom_bwd<T>(b[DE0 + cur], b[DUNIT], unit4, P.lattice.template as<T>(), P.offsets,
                        (T)h->cfg.gauss_coefficient, C, B, g, d, rv.d_dpos, st);
   if (rv.in_dpos || rv.in_dlat) {
     P.in_dcart.ensure((size_t)C * E * 3 * sizeof(double));
-    launch_geom_input_bwd<T>(b[DE0 + cur], b[DUNIT], unit4, c.d_pos, c.d_lat ? c.d_lat : P.lattice.template as<T>(),
-                             c.d_lat ? 9 : 0, P.offsets, (T)h->cfg.gauss_coefficient, C, B, g, d,
+    launch_geom_input_bwd<T>(b[DE0 + cur], b[DUNIT], unit4, c.io.pos, c.io.lat ? c.io.lat : P.lattice.template as<T>(),
+                             c.io.lat ? 9 : 0, P.offsets, (T)h->cfg.gauss_coefficient, C, B, g, d,
                              P.in_dcart.template as<double>(), rv.in_dpos, rv.in_dlat, st);
   }
   HIP_TRY(hipGetLastError());
@@ -1491,19 +1517,13 @@ void ensure_tape(rn_potgnn *h, int S) {
 
 // forward of S frames on lane 0 with the per-pass embeddings recorded
 template <typename T>
-ChunkRun<T> taped_forward(rn_potgnn *h, const double *d_pos, int S, const T *d_lat = nullptr, const int *d_types = nullptr) {
+ChunkRun<T> taped_forward(rn_potgnn *h, const ForwardIO<T> &io /* pos, lat, types */, int S) {
   Precision<T> &P = prec<T>(h);
   ensure_tape<T>(h, S);
   P.tape_on = true;
-  ChunkRun<T> c(h, P.lanes[0], d_pos, S, nullptr, nullptr, nullptr);
-  c.d_lat = d_lat;      // [S][9] per-sample lattices or null (the reference structure's)
-  c.d_types = d_types;  // [S][N] per-sample atom types or null
+  ChunkRun<T> c(h, P.lanes[0], io, S);
   try {
-    c.begin();
-    for (int p = 0; p < h->cfg.num_message_passes; ++p) {
-      c.stage_project(p);
-      c.stage_aggregate(p);
-    }
+    c.run_stages();
   } catch (...) {
     P.tape_on = false;
     throw;
@@ -1518,12 +1538,11 @@ ChunkRun<T> taped_forward(rn_potgnn *h, const double *d_pos, int S, const T *d_l
 template <typename T>
 void jacobian(rn_potgnn *h, const double *host_pos, double *host_jac /*[6][N*3]*/) {
   ensure_precision<T>(h);
-  Precision<T> &P = prec<T>(h);
   const int N = h->g.N;
   h->train_S = 0;  // the tape and lane 0 are reused: a pending train_forward is void
-  h->io_pos.ensure((size_t)N * 3 * sizeof(double));
-  HIP_TRY(hipMemcpy(h->io_pos.p, host_pos, (size_t)N * 3 * sizeof(double), hipMemcpyHostToDevice));
-  ChunkRun<T> c = taped_forward<T>(h, h->io_pos.as<double>(), 1);
+  ForwardIO<T> io;
+  io.pos = stage<double>(h->io_pos, host_pos, (size_t)N * 3 * sizeof(double));
+  ChunkRun<T> c = taped_forward<T>(h, io, 1);
   hipStream_t st = c.st();
   DeviceBuf dposbuf, seeds;
   dposbuf.ensure((size_t)6 * N * 3 * sizeof(double));
@@ -1538,21 +1557,25 @@ void jacobian(rn_potgnn *h, const double *host_pos, double *host_jac /*[6][N*3]*
   HIP_TRY(hipStreamSynchronize(st));
   check_ps_fail(h);
   HIP_TRY(hipMemcpy(host_jac, dposbuf.p, (size_t)6 * N * 3 * sizeof(double), hipMemcpyDeviceToHost));
-  (void)P;
 }
 
 // Frames per taped chunk of the input-gradient entry: the handle's work chunk, further bounded so that the tape, lane 0's
 // full-width buffers and the reverse pass's workspace of one chunk stay within kTapeBudget bytes (38 MB per frame of
 // config 3's shape -- 256 atoms, 4608 edges, Fn = Fe = 64, four passes -- in float32: 111 frames a chunk).
 constexpr size_t kTapeBudget = (size_t)4 << 30;
+size_t tape_elems(const rn_potgnn *h) {  // the tape of one frame (ensure_tape)
+  const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges, NP = h->cfg.num_message_passes;
+  return (NP + 1) * (N * h->d.FnP + 2 * E * h->d.FeP);
+}
+size_t reverse_elems(const rn_potgnn *h) {  // the reverse pass's workspace for one cotangent row of one frame (reverse_pass: sizes)
+  const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges;
+  const size_t FnP = h->d.FnP, FeP = h->d.FeP, HP = std::max<size_t>(FeP, 32);
+  return E * (2 * FeP + 4 * FeP + std::max(2 * FeP, HP) + FnP + 2 * FnP + 32 + 4 + HP + 32) + N * (3 * FnP + 6 * FeP + 2 * FnP);
+}
 template <typename T>
 int tape_frames(const rn_potgnn *h) {
-  const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges, NP = h->cfg.num_message_passes;
-  const size_t FnP = h->d.FnP, FeP = h->d.FeP, HP = std::max<size_t>(FeP, 32);
-  const size_t tape = (NP + 1) * (N * FnP + 2 * E * FeP);
-  const size_t bw = E * (2 * FeP + 4 * FeP + std::max(2 * FeP, HP) + FnP + 2 * FnP + 32 + 4 + HP + 32) +
-                    N * (3 * FnP + 6 * FeP + 2 * FnP);
-  const size_t per = (tape + per_structure_elems(h, false) + bw) * sizeof(T) + E * 3 * sizeof(double);
+  const size_t E = h->cfg.num_edges;
+  const size_t per = (tape_elems(h) + per_structure_elems(h, false) + reverse_elems(h)) * sizeof(T) + E * 3 * sizeof(double);
   return (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk_frames<T>(h), kTapeBudget / std::max<size_t>(per, 1)));
 }
 
@@ -1567,18 +1590,19 @@ void forward_vjp(rn_potgnn *h, const double *d_lat /* [S][9] or null */, const i
   const int N = h->g.N;
   h->train_S = 0;  // the tape and lane 0 are reused: a pending train_forward is void
   hipStream_t st = P.lanes[0].stream;
-  HIP_TRY(hipEventRecord(h->ev_start, user));
-  HIP_TRY(hipStreamWaitEvent(st, h->ev_start, 0));
+  behind_caller(h, user, P.lanes, 1);
   const int chunk = tape_frames<T>(h);
   for (int64_t s0 = 0; s0 < S; s0 += chunk) {
     const int s = (int)std::min<int64_t>(chunk, S - s0);
-    const T *lat = nullptr;
+    ForwardIO<T> io;
+    io.pos = d_pos + s0 * N * 3;
+    io.types = d_types ? d_types + s0 * N : nullptr;
     if (d_lat) {  // in the arithmetic of the run, as the forward casts them
       P.in_lat.ensure((size_t)s * 9 * sizeof(T));
       launch_cast_from_f64<T>(d_lat + s0 * 9, P.in_lat.template as<T>(), (int64_t)s * 9, st);
-      lat = P.in_lat.template as<T>();
+      io.lat = P.in_lat.template as<T>();
     }
-    ChunkRun<T> c = taped_forward<T>(h, d_pos + s0 * N * 3, s, lat, d_types ? d_types + s0 * N : nullptr);
+    ChunkRun<T> c = taped_forward<T>(h, io, s);
     P.seeds.ensure((size_t)s * 6 * sizeof(T));
     launch_cast_from_f64<T>(d_dvec6 + s0 * 6, P.seeds.template as<T>(), (int64_t)s * 6, st);
     Reverse<T> rv{s, 1, P.seeds.template as<T>(), nullptr, nullptr, false};
@@ -1586,10 +1610,7 @@ void forward_vjp(rn_potgnn *h, const double *d_lat /* [S][9] or null */, const i
     rv.in_dlat = d_dlat ? d_dlat + s0 * 9 : nullptr;
     reverse_pass<T>(h, c, rv);
   }
-  HIP_TRY(hipEventRecord(P.lanes[0].done, st));
-  HIP_TRY(hipStreamWaitEvent(user, P.lanes[0].done, 0));
-  HIP_TRY(hipStreamSynchronize(user));
-  check_ps_fail(h);
+  hand_back(h, user, P.lanes, 1, true);
 }
 
 // ---- atom-group contractions (rn_potgnn_group_increments_device, rn_potgnn_partial_raman_tensors); G <= kMaxGroups (kernels.hpp)
@@ -1625,13 +1646,10 @@ bool set_group_labels(rn_potgnn *h, const int32_t *labels, int G) {
 // Jacobian rows carried over, within `limit` bytes; 0 when not even one frame fits.
 template <typename T>
 int group_frames(const rn_potgnn *h, size_t limit) {
-  const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges, NP = h->cfg.num_message_passes;
-  const size_t FnP = h->d.FnP, FeP = h->d.FeP, HP = std::max<size_t>(FeP, 32);
-  const size_t tape = (NP + 1) * (N * FnP + 2 * E * FeP);
-  const size_t bw = E * (2 * FeP + 4 * FeP + std::max(2 * FeP, HP) + FnP + 2 * FnP + 32 + 4 + HP + 32) +
-                    N * (3 * FnP + 6 * FeP + 2 * FnP);
+  const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges;
   const size_t rows = 6 * N * 3 * sizeof(double);
-  const size_t per = (tape + per_structure_elems(h, false) + 6 * bw + 36) * sizeof(T) + 6 * E * 3 * sizeof(double) + rows;
+  const size_t per = (tape_elems(h) + per_structure_elems(h, false) + 6 * reverse_elems(h) + 36) * sizeof(T) +
+                     6 * E * 3 * sizeof(double) + rows;
   if (limit < per + rows) return 0;
   return (int)std::min<size_t>((size_t)chunk_frames<T>(h), (limit - rows) / per);
 }
@@ -1650,7 +1668,9 @@ void jacobian_rows(rn_potgnn *h, const double *d_pos, int s, double *d_jac) {
     HIP_TRY(hipMemcpy(P.eye_seeds.p, eye.data(), eye.size() * sizeof(T), hipMemcpyHostToDevice));
     P.eye_frames = s;
   }
-  ChunkRun<T> c = taped_forward<T>(h, d_pos, s);
+  ForwardIO<T> io;
+  io.pos = d_pos;
+  ChunkRun<T> c = taped_forward<T>(h, io, s);
   Reverse<T> rv{s, 6, P.eye_seeds.template as<T>(), nullptr, nullptr, false};
   rv.in_dpos = d_jac;
   reverse_pass<T>(h, c, rv);
@@ -1669,8 +1689,7 @@ void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_
   if (F < 1) throw HipError{hipErrorOutOfMemory, "group_increments: one step does not fit the workspace limit"};
   h->train_S = 0;  // the tape and lane 0 are reused: a pending train_forward is void
   hipStream_t st = P.lanes[0].stream;
-  HIP_TRY(hipEventRecord(h->ev_start, user));
-  HIP_TRY(hipStreamWaitEvent(st, h->ev_start, 0));
+  behind_caller(h, user, P.lanes, 1);
   const int64_t rows = (int64_t)6 * N * 3;
   h->grp_jac.ensure((size_t)(F + 1) * rows * sizeof(double));
   double *jac = h->grp_jac.as<double>();
@@ -1685,10 +1704,7 @@ void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_
                             d_out + t0 * G * 9, st);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(P.lanes[0].done, st));
-  HIP_TRY(hipStreamWaitEvent(user, P.lanes[0].done, 0));
-  HIP_TRY(hipStreamSynchronize(user));
-  check_ps_fail(h);
+  hand_back(h, user, P.lanes, 1, true);
 }
 
 // ---- device-resident optimisation step: which entries of the packed blob are parameters, which are
@@ -1761,11 +1777,35 @@ void sync_host(rn_potgnn *h) {
   if (h->f64.ready) upload_weights<double>(h);
 }
 
+// Per-sample lattices [S][9] (cast to the arithmetic of the run: the reference's forward computes in its default dtype) and
+// atom types [S][N] of the host entries, into h->io_lat / h->io_types; null stays null.
+template <typename T>
+const T *stage_lattices(rn_potgnn *h, const double *lat, int64_t S) {
+  if (!lat) return nullptr;
+  if constexpr (sizeof(T) == 8) {
+    return stage<T>(h->io_lat, lat, (size_t)S * 9 * sizeof(double));
+  } else {
+    const std::vector<float> lat32(lat, lat + S * 9);
+    return stage<T>(h->io_lat, lat32.data(), lat32.size() * sizeof(float));
+  }
+}
+const int *stage_types(rn_potgnn *h, const int32_t *types, int64_t S) {
+  return types ? stage<int>(h->io_types, types, (size_t)S * h->cfg.num_atoms * sizeof(int32_t)) : nullptr;
+}
+
 // ---- training: forward with batch-statistics BatchNorm, then parameter gradients (float32 for
 // the product path; float64 for validating the reverse pass against float64 autograd)
 // The taped forward + the training-mode readout (batch-statistics BatchNorm) over the S structures whose positions (and, per
 // h->train_lat / h->train_types, lattices and atom types) sit in h->io_pos / io_lat / io_types; everything is enqueued on lane
 // 0's stream, the standardised 6-vectors end up in h->io_vec6 / io_alpha and the batch statistics in P.mv.
+template <typename T>
+ForwardIO<T> train_io(rn_potgnn *h) {  // what the pending (or starting) train_forward runs with
+  ForwardIO<T> io;
+  io.pos = h->io_pos.as<double>();
+  io.lat = h->train_lat ? h->io_lat.as<T>() : nullptr;
+  io.types = h->train_types ? h->io_types.as<int>() : nullptr;
+  return io;
+}
 template <typename T>
 ChunkRun<T> train_forward_core(rn_potgnn *h, int S) {
   Precision<T> &P = prec<T>(h);
@@ -1773,8 +1813,7 @@ ChunkRun<T> train_forward_core(rn_potgnn *h, int S) {
   const Graph &g = h->g;
   const Dims d = h->d;
   const int HP = std::max(d.FeP, 32);
-  ChunkRun<T> c = taped_forward<T>(h, h->io_pos.as<double>(), S, h->train_lat ? h->io_lat.as<T>() : nullptr,
-                                   h->train_types ? h->io_types.as<int>() : nullptr);
+  ChunkRun<T> c = taped_forward<T>(h, train_io<T>(h), S);
   hipStream_t st = c.st();
   const int64_t R = (int64_t)S * g.E;
   T *Wd = P.weights.template as<T>();
@@ -1829,9 +1868,7 @@ inline void train_running_stats(rn_potgnn *h, hipStream_t st) {
   after_other_lanes(h, st);
   launch_bn_running(Wd + L.bn_rm, Wd + L.bn_rv, P.mv.as<float>(), P.mv.as<float>() + HP, d.Fe, 0.1,
                     rows / std::max(rows - 1.0, 1.0), st);
-  launch_setup<float>(Wd + L.emb, Wd + L.W2, Wd + L.b2, Wd + L.W4, Wd + L.b4, h->cfg.num_atom_types, h->d,
-                      Wd + L.node_table, Wd + L.b0, Wd + L.bn_w, Wd + L.bn_b, Wd + L.bn_rm, Wd + L.bn_rv,
-                      Wd + L.scale0, Wd + L.shift0, st);
+  device_setup<float>(h, Wd, st);
   h->host_stale = true;
 }
 
@@ -1843,21 +1880,11 @@ void train_forward(rn_potgnn *h, const double *host_pos, int S, T *vec6, T *batc
   const Graph &g = h->g;
   const Dims d = h->d;
   const int HP = std::max(d.FeP, 32);
-  const size_t pb = (size_t)S * g.N * 3 * sizeof(double);
-  h->io_pos.ensure(pb);
-  HIP_TRY(hipMemcpy(h->io_pos.p, host_pos, pb, hipMemcpyHostToDevice));
+  stage<double>(h->io_pos, host_pos, (size_t)S * g.N * 3 * sizeof(double));
   // per-sample lattices (in the arithmetic of the run, as the reference's forward casts them) and atom types: the graph
   // topology stays the reference structure's (_gnn.py:603-611, 541-557)
-  if (host_lat) {
-    std::vector<T> lat((size_t)S * 9);
-    for (size_t i = 0; i < lat.size(); ++i) lat[i] = (T)host_lat[i];
-    h->io_lat.ensure(lat.size() * sizeof(T));
-    HIP_TRY(hipMemcpy(h->io_lat.p, lat.data(), lat.size() * sizeof(T), hipMemcpyHostToDevice));
-  }
-  if (host_types) {
-    h->io_types.ensure((size_t)S * g.N * sizeof(int32_t));
-    HIP_TRY(hipMemcpy(h->io_types.p, host_types, (size_t)S * g.N * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
+  stage_lattices<T>(h, host_lat, S);
+  stage_types(h, host_types, S);
   h->train_lat = host_lat != nullptr;
   h->train_types = host_types != nullptr;
   ChunkRun<T> c = train_forward_core<T>(h, S);
@@ -1899,8 +1926,7 @@ inline void train_forward_device(rn_potgnn *h, const double *d_pos, int S, const
   Precision<float> &P = h->f32;
   const Graph &g = h->g;
   hipStream_t st = P.lanes[0].stream;
-  HIP_TRY(hipEventRecord(h->ev_start, user));
-  HIP_TRY(hipStreamWaitEvent(st, h->ev_start, 0));
+  behind_caller(h, user, P.lanes, 1);
   const size_t pb = (size_t)S * g.N * 3 * sizeof(double);
   h->io_pos.ensure(pb);  // (the reverse pass reads the positions again)
   HIP_TRY(hipMemcpyAsync(h->io_pos.p, d_pos, pb, hipMemcpyDeviceToDevice, st));
@@ -1917,8 +1943,7 @@ inline void train_forward_device(rn_potgnn *h, const double *d_pos, int S, const
   (void)train_forward_core<float>(h, S);
   HIP_TRY(hipMemcpyAsync(d_vec6, h->io_vec6.p, (size_t)S * 6 * sizeof(float), hipMemcpyDeviceToDevice, st));
   train_running_stats(h, st);
-  HIP_TRY(hipEventRecord(P.lanes[0].done, st));
-  HIP_TRY(hipStreamWaitEvent(user, P.lanes[0].done, 0));
+  hand_back(h, user, P.lanes, 1, false);
   h->train_S = S;
   h->train_prec = 4;
 }
@@ -1933,16 +1958,12 @@ void train_backward(rn_potgnn *h, const T *dvec6, T *grads /* null: leave the gr
   const int S = h->train_S;
   if (S <= 0 || h->train_prec != (int)sizeof(T))
     throw HipError{hipErrorInvalidValue, "train_backward without a train_forward of the same precision"};
-  ChunkRun<T> c(h, P.lanes[0], h->io_pos.as<double>(), S, nullptr, nullptr, nullptr);
-  c.d_lat = h->train_lat ? h->io_lat.as<T>() : nullptr;      // what the pending train_forward ran with
-  c.d_types = h->train_types ? h->io_types.as<int>() : nullptr;
+  ChunkRun<T> c(h, P.lanes[0], train_io<T>(h), S);
   hipStream_t st = c.st();
-  DeviceBuf &seeds = P.seeds;
-  seeds.ensure((size_t)S * 6 * sizeof(T));
-  HIP_TRY(hipMemcpy(seeds.p, dvec6, (size_t)S * 6 * sizeof(T), hipMemcpyHostToDevice));
+  const T *seeds = stage<T>(P.seeds, dvec6, (size_t)S * 6 * sizeof(T));
   P.grad.ensure(h->lay.total * sizeof(T));
   HIP_TRY(hipMemsetAsync(P.grad.p, 0, h->lay.total * sizeof(T), st));
-  Reverse<T> rv{S, 1, seeds.template as<T>(), nullptr, P.grad.template as<T>(), true};
+  Reverse<T> rv{S, 1, seeds, nullptr, P.grad.template as<T>(), true};
   const size_t npos = (size_t)S * h->g.N * 3;
   if (host_dpos || host_dlat) {  // input gradients from the same reverse pass (device scratch, copied out below)
     P.in_grads.ensure((npos + (size_t)S * 9) * sizeof(double));
@@ -1970,12 +1991,9 @@ inline void train_backward_device(rn_potgnn *h, const float *d_dvec6, hipStream_
   const int S = h->train_S;
   if (S <= 0 || h->train_prec != 4)
     throw HipError{hipErrorInvalidValue, "train_backward without a train_forward of the same precision"};
-  ChunkRun<float> c(h, P.lanes[0], h->io_pos.as<double>(), S, nullptr, nullptr, nullptr);
-  c.d_lat = h->train_lat ? h->io_lat.as<float>() : nullptr;
-  c.d_types = h->train_types ? h->io_types.as<int>() : nullptr;
+  ChunkRun<float> c(h, P.lanes[0], train_io<float>(h), S);
   hipStream_t st = c.st();
-  HIP_TRY(hipEventRecord(h->ev_start, user));
-  HIP_TRY(hipStreamWaitEvent(st, h->ev_start, 0));
+  behind_caller(h, user, P.lanes, 1);
   P.seeds.ensure((size_t)S * 6 * sizeof(float));
   HIP_TRY(hipMemcpyAsync(P.seeds.p, d_dvec6, (size_t)S * 6 * sizeof(float), hipMemcpyDeviceToDevice, st));
   P.grad.ensure(h->lay.total * sizeof(float));
@@ -1984,8 +2002,7 @@ inline void train_backward_device(rn_potgnn *h, const float *d_dvec6, hipStream_
   rv.in_dpos = d_dpos;  // (input gradients, when asked for, from the same reverse pass)
   rv.in_dlat = d_dlat;
   reverse_pass<float>(h, c, rv);
-  HIP_TRY(hipEventRecord(P.lanes[0].done, st));
-  HIP_TRY(hipStreamWaitEvent(user, P.lanes[0].done, 0));
+  hand_back(h, user, P.lanes, 1, false);
   h->train_S = 0;
   h->grads_on_device = true;
 }
@@ -2094,6 +2111,107 @@ int guarded(rn_potgnn *h, const std::function<void()> &fn) {
   } catch (...) {
     set_error(h, "internal error: unknown exception");
     return RN_ERR_HIP;
+  }
+}
+
+// ---- what the entries share: argument checks (each returns kGo, or the status the entry returns at once) and lazily
+// created streams / events
+
+constexpr int kGo = 1;  // (no rn_status is positive)
+
+int refuse(rn_potgnn *h, const char *text) {
+  set_error(h, "%s", text);
+  return RN_ERR_INVALID_ARGUMENT;
+}
+
+// A batch of S >= 0 frames: refused with `text` when S is negative or, for S > 0, one of `needed` is null; an empty batch is
+// RN_OK with nothing touched.  (A null handle is refused without a text: there is nowhere to keep one.)
+int check_batch(rn_potgnn *h, int64_t S, std::initializer_list<const void *> needed, const char *text) {
+  if (!h) return RN_ERR_INVALID_ARGUMENT;
+  bool ok = S >= 0;
+  if (S > 0)
+    for (const void *p : needed) ok = ok && p;
+  if (!ok) return refuse(h, text);
+  return S == 0 ? RN_OK : kGo;
+}
+
+int check_types(rn_potgnn *h, const int32_t *atom_types, int64_t S) {
+  if (!atom_types) return kGo;
+  const size_t SN = (size_t)S * h->cfg.num_atoms;
+  for (size_t i = 0; i < SN; ++i)
+    if (atom_types[i] < 0 || atom_types[i] >= h->cfg.num_atom_types) {
+      set_error(h, "atom type %d of sample %zu, atom %zu is outside [0,%d)", atom_types[i], i / h->cfg.num_atoms,
+                i % h->cfg.num_atoms, h->cfg.num_atom_types);
+      return RN_ERR_INVALID_ARGUMENT;
+    }
+  return kGo;
+}
+
+// The training entries read handle state in their checks: they take the handle's lock there and keep it through their
+// guarded() (`hold` lives in the entry).
+struct Checked {
+  int rc;
+  std::unique_lock<std::recursive_mutex> hold;
+};
+
+// Which training step an entry belongs to: float32 or float64 through host buffers, or the device-resident float32 one
+// (which needs rn_potgnn_set_device_training).
+enum TrainKind { kHostF32, kHostF64, kDeviceF32 };
+
+// A train_forward entry `name`: every pointer of `needed` given, 1 <= S <= the chunk of its precision and, for the
+// device-resident form, device training switched on.
+Checked check_train_batch(rn_potgnn *h, int64_t S, std::initializer_list<const void *> needed, const char *name,
+                          TrainKind kind) {
+  const bool f64 = kind == kHostF64, device = kind == kDeviceF32;
+  bool ok = h && S > 0;
+  for (const void *p : needed) ok = ok && p;
+  if (!ok) {
+    set_error(h, "invalid arguments to %s", name);
+    return {RN_ERR_INVALID_ARGUMENT, {}};
+  }
+  Checked c{kGo, std::unique_lock<std::recursive_mutex>(h->lock)};
+  if (device && !h->device_training) {
+    set_error(h, "%s needs device-resident training (rn_potgnn_set_device_training)", name);
+    c.rc = RN_ERR_INVALID_ARGUMENT;
+  } else if (f64 && S > chunk_frames<double>(h)) {
+    set_error(h, "training batch of %lld frames exceeds the float64 chunk of %d frames", (long long)S, chunk_frames<double>(h));
+    c.rc = RN_ERR_INVALID_ARGUMENT;
+  } else if (!f64 && S > h->chunk) {
+    set_error(h, "training batch of %lld frames exceeds max_chunk_structures = %d", (long long)S, h->chunk);
+    c.rc = RN_ERR_INVALID_ARGUMENT;
+  }
+  return c;
+}
+
+// A backward entry (`args_ok`: its own null-pointer rule; `name` for that text): the pending train_forward must have run in
+// the precision of `kind` -- and, device-resident, with device training on -- else `text`.
+Checked check_pending(rn_potgnn *h, bool args_ok, const char *name, TrainKind kind, const char *text) {
+  const int prec_bytes = kind == kHostF64 ? 8 : 4;
+  const bool device = kind == kDeviceF32;
+  if (!h || !args_ok) {
+    set_error(h, "invalid arguments to %s", name);
+    return {RN_ERR_INVALID_ARGUMENT, {}};
+  }
+  Checked c{kGo, std::unique_lock<std::recursive_mutex>(h->lock)};
+  if ((device && !h->device_training) || h->train_S <= 0 || h->train_prec != prec_bytes) c.rc = refuse(h, text);
+  return c;
+}
+
+void lazy_stream(hipStream_t &s) {
+  if (!s) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+}
+void lazy_event(hipEvent_t &e) {
+  if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+}
+
+// fn(T{}) in the precision asked for; float64 first brings the host master copy, from which its weights are made, up to date
+template <typename F>
+void with_precision(rn_potgnn *h, bool use_float64, F fn) {
+  if (use_float64) {
+    sync_host(h);
+    fn(double{});
+  } else {
+    fn(float{});
   }
 }
 }  // namespace
@@ -2338,8 +2456,8 @@ static void cast_to_float(const double *src, float *dst, size_t n) {
 static void staged_forward(rn_potgnn *h, const double *positions, int64_t S, double *d_alpha, bool sync) {
   const size_t per_frame = (size_t)h->cfg.num_atoms * 3;
   const int64_t chunk = std::max<int64_t>(1, h->chunk);
-  if (!h->exec_stream) HIP_TRY(hipStreamCreateWithFlags(&h->exec_stream, hipStreamNonBlocking));
-  if (!h->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+  lazy_stream(h->exec_stream);
+  lazy_stream(h->copy_stream);
   // Pieces are whole work chunks: a batch that fits one chunk goes through in ONE piece.  Measured on config 3's 1250-frame
   // share of an 8-GPU run (profiles/r06/host_boundary.txt): with the positions crossing as float32 from page-locked memory the
   // cast + copy of the whole block is 0.3 ms of 20, and every extra launch of the persistent kernels costs more in tails than
@@ -2363,7 +2481,7 @@ static void staged_forward(rn_potgnn *h, const double *positions, int64_t S, dou
       if (hs.pin[b]) (void)hipHostFree(hs.pin[b]);
       hs.pin[b] = nullptr;
       HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&hs.pin[b]), (size_t)piece * per_frame * sizeof(float), hipHostMallocDefault));
-      if (!hs.copied[b]) HIP_TRY(hipEventCreateWithFlags(&hs.copied[b], hipEventDisableTiming));
+      lazy_event(hs.copied[b]);
     }
     hs.elems = (size_t)piece * per_frame;
   }
@@ -2389,10 +2507,12 @@ static void staged_forward(rn_potgnn *h, const double *positions, int64_t S, dou
                            h->copy_stream));
     HIP_TRY(hipEventRecord(hs.copied[b], h->copy_stream));
     HIP_TRY(hipStreamWaitEvent(h->exec_stream, hs.copied[b], 0));
-    forward_device<float>(h, nullptr, n, d_alpha + first * 9, nullptr, nullptr, h->exec_stream, sync && first + n >= S,
-                          nullptr, nullptr, d_pos32 + first * per_frame);
+    ForwardIO<float> io;
+    io.pos32 = d_pos32 + first * per_frame;
+    io.alpha = d_alpha + first * 9;
+    forward_device<float>(h, io, n, h->exec_stream, sync && first + n >= S);
   }
-  if (!hs.done) HIP_TRY(hipEventCreateWithFlags(&hs.done, hipEventDisableTiming));
+  lazy_event(hs.done);
   HIP_TRY(hipEventRecord(hs.done, h->exec_stream));  // (everything this call enqueued, on every lane, precedes it)
   if (timing)
     fprintf(stderr, "[host timing] S=%lld pieces=%zu total %.0f us: cast %.0f, buffer waits %.0f, rest (enqueue%s) %.0f\n", (long long)S,
@@ -2401,44 +2521,35 @@ static void staged_forward(rn_potgnn *h, const double *positions, int64_t S, dou
 
 int rn_potgnn_forward_device(rn_potgnn *h, const double *d_positions, int64_t S, double *d_alpha,
                              float *d_vec6, void *stream, int synchronize) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && !d_positions)) {
-    set_error(h, "invalid positions / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
+  if (const int rc = check_batch(h, S, {d_positions}, "invalid positions / S"); rc != kGo) return rc;
   return guarded(h, [&]() {
-    forward_device<float>(h, d_positions, S, d_alpha, d_vec6, nullptr, (hipStream_t)stream,
-                          synchronize != 0);
+    ForwardIO<float> io;
+    io.pos = d_positions;
+    io.alpha = d_alpha;
+    io.vec6 = d_vec6;
+    forward_device<float>(h, io, S, (hipStream_t)stream, synchronize != 0);
   });
 }
 
 int rn_potgnn_forward_device_f64(rn_potgnn *h, const double *d_positions, int64_t S, double *d_alpha,
                                  void *stream, int synchronize) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!d_positions || !d_alpha))) {
-    set_error(h, "invalid positions / alpha / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
+  if (const int rc = check_batch(h, S, {d_positions, d_alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
   return guarded(h, [&]() {
     sync_host(h);  // the float64 copy of the weights is made from the host master copy
-    forward_device<double>(h, d_positions, S, d_alpha, nullptr, nullptr, (hipStream_t)stream, synchronize != 0);
+    ForwardIO<double> io;
+    io.pos = d_positions;
+    io.alpha = d_alpha;
+    forward_device<double>(h, io, S, (hipStream_t)stream, synchronize != 0);
   });
 }
 
 int rn_potgnn_calc_polarizabilities(rn_potgnn *h, const double *positions, int64_t S,
                                     double *alpha) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!positions || !alpha))) {
-    set_error(h, "invalid positions / alpha / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
+  if (const int rc = check_batch(h, S, {positions, alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
   return guarded(h, [&]() {
     const size_t per_frame = (size_t)h->cfg.num_atoms * 3;
     h->io_alpha.ensure((size_t)S * 9 * sizeof(double));
-    if (!h->exec_stream) HIP_TRY(hipStreamCreateWithFlags(&h->exec_stream, hipStreamNonBlocking));
+    lazy_stream(h->exec_stream);
     const int64_t chunk = std::max<int64_t>(1, h->chunk);
     static const bool stage_f32 = !(getenv("RN_POTGNN_HOST_F32") && atoi(getenv("RN_POTGNN_HOST_F32")) == 0);
     if (!stage_f32) {
@@ -2448,7 +2559,10 @@ int rn_potgnn_calc_polarizabilities(rn_potgnn *h, const double *positions, int64
         const int64_t n = std::min<int64_t>(chunk, S - first);
         double *d_pos = h->io_pos.as<double>() + first * per_frame;
         HIP_TRY(hipMemcpy(d_pos, positions + first * per_frame, (size_t)n * per_frame * sizeof(double), hipMemcpyHostToDevice));
-        forward_device<float>(h, d_pos, n, h->io_alpha.as<double>() + first * 9, nullptr, nullptr, h->exec_stream, first + n >= S);
+        ForwardIO<float> io;
+        io.pos = d_pos;
+        io.alpha = h->io_alpha.as<double>() + first * 9;
+        forward_device<float>(h, io, n, h->exec_stream, first + n >= S);
       }
       HIP_TRY(hipMemcpy(alpha, h->io_alpha.p, (size_t)S * 9 * sizeof(double), hipMemcpyDeviceToHost));
       return;
@@ -2479,18 +2593,13 @@ int rn_potgnn_calc_polarizabilities(rn_potgnn *h, const double *positions, int64
 }
 
 int rn_potgnn_calc_polarizabilities_to_device(rn_potgnn *h, const double *positions, int64_t S, double *d_alpha, void *stream) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!positions || !d_alpha))) {
-    set_error(h, "invalid positions / d_alpha / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
+  if (const int rc = check_batch(h, S, {positions, d_alpha}, "invalid positions / d_alpha / S"); rc != kGo) return rc;
   return guarded(h, [&]() {
     // The evaluation starts behind what the caller queued on `stream` before the call: an earlier reader of d_alpha (the
     // previous all-gather on the same tensor, the last user of a block torch's caching allocator handed out again).
     auto &hs = h->hstage;
-    if (!h->exec_stream) HIP_TRY(hipStreamCreateWithFlags(&h->exec_stream, hipStreamNonBlocking));
-    if (!hs.caller) HIP_TRY(hipEventCreateWithFlags(&hs.caller, hipEventDisableTiming));
+    lazy_stream(h->exec_stream);
+    lazy_event(hs.caller);
     HIP_TRY(hipEventRecord(hs.caller, (hipStream_t)stream));
     HIP_TRY(hipStreamWaitEvent(h->exec_stream, hs.caller, 0));
     staged_forward(h, positions, S, d_alpha, false);
@@ -2500,36 +2609,26 @@ int rn_potgnn_calc_polarizabilities_to_device(rn_potgnn *h, const double *positi
 }
 
 int rn_potgnn_calc_polarizabilities_f64(rn_potgnn *h, const double *positions, int64_t S, double *alpha) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!positions || !alpha))) {
-    set_error(h, "invalid positions / alpha / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
+  if (const int rc = check_batch(h, S, {positions, alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
   return guarded(h, [&]() {
     sync_host(h);  // the float64 copy of the weights is made from the host master copy
-    const size_t pb = (size_t)S * h->cfg.num_atoms * 3 * sizeof(double);
-    h->io_pos.ensure(pb);
+    ForwardIO<double> io;
+    io.pos = stage<double>(h->io_pos, positions, (size_t)S * h->cfg.num_atoms * 3 * sizeof(double));
     h->io_alpha.ensure((size_t)S * 9 * sizeof(double));
-    HIP_TRY(hipMemcpy(h->io_pos.p, positions, pb, hipMemcpyHostToDevice));
-    forward_device<double>(h, h->io_pos.as<double>(), S, h->io_alpha.as<double>(), nullptr, nullptr, nullptr, true);
+    io.alpha = h->io_alpha.as<double>();
+    forward_device<double>(h, io, S, nullptr, true);
     HIP_TRY(hipMemcpy(alpha, h->io_alpha.p, (size_t)S * 9 * sizeof(double), hipMemcpyDeviceToHost));
   });
 }
 
 int rn_potgnn_calc_polarizabilities_async(rn_potgnn *h, const double *positions, int64_t S, double *alpha) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!positions || !alpha))) {
-    set_error(h, "invalid positions / alpha / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
+  if (const int rc = check_batch(h, S, {positions, alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
   return guarded(h, [&]() {
-    if (!h->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    if (!h->exec_stream) HIP_TRY(hipStreamCreateWithFlags(&h->exec_stream, hipStreamNonBlocking));
-    for (auto &sl : h->slots) {  // (the streams may exist already: the synchronous host entry uses them too)
-      if (!sl.copied) HIP_TRY(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
-      if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    lazy_stream(h->copy_stream);  // (the streams may exist already: the synchronous host entry uses them too)
+    lazy_stream(h->exec_stream);
+    for (auto &sl : h->slots) {
+      lazy_event(sl.copied);
+      lazy_event(sl.done);
     }
     auto &sl = h->slots[h->next_slot];
     h->next_slot ^= 1;
@@ -2540,8 +2639,10 @@ int rn_potgnn_calc_polarizabilities_async(rn_potgnn *h, const double *positions,
     HIP_TRY(hipMemcpyAsync(sl.pos.p, positions, pb, hipMemcpyHostToDevice, h->copy_stream));
     HIP_TRY(hipEventRecord(sl.copied, h->copy_stream));
     HIP_TRY(hipStreamWaitEvent(h->exec_stream, sl.copied, 0));
-    forward_device<float>(h, sl.pos.as<double>(), S, sl.alpha.as<double>(), nullptr, nullptr, h->exec_stream,
-                          false);
+    ForwardIO<float> io;
+    io.pos = sl.pos.as<double>();
+    io.alpha = sl.alpha.as<double>();
+    forward_device<float>(h, io, S, h->exec_stream, false);
     HIP_TRY(hipMemcpyAsync(alpha, sl.alpha.p, (size_t)S * 9 * sizeof(double), hipMemcpyDeviceToHost,
                            h->exec_stream));
     HIP_TRY(hipEventRecord(sl.done, h->exec_stream));
@@ -2581,114 +2682,45 @@ void rn_host_buffer_free(void *p) {
 }
 
 int rn_potgnn_forward(rn_potgnn *h, const double *positions, int64_t S, float *vec6) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!positions || !vec6))) {
-    set_error(h, "invalid positions / vec6 / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
-  return guarded(h, [&]() {
-    const size_t pb = (size_t)S * h->cfg.num_atoms * 3 * sizeof(double);
-    h->io_pos.ensure(pb);
-    h->io_vec6.ensure((size_t)S * 6 * sizeof(float));
-    HIP_TRY(hipMemcpy(h->io_pos.p, positions, pb, hipMemcpyHostToDevice));
-    forward_device<float>(h, h->io_pos.as<double>(), S, nullptr, h->io_vec6.as<float>(), nullptr,
-                          nullptr, true);
-    HIP_TRY(hipMemcpy(vec6, h->io_vec6.p, (size_t)S * 6 * sizeof(float), hipMemcpyDeviceToHost));
-  });
+  return rn_potgnn_forward_samples(h, nullptr, nullptr, positions, S, vec6);
 }
 
 int rn_potgnn_forward_lattices(rn_potgnn *h, const double *lattices, const double *positions, int64_t S,
                                float *vec6) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!lattices || !positions || !vec6))) {
-    set_error(h, "invalid lattices / positions / vec6 / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
-  return guarded(h, [&]() {
-    const size_t pb = (size_t)S * h->cfg.num_atoms * 3 * sizeof(double);
-    std::vector<float> lat32((size_t)S * 9);  // the reference's forward computes in float32
-    for (size_t i = 0; i < lat32.size(); ++i) lat32[i] = (float)lattices[i];
-    h->io_pos.ensure(pb);
-    h->io_lat.ensure(lat32.size() * sizeof(float));
-    h->io_vec6.ensure((size_t)S * 6 * sizeof(float));
-    HIP_TRY(hipMemcpy(h->io_pos.p, positions, pb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->io_lat.p, lat32.data(), lat32.size() * sizeof(float), hipMemcpyHostToDevice));
-    forward_device<float>(h, h->io_pos.as<double>(), S, nullptr, h->io_vec6.as<float>(), nullptr,
-                          nullptr, true, h->io_lat.as<float>());
-    HIP_TRY(hipMemcpy(vec6, h->io_vec6.p, (size_t)S * 6 * sizeof(float), hipMemcpyDeviceToHost));
-  });
+  if (const int rc = check_batch(h, S, {lattices, positions, vec6}, "invalid lattices / positions / vec6 / S"); rc != kGo) return rc;
+  return rn_potgnn_forward_samples(h, lattices, nullptr, positions, S, vec6);
 }
 
 int rn_potgnn_forward_samples(rn_potgnn *h, const double *lattices, const int32_t *atom_types,
                               const double *positions, int64_t S, float *vec6) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!positions || !vec6))) {
-    set_error(h, "invalid positions / vec6 / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
-  const size_t SN = (size_t)S * h->cfg.num_atoms;
-  if (atom_types)
-    for (size_t i = 0; i < SN; ++i)
-      if (atom_types[i] < 0 || atom_types[i] >= h->cfg.num_atom_types) {
-        set_error(h, "atom type %d of sample %zu, atom %zu is outside [0,%d)", atom_types[i],
-                  i / h->cfg.num_atoms, i % h->cfg.num_atoms, h->cfg.num_atom_types);
-        return RN_ERR_INVALID_ARGUMENT;
-      }
+  if (const int rc = check_batch(h, S, {positions, vec6}, "invalid positions / vec6 / S"); rc != kGo) return rc;
+  if (const int rc = check_types(h, atom_types, S); rc != kGo) return rc;
   return guarded(h, [&]() {
-    h->io_pos.ensure(SN * 3 * sizeof(double));
+    ForwardIO<float> io;
+    io.pos = stage<double>(h->io_pos, positions, (size_t)S * h->cfg.num_atoms * 3 * sizeof(double));
+    io.lat = stage_lattices<float>(h, lattices, S);  // the reference's forward computes in float32
+    io.types = stage_types(h, atom_types, S);
     h->io_vec6.ensure((size_t)S * 6 * sizeof(float));
-    HIP_TRY(hipMemcpy(h->io_pos.p, positions, SN * 3 * sizeof(double), hipMemcpyHostToDevice));
-    if (lattices) {
-      std::vector<float> lat32((size_t)S * 9);  // the reference's forward computes in float32
-      for (size_t i = 0; i < lat32.size(); ++i) lat32[i] = (float)lattices[i];
-      h->io_lat.ensure(lat32.size() * sizeof(float));
-      HIP_TRY(hipMemcpy(h->io_lat.p, lat32.data(), lat32.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (atom_types) {
-      h->io_types.ensure(SN * sizeof(int32_t));
-      HIP_TRY(hipMemcpy(h->io_types.p, atom_types, SN * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    forward_device<float>(h, h->io_pos.as<double>(), S, nullptr, h->io_vec6.as<float>(), nullptr, nullptr, true,
-                          lattices ? h->io_lat.as<float>() : nullptr, atom_types ? h->io_types.as<int>() : nullptr);
+    io.vec6 = h->io_vec6.as<float>();
+    forward_device<float>(h, io, S, nullptr, true);
     HIP_TRY(hipMemcpy(vec6, h->io_vec6.p, (size_t)S * 6 * sizeof(float), hipMemcpyDeviceToHost));
   });
 }
 
 int rn_potgnn_forward_samples_f64(rn_potgnn *h, const double *lattices, const int32_t *atom_types,
                                   const double *positions, int64_t S, double *vec6) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!positions || !vec6))) {
-    set_error(h, "invalid positions / vec6 / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
-  const size_t SN = (size_t)S * h->cfg.num_atoms;
-  if (atom_types)
-    for (size_t i = 0; i < SN; ++i)
-      if (atom_types[i] < 0 || atom_types[i] >= h->cfg.num_atom_types) {
-        set_error(h, "atom type %d of sample %zu, atom %zu is outside [0,%d)", atom_types[i],
-                  i / h->cfg.num_atoms, i % h->cfg.num_atoms, h->cfg.num_atom_types);
-        return RN_ERR_INVALID_ARGUMENT;
-      }
+  if (const int rc = check_batch(h, S, {positions, vec6}, "invalid positions / vec6 / S"); rc != kGo) return rc;
+  if (const int rc = check_types(h, atom_types, S); rc != kGo) return rc;
   return guarded(h, [&]() {
     sync_host(h);  // the float64 copy of the weights is made from the host master copy
-    h->io_pos.ensure(SN * 3 * sizeof(double));
-    h->io_alpha.ensure((size_t)S * 9 * sizeof(double));
-    HIP_TRY(hipMemcpy(h->io_pos.p, positions, SN * 3 * sizeof(double), hipMemcpyHostToDevice));
-    if (lattices) {
-      h->io_lat.ensure((size_t)S * 9 * sizeof(double));
-      HIP_TRY(hipMemcpy(h->io_lat.p, lattices, (size_t)S * 9 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (atom_types) {
-      h->io_types.ensure(SN * sizeof(int32_t));
-      HIP_TRY(hipMemcpy(h->io_types.p, atom_types, SN * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    ForwardIO<double> io;
+    io.pos = stage<double>(h->io_pos, positions, (size_t)S * h->cfg.num_atoms * 3 * sizeof(double));
+    io.lat = stage_lattices<double>(h, lattices, S);
+    io.types = stage_types(h, atom_types, S);
     // the standardised tensor (what PotGNN.forward returns as a 6-vector) is the reduction's value before alpha * sigma + mu
-    forward_device<double>(h, h->io_pos.as<double>(), S, nullptr, nullptr, h->io_alpha.as<double>(), nullptr, true,
-                           lattices ? h->io_lat.as<double>() : nullptr, atom_types ? h->io_types.as<int>() : nullptr);
+    h->io_alpha.ensure((size_t)S * 9 * sizeof(double));
+    io.alpha_raw = h->io_alpha.as<double>();
+    forward_device<double>(h, io, S, nullptr, true);
     std::vector<double> raw((size_t)S * 9);
     HIP_TRY(hipMemcpy(raw.data(), h->io_alpha.p, raw.size() * sizeof(double), hipMemcpyDeviceToHost));
     const int pick[6] = {0, 4, 8, 1, 2, 5};  // (xx, yy, zz, xy, xz, yz): dataset/torch/utils.py:44-60
@@ -2716,11 +2748,11 @@ int rn_potgnn_raman_tensors(rn_potgnn *h, const double *ref_positions, const dou
         pos[(2 * m + 1) * n3 + i] = ref_positions[i] - eps;
       }
     sync_host(h);  // (device-resident training may have moved the weights ahead of the float64 copy)
-    h->io_pos.ensure(pos.size() * sizeof(double));
+    ForwardIO<double> io;
+    io.pos = stage<double>(h->io_pos, pos.data(), pos.size() * sizeof(double));
     h->io_alpha.ensure((size_t)2 * M * 9 * sizeof(double));
-    HIP_TRY(hipMemcpy(h->io_pos.p, pos.data(), pos.size() * sizeof(double), hipMemcpyHostToDevice));
-    forward_device<double>(h, h->io_pos.as<double>(), 2 * M, h->io_alpha.as<double>(), nullptr,
-                           nullptr, nullptr, true);
+    io.alpha = h->io_alpha.as<double>();
+    forward_device<double>(h, io, 2 * M, nullptr, true);
     std::vector<double> a((size_t)2 * M * 9);
     HIP_TRY(hipMemcpy(a.data(), h->io_alpha.p, a.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int64_t m = 0; m < M; ++m)
@@ -2734,14 +2766,7 @@ int rn_potgnn_alpha_jacobian(rn_potgnn *h, const double *positions, int use_floa
     set_error(h, "invalid arguments to alpha_jacobian");
     return RN_ERR_INVALID_ARGUMENT;
   }
-  return guarded(h, [&]() {
-    if (use_float64) {
-      sync_host(h);
-      jacobian<double>(h, positions, jac);
-    } else {
-      jacobian<float>(h, positions, jac);
-    }
-  });
+  return guarded(h, [&]() { with_precision(h, use_float64, [&](auto t) { jacobian<decltype(t)>(h, positions, jac); }); });
 }
 
 int rn_potgnn_raman_tensors_analytic(rn_potgnn *h, const double *ref_positions,
@@ -2791,59 +2816,25 @@ int rn_potgnn_set_weights(rn_potgnn *h, const float *weights, size_t num_weights
 
 int rn_potgnn_train_forward(rn_potgnn *h, const double *positions, int64_t S, float *vec6,
                             float *batch_mean, float *batch_var) {
-  if (!h || S <= 0 || !positions || !vec6 || !batch_mean || !batch_var) {
-    set_error(h, "invalid arguments to train_forward");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (S > h->chunk) {
-    set_error(h, "training batch of %lld frames exceeds max_chunk_structures = %d", (long long)S,
-              h->chunk);
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  const Checked c = check_train_batch(h, S, {positions, vec6, batch_mean, batch_var}, "train_forward", kHostF32);
+  if (c.rc != kGo) return c.rc;
   return guarded(h, [&]() { train_forward<float>(h, positions, (int)S, vec6, batch_mean, batch_var); });
-}
-
-static int check_types(rn_potgnn *h, const int32_t *atom_types, int64_t S) {
-  if (!atom_types) return RN_OK;
-  const size_t SN = (size_t)S * h->cfg.num_atoms;
-  for (size_t i = 0; i < SN; ++i)
-    if (atom_types[i] < 0 || atom_types[i] >= h->cfg.num_atom_types) {
-      set_error(h, "atom type %d of sample %zu, atom %zu is outside [0,%d)", atom_types[i], i / h->cfg.num_atoms,
-                i % h->cfg.num_atoms, h->cfg.num_atom_types);
-      return RN_ERR_INVALID_ARGUMENT;
-    }
-  return RN_OK;
 }
 
 int rn_potgnn_train_forward_samples(rn_potgnn *h, const double *lattices, const int32_t *atom_types, const double *positions,
                                     int64_t S, float *vec6, float *batch_mean, float *batch_var) {
-  if (!h || S <= 0 || !positions || !vec6 || !batch_mean || !batch_var) {
-    set_error(h, "invalid arguments to train_forward_samples");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (S > h->chunk) {
-    set_error(h, "training batch of %lld frames exceeds max_chunk_structures = %d", (long long)S, h->chunk);
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (const int rc = check_types(h, atom_types, S); rc != RN_OK) return rc;
+  const Checked c = check_train_batch(h, S, {positions, vec6, batch_mean, batch_var}, "train_forward_samples", kHostF32);
+  if (c.rc != kGo) return c.rc;
+  if (const int rc = check_types(h, atom_types, S); rc != kGo) return rc;
   return guarded(h, [&]() { train_forward<float>(h, positions, (int)S, vec6, batch_mean, batch_var, lattices, atom_types); });
 }
 
 int rn_potgnn_train_forward_samples_f64(rn_potgnn *h, const double *lattices, const int32_t *atom_types,
                                         const double *positions, int64_t S, double *vec6, double *batch_mean,
                                         double *batch_var) {
-  if (!h || S <= 0 || !positions || !vec6 || !batch_mean || !batch_var) {
-    set_error(h, "invalid arguments to train_forward_samples_f64");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (S > chunk_frames<double>(h)) {
-    set_error(h, "training batch of %lld frames exceeds the float64 chunk of %d frames", (long long)S, chunk_frames<double>(h));
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (const int rc = check_types(h, atom_types, S); rc != RN_OK) return rc;
+  const Checked c = check_train_batch(h, S, {positions, vec6, batch_mean, batch_var}, "train_forward_samples_f64", kHostF64);
+  if (c.rc != kGo) return c.rc;
+  if (const int rc = check_types(h, atom_types, S); rc != kGo) return rc;
   return guarded(h, [&]() {
     sync_host(h);
     train_forward<double>(h, positions, (int)S, vec6, batch_mean, batch_var, lattices, atom_types);
@@ -2852,46 +2843,28 @@ int rn_potgnn_train_forward_samples_f64(rn_potgnn *h, const double *lattices, co
 
 int rn_potgnn_train_forward_samples_device(rn_potgnn *h, const float *d_lattices, const int32_t *d_atom_types,
                                            const double *d_positions, int64_t S, float *d_vec6, void *stream) {
-  if (!h || S <= 0 || !d_positions || !d_vec6) {
-    set_error(h, "invalid arguments to train_forward_samples_device");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (!h->device_training) {
-    set_error(h, "train_forward_samples_device needs device-resident training (rn_potgnn_set_device_training)");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S > h->chunk) {
-    set_error(h, "training batch of %lld frames exceeds max_chunk_structures = %d", (long long)S, h->chunk);
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  const Checked c = check_train_batch(h, S, {d_positions, d_vec6}, "train_forward_samples_device", kDeviceF32);
+  if (c.rc != kGo) return c.rc;
   return guarded(h, [&]() { train_forward_device(h, d_positions, (int)S, d_lattices, d_atom_types, d_vec6, (hipStream_t)stream); });
 }
 
 int rn_potgnn_train_backward_samples_device(rn_potgnn *h, const float *d_dvec6, void *stream) {
-  if (!h || !d_dvec6) {
-    set_error(h, "invalid arguments to train_backward_samples_device");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (!h->device_training || h->train_S <= 0 || h->train_prec != 4) {
-    set_error(h, "train_backward_samples_device needs device-resident training and a preceding float32 train_forward");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  const Checked c = check_pending(h, d_dvec6, "train_backward_samples_device", kDeviceF32,
+                                  "train_backward_samples_device needs device-resident training and a preceding float32 train_forward");
+  if (c.rc != kGo) return c.rc;
   return guarded(h, [&]() { train_backward_device(h, d_dvec6, (hipStream_t)stream); });
 }
 
 int rn_potgnn_forward_samples_device(rn_potgnn *h, const float *d_lattices, const int32_t *d_atom_types,
                                      const double *d_positions, int64_t S, float *d_vec6, void *stream, int synchronize) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 0 || (S > 0 && (!d_positions || !d_vec6))) {
-    set_error(h, "invalid positions / vec6 / S");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  if (S == 0) return RN_OK;
+  if (const int rc = check_batch(h, S, {d_positions, d_vec6}, "invalid positions / vec6 / S"); rc != kGo) return rc;
   return guarded(h, [&]() {
-    forward_device<float>(h, d_positions, S, nullptr, d_vec6, nullptr, (hipStream_t)stream, synchronize != 0, d_lattices,
-                          d_atom_types);
+    ForwardIO<float> io;
+    io.pos = d_positions;
+    io.lat = d_lattices;
+    io.types = d_atom_types;
+    io.vec6 = d_vec6;
+    forward_device<float>(h, io, S, (hipStream_t)stream, synchronize != 0);
   });
 }
 
@@ -2905,12 +2878,9 @@ int rn_potgnn_forward_vjp_device(rn_potgnn *h, const double *d_lattices, const i
   }
   if (S == 0) return RN_OK;
   return guarded(h, [&]() {
-    if (use_float64) {
-      sync_host(h);
-      forward_vjp<double>(h, d_lattices, d_atom_types, d_positions, S, d_dvec6, d_dpos, d_dlat, (hipStream_t)stream);
-    } else {
-      forward_vjp<float>(h, d_lattices, d_atom_types, d_positions, S, d_dvec6, d_dpos, d_dlat, (hipStream_t)stream);
-    }
+    with_precision(h, use_float64, [&](auto t) {
+      forward_vjp<decltype(t)>(h, d_lattices, d_atom_types, d_positions, S, d_dvec6, d_dpos, d_dlat, (hipStream_t)stream);
+    });
   });
 }
 
@@ -2927,12 +2897,9 @@ int rn_potgnn_group_increments_device(rn_potgnn *h, const double *d_positions, i
       throw RnInvalid{};
     }
     const size_t limit = workspace_limit ? workspace_limit : kTapeBudget;
-    if (use_float64) {
-      sync_host(h);
-      group_increments<double>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream);
-    } else {
-      group_increments<float>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream);
-    }
+    with_precision(h, use_float64, [&](auto t) {
+      group_increments<decltype(t)>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream);
+    });
   });
 }
 
@@ -2956,13 +2923,11 @@ int rn_potgnn_partial_raman_tensors(rn_potgnn *h, const double *ref_positions, c
     const size_t n3 = (size_t)N * 3;
     hipStream_t st = h->f64.lanes[0].stream;
     HIP_TRY(hipStreamSynchronize(st));  // (io_pos and the staging below are filled from the null stream)
-    h->io_pos.ensure(n3 * sizeof(double));
-    h->grp_disp.ensure((size_t)M * n3 * sizeof(double));
     h->grp_out.ensure((size_t)M * G * 9 * sizeof(double));
     h->grp_jac.ensure(6 * n3 * sizeof(double));
-    HIP_TRY(hipMemcpy(h->io_pos.p, ref_positions, n3 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->grp_disp.p, displacements, (size_t)M * n3 * sizeof(double), hipMemcpyHostToDevice));
-    jacobian_rows<double>(h, h->io_pos.as<double>(), 1, h->grp_jac.as<double>());
+    const double *d_ref = stage<double>(h->io_pos, ref_positions, n3 * sizeof(double));
+    stage<double>(h->grp_disp, displacements, (size_t)M * n3 * sizeof(double));
+    jacobian_rows<double>(h, d_ref, 1, h->grp_jac.as<double>());
     // R[m][g] = 2 sigma (.) sum_{i in g} J_i . d_{m,i}: the kernel's 1/2 (J + J) . (2 d)
     const int *perm = h->grp_csr.as<int>();
     launch_group_increments(h->grp_jac.as<double>(), 0, nullptr, h->grp_disp.as<double>(), 2.0, M, N, perm, perm + N, G,
@@ -2975,45 +2940,25 @@ int rn_potgnn_partial_raman_tensors(rn_potgnn *h, const double *ref_positions, c
 }
 
 int rn_potgnn_train_backward_inputs(rn_potgnn *h, const float *dvec6, float *grads, double *dpos, double *dlat) {
-  if (!h || !dvec6 || (!dpos && !dlat)) {
-    set_error(h, "invalid arguments to train_backward_inputs");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (h->train_S <= 0 || h->train_prec != 4) {
-    set_error(h, "train_backward_inputs needs a preceding train_forward (an evaluation or Jacobian call in "
-                 "between discards its tape)");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  const Checked c = check_pending(h, dvec6 && (dpos || dlat), "train_backward_inputs", kHostF32,
+                                  "train_backward_inputs needs a preceding train_forward (an evaluation or Jacobian call in "
+                                  "between discards its tape)");
+  if (c.rc != kGo) return c.rc;
   return guarded(h, [&]() { train_backward<float>(h, dvec6, grads, dpos, dlat); });
 }
 
 int rn_potgnn_train_backward_inputs_device(rn_potgnn *h, const float *d_dvec6, double *d_dpos, double *d_dlat,
                                            void *stream) {
-  if (!h || !d_dvec6 || (!d_dpos && !d_dlat)) {
-    set_error(h, "invalid arguments to train_backward_inputs_device");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (!h->device_training || h->train_S <= 0 || h->train_prec != 4) {
-    set_error(h, "train_backward_inputs_device needs device-resident training and a preceding float32 train_forward");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  const Checked c = check_pending(h, d_dvec6 && (d_dpos || d_dlat), "train_backward_inputs_device", kDeviceF32,
+                                  "train_backward_inputs_device needs device-resident training and a preceding float32 train_forward");
+  if (c.rc != kGo) return c.rc;
   return guarded(h, [&]() { train_backward_device(h, d_dvec6, (hipStream_t)stream, d_dpos, d_dlat); });
 }
 
 int rn_potgnn_train_forward_f64(rn_potgnn *h, const double *positions, int64_t S, double *vec6,
                                 double *batch_mean, double *batch_var) {
-  if (!h || S <= 0 || !positions || !vec6 || !batch_mean || !batch_var) {
-    set_error(h, "invalid arguments to train_forward_f64");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (S > chunk_frames<double>(h)) {
-    set_error(h, "training batch of %lld frames exceeds the float64 chunk of %d frames", (long long)S,
-              chunk_frames<double>(h));
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  const Checked c = check_train_batch(h, S, {positions, vec6, batch_mean, batch_var}, "train_forward_f64", kHostF64);
+  if (c.rc != kGo) return c.rc;
   return guarded(h, [&]() {
     sync_host(h);
     train_forward<double>(h, positions, (int)S, vec6, batch_mean, batch_var);
@@ -3021,15 +2966,9 @@ int rn_potgnn_train_forward_f64(rn_potgnn *h, const double *positions, int64_t S
 }
 
 int rn_potgnn_train_backward_f64(rn_potgnn *h, const double *dvec6, double *grads) {
-  if (!h || !dvec6 || !grads) {
-    set_error(h, "invalid arguments to train_backward_f64");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (h->train_S <= 0 || h->train_prec != 8) {
-    set_error(h, "train_backward_f64 needs a preceding train_forward_f64");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  const Checked c = check_pending(h, dvec6 && grads, "train_backward_f64", kHostF64,
+                                  "train_backward_f64 needs a preceding train_forward_f64");
+  if (c.rc != kGo) return c.rc;
   return guarded(h, [&]() { train_backward<double>(h, dvec6, grads); });
 }
 
@@ -3041,16 +2980,10 @@ int rn_potgnn_set_device_training(rn_potgnn *h, int enabled) {
 }
 
 int rn_potgnn_train_backward_device(rn_potgnn *h, const float *dvec6) {
-  if (!h || !dvec6) {
-    set_error(h, "invalid arguments to train_backward_device");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (h->train_S <= 0 || h->train_prec != 4) {
-    set_error(h, "train_backward_device needs a preceding train_forward (an evaluation or Jacobian call "
-                 "in between discards its tape)");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  const Checked c = check_pending(h, dvec6, "train_backward_device", kHostF32,
+                                  "train_backward_device needs a preceding train_forward (an evaluation or Jacobian call "
+                                  "in between discards its tape)");
+  if (c.rc != kGo) return c.rc;
   return guarded(h, [&]() { train_backward<float>(h, dvec6, nullptr); });
 }
 
@@ -3100,9 +3033,7 @@ int rn_potgnn_adam_step(rn_potgnn *h, double lr, double beta1, double beta2, dou
                 (h->plan.use_ps && h->ps_fail.p) ? h->ps_fail.as<int>() : nullptr);
     launch_refresh_derived(w, h->derived_ops.as<DerivedOp>(), h->derived_first_stage, st);
     launch_refresh_derived(w, h->derived_ops.as<DerivedOp>() + h->derived_first_stage, h->num_derived_ops - h->derived_first_stage, st);
-    launch_setup<float>(w + L.emb, w + L.W2, w + L.b2, w + L.W4, w + L.b4, h->cfg.num_atom_types, h->d,
-                        w + L.node_table, w + L.b0, w + L.bn_w, w + L.bn_b, w + L.bn_rm, w + L.bn_rv,
-                        w + L.scale0, w + L.shift0, st);
+    device_setup<float>(h, w, st);
     HIP_TRY(hipGetLastError());
     // The host looks at three kinds of entries after a step: c3_norm_1's folded constants (the triplet loop's folded-scale
     // variant is chosen from them), the prescale pairs (which double as the finiteness flags of the weight blocks,
@@ -3175,16 +3106,10 @@ double rn_potgnn_train_row_count(const rn_potgnn *h) {
 }
 
 int rn_potgnn_train_backward(rn_potgnn *h, const float *dvec6, float *grads) {
-  if (!h || !dvec6 || !grads) {
-    set_error(h, "invalid arguments to train_backward");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the checks below read handle state)
-  if (h->train_S <= 0 || h->train_prec != 4) {
-    set_error(h, "train_backward needs a preceding train_forward (an evaluation or Jacobian call in "
-                 "between discards its tape)");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  const Checked c = check_pending(h, dvec6 && grads, "train_backward", kHostF32,
+                                  "train_backward needs a preceding train_forward (an evaluation or Jacobian call in "
+                                  "between discards its tape)");
+  if (c.rc != kGo) return c.rc;
   return guarded(h, [&]() { train_backward<float>(h, dvec6, grads); });
 }
 
@@ -3276,9 +3201,7 @@ int rn_potgnn_debug_stage(rn_potgnn *h, int stage, int index, float *out, size_t
     return RN_ERR_UNSUPPORTED;
   }
   const int S = h->last_chunk_structs;
-  const int lane_of_last = 0;  // debug use: evaluate <= one chunk so lane 0 holds it
-  (void)lane_of_last;
-  Precision<float> &P = h->f32;
+  Precision<float> &P = h->f32;  // (debug use: evaluate <= one chunk so lane 0 holds it)
   return guarded(h, [&]() {
     HIP_TRY(hipDeviceSynchronize());
     const float *src = nullptr;
