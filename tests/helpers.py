@@ -19,6 +19,56 @@ def product_model_from_golden(g, mean=None, stddev=None, **kw):
     return model
 
 
+# ----------------------------------------------------------------------------- sparse and tiny graphs
+def sparse_structures():
+    """name -> (lattice, fractional positions, atomic numbers, cutoff): five deterministic structures in a 14 A slightly
+    triclinic box whose graphs have what the fixtures' graphs lack -- atoms without edges, atoms of degree 1, destination
+    edges without a triplet, no triplet at all, fewer atoms than one 16-atom tile, one species, five species.
+    ``SPARSE_PROPERTIES`` lists what each must have; tests/test_host_logic.py asserts it."""
+    rng = np.random.default_rng(0)
+    lattice = np.diag([14.0, 15.4, 12.6]) + 0.4 * rng.normal(size=(3, 3))
+
+    def frac(cart):
+        return (np.asarray(cart, dtype=np.float64) @ np.linalg.inv(lattice)) % 1.0
+
+    out = {}
+    out["dimer"] = (lattice, frac([[1, 1, 1], [2.2, 1, 1]]), [14, 14], 2.0)
+    out["iso_dimer_iso"] = (lattice, frac([[7, 7, 7], [1, 1, 1], [2.2, 1.1, 1], [10, 3, 9]]), [8, 1, 8, 1], 2.0)
+    out["chain5"] = (lattice, frac([[1 + 1.0 * i, 2 + 0.1 * i * i, 3] for i in range(5)]), [6, 1, 7, 8, 9], 1.25)
+    # hub17: atom 0 isolated, atom 1 a hub with 14 shell atoms 2.0 A away, atom 16 isolated and alone in the second 16-atom tile
+    shell = np.random.default_rng(3).normal(size=(14, 3))
+    shell = 2.0 * shell / np.linalg.norm(shell, axis=1)[:, None] + 7.0
+    out["hub17"] = (lattice, frac(np.vstack([[1, 1, 1], [7, 7, 7], shell, [12, 12, 1.5]])), [8, 22] + [8] * 14 + [22], 2.1)
+    # molecules33: eleven bent three-atom molecules, 4 A and more apart
+    rng, cart, zs = np.random.default_rng(4), [], []
+    for m in range(11):
+        o = np.array([1.5 + (m % 3) * 4.2, 1.5 + ((m // 3) % 3) * 4.5, 1.5 + (m // 9) * 4.0]) + 0.2 * rng.normal(size=3)
+        cart += [o, o + [0.96, 0.05 * m, 0], o + [-0.24, 0.93, 0.03 * m]]
+        zs += [8, 1, 1]
+    out["molecules33"] = (lattice, frac(cart), zs, 1.2)
+    return out
+
+
+# N, E, T, species, atoms without an edge, destination edges without a triplet (tuple slot 5 of the triplets never names
+# them: their c3 sum is empty), atoms of degree 1
+SPARSE_PROPERTIES = {
+    "dimer": dict(N=2, E=2, T=0, K=1, edge_free=0, triplet_less=2, degree_one=2),
+    "iso_dimer_iso": dict(N=4, E=2, T=0, K=2, edge_free=2, triplet_less=2, degree_one=2),
+    "chain5": dict(N=5, E=8, T=6, K=5, edge_free=0, triplet_less=2, degree_one=2),
+    "hub17": dict(N=17, E=82, T=468, K=2, edge_free=2, triplet_less=0, degree_one=0),
+    "molecules33": dict(N=33, E=44, T=22, K=2, edge_free=0, triplet_less=22, degree_one=22),
+}
+
+
+def sparse_fixture(name, frames=5, seed=0):
+    """The fixture-like dict ``tests/test_gpu_parity.py: _random_model`` takes, for one of ``sparse_structures()``:
+    ``pos_batch`` = the reference positions + N(0, 2e-3), seeded.  Returns (dict, cutoff)."""
+    lattice, positions, zs, cutoff = sparse_structures()[name]
+    rng = np.random.default_rng(1000 + seed)
+    pos_batch = positions[None] + rng.normal(scale=2e-3, size=(frames,) + positions.shape)
+    return {"lattice": lattice, "positions": positions, "atomic_numbers": np.asarray(zs), "pos_batch": pos_batch}, cutoff
+
+
 # ----------------------------------------------------------------------------- graph plans (rn_potgnn_debug_plan)
 PLAN_WIDTHS = ((5, 14), (16, 16), (20, 48), (32, 64), (64, 64), (50, 40), (64, 16), (128, 128))
 PLAN_FIXTURES = ("triclinic20", "rocksalt64_parity", "rocksalt64_perf", "tio2_gnn_test")

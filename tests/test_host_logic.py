@@ -739,6 +739,58 @@ def test_graph_plan_partitions_hold_their_invariants():
     assert all(hit.values()), hit
 
 
+def test_sparse_structures_keep_their_degenerate_graphs_and_get_a_plan():
+    """tests/helpers.py ``sparse_structures()`` -- what tests/test_sparse_graphs_gpu.py runs on -- have the graphs they are
+    there for (those tests would pass trivially if a coordinate drifted): N, E, T, species, atoms without an edge, atoms
+    of degree 1, destination edges without a triplet, the hub's degree, an edge-free atom alone in the second 16-atom
+    tile.  Product graph code equals the oracle's bit for bit, and the planner accepts every one of them at every width
+    pair of ``PLAN_WIDTHS`` with partitions that start at 0, end at N, never step back and hold every atom once."""
+    from oracle import potgnn_oracle as O
+    from tests.helpers import PLAN_WIDTHS, SPARSE_PROPERTIES, sparse_structures
+    from tests.plan_worker import debug_plan
+    lib = _lib.load()
+    structures = sparse_structures()
+    assert list(structures) == list(SPARSE_PROPERTIES) == ["dimer", "iso_dimer_iso", "chain5", "hub17", "molecules33"]
+    for name, (lattice, positions, zs, cutoff) in structures.items():
+        n = len(zs)
+        edges = G.radius_graph_pbc(lattice, positions, cutoff)
+        trip = G.reference_order_triplets(edges, n)
+        degree = np.bincount(edges[0], minlength=n)
+        np.testing.assert_array_equal(degree, np.bincount(edges[1], minlength=n), err_msg=name)  # (a -> b comes with b -> a)
+        per_edge = np.bincount(trip[5], minlength=edges.shape[1])
+        got = dict(N=n, E=edges.shape[1], T=len(trip[2]), K=len(set(zs)), edge_free=int((degree == 0).sum()),
+                   triplet_less=int((per_edge == 0).sum()), degree_one=int((degree == 1).sum()))
+        assert got == SPARSE_PROPERTIES[name], (name, got)
+        o_edges, o_trip, o_map = O.build_topology(lattice, positions, zs, cutoff)
+        np.testing.assert_array_equal(edges, o_edges.numpy()[1:], err_msg=name)
+        assert len(trip) == len(o_trip) == 7
+        for mine, ref in zip(trip, o_trip):
+            assert mine.dtype == np.int64
+            np.testing.assert_array_equal(mine, ref.numpy(), err_msg=name)
+        tmap = G.atom_type_map(zs)
+        np.testing.assert_array_equal(tmap, o_map.numpy(), err_msg=name)
+        ea, eb = (np.ascontiguousarray(x, dtype=np.int32) for x in edges)
+        types = np.ascontiguousarray(tmap[np.asarray(zs)], dtype=np.int32)
+        for fn, fe in PLAN_WIDTHS:
+            flat = debug_plan(lib, (n, len(ea), got["K"], fn, fe), ea, eb, types, 256)  # (asserts RN_OK)
+            plan = _parse_plan(flat, n, len(ea))
+            assert plan["T"] == got["T"], (name, fn, fe)
+            for part in ("tile", "nt", "et", "bt", "pt"):
+                begin, maxima = plan[part]
+                if len(begin) == 0:
+                    assert part in ("et", "bt", "pt"), (name, fn, fe, part)
+                    continue
+                assert begin[0] == 0 and begin[-1] == n and np.all(np.diff(begin) >= 0), (name, fn, fe, part, begin)
+                owners = np.concatenate([np.arange(lo, hi) for lo, hi in zip(begin[:-1], begin[1:])])
+                np.testing.assert_array_equal(owners, np.arange(n), err_msg=f"{name} {fn}/{fe} {part}")
+                assert maxima[2] == np.diff(begin).max(), (name, fn, fe, part)
+    chain = G.radius_graph_pbc(*structures["chain5"][:2], structures["chain5"][3])
+    assert np.bincount(chain[0]).tolist() == [1, 2, 2, 2, 1]
+    lattice, positions, zs, cutoff = structures["hub17"]
+    degree = np.bincount(G.radius_graph_pbc(lattice, positions, cutoff)[0], minlength=17)
+    assert degree[0] == 0 and degree[1] == 14 and degree[16] == 0 and degree[2:16].min() == 3 and degree[2:16].max() == 8
+
+
 def test_debug_plan_rejects_what_create_rejects():
     """The bad inputs of ``test_create_rejects_bad_arguments_without_touching_the_gpu`` (and the documented size limits)
     through ``rn_potgnn_debug_plan``: the same status codes and texts, from the same code."""
