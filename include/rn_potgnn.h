@@ -530,10 +530,7 @@ int rn_md_raman_segments_device(const double *d_alpha, int64_t S, int64_t segmen
  * requested but the range guard refused it (a non-finite weight, or readout hidden activations
  * that the weights allow beyond 3e4): the exact-f32 MFMA instantiations run instead.  Weight
  * matrices of any finite scale are fine: each is prescaled by a power of two into f16's range;
- * bit 7 = the library was built with -DRN_EXPERIMENTS=1 and carries the opt-in round-3 experiment kernels
- * (experiments/ at the repository root); only then can bit 5 (RN_POTGNN_EDGE2=1 at create time: frame-pipelined EdgeBlock,
- * edge_block2_kernel + edge_c2_kernel) or bit 6 (RN_POTGNN_EDGE3=1: twelve-wave EdgeBlock, edge_block3_kernel +
- * edge_c2_kernel) be set.  The product build ignores those knobs.
+ * bits 5 to 7 = reserved, 0.
  * bit 8 = every pass of a float32 evaluation takes the role-specialised fused EdgeBlock (edge_block_ps_kernel,
  * csrc/kernels_edge_ps.hip: producer waves + consumer waves in one 768-thread workgroup per CU; needs bits 0-2;
  * RN_POTGNN_EDGE_PS=0 at create time keeps the per-frame kernel of bit 0).
@@ -561,11 +558,11 @@ int rn_potgnn_debug_ps_schedule(const int32_t *rb, const int32_t *re, int32_t nu
  * num_cus compute units, under the RN_POTGNN_* knobs of the environment.  The arguments are validated as rn_potgnn_create
  * validates them (same status codes and texts through rn_potgnn_last_error(NULL)).  The plan is written as int32 values:
  *   FnP, FeP                                   padded widths
- *   five partitions, in the order EdgeBlock (Graph::tile_begin), NodeBlock (nt_), twelve-wave EdgeBlock (et_, experiment
- *   builds), reverse EdgeBlock (bt_), role-specialised EdgeBlock (pt_); each as
+ *   five partition slots, in the order EdgeBlock (Graph::tile_begin), NodeBlock (nt_), a reserved slot (always 0, 0, 0, 0),
+ *   reverse EdgeBlock (bt_), role-specialised EdgeBlock (pt_); each as
  *     L, begin[0 .. L), max_out_rows, max_in_rows, max_nodes      (L = tiles + 1, or 0: no such partition)
  *   nt_narrow, na_num, na_max_deg, pt_back, pt_gram, T
- *   use_fused, use_edge2, use_edge3, use_ps, use_narrow, use_node_fused, use_readout_fused, num_lanes
+ *   use_fused, two reserved words (always 0), use_ps, use_narrow, use_node_fused, use_readout_fused, num_lanes
  *   out_ptr[N+1], in_ptr[N+1], in_edge[E], in_pos[E], rev_edge[E], trip_off[E+1]
  * *count = the number of values; when out is NULL or capacity < *count nothing is written and the call returns
  * RN_ERR_INVALID_ARGUMENT with *count set.

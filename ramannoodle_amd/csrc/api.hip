@@ -116,7 +116,6 @@ struct Lane {
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;
   DeviceBuf unit4, node[2], edge[2], npc1, np3, bufA, bufB;
-  DeviceBuf c2;  // frame-pipelined EdgeBlock: the finished c2 embedding of every edge [S*E, FeP]
   DeviceBuf fbA, fbB;  // a block of frames' c2 / c3 edge projections for a pass the fused pipeline hands to the unfused EdgeBlock
 };
 
@@ -593,7 +592,7 @@ size_t per_structure_elems(const rn_potgnn *h, bool lean) {
   const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges;
   const size_t FnP = h->d.FnP, FeP = h->d.FeP;
   return E * 4 + 2 * N * FnP + 2 * E * FeP + N * 2 * FnP + N * 6 * FeP + E * bufA_width(h, lean) +
-         (lean ? 0 : E * 4 * FeP) + ((h->plan.use_edge2 || h->plan.use_edge3) ? E * FeP : 0);
+         (lean ? 0 : E * 4 * FeP);
 }
 
 // May the fused kernels run their matrix products as split-f16 MFMAs (device_utils.hpp)?
@@ -765,7 +764,6 @@ void ensure_precision(rn_potgnn *h) {
     ln.np3.ensure(S * N * 6 * FeP * sizeof(T));
     ln.bufA.ensure(S * E * bufA * sizeof(T));
     if (!lean) ln.bufB.ensure(S * E * 4 * FeP * sizeof(T));
-    if (sizeof(T) == 4 && (h->plan.use_edge2 || h->plan.use_edge3)) ln.c2.ensure(S * E * FeP * sizeof(T));
   }
   if (h->keep_stages) {
     const int np = h->cfg.num_message_passes + 1;
@@ -857,7 +855,7 @@ struct ChunkRun {
   ForwardIO<T> io;  // this chunk's slice
   int S;
   int cur = 0;
-  T *node[2], *edge[2], *unit4, *npc1, *np3, *bufA, *bufB, *c2;
+  T *node[2], *edge[2], *unit4, *npc1, *np3, *bufA, *bufB;
   int64_t MN, ME;
 
   ChunkRun(rn_potgnn *h_, Lane<T> &l, const ForwardIO<T> &io_, int S_) : h(h_), ln(&l), io(io_), S(S_) {
@@ -870,7 +868,6 @@ struct ChunkRun {
     np3 = l.np3.template as<T>();
     bufA = l.bufA.template as<T>();
     bufB = l.bufB.template as<T>();
-    c2 = l.c2.template as<T>();
     MN = (int64_t)S * h->g.N;
     ME = (int64_t)S * h->g.E;
   }
@@ -932,6 +929,17 @@ struct ChunkRun {
     }
   }
 
+  // Y[R rows] = X W (+ bias): float32 with the split-f16 products enabled -> rowgemm_split_kernel where it serves the shape
+  // (K a multiple of 64), else the exact-f32 MFMA projection kernel
+  void project(const T *X, int64_t R, int K, const T *WT, int NOUT, T *Y, const T *bias, int amode, const T *nd) {
+    if constexpr (sizeof(T) == 4) {
+      if (h->mfma_f16 && h->split_projections &&
+          launch_rowgemm_split(X, K, K, R, WT, NOUT, Y, false, bias, amode, nd, h->g, st()))
+        return;
+    }
+    launch_rowgemm<T>(X, R, K, WT, NOUT, Y, nullptr, bias, false, amode, nd, h->g, st());
+  }
+
   // "G" stage of pass p: NodeBlock + every dense projection the EdgeBlock needs
   // (matrix pipe / HBM bound)
   void stage_project(int p) {
@@ -940,16 +948,6 @@ struct ChunkRun {
     const Dims d = h->d;
     const int nxt = cur ^ 1;
     target_tape(p + 1, nxt);
-    // Y = X W (+ bias): float32 with the split-f16 products enabled -> rowgemm_split_kernel where it serves the shape
-    // (K a multiple of 64), else the exact-f32 MFMA projection kernel
-    auto project = [&](const T *X, int64_t R, int K, const T *WT, int NOUT, T *Y, const T *bias, int amode, const T *nd) {
-      if constexpr (sizeof(T) == 4) {
-        if (h->mfma_f16 && h->split_projections &&
-            launch_rowgemm_split(X, K, K, R, WT, NOUT, Y, false, bias, amode, nd, g, st()))
-          return;
-      }
-      launch_rowgemm<T>(X, R, K, WT, NOUT, Y, nullptr, bias, false, amode, nd, g, st());
-    };
     if constexpr (sizeof(T) == 4) {
       if (narrow()) {  // the whole NodeBlock, projections included, in one launch
         Timer t(h, st(), K_NODE_AGG);
@@ -986,14 +984,6 @@ struct ChunkRun {
       if (role_split(w)) project(node[nxt], MN, d.FnP, w.c3_WnT_c, 6 * d.FeP, np3, w.c3_nshift_c, 0, nullptr);  // zero row mean
       else project(node[nxt], MN, d.FnP, w.c3_WnT, 6 * d.FeP, np3, w.c3_nshift, 0, nullptr);
     }
-    if constexpr (sizeof(T) == 4) {
-#if RN_EXPERIMENTS
-      if (fused() && (h->plan.use_edge2 || (h->plan.use_edge3 && edge3_applicable(w, h->mfma_f16)))) {  // c2 branch of the EdgeBlock, one finished row per edge
-        Timer t(h, st(), K_PROJ_C2);
-        launch_edge_c2(node[nxt], c2, S, g, d, w, h->mfma_f16, st());
-      }
-#endif
-    }
     if (!fused()) {
       {
         Timer t(h, st(), K_PROJ_EDGE_C3);
@@ -1014,17 +1004,7 @@ struct ChunkRun {
       Timer t(h, st(), K_EDGE_AGG);
       if constexpr (sizeof(T) == 4) {
         if (narrow()) launch_edge_narrow(edge[cur], edge[nxt], node[nxt], S, h->g, h->d, w, st());
-#if RN_EXPERIMENTS
-        else if (fused() && h->plan.use_edge3 && edge3_applicable(w, h->mfma_f16))
-          launch_edge3(edge[cur], edge[nxt], np3, c2, tape_agg(p), S, h->g, h->d, w, st());
-        else if (fused() && h->plan.use_edge2)
-          launch_edge2(edge[cur], edge[nxt], np3, c2, tape_agg(p), S, h->g, h->d, w, h->mfma_f16, st());
-#endif
         else if (role_split(w)) launch_edge_ps(edge[cur], edge[nxt], node[nxt], np3, tape_agg(p), S, h->g, h->d, w, h->ps_fail.as<int>(), st(), pair_rows(), h->mfma_f16);
-#if RN_EXPERIMENTS
-        else if (fused() && getenv("RN_POTGNN_EDGE_FRAME") && atoi(getenv("RN_POTGNN_EDGE_FRAME")) != 0)  // the retired per-frame kernel
-          launch_edge_fused(edge[cur], edge[nxt], node[nxt], np3, tape_agg(p), S, h->g, h->d, w, h->mfma_f16, st());
-#endif
         else if (fused()) edge_unfused_in_blocks(p);
         else launch_edge_agg<T>(bufB, np3, bufA, edge[cur], edge[nxt], S, h->g, h->d, w, tape_agg(p), st());
       } else {
@@ -1039,7 +1019,7 @@ struct ChunkRun {
   // without the folded gate scale, exact-f32 products, RN_POTGNN_EDGE_PS=0 / RN_POTGNN_TAPE_PS=0): the unfused EdgeBlock --
   // the two per-edge projections + edge_agg_kernel, what the float64 instantiation always runs -- block of frames by block
   // of frames, because the fused pipeline's lean workspace holds no per-edge projection buffers (6 FeP floats per edge).
-  // Through round 4 these passes took the per-frame fused kernel (now experiments/kernels_edge_frame.hip).
+  // Through round 4 these passes took the per-frame fused kernel (retired; see profiles/r04/mfma_k32.txt and git history).
   void edge_unfused_in_blocks(int p) {
     const PassW<T> &w = prec<T>(h).pass[p];
     const Graph &g = h->g;
@@ -1056,14 +1036,8 @@ struct ChunkRun {
       const int sb = std::min(block, S - s0);
       const int64_t rows = (int64_t)sb * g.E;
       const T *e_in = edge[cur] + (size_t)s0 * g.E * d.FeP, *nd = node[nxt] + (size_t)s0 * g.N * d.FnP;
-      auto project = [&](const T *X, int K, const T *WT, int NOUT, T *Y, const T *bias, int amode, const T *ndp) {
-        if constexpr (sizeof(T) == 4) {
-          if (h->mfma_f16 && h->split_projections && launch_rowgemm_split(X, K, K, rows, WT, NOUT, Y, false, bias, amode, ndp, g, st())) return;
-        }
-        launch_rowgemm<T>(X, rows, K, WT, NOUT, Y, nullptr, bias, false, amode, ndp, g, st());
-      };
-      project(e_in, d.FeP, w.c3_WeT, 4 * d.FeP, fb, nullptr, 0, nullptr);
-      project(nullptr, d.FnP, w.c2_WT, 2 * d.FeP, fa, w.c2_bias, 1, nd);
+      project(e_in, rows, d.FeP, w.c3_WeT, 4 * d.FeP, fb, nullptr, 0, nullptr);
+      project(nullptr, rows, d.FnP, w.c2_WT, 2 * d.FeP, fa, w.c2_bias, 1, nd);
       launch_edge_agg<T>(fb, np3 + (size_t)s0 * g.N * 6 * d.FeP, fa, e_in, edge[nxt] + (size_t)s0 * g.E * d.FeP, sb, g, d, w,
                          agg ? agg + (size_t)s0 * g.E * d.FeP : nullptr, st());
     }
@@ -2248,7 +2222,7 @@ static Graph upload(const GraphPlan &plan, DeviceBuf &buf) {
   const size_t o_a = push(plan.edge_a), o_b = push(plan.edge_b), o_op = push(plan.out_ptr),
                o_ip = push(plan.in_ptr), o_ie = push(plan.in_edge), o_at = push(plan.atom_type),
                o_tb = push(plan.tile.begin), o_to = push(plan.trip_off), o_rv = push(plan.rev_edge),
-               o_nt = push(plan.nt.begin), o_et = push(plan.et.begin), o_bt = push(plan.bt.begin), o_pt = push(plan.pt.begin), o_ipos = push(plan.in_pos);
+               o_nt = push(plan.nt.begin), o_bt = push(plan.bt.begin), o_pt = push(plan.pt.begin), o_ipos = push(plan.in_pos);
   buf.ensure(ints.size() * sizeof(int));
   HIP_TRY(hipMemcpy(buf.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
   const int *base = buf.as<int>();
@@ -2264,7 +2238,6 @@ static Graph upload(const GraphPlan &plan, DeviceBuf &buf) {
   g.tile_begin = base + o_tb;
   g.trip_off = base + o_to;
   g.nt_begin = base + o_nt;
-  g.et_begin = base + o_et;
   g.pt_begin = base + o_pt;
   g.bt_begin = base + o_bt;
   return g;
@@ -3145,7 +3118,7 @@ int rn_potgnn_config_flags(const rn_potgnn *h) {
   if (!h) return -1;
   std::lock_guard<std::recursive_mutex> hold(h->lock);  // (the pass flags are rewritten when weights change)
   int flags = (h->plan.use_fused ? 1 : 0) | ((h->plan.use_fused && h->mfma_f16) ? 4 : 0) | (h->plan.use_narrow ? 8 : 0) |
-              ((h->plan.use_fused && h->mfma_range_fallback) ? 16 : 0) | (h->plan.use_edge2 ? 32 : 0) | (h->plan.use_edge3 ? 64 : 0) | (RN_EXPERIMENTS ? 128 : 0);
+              ((h->plan.use_fused && h->mfma_range_fallback) ? 16 : 0);
   {  // bit 8: every pass of a float32 evaluation takes the role-specialised EdgeBlock (kernels_edge_ps.hip)
     bool ps = h->plan.use_fused && h->plan.use_ps && !h->f32.pass.empty();  // (split-f16 or exact-f32 products: the same kernel)
     for (const auto &p : h->f32.pass) ps = ps && (p.c3_fast & 1);

@@ -11,9 +11,7 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function ${R
 bdir="build${tag:+_$tag}"
 mkdir -p "$here/$bdir"
 pids=()
-# RN_EXTRA_FLAGS=-DRN_EXPERIMENTS=1 adds the opt-in round-3 experiment kernels (experiments/ at the repository root, outside the package); the product build has none.
 hip_srcs="api graph_plan kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group spectrum spectrum_polarized spectrum_partial spectrum_segments"
-case " ${RN_EXTRA_FLAGS:-} " in *" -DRN_EXPERIMENTS=1 "*) hip_srcs="$hip_srcs ../../experiments/kernels_fused_experiments ../../experiments/kernels_edge_frame";; esac
 objs=()
 for f in $hip_srcs; do
   o="$here/$bdir/$(basename "$f").o"

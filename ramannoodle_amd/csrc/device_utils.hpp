@@ -244,8 +244,8 @@ __device__ __forceinline__ void split_f16x8(const float *x, f16x8 &hi, f16x8 &lo
 // evaluations -- while every other kernel of the library is: round 4 re-ran the probe on the K = 32 build with the
 // role-specialised EdgeBlock (one workgroup per CU, MFMAs only in the producer waves) and found 0 differing frames in
 // 5 x 4 x 10 000 evaluations (fused NodeBlock at four workgroups per CU, fused readout, split projections, unfused chain).
-// So K = 32 is the default everywhere EXCEPT in edge_block_fused_kernel, which keeps the two-instruction form
-// (WaveB::product_split16) and stays bit-reproducible; -DRN_MFMA_K32=0 builds the whole library on K = 16.
+// So K = 32 is the default everywhere; edge_block_fused_kernel, which kept the two-instruction form, is retired (git
+// history).  The K32 = false form stays for -DRN_MFMA_K32=0, which builds the whole library on K = 16.
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 #ifndef RN_MFMA_K32
 #define RN_MFMA_K32 1

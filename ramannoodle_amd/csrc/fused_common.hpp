@@ -1,6 +1,5 @@
-// Definitions shared by the fused kernels (kernels_fused.hip, kernels_edge_ps.hip) and the opt-in experiment
-// kernels (experiments/kernels_fused_experiments.hip): tile constants, the resident weight fragments of a wave,
-// LDS-DMA and split-f16 operand helpers.  gfx950 / wave64 only.
+// Definitions shared by the fused kernels (kernels_fused.hip, kernels_edge_ps.hip): tile constants, the resident
+// weight fragments of a wave, LDS-DMA and split-f16 operand helpers.  gfx950 / wave64 only.
 #pragma once
 #include "device_utils.hpp"
 #include "kernels.hpp"
@@ -132,7 +131,7 @@ struct WaveB<true> {  // split f16 (device_utils.hpp: mfma_split3), K = 32 slice
     product_split<K32>(ah, al, acc);
   }
   // the same with an A operand that is already split (slice s = k 16 quad + 8 s .. + 7)
-  // (K32 = false: the two-instruction form, device_utils.hpp -- what edge_block_fused_kernel must use)
+  // (K32 = false: the two-instruction form, device_utils.hpp -- what a -DRN_MFMA_K32=0 build uses)
   template <bool K32 = (RN_MFMA_K32 != 0)>
   __device__ __forceinline__ void product_split(const f16x8 (&ah)[2], const f16x8 (&al)[2], f32x4 (&acc)[2]) const {
 #pragma unroll
@@ -385,9 +384,5 @@ __host__ __device__ inline NodeFusedLds node_fused_lds(int maxD, int maxN) {
   return L;
 }
 }  // namespace
-
-#if RN_EXPERIMENTS
-void launch_node_wave(const NodeFusedArgs &a, hipStream_t st);  // experiments/: wave-autonomous NodeBlock
-#endif
 
 }  // namespace rn

@@ -126,12 +126,8 @@ Partition edge_tiles(const GraphPlan &g, const PlanKnobs &k, bool fused_mode, bo
     const Partition p = greedy_tiles(g, Rows::Out, std::max<size_t>(1, kb * 1024 / row_bytes));
     const int mr = p.max_out_rows, max_in = p.max_in_rows, max_nodes = p.max_nodes;
     const int rounds = std::max(1, (max_in + G - 1) / G);
-#if RN_EXPERIMENTS
-    const size_t fused_lds_need = k.want_edge2 ? edge2_lds_bytes(mr, max_in, max_nodes) : edge_fused_lds_bytes(mr, max_in, max_nodes);
-#else
-    const size_t fused_lds_need = edge_fused_lds_bytes(mr, max_in, max_nodes);
-#endif
-    const size_t lds = fused_mode ? fused_lds_need
+    // (fused: the footprint of the retired per-frame kernel still sizes these tiles -- kernels_fused.hip says why)
+    const size_t lds = fused_mode ? edge_fused_lds_bytes(mr, max_in, max_nodes)
                                   : (size_t)mr * (row_bytes + 4) + (size_t)max_nodes * row_bytes +
                                         (size_t)12 * d.FeP * 4 + (size_t)mr * 4 + (size_t)max_in * 24 + 96;
     // unfused: two aggregation workgroups + one projection workgroup (34 KiB) share a CU
@@ -145,33 +141,6 @@ Partition edge_tiles(const GraphPlan &g, const PlanKnobs &k, bool fused_mode, bo
   }
   return chosen;
 }
-
-#if RN_EXPERIMENTS
-// node tiles of the twelve-wave EdgeBlock (edge_block3_kernel): one 768-thread workgroup per CU with the CU's LDS,
-// 48 destinations per round -> as few rounds as possible in total; among equals the larger tiles (fewer per-tile phases)
-Partition edge3_tiles(const GraphPlan &g, const PlanKnobs &k) {
-  double best = 0;
-  Partition chosen;
-  const int forced = k.edge3_tile_rows;  // experiment knob
-  for (size_t budget = forced > 0 ? forced : 16; budget <= (size_t)(forced > 0 ? forced : 300); budget += 2) {
-    const Partition p = greedy_tiles(g, Rows::Out, budget);
-    double cost = 0;
-    for (int t = 0; t < p.num(); ++t) {
-      const int din = g.in_ptr[p.begin[t + 1]] - g.in_ptr[p.begin[t]];
-      cost += (double)((din + edge3_dests_per_round() - 1) / edge3_dests_per_round());
-    }
-    if (edge3_lds_bytes(p.max_out_rows, p.max_in_rows, p.max_nodes) > kEdge3LdsBudget) {
-      if (!chosen.begin.empty()) break;
-      continue;
-    }
-    if (chosen.begin.empty() || cost <= best) {
-      best = cost;
-      chosen = p;
-    }
-  }
-  return chosen;
-}
-#endif
 
 // node tiles of the EdgeBlock reverse kernel: the largest whose float32 LDS footprint leaves room for two workgroups
 // per CU (RN_POTGNN_BWD_TILES=0: the forward kernel's tiles, one 512-thread workgroup per CU)
@@ -218,30 +187,11 @@ Partition node_tiles_narrow(const GraphPlan &g, const PlanKnobs &k) {
 Partition node_tiles_wide(const GraphPlan &g, const PlanKnobs &k) {
   double best = 0;
   Partition chosen;
-#if RN_EXPERIMENTS
-  const bool node_wave = node_fused_wave_tiles() && g.d.FnP == 64 && g.d.FeP == 64;
-#else
-  const bool node_wave = false;
-#endif
   const int forced = k.node_tile_rows_set ? k.node_tile_rows : 0;  // experiment knob
   for (int budget = forced > 0 ? forced : 16; budget <= (forced > 0 ? forced : 256); budget += 8) {
     const Partition p = greedy_tiles(g, Rows::In, (size_t)budget);
-    double cost;
-    if (node_wave) {
-      // wave-autonomous kernel: a workgroup's four waves take the tile's 16-row pieces four at a time;
-      // two workgroups per CU (register-bound), so up to 72 KiB of LDS each
-#if RN_EXPERIMENTS
-      if (node_wave_lds_bytes(p.max_in_rows, p.max_nodes) > (size_t)72 * 1024 && !chosen.begin.empty()) break;
-#endif
-      cost = 0;
-      for (int t = 0; t < p.num(); ++t) {
-        const int rows_t = g.in_ptr[p.begin[t + 1]] - g.in_ptr[p.begin[t]];
-        cost += (double)(((rows_t + 15) / 16 + 3) / 4);
-      }
-    } else {
-      if (node_fused_lds_bytes(p.max_in_rows, p.max_nodes) > (size_t)40 * 1024 && !chosen.begin.empty()) break;
-      cost = (double)((p.max_in_rows + 15) / 16) * (double)p.num();
-    }
+    if (node_fused_lds_bytes(p.max_in_rows, p.max_nodes) > (size_t)40 * 1024 && !chosen.begin.empty()) break;
+    const double cost = (double)((p.max_in_rows + 15) / 16) * (double)p.num();
     if (chosen.begin.empty() || cost < best * 0.995) {
       best = cost;
       chosen = p;
@@ -386,13 +336,6 @@ PlanKnobs read_plan_knobs() {
   k.want_node_fused = knob_flag("RN_POTGNN_NODE_FUSED", true);
   k.want_readout_fused = knob_flag("RN_POTGNN_READOUT_FUSED", true);
   if (const char *e = knob("RN_POTGNN_LANES")) k.lanes = std::max(1, std::min(2, atoi(e)));
-  // Experiment builds (-DRN_EXPERIMENTS=1) only -- RN_POTGNN_EDGE2=1: the frame-pipelined form of the fused EdgeBlock
-  // (edge_block2_kernel + edge_c2_kernel), measured level with the per-frame form (profiles/r03/edge2_experiment.txt).
-#if RN_EXPERIMENTS
-  k.want_edge2 = knob_flag("RN_POTGNN_EDGE2", false);
-  k.want_edge3 = knob_flag("RN_POTGNN_EDGE3", false);
-  if (const char *e = knob("RN_POTGNN_EDGE3_TILE_ROWS")) k.edge3_tile_rows = atoi(e);  // experiment knob
-#endif
   return k;
 }
 
@@ -482,9 +425,6 @@ GraphPlan plan_graph(const rn_potgnn_config &cfg, Dims d, const int32_t *edge_a,
   const bool fused_mode = k.want_fused && d.FnP == 64 && d.FeP == 64;
   const bool narrow_mode = k.want_narrow && narrow_supported(d);
   g.tile = edge_tiles(g, k, fused_mode, narrow_mode);
-#if RN_EXPERIMENTS
-  if (fused_mode && k.want_edge3) g.et = edge3_tiles(g, k);
-#endif
   if (k.bwd_tiles) g.bt = reverse_tiles(g);
   if (narrow_mode) g.nt = node_tiles_narrow(g, k);
   g.nt_narrow = g.nt.num() > 0;
@@ -495,14 +435,8 @@ GraphPlan plan_graph(const rn_potgnn_config &cfg, Dims d, const int32_t *edge_a,
   // The fused kernels (kernels_fused.hip) are the default where they apply (float32, Fn and
   // Fe padded to 64); RN_POTGNN_FUSED=0 selects projections + edge_agg_kernel.
   const Graph s = g.scalars();
-#if RN_EXPERIMENTS
-  g.use_edge2 = k.want_fused && k.want_edge2 && edge2_supported(s, d);
-#endif
-  g.use_fused = g.use_edge2 || (k.want_fused && edge_fused_supported(s, d));
-#if RN_EXPERIMENTS
-  g.use_edge3 = g.use_fused && !g.use_edge2 && k.want_edge3 && edge3_supported(s, d);
-#endif
-  g.use_ps = g.use_fused && !g.use_edge2 && !g.use_edge3 && g.pt.num() > 0;
+  g.use_fused = k.want_fused && edge_fused_supported(s, d);
+  g.use_ps = g.use_fused && g.pt.num() > 0;
   g.use_narrow = narrow_mode && edge_narrow_lds_bytes(d.Fn, d.Fe, g.tile.max_out_rows, g.tile.max_in_rows) <= (size_t)64 * 1024;
   g.use_node_fused = g.use_fused && k.want_node_fused && node_fused_lds_bytes(s) <= 64 * 1024;
   g.use_readout_fused = g.use_fused && k.want_readout_fused;
@@ -522,7 +456,6 @@ Graph GraphPlan::scalars() const {
   s.num_tiles = tile.num(), s.max_tile_out_rows = tile.max_out_rows, s.max_tile_in_rows = tile.max_in_rows, s.max_tile_nodes = tile.max_nodes;
   s.nt_num = nt.num(), s.nt_max_in_rows = nt.max_in_rows, s.nt_max_nodes = nt.max_nodes, s.nt_narrow = nt_narrow ? 1 : 0;
   s.na_num = na_num, s.na_max_deg = na_max_deg;
-  s.et_num = et.num(), s.et_max_out_rows = et.max_out_rows, s.et_max_in_rows = et.max_in_rows, s.et_max_nodes = et.max_nodes;
   s.pt_num = pt.num(), s.pt_max_out_rows = pt.max_out_rows, s.pt_max_in_rows = pt.max_in_rows, s.pt_back = pt_back, s.pt_gram = pt_gram;
   s.bt_num = bt.num(), s.bt_max_out_rows = bt.max_out_rows, s.bt_max_in_rows = bt.max_in_rows, s.bt_max_nodes = bt.max_nodes;
   return s;
@@ -530,13 +463,14 @@ Graph GraphPlan::scalars() const {
 
 std::vector<int32_t> GraphPlan::flat() const {
   std::vector<int32_t> o = {d.FnP, d.FeP};
-  for (const Partition *p : {&tile, &nt, &et, &bt, &pt}) {
+  const Partition reserved;  // the third slot held a retired kernel's partition: written empty, so the layout keeps its positions
+  for (const Partition *p : {&tile, &nt, &reserved, &bt, &pt}) {
     o.push_back((int32_t)p->begin.size());
     o.insert(o.end(), p->begin.begin(), p->begin.end());
     o.insert(o.end(), {p->max_out_rows, p->max_in_rows, p->max_nodes});
   }
   o.insert(o.end(), {nt_narrow ? 1 : 0, na_num, na_max_deg, pt_back, pt_gram, (int32_t)T});
-  o.insert(o.end(), {use_fused, use_edge2, use_edge3, use_ps, use_narrow, use_node_fused, use_readout_fused, num_lanes});
+  o.insert(o.end(), {use_fused, 0 /* reserved */, 0 /* reserved */, use_ps, use_narrow, use_node_fused, use_readout_fused, num_lanes});
   for (const std::vector<int> *v : {&out_ptr, &in_ptr, &in_edge, &in_pos, &rev_edge, &trip_off}) o.insert(o.end(), v->begin(), v->end());
   return o;
 }

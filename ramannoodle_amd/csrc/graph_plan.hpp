@@ -34,8 +34,6 @@ struct PlanKnobs {
   bool want_node_fused = true;     // NODE_FUSED
   bool want_readout_fused = true;  // READOUT_FUSED
   int lanes = 0;               // LANES (1 or 2; 0: by kernel family)
-  bool want_edge2 = false, want_edge3 = false;  // experiment builds only
-  int edge3_tile_rows = 0;
 };
 PlanKnobs read_plan_knobs();
 
@@ -66,14 +64,12 @@ struct GraphPlan {
   std::vector<int> rev_edge;         // [E] id of (b -> a) or -1
   std::vector<int> trip_off;         // [E+1] exclusive prefix of triplets per destination edge
   int64_t T = 0;
-  Partition tile, nt, et, bt, pt;    // Graph::tile_begin / nt_ / et_ / bt_ / pt_ (kernels.hpp says which kernel each serves)
+  Partition tile, nt, bt, pt;        // Graph::tile_begin / nt_ / bt_ / pt_ (kernels.hpp says which kernel each serves)
   bool nt_narrow = false;
   int na_num = 0, na_max_deg = 0;
   int pt_back = 2, pt_gram = 0;
   // kernel family (rn_potgnn_config_flags reports it)
   bool use_fused = false;
-  bool use_edge2 = false;  // fused EdgeBlock in its frame-pipelined form (edge_block2_kernel + edge_c2_kernel)
-  bool use_edge3 = false;  // fused EdgeBlock on twelve waves, one workgroup per CU (edge_block3_kernel + edge_c2_kernel)
   bool use_ps = false;     // role-specialised fused EdgeBlock (kernels_edge_ps.hip) on its own atom tiles (Graph::pt_*)
   bool use_narrow = false;  // narrow-width kernels (kernels_narrow.hip): Fn, Fe <= 16, one lane per row
   bool use_node_fused = false;  // fused NodeBlock (only together with the fused EdgeBlock)

@@ -33,10 +33,6 @@ struct Graph {
   // atom-owning fused NodeBlock (kernels_node_atom.hip): tiles of 16 consecutive atoms, round r = their r-th in-edges
   int na_num;             // ceil(N / 16), or 0 when that kernel does not serve the graph
   int na_max_deg;         // largest in-degree
-  // node tiles of the twelve-wave EdgeBlock kernel (edge_block3_kernel: one workgroup per CU, 48 destinations a round)
-  int et_num;
-  const int *et_begin;    // [et_num+1] node ranges
-  int et_max_out_rows, et_max_in_rows, et_max_nodes;
   // node tiles of the role-specialised EdgeBlock (kernels_edge_ps.hip: one twelve-wave workgroup per CU, 16 destinations a round)
   int pt_num;
   const int *pt_begin;    // [pt_num+1] node ranges
@@ -294,6 +290,9 @@ void launch_group_increments(const double *jac, int64_t jac_stride, const double
 // Fused EdgeBlock (kernels_fused.hip): float32, FnP == FeP == 64.  Two workgroups per CU
 // need their LDS footprint within this budget.
 constexpr size_t kFusedLdsBudget = 80 * 1024;
+// (edge_fused_lds_bytes: the footprint of the per-frame kernel retired in round 5 -- see profiles/r04/mfma_k32.txt and git
+// history; the planner still sizes the EdgeBlock's atom tiles and decides use_fused with it, so it stays)
+size_t edge_fused_lds_bytes(const Graph &g);
 size_t edge_fused_lds_bytes(int tile_out_rows, int tile_in_rows, int tile_nodes);
 bool edge_fused_supported(const Graph &g, Dims d);
 size_t node_fused_lds_bytes(const Graph &g);
@@ -322,42 +321,6 @@ bool edge_ps_tile_ok(const int *rb, const int *re, int D, int back, int ring, in
 void launch_edge_ps(const float *edge_in, float *edge_out, const float *node, const float *np3, float *agg_out, int S,
                     const Graph &g, Dims d, const PassW<float> &w, int *fail, hipStream_t st, bool pair_rows = false,
                     bool f16 = true /* false: exact-f32 MFMA products (float32 rows, no Gram tables) */);
-
-// Opt-in experiment kernels (experiments/kernels_fused_experiments.hip): compiled and reachable only with
-// -DRN_EXPERIMENTS=1; the product build has neither the kernels nor the RN_POTGNN_EDGE2 / EDGE3 / NODE_WAVE knobs.
-#ifndef RN_EXPERIMENTS
-#define RN_EXPERIMENTS 0
-#endif
-#if RN_EXPERIMENTS
-// Per-frame fused EdgeBlock (edge_block_fused_kernel, retired from the product build in round 5: experiments/kernels_edge_frame.hip)
-size_t edge_fused_lds_bytes(const Graph &g);
-// `agg_out` (taped runs, else null): the pre-LayerNorm triplet sums per destination edge
-void launch_edge_fused(const float *edge_in, float *edge_out, const float *node, const float *np3,
-                       float *agg_out, int S, const Graph &g, Dims d, const PassW<float> &w, bool f16,
-                       hipStream_t st);
-// Twelve-wave EdgeBlock (edge_block3_kernel + edge_c2_kernel): ONE 768-thread workgroup per CU with the CU's LDS.
-#ifndef RN_E3_WAVES
-#define RN_E3_WAVES 12
-#endif
-constexpr size_t kEdge3LdsBudget = RN_E3_WAVES <= 4 ? 54272 : (RN_E3_WAVES <= 6 ? 80 : 158) * 1024;
-size_t edge3_lds_bytes(int rows, int in_rows, int nodes);
-inline int edge3_dests_per_round() { return 4 * RN_E3_WAVES; }
-bool edge3_supported(const Graph &g, Dims d);
-bool edge3_applicable(const PassW<float> &w, bool f16);
-void launch_edge3(const float *edge_in, float *edge_out, const float *np3, const float *c2, float *agg_out, int S,
-                  const Graph &g, Dims d, const PassW<float> &w, hipStream_t st);
-bool node_fused_wave_tiles();  // the split-f16 NodeBlock runs wave-autonomous: 16-row tiles, four per workgroup step
-size_t node_wave_lds_bytes(int tile_in_rows, int tile_nodes);
-// Frame-pipelined EdgeBlock (kernels_fused.hip: edge_block2_kernel) and the c2 branch as its own
-// streaming kernel: float32, FnP == FeP == 64, same LDS budget for two workgroups per CU.
-size_t edge2_lds_bytes(int tile_out_rows, int tile_in_rows, int tile_nodes);
-bool edge2_supported(const Graph &g, Dims d);
-// c2[S*E, FeP] = LayerNorm(gate(LayerNorm(c2_linear(node[b] * node[a]))))  (_gnn.py:200-228)
-void launch_edge_c2(const float *node, float *c2, int S, const Graph &g, Dims d, const PassW<float> &w, bool f16,
-                    hipStream_t st);
-void launch_edge2(const float *edge_in, float *edge_out, const float *np3, const float *c2, float *agg_out, int S,
-                  const Graph &g, Dims d, const PassW<float> &w, bool f16, hipStream_t st);
-#endif  // RN_EXPERIMENTS
 
 // Device-resident optimisation step (kernels_train.hip); offsets index the packed weight blob.
 struct DerivedOp {

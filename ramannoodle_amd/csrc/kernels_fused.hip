@@ -6,8 +6,8 @@
 // split-f16 instantiation was not bit-reproducible on v_mfma_f32_16x16x32_f16 when two of its workgroups shared a CU
 // (profiles/r04/mfma_k32.txt) and the cause was never found.  Its callers -- graphs the role-specialised kernel's ring
 // refuses, passes without the folded gate scale, the exact-f32 mode, RN_POTGNN_EDGE_PS=0 / RN_POTGNN_TAPE_PS=0 -- now run
-// the unfused chain (projections + edge_agg_kernel, api.hip: edge_unfused_in_blocks).  The kernel is kept, unchanged, in
-// experiments/kernels_edge_frame.hip (-DRN_EXPERIMENTS=1 builds only, RN_POTGNN_EDGE_FRAME=1 to select it).
+// the unfused chain (projections + edge_agg_kernel, api.hip: edge_unfused_in_blocks).  The kernel itself is in git history;
+// what remains of it here is its LDS footprint (edge_fused_lds_bytes, below), which still sizes the EdgeBlock's atom tiles.
 #include "fused_common.hpp"
 
 namespace rn {
@@ -216,12 +216,6 @@ void launch_node_fused(const float *edge, const float *node_in, const float *npc
   if (S == 0 || g.N == 0) return;
   NodeFusedArgs a{edge, node_in, npc1, node_out, S, g, d, w};
   const bool pad = d.Fn != d.FnP;
-#if RN_EXPERIMENTS
-  if (f16 && node_fused_wave_tiles()) {  // opt-in wave-autonomous form (experiments/)
-    launch_node_wave(a, st);
-    return;
-  }
-#endif
   const size_t lds = node_fused_lds_bytes(g);
   auto kern = f16 ? (centred ? (pad ? &node_block_fused_kernel<true, true, true> : &node_block_fused_kernel<false, true, true>)
                              : (pad ? &node_block_fused_kernel<true, true> : &node_block_fused_kernel<false, true>))
@@ -430,6 +424,8 @@ void launch_readout_fused(const float *edge, int64_t M, const ReadoutW<float> &w
   else launch(&readout_fused_kernel<false>, 4, false);
 }
 
+// LDS footprint of the retired per-frame EdgeBlock kernel.  The planner (graph_plan.hip) still sizes the EdgeBlock's atom
+// tiles with it and derives use_fused from it: another measure would change plans (tests/golden/graph_plans.npz).
 size_t edge_fused_lds_bytes(const Graph &g) {
   return fused_lds(g.max_tile_out_rows, g.max_tile_in_rows, g.max_tile_nodes).total;
 }

@@ -1053,8 +1053,7 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         flags = _lib.load().rn_potgnn_config_flags(self._ensure_handle())
         return {"fused_edge_block": bool(flags & 1), "folded_gate_scale": bool(flags & 2),
                 "split_f16_mfma": bool(flags & 4), "narrow_kernels": bool(flags & 8),
-                "mfma_range_fallback": bool(flags & 16), "pipelined_edge_block": bool(flags & 32),
-                "twelve_wave_edge_block": bool(flags & 64), "experiment_kernels": bool(flags & 128),
+                "mfma_range_fallback": bool(flags & 16),
                 "role_split_edge_block": bool(flags & 256), "atom_owning_node_block": bool(flags & 512),
                 "split_f16_pair_rows": bool(flags & 1024)}
 

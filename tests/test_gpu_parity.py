@@ -657,7 +657,7 @@ def test_repeated_evaluation_is_bit_identical(monkeypatch, edge_ps):
     workgroup a frame lands in.  Perf and parity widths; with the role-specialised EdgeBlock (the default, split
     products on the K = 32 f16 MFMA like every other kernel) and with ``RN_POTGNN_EDGE_PS=0``, which since round 5 hands
     the EdgeBlock of the fused pipeline to the unfused chain (the per-frame fused kernel that was NOT reproducible on the
-    K = 32 instruction is retired from the product build: ``experiments/kernels_edge_frame.hip``)."""
+    K = 32 instruction is retired: ``profiles/r04/mfma_k32.txt`` and git history)."""
     from bench import make_workload
     monkeypatch.setenv("RN_POTGNN_EDGE_PS", edge_ps)
     for hparams, frames in (("perf", 3000), ("parity", 3000)):
@@ -823,29 +823,6 @@ def test_every_width_up_to_16_takes_the_narrow_kernels(fn, fe):
     assert model.config_flags()["narrow_kernels"]
     want = O.calc_polarizabilities(oracle, pos, faithful=False)
     assert _rel_err((got - oracle.mean) / oracle.std, (want - oracle.mean) / oracle.std) < REL, (fn, fe)
-
-
-@pytest.mark.parametrize("knob, flag", [("RN_POTGNN_EDGE2", "pipelined_edge_block"), ("RN_POTGNN_EDGE3", "twelve_wave_edge_block")])
-@pytest.mark.parametrize("case, cutoff, fn, fe, frames", [("triclinic20", 3.4, 64, 64, 5), ("rocksalt64_parity", 3.2, 50, 40, 9)])
-def test_opt_in_edge_block_kernels_against_oracle(monkeypatch, knob, flag, case, cutoff, fn, fe, frames):
-    """Experiment builds only (experiments/, -DRN_EXPERIMENTS=1; skipped on the product library).
-    The two restructured forms of the fused EdgeBlock that stay in the tree as measured alternatives
-    (frame-pipelined: profiles/r03/edge2_experiment.txt; twelve waves with the c2 branch in its own kernel:
-    profiles/r03/edge3_experiment.txt) compute the same thing as the default kernel: ragged and regular graph,
-    full and padded widths, several frames per workgroup."""
-    from oracle import potgnn_oracle as O
-    monkeypatch.setenv(knob, "1")
-    g = load_golden(case)
-    model, oracle = _random_model(g, cutoff, fn, fe, 2, seed=fn * 31 + fe)
-    rng = np.random.default_rng(11)
-    base = g["pos_batch"]
-    pos = base[rng.integers(0, len(base), size=frames)] + rng.normal(scale=2e-3, size=(frames,) + base.shape[1:])
-    got = model.calc_polarizabilities(pos)
-    if not model.config_flags()["experiment_kernels"]:
-        pytest.skip("product build: the experiment kernels need RN_EXTRA_FLAGS=-DRN_EXPERIMENTS=1 (csrc/build.sh)")
-    assert model.config_flags()[flag]
-    want = O.calc_polarizabilities(oracle, pos, faithful=False)
-    assert _rel_err((got - oracle.mean) / oracle.std, (want - oracle.mean) / oracle.std) < REL, (knob, case)
 
 
 @pytest.mark.parametrize("fn, fe", [(32, 64), (20, 48), (5, 64), (16, 40)])

@@ -621,10 +621,11 @@ def _parse_plan(flat, n, e):
         length = int(flat[i])
         plan[part] = (flat[i + 1:i + 1 + length], tuple(int(v) for v in flat[i + 1 + length:i + 4 + length]))
         i += length + 4
-    for key in ("nt_narrow", "na_num", "na_max_deg", "pt_back", "pt_gram", "T", "use_fused", "use_edge2", "use_edge3", "use_ps",
+    for key in ("nt_narrow", "na_num", "na_max_deg", "pt_back", "pt_gram", "T", "use_fused", "reserved0", "reserved1", "use_ps",
                 "use_narrow", "use_node_fused", "use_readout_fused", "num_lanes"):
         plan[key] = int(flat[i])
         i += 1
+    assert plan["reserved0"] == 0 and plan["reserved1"] == 0
     plan["head"] = flat[:i]
     for key, size in (("out_ptr", n + 1), ("in_ptr", n + 1), ("in_edge", e), ("in_pos", e), ("rev_edge", e), ("trip_off", e + 1)):
         plan[key] = flat[i:i + size]
