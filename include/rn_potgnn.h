@@ -522,6 +522,60 @@ int rn_md_raman_segments_device(const double *d_alpha, int64_t S, int64_t segmen
                                 const double *weights, int64_t K, int average, int device, size_t workspace_limit,
                                 double *intensities, int64_t num_bins, void *stream);
 
+/*
+ * rn_md_raman_segments with the segments laid by a table: segment q starts at step starts[q] (host int64[Q], Q >= 1)
+ * instead of q * hop, d_q[t] = tau[t] (alpha[starts[q] + t + 1] - alpha[starts[q] + t]).  alpha may be several runs
+ * joined end to end: the caller lays the table so that no segment crosses a run boundary (the difference across one is
+ * a jump that would put a broadband artefact into every bin), and average = 1 is then the mean over all segments of
+ * all runs in one call.  intensities: host float64[Q][K][num_bins] (average = 0, rows in table order) or
+ * float64[K][num_bins] (average = 1).  Taper, weights, num_bins, the mean on the power spectra in table order without
+ * atomics, workspace_limit (which also counts the 8 Q bytes of the table), RN_ERR_OUT_OF_MEMORY and the null stream are
+ * rn_md_raman_segments'; with starts[q] = q * hop the result is bit-identical to it (the same arithmetic in the same
+ * order).  Checks, before any device work: a null pointer, K < 1, segment_steps < 3 or > S, Q < 1, a wrong num_bins,
+ * average not 0 or 1, a start < 0 or > S - segment_steps (RN_ERR_INVALID_ARGUMENT each); then hipFFT and the device as
+ * there.  Plans and work buffers are cached in a cache of their own, shared with rn_md_raman_partial_segments and apart
+ * from the caches of the other four reducers.
+ */
+int rn_md_raman_segments_at(const double *alpha, int64_t S, int64_t segment_steps, const int64_t *starts, int64_t Q,
+                            const double *taper, const double *weights, int64_t K, int average, int device,
+                            size_t workspace_limit, double *intensities, int64_t num_bins);
+/* The same for a time series already in HBM (d_alpha: device float64[S][3][3], produced on `stream`): the call
+ * synchronises `stream` before it reads d_alpha; starts, taper and weights stay host arrays. */
+int rn_md_raman_segments_at_device(const double *d_alpha, int64_t S, int64_t segment_steps, const int64_t *starts,
+                                   int64_t Q, const double *taper, const double *weights, int64_t K, int average,
+                                   int device, size_t workspace_limit, double *intensities, int64_t num_bins,
+                                   void *stream);
+
+/*
+ * Segment-averaged (Welch) and time-resolved partial (atom-group) MD Raman spectra: rn_md_raman_partial per segment of a
+ * start table.  increments: host float64[N][G][9], 1 <= G <= 16; increment t belongs to the step from frame t to frame
+ * t + 1 of the N + 1 frames, so frame indices mean what they mean in rn_md_raman_segments_at: a segment of
+ * segment_steps = W frames starting at frame starts[q] uses the n = W - 1 increments starts[q] .. starts[q] + W - 2,
+ * multiplied by tau[0..n-1], and 0 <= starts[q], starts[q] + W - 1 <= N.  Runs are joined with one row between them
+ * (the increment across the boundary, or zeros) that no segment of a boundary-respecting table reads.  Row (q, k, g <= h)
+ * is rn_md_raman_partial's I_k[g][h](f) of segment q's tapered increments, bins 1..num_bins of fftfreq(n),
+ * num_bins = ceil(n/2) - 1.  intensities: host float64[Q][K][G(G+1)/2][num_bins] (average = 0) or
+ * float64[K][G(G+1)/2][num_bins] (average = 1: the arithmetic mean over the segments, taken on the contracted cross-power
+ * spectra before the inverse transform, summed per (row, frequency) by one thread in table order: repeated calls are
+ * bit-identical), the pairs packed as in rn_md_raman_partial.  The mean costs 6 G Q forward FFTs and 2 K G(G+1)/2 more.
+ * Checks, before any device work: a null pointer, G < 1 or > 16, N < 1, K < 1, segment_steps < 3 or > N + 1, Q < 1, a
+ * wrong num_bins, average not 0 or 1, a start out of range (RN_ERR_INVALID_ARGUMENT each); then hipFFT
+ * (RN_ERR_UNSUPPORTED) and the device (RN_ERR_NO_DEVICE).  workspace_limit (bytes, 0 = 4 GiB) bounds the device memory
+ * besides the staged increments: segments go through the forward FFTs in blocks and rows through the back half in
+ * sub-blocks; a limit that one segment and one row do not fit in returns RN_ERR_OUT_OF_MEMORY.  Work runs on the null
+ * stream; the call returns when the intensities are on the host.
+ */
+int rn_md_raman_partial_segments(const double *increments, int64_t N, int G, int64_t segment_steps,
+                                 const int64_t *starts, int64_t Q, const double *taper, const double *weights,
+                                 int64_t K, int average, int device, size_t workspace_limit, double *intensities,
+                                 int64_t num_bins);
+/* The same for increments already in HBM (d_increments: device float64[N][G][9], produced on `stream`): the call
+ * synchronises `stream` before it reads them; only the intensities travel to the host. */
+int rn_md_raman_partial_segments_device(const double *d_increments, int64_t N, int G, int64_t segment_steps,
+                                        const int64_t *starts, int64_t Q, const double *taper, const double *weights,
+                                        int64_t K, int average, int device, size_t workspace_limit,
+                                        double *intensities, int64_t num_bins, void *stream);
+
 /* Introspection: bit 0 = the fused EdgeBlock kernel is in use (float32, Fn and Fe padded to
  * 64); bit 1 = every pass takes the folded-LayerNorm-scale triplet loop; bit 2 = the fused
  * kernels' matrix products run as split-f16 MFMA (default; RN_POTGNN_MFMA=f32 at create time

@@ -107,6 +107,14 @@ SIGNATURES = {
                                        C.c_size_t, _P, C.c_int64]),
     "rn_md_raman_segments_device": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int, C.c_int,
                                               C.c_size_t, _P, C.c_int64, _P]),
+    "rn_md_raman_segments_at": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int, C.c_int,
+                                          C.c_size_t, _P, C.c_int64]),
+    "rn_md_raman_segments_at_device": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int,
+                                                 C.c_int, C.c_size_t, _P, C.c_int64, _P]),
+    "rn_md_raman_partial_segments": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64,
+                                               C.c_int, C.c_int, C.c_size_t, _P, C.c_int64]),
+    "rn_md_raman_partial_segments_device": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P,
+                                                      C.c_int64, C.c_int, C.c_int, C.c_size_t, _P, C.c_int64, _P]),
     # include/rn_ingest.h (host-only trajectory reader)
     "rn_xdatcar_open": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "rn_xdatcar_close": (None, [_P]),

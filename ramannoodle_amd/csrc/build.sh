@@ -11,7 +11,7 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function ${R
 bdir="build${tag:+_$tag}"
 mkdir -p "$here/$bdir"
 pids=()
-hip_srcs="api graph_plan kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group spectrum spectrum_polarized spectrum_partial spectrum_segments"
+hip_srcs="api graph_plan kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group spectrum spectrum_polarized spectrum_partial spectrum_segments spectrum_ensemble"
 objs=()
 for f in $hip_srcs; do
   o="$here/$bdir/$(basename "$f").o"
@@ -19,7 +19,7 @@ for f in $hip_srcs; do
   if [ ! -f "$o" ] || [ "$here/$f.hip" -nt "$o" ] || [ "$here/fused_common.hpp" -nt "$o" ] || \
      [ "$here/kernels.hpp" -nt "$o" ] || [ "$here/device_utils.hpp" -nt "$o" ] || \
      [ "$here/graph_plan.hpp" -nt "$o" ] || \
-     [ "$here/spectrum_common.hpp" -nt "$o" ] || \
+     [ "$here/spectrum_common.hpp" -nt "$o" ] || [ "$here/spectrum_segment_core.hpp" -nt "$o" ] || \
      [ "$here/../../include/rn_potgnn.h" -nt "$o" ]; then
     extra=""
     # (the two kernels with hand-counted vmcnt waits keep their assembly listing for tools/check_ps_isa.py, below)

@@ -1,5 +1,5 @@
-// What the four on-device MD spectrum reducers share (spectrum.hip, spectrum_polarized.hip, spectrum_partial.hip,
-// spectrum_segments.hip): the hipFFT loader, the series-length arithmetic, RAII holders for plans and device buffers, the
+// What the on-device MD spectrum reducers share (spectrum.hip, spectrum_polarized.hip, spectrum_partial.hip,
+// spectrum_segments.hip, spectrum_ensemble.hip): the hipFFT loader, the series-length arithmetic, RAII holders for plans and device buffers, the
 // most-recently-used plan cache, the argument / device check, the host-or-HBM source of a call and the two per-slot
 // kernels of the polarized, partial and segment pipelines.  Each reducer keeps its own signal builder, power /
 // contraction kernel, plans struct, workspace arithmetic and pipeline.
@@ -11,7 +11,8 @@
 //    (`alpha`, `incr`) are outside the accounting by rn_potgnn.h's own words and use Fit::kGrowOnly.
 //  * Shrink and retry.  The polarized reducer shrinks G (pairs per group, then balanced over ceil(21/G) groups), the
 //    partial reducer shrinks B (rows per block, capped by the row count) and the segment reducer shrinks B and R
-//    (segments and rows per block) together; they differ in the key, the balancing, the
+//    (segments and rows per block) together, as do the start-table reducers of spectrum_ensemble.hip through the same
+//    spectrum_segment_core.hpp; they differ in the key, the balancing, the
 //    per-slot cost and what the leftover bytes are used for, and share only "make, measure the work areas, drop".
 //    So each keeps its own loop over the shared cache and arithmetic below.
 #pragma once

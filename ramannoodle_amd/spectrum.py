@@ -328,14 +328,17 @@ def _segment_starts(steps: int, width: int, hop: int) -> NDArray[np.int64]:
 _SEGMENT_CHUNK_ELEMENTS = 1 << 23  # complex spectra held at once by the host path
 
 
-def _md_segments_host(polarizability_ts, timestep: float, weights, width: int, hop: int, tau, average: bool):
+def _md_segments_host(polarizability_ts, timestep: float, weights, width: int, hop, tau, average: bool, starts=None):
     """(wavenumbers, ``I[K][bins]`` or ``I[Q][K][bins]``) on the host, from the definition (``include/rn_potgnn.h``,
     ``rn_md_raman_segments``): per segment the zero-padded transforms of the six tapered difference components, the
     contracted power spectrum of each configuration, its inverse transform, the positive lags and their length-n
-    transform; the mean over the segments is taken on the power spectra."""
+    transform; the mean over the segments is taken on the power spectra.  ``starts`` (the first step of each segment,
+    ``rn_md_raman_segments_at``) replaces the grid of ``hop``: a table that respects the run boundaries of a
+    concatenated series never reads a difference across one."""
     d = _symmetric_components(np.diff(np.asarray(polarizability_ts, dtype=np.float64), axis=0))  # (S - 1, 6)
     n = width - 1
-    starts = _segment_starts(d.shape[0] + 1, width, hop)
+    if starts is None:
+        starts = _segment_starts(d.shape[0] + 1, width, hop)
     wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
     keep = np.flatnonzero(wavenumbers >= 0)[1:]
     length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
@@ -372,6 +375,47 @@ def _md_segments_on_device(alpha, timestep: float, weights, width: int, hop: int
     return _call_md_reducer("rn_md_raman_segments", alpha, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
                             (steps, width, hop, C.c_void_p(tau.ctypes.data), *weight_args, int(bool(average))),
                             (workspace_limit,))
+
+
+def ensemble_segment_starts(run_lengths, segment_steps, hop=None) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
+    """The segments of several runs joined end to end: ``(starts, run_index)``, both ``int64[Q]``.
+
+    ``run_lengths``: the number of steps ``S_r`` of each run; ``segment_steps`` and ``hop`` as in ``segment_plan``.
+    Run r contributes its own ``(S_r - segment_steps) // hop + 1`` segments, in run order; ``starts`` counts steps of
+    the concatenated series (the run's offset plus the start within the run) and ``run_index`` names the run, so no
+    segment crosses a run boundary.  A run shorter than ``segment_steps`` is a ``ValueError``."""
+    lengths = [int(length) for length in run_lengths]
+    if not lengths:
+        raise ValueError("an ensemble needs at least one run")
+    starts, run_index, offset = [], [], 0
+    for run, length in enumerate(lengths):
+        width, step, _ = segment_plan(length, segment_steps, hop, "boxcar")
+        own = _segment_starts(length, width, step)
+        starts.append(own + offset)
+        run_index.append(np.full(len(own), run, dtype=np.int64))
+        offset += length
+    return np.concatenate(starts), np.concatenate(run_index)
+
+
+def _table_arguments(starts):
+    """``(contiguous int64 starts, their (pointer, Q) arguments)``."""
+    import ctypes as C
+    starts = np.ascontiguousarray(starts, dtype=np.int64)
+    return starts, (C.c_void_p(starts.ctypes.data), starts.shape[0])
+
+
+def _md_segments_at_on_device(alpha, timestep: float, weights, width: int, starts, tau, average: bool, device: int,
+                              stream=None, workspace_limit: int = 0):
+    """(wavenumbers, uncorrected ``I[K][bins]`` or ``I[Q][K][bins]``) from ``rn_md_raman_segments_at`` (host alpha) or,
+    with a torch CUDA tensor, ``rn_md_raman_segments_at_device`` ordered after ``stream``."""
+    import ctypes as C
+    weights, weight_args = _weights_arguments(weights)
+    starts, table_args = _table_arguments(starts)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    shape = (weights.shape[0],) if average else (len(starts), weights.shape[0])
+    return _call_md_reducer("rn_md_raman_segments_at", alpha, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
+                            (alpha.shape[0], width, *table_args, C.c_void_p(tau.ctypes.data), *weight_args,
+                             int(bool(average))), (workspace_limit,))
 
 
 class PhononRamanSpectrum(RamanSpectrum):
@@ -670,6 +714,140 @@ class DeviceMDRamanSpectrum(_DeviceResident, MDRamanSpectrum):
         return _md_segments_on_device(source, self._timestep, weights, width, hop, tau, average, device, stream=stream)
 
 
+# ----------------------------------------------------------------------------- ensembles of runs
+def _run_offsets(run_lengths) -> NDArray[np.int64]:
+    return np.concatenate([[0], np.cumsum(run_lengths)[:-1]]).astype(np.int64)
+
+
+def _equal_run_length(run_lengths) -> int:
+    if len(set(run_lengths)) != 1:
+        raise ValueError(f"the mean of the runs' whole spectra needs runs of one length, not {sorted(set(run_lengths))}: "
+                         "use measure_segments")
+    return run_lengths[0]
+
+
+class MDRamanEnsemble(MDRamanSpectrum):
+    """Spectra averaged over several independent runs (an addition): ``runs`` is a sequence of polarizability time
+    series ``(S_r,3,3)`` sharing ``timestep`` (fs), for example NVE branches started from NVT snapshots.
+
+    ``measure_segments`` / ``measure_segments_polarized`` are ``MDRamanSpectrum``'s with the segments of every run
+    (``ensemble_segment_starts``): ``average=True`` is the mean over all segments of all runs, ``average=False`` gives
+    the rows in run order.  No segment crosses a run boundary, where the difference of the joined series is a jump
+    that would put a broadband artefact into every bin.  ``measure`` / ``measure_polarized`` are the mean of the runs'
+    whole spectra (the boxcar segment of ``S_r`` steps), defined when the runs have one length.  ``device`` (an int)
+    reduces all runs in one call on that GPU (``rn_md_raman_segments_at``)."""
+
+    def __init__(self, runs, timestep: float):  # pylint: disable=super-init-not-called
+        runs = list(runs)
+        if not runs:
+            raise ValueError("an ensemble needs at least one run")
+        for index, run in enumerate(runs):
+            verify_ndarray_shape(f"runs[{index}]", run, (None, 3, 3))
+        self._run_lengths = [int(run.shape[0]) for run in runs]
+        self._polarizability_ts = np.concatenate([np.asarray(run, dtype=np.float64) for run in runs], axis=0)
+        self._timestep = timestep
+
+    @property
+    def run_lengths(self) -> list[int]:
+        return list(self._run_lengths)
+
+    @property
+    def runs(self):
+        """The runs' series, views of the joined ``polarizability_ts``."""
+        bounds = np.cumsum(self._run_lengths)[:-1]
+        return np.split(self._polarizability_ts, bounds, axis=0)
+
+    def _segments_at_on_device(self, weights, width, starts, tau, average, device: int):
+        return _md_segments_at_on_device(self._polarizability_ts, self._timestep, weights, width, starts, tau, average,
+                                         device)
+
+    def _segments(self, weights, segment_steps, hop, taper, average, device):
+        width, hop, tau = segment_plan(min(self._run_lengths), segment_steps, hop, taper)
+        starts, _ = ensemble_segment_starts(self._run_lengths, width, hop)
+        if device is not None:
+            return self._segments_at_on_device(weights, width, starts, tau, bool(average), int(device))
+        return _md_segments_host(self._polarizability_ts, self._timestep, weights, width, hop, tau, bool(average),
+                                 starts=starts)
+
+    def segment_starts(self, segment_steps, hop=None) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
+        """``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
+        starts, run_index = ensemble_segment_starts(self._run_lengths, segment_steps, hop)
+        return run_index, starts - _run_offsets(self._run_lengths)[run_index]
+
+    def _whole(self, weights, device):
+        """The mean over the runs of each run's whole spectrum: one boxcar segment per run."""
+        steps = _equal_run_length(self._run_lengths)
+        return self._segments(weights, steps, steps, "boxcar", True, device)
+
+    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
+                bose_einstein_correction=False, temperature=300, device=None):
+        """The mean of ``MDRamanSpectrum(run, timestep).measure()`` over the runs; a ``ValueError`` unless they have
+        one length (their wavenumbers differ otherwise)."""
+        _require_polycrystalline(orientation)
+        wavenumbers, intensities = self._whole(_measure_weights(), device)
+        intensities = _apply_corrections(wavenumbers, intensities[0], laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities
+
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False, laser_wavelength=522,
+                          bose_einstein_correction=False, temperature=300, device=None):
+        """The mean of the runs' ``measure_polarized``; a ``ValueError`` unless they have one length."""
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        wavenumbers, intensities = self._whole(weights, device)
+        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities[0] if squeeze else intensities
+
+
+def _joined_tensor(name: str, runs, run_lengths, rows_short: int):
+    """``(tensor, run_lengths)`` of a device ensemble: ``runs`` is one CUDA tensor holding the runs end to end, with
+    ``run_lengths`` (steps per run; the tensor has ``sum(run_lengths) - rows_short`` rows), or a sequence of tensors."""
+    import torch
+    if isinstance(runs, torch.Tensor):
+        if run_lengths is None:
+            raise ValueError(f"{name}: one joined tensor needs run_lengths")
+        lengths = [int(length) for length in run_lengths]
+        if not lengths or min(lengths) < 1 or sum(lengths) - rows_short != runs.shape[0]:
+            raise ValueError(f"{name}: run_lengths {lengths} do not add up to the {runs.shape[0]} rows of the tensor")
+        return runs, lengths
+    if run_lengths is not None:
+        raise ValueError(f"{name}: run_lengths goes with one joined tensor, not with a sequence of runs")
+    runs = list(runs)
+    if not runs:
+        raise ValueError("an ensemble needs at least one run")
+    return runs, None
+
+
+class DeviceMDRamanEnsemble(_DeviceResident, MDRamanEnsemble):
+    """``MDRamanEnsemble`` whose runs stay in HBM: ``runs`` is a sequence of contiguous float64 CUDA tensors
+    ``(S_r,3,3)`` (joined here, on the GPU), or one tensor holding them end to end plus ``run_lengths``, as one batched
+    evaluation writes it.  Every measurement reduces on that GPU (``rn_md_raman_segments_at_device``, ordered after
+    torch's current stream) unless ``host=True``."""
+
+    def __init__(self, runs, timestep: float, run_lengths=None):  # pylint: disable=super-init-not-called
+        import torch
+        runs, lengths = _joined_tensor("runs", runs, run_lengths, 0)
+        if lengths is None:
+            lengths = [int(run.shape[0]) for run in runs]
+            runs = runs[0] if len(runs) == 1 else torch.cat(runs, dim=0)
+        self._set_tensor("runs", runs, 3, "(_,3,3)")
+        self._run_lengths = lengths
+        self._timestep = timestep
+
+    @property
+    def polarizability_ts(self):
+        return self._host()
+
+    @property
+    def _polarizability_ts(self):  # what the host paths read
+        return self._host()
+
+    def _segments_at_on_device(self, weights, width, starts, tau, average, device: int):
+        source, stream = self._source(device)
+        return _md_segments_at_on_device(source, self._timestep, weights, width, starts, tau, average, device,
+                                         stream=stream)
+
+
 # ----------------------------------------------------------------------------- atom-group (partial) spectra
 MAX_GROUPS = 16  # kMaxGroups of csrc/kernels.hpp
 
@@ -765,6 +943,69 @@ def _md_partial_on_device(increments, timestep: float, weights, device: int, str
     return wavenumbers, _unpack_pairs(packed, num_groups)
 
 
+def _md_partial_segments_host(increments, timestep: float, weights, width: int, starts, tau, average: bool):
+    """(wavenumbers, ``I[K,G,G,bins]`` or ``I[Q,K,G,G,bins]``) on the host, from the definition (``include/rn_potgnn.h``,
+    ``rn_md_raman_partial_segments``): per segment of ``width`` frames starting at frame ``starts[q]`` the zero-padded
+    transforms of the tapered components of increments ``starts[q] .. starts[q] + width - 2``, for each pair of groups
+    their cross-power contracted with each configuration's form, its inverse transform, the positive lags and their
+    length-n transform; the mean over the segments is taken on the contracted cross-powers."""
+    d = _symmetric_components(np.asarray(increments, dtype=np.float64))  # (N, G, 6)
+    num_groups = d.shape[1]
+    n = width - 1
+    starts = np.asarray(starts, dtype=np.int64)
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    keep = np.flatnonzero(wavenumbers >= 0)[1:]
+    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    forms = _weight_forms(weights)
+    count = weights.shape[0]
+    rows, cols = np.triu_indices(num_groups)
+
+    def finish(power):  # (..., length / 2 + 1) -> (..., bins)
+        lags = np.fft.irfft(power, n=length, axis=-1)[..., :n]
+        return np.real(scipy.fftpack.fft(lags, axis=-1))[..., keep]
+
+    out = None if average else np.empty((len(starts), count, len(rows), len(keep)))
+    mean = np.zeros((count, len(rows), length // 2 + 1))
+    per_segment = (length // 2 + 1) * max(6 * num_groups, 36, count)
+    chunk = max(1, _SEGMENT_CHUNK_ELEMENTS // per_segment)
+    for first in range(0, len(starts), chunk):
+        index = starts[first:first + chunk, None] + np.arange(n)[None, :]
+        spectra = np.fft.rfft(d[index] * tau[None, :, None, None], n=length, axis=1)  # (q, length / 2 + 1, G, 6)
+        for pair, (g, h) in enumerate(zip(rows, cols)):
+            cross = np.real(spectra[:, :, g, :, None] * np.conj(spectra[:, :, h, None, :]))
+            power = np.einsum("kce,qfce->qkf", forms, cross)
+            if average:
+                mean[:, pair] += power.sum(axis=0)
+            else:
+                out[first:first + chunk, :, pair] = finish(power)
+    if average:
+        return wavenumbers[keep], _unpack_pairs(finish(mean / len(starts)), num_groups)
+    unpacked = _unpack_pairs(out.reshape(len(starts) * count, len(rows), len(keep)), num_groups)
+    return wavenumbers[keep], unpacked.reshape(len(starts), count, num_groups, num_groups, len(keep))
+
+
+def _md_partial_segments_on_device(increments, timestep: float, weights, width: int, starts, tau, average: bool,
+                                   device: int, stream=None, workspace_limit: int = 0):
+    """(wavenumbers, uncorrected ``I[K,G,G,bins]`` or ``I[Q,K,G,G,bins]``) from ``rn_md_raman_partial_segments`` (host
+    increments) or, with a torch CUDA tensor, ``rn_md_raman_partial_segments_device`` ordered after ``stream``."""
+    import ctypes as C
+    steps, num_groups = increments.shape[0], increments.shape[1]
+    pairs = num_groups * (num_groups + 1) // 2
+    weights, weight_args = _weights_arguments(weights)
+    starts, table_args = _table_arguments(starts)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    count = weights.shape[0]
+    shape = (count, pairs) if average else (len(starts) * count, pairs)
+    wavenumbers, packed = _call_md_reducer(
+        "rn_md_raman_partial_segments", increments, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
+        (steps, num_groups, width, *table_args, C.c_void_p(tau.ctypes.data), *weight_args, int(bool(average))),
+        (workspace_limit,))
+    unpacked = _unpack_pairs(packed, num_groups)
+    if not average:
+        unpacked = unpacked.reshape(len(starts), count, num_groups, num_groups, -1)
+    return wavenumbers, unpacked
+
+
 class _PartialSpectrum:
     """``measure`` / ``measure_polarized`` of the partial spectra: ``_partial(weights, device)`` returns the uncorrected
     ``(wavenumbers, I[K,G,G,bins])``; the corrections apply to every ``(g, h)`` row."""
@@ -847,11 +1088,62 @@ class PartialMDRamanSpectrum(_PartialSpectrum):
             return _md_partial_on_device(self.increments, self._timestep, weights, int(device))
         return _md_partial_host(self.increments, self._timestep, weights)
 
+    def _num_increments(self) -> int:
+        return self.increments.shape[0]
+
+    def _segment_table(self, segment_steps, hop, taper):
+        """``(W, tau, starts)``: the segments of the ``S = N + 1`` frames that the ``N`` increments join."""
+        steps = self._num_increments() + 1
+        width, hop, tau = segment_plan(steps, segment_steps, hop, taper)
+        return width, tau, _segment_starts(steps, width, hop)
+
+    def _partial_segments_on_device(self, weights, width, starts, tau, average, device: int):
+        return _md_partial_segments_on_device(self.increments, self._timestep, weights, width, starts, tau, average,
+                                              device)
+
+    def _partial_segments(self, weights, segment_steps, hop, taper, average, device):
+        """The uncorrected ``(wavenumbers, I[K,G,G,bins] or I[Q,K,G,G,bins])`` of both segment measurements."""
+        width, tau, starts = self._segment_table(segment_steps, hop, taper)
+        if device is not None:
+            return self._partial_segments_on_device(weights, width, starts, tau, bool(average), int(device))
+        return _md_partial_segments_host(self.increments, self._timestep, weights, width, starts, tau, bool(average))
+
+    def segment_starts(self, segment_steps, hop=None) -> NDArray[np.int64]:
+        """The first frame of each segment of ``measure_segments`` (frame t is where increment t begins)."""
+        return self._segment_table(segment_steps, hop, "boxcar")[2]
+
+    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
+                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
+                         device=None):
+        """Segment-averaged (Welch) or time-resolved partial spectra: ``MDRamanSpectrum.measure_segments``' segments of
+        ``segment_steps`` frames (``segment_steps - 1`` increments each), with ``I[g,h]`` of ``measure()`` per segment.
+        ``average=True`` returns ``(wavenumbers, I[G,G,bins])``, the mean over the segments, whose variance falls with
+        their number; ``average=False`` the rows ``(wavenumbers, I[Q,G,G,bins])``.  With ``taper="boxcar"`` row q is
+        ``PartialMDRamanSpectrum(increments[a:a + segment_steps - 1], timestep).measure()`` for
+        ``a = segment_starts(...)[q]``.  ``device`` (an int) reduces on that GPU (``rn_md_raman_partial_segments``)."""
+        _require_polycrystalline(orientation)
+        wavenumbers, intensities = self._partial_segments(_measure_weights(), segment_steps, hop, taper, average, device)
+        intensities = _apply_corrections(wavenumbers, intensities[..., 0, :, :, :], laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities
+
+    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
+                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
+                                   bose_einstein_correction=False, temperature=300, device=None):
+        """``measure_segments`` for the configurations of ``polarized_weights``: ``I[K,G,G,bins]``, or
+        ``I[Q,K,G,G,bins]`` with ``average=False``; the ``K`` axis is squeezed when no argument has one."""
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        wavenumbers, intensities = self._partial_segments(weights, segment_steps, hop, taper, average, device)
+        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities[..., 0, :, :, :] if squeeze else intensities
+
 
 class DevicePartialMDRamanSpectrum(_DeviceResident, PartialMDRamanSpectrum):
     """``PartialMDRamanSpectrum`` whose increments stay in HBM (a contiguous float64 CUDA tensor ``(S-1,G,3,3)``):
-    ``measure`` / ``measure_polarized`` reduce them on that GPU (``rn_md_raman_partial_device``, ordered after torch's
-    current stream) unless ``host=True``; ``increments`` copies them to the host on first use."""
+    ``measure`` / ``measure_polarized`` and the segment measurements reduce them on that GPU
+    (``rn_md_raman_partial_device``, ``rn_md_raman_partial_segments_device``, ordered after torch's current stream)
+    unless ``host=True``; ``increments`` copies them to the host on first use."""
 
     def __init__(self, increments_device, timestep: float):  # pylint: disable=super-init-not-called
         self._set_tensor("increments", increments_device, 4, "(_,_,3,3)")
@@ -866,3 +1158,82 @@ class DevicePartialMDRamanSpectrum(_DeviceResident, PartialMDRamanSpectrum):
             return super()._partial(weights, None)
         source, stream = self._source(int(device))
         return _md_partial_on_device(source, self._timestep, weights, int(device), stream=stream)
+
+    def _num_increments(self) -> int:
+        return self._tensor.shape[0]
+
+    def _partial_segments_on_device(self, weights, width, starts, tau, average, device: int):
+        source, stream = self._source(device)
+        return _md_partial_segments_on_device(source, self._timestep, weights, width, starts, tau, average, device,
+                                              stream=stream)
+
+
+class PartialMDRamanEnsemble(PartialMDRamanSpectrum):
+    """Atom-group spectra averaged over several runs: ``runs`` is a sequence of per-group increments ``(S_r-1,G,3,3)``
+    sharing ``G`` and ``timestep``.  The runs are joined with one zero row between them, so that increment t still
+    belongs to frame t of the joined frames; no segment reads that row.  ``measure_segments`` /
+    ``measure_segments_polarized`` take the segments of every run (``ensemble_segment_starts`` of the runs' ``S_r``
+    frames; rows in run order, ``average=True`` the mean over all of them), ``measure`` / ``measure_polarized`` the mean
+    of the runs' whole spectra when the runs have one length.  ``device`` (an int) reduces all runs in one call
+    (``rn_md_raman_partial_segments``)."""
+
+    def __init__(self, runs, timestep: float):  # pylint: disable=super-init-not-called
+        runs = list(runs)
+        if not runs:
+            raise ValueError("an ensemble needs at least one run")
+        for index, run in enumerate(runs):
+            verify_ndarray_shape(f"runs[{index}]", run, (None, runs[0].shape[1], 3, 3))
+        self._run_lengths = [int(run.shape[0]) + 1 for run in runs]  # frames
+        gap = np.zeros((1, *runs[0].shape[1:]))
+        parts = [part for run in runs for part in (np.asarray(run, dtype=np.float64), gap)][:-1]
+        self._increments = np.concatenate(parts, axis=0)
+        self._timestep = timestep
+
+    @property
+    def run_lengths(self) -> list[int]:
+        """Frames per run (one more than its increments)."""
+        return list(self._run_lengths)
+
+    def _segment_table(self, segment_steps, hop, taper):
+        width, hop, tau = segment_plan(min(self._run_lengths), segment_steps, hop, taper)
+        return width, tau, ensemble_segment_starts(self._run_lengths, width, hop)[0]
+
+    def segment_starts(self, segment_steps, hop=None) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
+        """``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
+        starts, run_index = ensemble_segment_starts(self._run_lengths, segment_steps, hop)
+        return run_index, starts - _run_offsets(self._run_lengths)[run_index]
+
+    def _partial(self, weights, device):
+        """The mean over the runs of each run's whole partial spectra: one boxcar segment per run."""
+        steps = _equal_run_length(self._run_lengths)
+        return self._partial_segments(weights, steps, steps, "boxcar", True, device)
+
+
+class DevicePartialMDRamanEnsemble(_DeviceResident, PartialMDRamanEnsemble):
+    """``PartialMDRamanEnsemble`` whose increments stay in HBM: a sequence of contiguous float64 CUDA tensors
+    ``(S_r-1,G,3,3)`` (joined here, on the GPU, with a zero row between them), or one tensor ``(sum(S_r)-1,G,3,3)``
+    plus ``run_lengths`` (frames per run), as one batched evaluation of the joined frames writes it: its rows across
+    the run boundaries stand where the zero rows would and are never read."""
+
+    def __init__(self, runs, timestep: float, run_lengths=None):  # pylint: disable=super-init-not-called
+        import torch
+        runs, lengths = _joined_tensor("runs", runs, run_lengths, 1)
+        if lengths is None:
+            lengths = [int(run.shape[0]) + 1 for run in runs]
+            gap = runs[0].new_zeros((1, *runs[0].shape[1:]))
+            runs = torch.cat([part for run in runs for part in (run, gap)][:-1], dim=0)
+        self._set_tensor("runs", runs, 4, "(_,_,3,3)")
+        self._run_lengths = lengths
+        self._timestep = timestep
+
+    @property
+    def increments(self):
+        return self._host()
+
+    def _num_increments(self) -> int:
+        return self._tensor.shape[0]
+
+    def _partial_segments_on_device(self, weights, width, starts, tau, average, device: int):
+        source, stream = self._source(device)
+        return _md_partial_segments_on_device(source, self._timestep, weights, width, starts, tau, average, device,
+                                              stream=stream)
