@@ -624,6 +624,19 @@ int rn_potgnn_debug_ps_schedule(const int32_t *rb, const int32_t *re, int32_t nu
 int rn_potgnn_debug_plan(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
                          const int32_t *atom_types, int32_t num_cus, int32_t *out, size_t capacity, size_t *count);
 
+/*
+ * Host-only, validated like rn_potgnn_debug_plan: the dynamic LDS bytes each kernel family of that plan would ask for, from
+ * the kernels' own footprint functions.  Written as int64 pairs (float32 instantiation, float64 instantiation), 0 where the
+ * family does not run on this plan or has no such instantiation, in the order
+ *   unfused EdgeBlock (edge_agg_kernel), reverse EdgeBlock (edge_bwd_tile2_kernel / edge_bwd_tile_kernel; 0: the per-row
+ *   kernel without dynamic LDS takes the graph), narrow EdgeBlock, narrow NodeBlock, role-specialised EdgeBlock,
+ *   atom-owning NodeBlock, row-ordered fused NodeBlock.
+ * A compute unit has 163840 bytes; rn_potgnn_create accepts no graph for which an entry is larger.  *count and the
+ * out == NULL / capacity protocol are those of rn_potgnn_debug_plan.
+ */
+int rn_potgnn_debug_plan_lds(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
+                             const int32_t *atom_types, int32_t num_cus, int64_t *out, size_t capacity, size_t *count);
+
 /* Number of edge triplets T of the frozen graph. */
 int64_t rn_potgnn_num_triplets(const rn_potgnn *h);
 

@@ -1006,9 +1006,9 @@ struct ChunkRun {
         if (narrow()) launch_edge_narrow(edge[cur], edge[nxt], node[nxt], S, h->g, h->d, w, st());
         else if (role_split(w)) launch_edge_ps(edge[cur], edge[nxt], node[nxt], np3, tape_agg(p), S, h->g, h->d, w, h->ps_fail.as<int>(), st(), pair_rows(), h->mfma_f16);
         else if (fused()) edge_unfused_in_blocks(p);
-        else launch_edge_agg<T>(bufB, np3, bufA, edge[cur], edge[nxt], S, h->g, h->d, w, tape_agg(p), st());
+        else HIP_TRY(launch_edge_agg<T>(bufB, np3, bufA, edge[cur], edge[nxt], S, h->g, h->d, w, tape_agg(p), st()));
       } else {
-        launch_edge_agg<T>(bufB, np3, bufA, edge[cur], edge[nxt], S, h->g, h->d, w, tape_agg(p), st());
+        HIP_TRY(launch_edge_agg<T>(bufB, np3, bufA, edge[cur], edge[nxt], S, h->g, h->d, w, tape_agg(p), st()));
       }
     }
     cur = nxt;
@@ -1038,8 +1038,8 @@ struct ChunkRun {
       const T *e_in = edge[cur] + (size_t)s0 * g.E * d.FeP, *nd = node[nxt] + (size_t)s0 * g.N * d.FnP;
       project(e_in, rows, d.FeP, w.c3_WeT, 4 * d.FeP, fb, nullptr, 0, nullptr);
       project(nullptr, rows, d.FnP, w.c2_WT, 2 * d.FeP, fa, w.c2_bias, 1, nd);
-      launch_edge_agg<T>(fb, np3 + (size_t)s0 * g.N * 6 * d.FeP, fa, e_in, edge[nxt] + (size_t)s0 * g.E * d.FeP, sb, g, d, w,
-                         agg ? agg + (size_t)s0 * g.E * d.FeP : nullptr, st());
+      HIP_TRY(launch_edge_agg<T>(fb, np3 + (size_t)s0 * g.N * 6 * d.FeP, fa, e_in, edge[nxt] + (size_t)s0 * g.E * d.FeP, sb, g, d, w,
+                                 agg ? agg + (size_t)s0 * g.E * d.FeP : nullptr, st()));
     }
   }
 
@@ -1418,8 +1418,8 @@ void reverse_pass(rn_potgnn *h, ChunkRun<T> &c, const Reverse<T> &rv) {
     project(nullptr, fe, d.FnP, w.c2_WT, 2 * d.FeP, bufA, w.c2_bias, 1, node1);
     // EdgeBlock
     chain_after_side();  // (the previous pass's products have read the dY buffers this pass overwrites)
-    launch_edge_bwd<T>(bufB, c.np3, bufA, edge1, P.tape_agg[p].template as<T>(), de_next, de_prev, b[DPQ],
-                       b[DNP3], b[DC2], C, B, g, d, w, G ? &gw : nullptr, st);
+    HIP_TRY(launch_edge_bwd<T>(bufB, c.np3, bufA, edge1, P.tape_agg[p].template as<T>(), de_next, de_prev, b[DPQ],
+                               b[DNP3], b[DC2], C, B, g, d, w, G ? &gw : nullptr, st));
     side_after_chain(0);
     back_gemm(b[DPQ], ce, 4 * d.FeP, L.pass[p].c3_WeT, L.pass[p].t_c3We, d.FeP, de_prev, true);
     // node_{p+1} cotangent: incoming + projections + c2 operand
@@ -2356,6 +2356,32 @@ int rn_potgnn_debug_plan(const rn_potgnn_config *cfg, const int32_t *edge_a, con
       return RN_ERR_INVALID_ARGUMENT;
     }
     std::memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
+    return RN_OK;
+  } catch (const std::bad_alloc &) {
+    set_error(nullptr, "host allocation failed");
+    return RN_ERR_OUT_OF_MEMORY;
+  }
+}
+
+int rn_potgnn_debug_plan_lds(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
+                             const int32_t *atom_types, int32_t num_cus, int64_t *out, size_t capacity, size_t *count) {
+  if (!count || num_cus <= 0) return RN_ERR_INVALID_ARGUMENT;
+  *count = 0;
+  std::string invalid;
+  const int rc = validate_create_args(cfg, edge_a, edge_b, atom_types, false, nullptr, invalid);
+  if (rc != RN_OK) {
+    set_error(nullptr, "%s", invalid.c_str());
+    return rc;
+  }
+  try {
+    const PlanKnobs knobs = read_plan_knobs();
+    const std::vector<int64_t> lds = plan_graph(*cfg, plan_dims(*cfg, knobs), edge_a, edge_b, atom_types, num_cus, knobs).lds_requests();
+    *count = lds.size();
+    if (!out || capacity < lds.size()) {
+      set_error(nullptr, "out holds %zu values, the table has %zu", out ? capacity : (size_t)0, lds.size());
+      return RN_ERR_INVALID_ARGUMENT;
+    }
+    std::memcpy(out, lds.data(), lds.size() * sizeof(int64_t));
     return RN_OK;
   } catch (const std::bad_alloc &) {
     set_error(nullptr, "host allocation failed");

@@ -76,6 +76,23 @@ Partition greedy_tiles(const GraphPlan &g, Rows what, size_t budget, int cap = 0
   return p;
 }
 
+// what edge_agg_kernel asks of LDS on a partition, in float64 (the float64 chain has no other EdgeBlock)
+size_t edge_agg_f64_lds_bytes(Dims d, int max_out_rows, int max_in_rows, int max_nodes) {
+  Graph s{};
+  s.max_tile_out_rows = max_out_rows, s.max_tile_in_rows = max_in_rows, s.max_tile_nodes = max_nodes;
+  return edge_agg_lds_bytes(s, d, sizeof(double));
+}
+
+// every atom a tile of its own: the partition with the smallest footprint there is (validate_create_args admits a graph
+// when this one fits the CU in float64)
+Partition one_atom_tiles(const GraphPlan &g) {
+  Partition p;
+  p.begin.resize(g.N + 1);
+  for (int n = 0; n <= g.N; ++n) p.begin[n] = n;
+  fill_maxima(p, g);
+  return p;
+}
+
 // node tiles: consecutive atoms whose outgoing-edge rows fit an LDS budget (counted in
 // float32 rows; the float64 path uses twice the bytes for the same tiles).  A workgroup
 // serves its tile's destination edges G at a time (G lane groups), so the budget is chosen
@@ -352,8 +369,15 @@ Dims plan_dims(const rn_potgnn_config &cfg, const PlanKnobs &knobs) {
   return d;
 }
 
-// the rows of one atom's outgoing edges, 2 FeP float64 values (+ an index) each, have to fit a 150 KB LDS tile
-size_t max_out_degree(int FeP) { return (size_t)150 * 1024 / ((size_t)2 * FeP * sizeof(double) + 4); }
+// The float64 EdgeBlock (edge_agg_kernel) keeps a tile's source rows, their scalars, the tile's node rows, the pass's
+// LayerNorm weights and two index tables in LDS.  The smallest tile there is holds one atom: the cap is the largest degree
+// D at which such a tile, with D out-edges and D in-edges (a radius graph has b -> a beside a -> b), still fits the CU --
+// 554 / 292 / 147 / 71 at FeP = 16 / 32 / 64 / 128.
+size_t max_out_degree(Dims d) {
+  size_t deg = 0;
+  while (edge_agg_f64_lds_bytes(d, (int)deg + 1, (int)deg + 1, 1) <= kCuLdsBytes) ++deg;
+  return deg;
+}
 
 int validate_create_args(const rn_potgnn_config *cfg_in, const int32_t *edge_a, const int32_t *edge_b, const int32_t *atom_types,
                          bool others_null, const size_t *num_weights, std::string &error) {
@@ -397,16 +421,26 @@ int validate_create_args(const rn_potgnn_config *cfg_in, const int32_t *edge_a, 
       error = format("atom %d has type %d outside [0,%d)", n, atom_types[n], cfg.num_atom_types);
       return RN_ERR_INVALID_ARGUMENT;
     }
-  // an atom's outgoing-edge rows (in float64) must fit one workgroup's LDS tile
-  const size_t cap = max_out_degree(pad_pow2(cfg.size_edge_embedding));
-  std::vector<int> deg(N, 0);
-  for (int e = 0; e < E; ++e) deg[edge_a[e]]++;
+  // a one-atom tile of the float64 EdgeBlock must fit the CU's LDS at the widths the model is PLANNED at (24 / 20 runs
+  // 64 wide); plan_graph falls back to one-atom tiles where its own choice does not fit, so accepted => every request fits
+  const Dims d = plan_dims(cfg, read_plan_knobs());
+  const size_t cap = max_out_degree(d);
+  std::vector<int> deg(N, 0), deg_in(N, 0);
+  for (int e = 0; e < E; ++e) deg[edge_a[e]]++, deg_in[edge_b[e]]++;
   for (int n = 0; n < N; ++n)
     if ((size_t)deg[n] > cap) {
       error = format("atom %d has %d outgoing edges; more than %zu per atom is unsupported "
                      "for size_edge_embedding=%d", n, deg[n], cap, cfg.size_edge_embedding);
       return RN_ERR_UNSUPPORTED;
     }
+  // (a directed graph whose in-degrees exceed its out-degrees: the tables of the destination edges count as well)
+  const int max_out = *std::max_element(deg.begin(), deg.end()), max_in = *std::max_element(deg_in.begin(), deg_in.end());
+  const size_t need = edge_agg_f64_lds_bytes(d, max_out, max_in, 1);
+  if (need > kCuLdsBytes) {
+    error = format("an atom with %d outgoing edges beside one with %d incoming edges needs %zu bytes of LDS per tile in "
+                   "float64 (%zu available) for size_edge_embedding=%d", max_out, max_in, need, kCuLdsBytes, cfg.size_edge_embedding);
+    return RN_ERR_UNSUPPORTED;
+  }
   return RN_OK;
 }
 
@@ -425,6 +459,13 @@ GraphPlan plan_graph(const rn_potgnn_config &cfg, Dims d, const int32_t *edge_a,
   const bool fused_mode = k.want_fused && d.FnP == 64 && d.FeP == 64;
   const bool narrow_mode = k.want_narrow && narrow_supported(d);
   g.tile = edge_tiles(g, k, fused_mode, narrow_mode);
+  // The searches above size tiles in float32 and always keep their first candidate; the maxima of a partition also mix
+  // tiles (the rows of a hub's tile with the atoms of a tile of low-degree atoms).  Where the float64 EdgeBlock could not
+  // hold the result, every atom gets its own tile: that fits whenever validate_create_args accepted the graph.  The
+  // float32 kernels share Graph::tile_begin, so they run on the one-atom tiles too (slower for such a graph, never wrong:
+  // every kernel that reads this partition -- edge_agg, the narrow EdgeBlock, the reverse kernels without bt_ -- takes any
+  // partition of consecutive atoms and sizes its LDS from the maxima; use_fused / use_narrow below are decided on it).
+  if (edge_agg_f64_lds_bytes(d, g.tile.max_out_rows, g.tile.max_in_rows, g.tile.max_nodes) > kCuLdsBytes) g.tile = one_atom_tiles(g);
   if (k.bwd_tiles) g.bt = reverse_tiles(g);
   if (narrow_mode) g.nt = node_tiles_narrow(g, k);
   g.nt_narrow = g.nt.num() > 0;
@@ -459,6 +500,21 @@ Graph GraphPlan::scalars() const {
   s.pt_num = pt.num(), s.pt_max_out_rows = pt.max_out_rows, s.pt_max_in_rows = pt.max_in_rows, s.pt_back = pt_back, s.pt_gram = pt_gram;
   s.bt_num = bt.num(), s.bt_max_out_rows = bt.max_out_rows, s.bt_max_in_rows = bt.max_in_rows, s.bt_max_nodes = bt.max_nodes;
   return s;
+}
+
+std::vector<int64_t> GraphPlan::lds_requests() const {
+  const Graph s = scalars();
+  const bool node_fused = use_fused && use_node_fused;
+  std::vector<int64_t> o;
+  auto add = [&o](size_t f32, size_t f64) { o.insert(o.end(), {(int64_t)f32, (int64_t)f64}); };
+  add(edge_agg_lds_bytes(s, d, sizeof(float)), edge_agg_lds_bytes(s, d, sizeof(double)));
+  add(edge_bwd_lds_bytes(s, d.FeP, sizeof(float)), edge_bwd_lds_bytes(s, d.FeP, sizeof(double)));
+  add(use_narrow ? edge_narrow_lds_bytes(d.Fn, d.Fe, tile.max_out_rows, tile.max_in_rows) : 0, 0);
+  add(use_narrow && nt_narrow ? node_tiled_lds_bytes(d.Fn, d.Fe, nt.max_in_rows, nt.max_nodes) : 0, 0);
+  add(use_ps ? edge_ps_lds_bytes(pt.max_out_rows, pt.max_in_rows, pt_gram != 0) : 0, 0);
+  add(node_fused && na_num > 0 ? node_atom_lds_bytes(na_max_deg) : 0, 0);
+  add(node_fused ? node_fused_lds_bytes(s) : 0, 0);
+  return o;
 }
 
 std::vector<int32_t> GraphPlan::flat() const {

@@ -40,8 +40,9 @@ PlanKnobs read_plan_knobs();
 int pad_pow2(int f);
 // Which padded widths a model runs at (widen_for_fused decides where a narrower Fn / Fe pads up to the fused kernels' 64).
 Dims plan_dims(const rn_potgnn_config &cfg, const PlanKnobs &knobs);
-// Largest out-degree the tiled kernels take (590 for FeP = 16, 149 for 64, 74 for 128).
-size_t max_out_degree(int FeP);
+// Largest out-degree the tiled kernels take at the planned widths (554 / 292 / 147 / 71 for FeP = 16 / 32 / 64 / 128): what
+// validate_create_args refuses above, from the float64 footprint of edge_agg_kernel (edge_agg_lds_bytes) on a one-atom tile.
+size_t max_out_degree(Dims d);
 
 // The checks of rn_potgnn_create that need no device, in its order (null arguments, the configuration, the weight count
 // unless `num_weights` is null, the edge list, the atom types, the out-degrees).  RN_OK, or the status with its text in `error`.
@@ -78,6 +79,9 @@ struct GraphPlan {
 
   // The scalar fields of Graph; every pointer null (api.hip's upload fills them).
   Graph scalars() const;
+  // Dynamic LDS bytes (float32, float64) each kernel family would ask for on this plan, in the order documented at
+  // rn_potgnn_debug_plan_lds (include/rn_potgnn.h); 0 where the family does not run.  From the kernels' own *_lds_bytes.
+  std::vector<int64_t> lds_requests() const;
   // The plan as rn_potgnn_debug_plan writes it (include/rn_potgnn.h documents the layout).
   std::vector<int32_t> flat() const;
 };

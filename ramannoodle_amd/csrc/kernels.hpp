@@ -162,6 +162,9 @@ void launch_rowgemm(const T *X, int64_t M, int KP, const T *WT, int NOUT, T *Y,
 // float32 only: Y (+)= X[:, 0:N] * Wt[N, NOUT] on the MFMA kernel; false if the shape is unsupported
 // LDS bytes of edge_bwd_tile2_kernel for a tile with these maxima (element size 4 or 8)
 size_t edge_bwd_tile2_lds_bytes(int rows, int in_rows, int nodes, int FP, size_t elem);
+// dynamic LDS bytes the reverse EdgeBlock asks for on this graph: the two-pass kernel on the bt_ tiles (or the forward
+// tiles), else the one-pass tile kernel, else 0 -- the per-row kernel that takes what fits neither uses no dynamic LDS
+size_t edge_bwd_lds_bytes(const Graph &g, int FP, size_t elem);
 // split-f16 row product for the reverse pass (kernels_gemm.hip: rowgemm_split_kernel); false = shape not served
 bool launch_rowgemm_split(const float *X, int ldx, int K, int64_t M, const float *Wt, int NOUT, float *Y,
                           bool accumulate, const float *bias, int amode, const float *node, const Graph &g,
@@ -173,11 +176,13 @@ template <typename T>
 void launch_node_agg(const T *npc1, const T *bc1, const T *node_in, T *node_out, int S,
                      const Graph &g, Dims d, const PassW<T> &w, hipStream_t st);
 
+// (returns what hipFuncSetAttribute or the launch answered: a tile that asks for more LDS than the CU has is an error of
+//  the call, never a silent no-op)
 template <typename T>
-void launch_edge_agg(const T *pq, const T *np3, const T *c2pre, const T *edge_in,
-                     T *edge_out, int S, const Graph &g, Dims d, const PassW<T> &w,
-                     T *agg_out /* optional tape of the pre-LayerNorm triplet sums */,
-                     hipStream_t st);
+hipError_t launch_edge_agg(const T *pq, const T *np3, const T *c2pre, const T *edge_in,
+                           T *edge_out, int S, const Graph &g, Dims d, const PassW<T> &w,
+                           T *agg_out /* optional tape of the pre-LayerNorm triplet sums */,
+                           hipStream_t st);
 
 template <typename T>
 void launch_readout_reduce(const T *pol, const T *unit4, int S, const Graph &g,
@@ -190,6 +195,9 @@ void launch_radius_graph(const double *lattice, const double *pos, int N, float 
 void launch_enum_triplets(const Graph &g, int *idx_i, int *idx_j, int *idx_k, int *slot5,
                           int *slot6, hipStream_t st);
 
+// LDS of one CU (gfx950): no workgroup can ask for more
+constexpr size_t kCuLdsBytes = 160 * 1024;
+// dynamic LDS bytes edge_agg_kernel asks for on the tiles of `g` (max_tile_out_rows, max_tile_in_rows, max_tile_nodes)
 size_t edge_agg_lds_bytes(const Graph &g, Dims d, size_t elem);
 
 // ---- reverse mode w.r.t. activations / positions (kernels_bwd.hip).  C cotangent
@@ -204,11 +212,11 @@ template <typename T>
 void launch_ssp_bwd(T *d, const T *h, const T *scale, int64_t rows_per_frame, int width, int C,
                     int B, hipStream_t st);
 template <typename T>
-void launch_edge_bwd(const T *pq, const T *np3, const T *c2pre, const T *edge_next,
-                     const T *agg /* taped pre-LayerNorm triplet sums [S*E, FeP] */,
-                     const T *dedge_next, T *dedge_prev, T *dpq, T *dnp3, T *dc2pre, int C, int B,
-                     const Graph &g, Dims d, const PassW<T> &w, const PassW<T> *grad_w,
-                     hipStream_t st);  // grad_w: same layout as w inside the gradient blob, or null
+hipError_t launch_edge_bwd(const T *pq, const T *np3, const T *c2pre, const T *edge_next,
+                           const T *agg /* taped pre-LayerNorm triplet sums [S*E, FeP] */,
+                           const T *dedge_next, T *dedge_prev, T *dpq, T *dnp3, T *dc2pre, int C, int B,
+                           const Graph &g, Dims d, const PassW<T> &w, const PassW<T> *grad_w,
+                           hipStream_t st);  // grad_w: same layout as w inside the gradient blob, or null
 template <typename T>
 void launch_prod_fwd(const T *node, T *prod, int64_t rows, const Graph &g, Dims d, hipStream_t st);
 template <typename T>

@@ -764,7 +764,7 @@ size_t edge_agg_lds_bytes(const Graph &g, Dims d, size_t elem) {
 }
 
 template <int FP, int VPL, bool PAD, typename T>
-static void launch_edge_agg_cfg(const T *pq, const T *np3, const T *c2pre, const T *edge_in,
+static hipError_t launch_edge_agg_cfg(const T *pq, const T *np3, const T *c2pre, const T *edge_in,
                                 T *edge_out, int S, const Graph &g, Dims d, const PassW<T> &w,
                                 size_t lds, T *agg_out, hipStream_t st) {
   // Persistent workgroups: one per (tile, frame group).  The grid is sized to exactly the
@@ -774,29 +774,34 @@ static void launch_edge_agg_cfg(const T *pq, const T *np3, const T *c2pre, const
   auto kern = agg_out ? &edge_agg_kernel<FP, VPL, PAD, T, true, false>
                       : ((kFloat && (w.c3_fast & 2)) ? &edge_agg_kernel<FP, VPL, PAD, T, false, kFloat>
                                                : &edge_agg_kernel<FP, VPL, PAD, T, false, false>);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > kCuLdsBytes) return hipErrorLaunchOutOfResources;  // (validate_create_args refuses such graphs: never in a handle)
+  if (lds > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
   per_cu = std::min(per_cu, agg_wgs_per_cu_cap());
   int nsg = per_cu * num_cus() / g.num_tiles;
   nsg = nsg < 1 ? 1 : (nsg > S ? S : nsg);
+  (void)hipGetLastError();  // (what was tolerated above -- the occupancy query falls back to 1 -- is not this launch's status)
   kern<<<(unsigned)nsg * (unsigned)g.num_tiles, 256, lds, st>>>(pq, np3, c2pre, edge_in, edge_out, S,
                                                                 g, d, w, agg_out);
+  return hipGetLastError();
 }
 
 template <typename T>
-void launch_edge_agg(const T *pq, const T *np3, const T *c2pre, const T *edge_in, T *edge_out,
+hipError_t launch_edge_agg(const T *pq, const T *np3, const T *c2pre, const T *edge_in, T *edge_out,
                      int S, const Graph &g, Dims d, const PassW<T> &w, T *agg_out, hipStream_t st) {
-  if (S == 0 || g.E == 0) return;
+  if (S == 0 || g.E == 0) return hipSuccess;
   const size_t lds = edge_agg_lds_bytes(g, d, sizeof(T));
   const bool pad = d.Fe != d.FeP;
 #define RN_EA(FPV, VPLV)                                                                          \
   do {                                                                                            \
-    if (pad) launch_edge_agg_cfg<FPV, VPLV, true, T>(pq, np3, c2pre, edge_in, edge_out, S, g, d, w, lds, agg_out, st); \
-    else launch_edge_agg_cfg<FPV, VPLV, false, T>(pq, np3, c2pre, edge_in, edge_out, S, g, d, w, lds, agg_out, st); \
+    if (pad) return launch_edge_agg_cfg<FPV, VPLV, true, T>(pq, np3, c2pre, edge_in, edge_out, S, g, d, w, lds, agg_out, st); \
+    return launch_edge_agg_cfg<FPV, VPLV, false, T>(pq, np3, c2pre, edge_in, edge_out, S, g, d, w, lds, agg_out, st); \
   } while (0)
   const bool wide = sizeof(T) == 4 && agg_vpl() == 8;  // 8 columns per lane: float32, opt-in
   switch (d.FeP) {
@@ -806,13 +811,14 @@ void launch_edge_agg(const T *pq, const T *np3, const T *c2pre, const T *edge_in
     case 128: if (wide) RN_EA(128, 8); else RN_EA(128, 4); break;
   }
 #undef RN_EA
+  return hipErrorInvalidValue;  // (no instantiation for this width: plan_dims pads to 16 / 32 / 64 / 128)
 }
-template void launch_edge_agg<float>(const float *, const float *, const float *, const float *,
-                                     float *, int, const Graph &, Dims, const PassW<float> &,
-                                     float *, hipStream_t);
-template void launch_edge_agg<double>(const double *, const double *, const double *,
-                                      const double *, double *, int, const Graph &, Dims,
-                                      const PassW<double> &, double *, hipStream_t);
+template hipError_t launch_edge_agg<float>(const float *, const float *, const float *, const float *,
+                                           float *, int, const Graph &, Dims, const PassW<float> &,
+                                           float *, hipStream_t);
+template hipError_t launch_edge_agg<double>(const double *, const double *, const double *,
+                                            const double *, double *, int, const Graph &, Dims,
+                                            const PassW<double> &, double *, hipStream_t);
 
 // ============================================================================ readout
 // Edge 6-vectors from the 12-wide readout embedding and the bond direction, closed form of

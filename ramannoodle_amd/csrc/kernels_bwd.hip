@@ -1517,30 +1517,37 @@ static bool edge_bwd_two_pass(const Graph &g, int FP, size_t elem) {
   static const bool no_two_pass = getenv("RN_POTGNN_BWD_ATOMIC") && atoi(getenv("RN_POTGNN_BWD_ATOMIC")) != 0;
   static const bool simple = getenv("RN_POTGNN_BWD_SIMPLE") && atoi(getenv("RN_POTGNN_BWD_SIMPLE")) != 0;
   if (FP != 16 && FP != 32 && FP != 64 && FP != 128) return false;
-  return !simple && !no_two_pass && edge_bwd_tile2_lds(g, FP, elem) <= 160 * 1024 - 512;
+  return !simple && !no_two_pass && edge_bwd_tile2_lds(g, FP, elem) <= kCuLdsBytes - 512;
 }
 
+size_t edge_bwd_lds_bytes(const Graph &g, int FP, size_t elem) {
+  const size_t lds = edge_bwd_two_pass(g, FP, elem) ? edge_bwd_tile2_lds(g, FP, elem) : edge_bwd_tile_lds(g, FP, elem);
+  return lds > kCuLdsBytes - 512 ? 0 : lds;
+}
+
+// false: the tile kernels do not serve this graph (the per-row kernel does); *err: what hipFuncSetAttribute answered
 template <int FP, typename T>
 static bool launch_edge_bwd_tile(const T *pq, const T *np3, const T *c2pre, const T *edge_next,
                                  const T *agg, const T *dedge_next, T *dedge_prev, T *dpq, T *dnp3,
                                  T *dc2pre, int C, int B, const Graph &g, Dims d, const PassW<T> &w,
-                                 const PassW<T> &gwv, int want, hipStream_t st) {
-  const size_t lds2 = edge_bwd_tile2_lds(g, FP, sizeof(T));
+                                 const PassW<T> &gwv, int want, hipStream_t st, hipError_t *err) {
   const bool two_pass = edge_bwd_two_pass(g, FP, sizeof(T));
-  const size_t lds = two_pass ? lds2 : edge_bwd_tile_lds(g, FP, sizeof(T));
-  if (lds > 160 * 1024 - 512) return false;
+  const size_t lds = edge_bwd_lds_bytes(g, FP, sizeof(T));
+  if (lds == 0) return false;
   // with its own small tiles: two 256-thread workgroups per CU (independent workgroups fill each other's latency-bound
   // phases); on the forward kernel's tiles: one 512-thread workgroup per CU
   if (two_pass && g.bt_num > 0) {
     constexpr int NTS = 256;
     auto k2 = &edge_bwd_tile2_kernel<FP, T, NTS>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > 48 * 1024) *err = hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (*err != hipSuccess) return true;
     int per_cu2 = 0, dev2 = 0, cus2 = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu2, k2, NTS, lds) != hipSuccess || per_cu2 < 1) per_cu2 = 1;
     hipDeviceProp_t prop2;
     if (hipGetDevice(&dev2) == hipSuccess && hipGetDeviceProperties(&prop2, dev2) == hipSuccess) cus2 = prop2.multiProcessorCount;
     int ncg2 = per_cu2 * cus2 / g.bt_num;
     ncg2 = ncg2 < 1 ? 1 : (ncg2 > C ? C : ncg2);
+    (void)hipGetLastError();  // (tolerated failures above are not this launch's status)
     edge_bwd_tile2_kernel<FP, T, NTS><<<(unsigned)ncg2 * (unsigned)g.bt_num, NTS, lds, st>>>(pq, np3, c2pre, edge_next, agg, dedge_next,
                                                                                     dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want);
     return true;
@@ -1549,7 +1556,8 @@ static bool launch_edge_bwd_tile(const T *pq, const T *np3, const T *c2pre, cons
   const void *kern = two_pass ? reinterpret_cast<const void *>(&edge_bwd_tile2_kernel<FP, T, NT2>)
                               : reinterpret_cast<const void *>(&edge_bwd_tile_kernel<FP, T>);
   const int threads = two_pass ? NT2 : 256;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 48 * 1024) *err = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (*err != hipSuccess) return true;
   int per_cu = 0, dev = 0, cus = 256;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
@@ -1559,6 +1567,7 @@ static bool launch_edge_bwd_tile(const T *pq, const T *np3, const T *c2pre, cons
   int ncg = per_cu * cus / g.num_tiles;
   ncg = ncg < 1 ? 1 : (ncg > C ? C : ncg);
   const unsigned grid = (unsigned)ncg * (unsigned)g.num_tiles;
+  (void)hipGetLastError();  // (tolerated failures above are not this launch's status)
   if (two_pass)
     edge_bwd_tile2_kernel<FP, T, NT2><<<grid, NT2, lds, st>>>(pq, np3, c2pre, edge_next, agg, dedge_next,
                                                               dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want);
@@ -1569,14 +1578,14 @@ static bool launch_edge_bwd_tile(const T *pq, const T *np3, const T *c2pre, cons
 }
 
 template <typename T>
-void launch_edge_bwd(const T *pq, const T *np3, const T *c2pre, const T *edge_next, const T *agg,
-                     const T *dedge_next, T *dedge_prev, T *dpq, T *dnp3, T *dc2pre, int C, int B,
-                     const Graph &g, Dims d, const PassW<T> &w, const PassW<T> *gw, hipStream_t st) {
+hipError_t launch_edge_bwd(const T *pq, const T *np3, const T *c2pre, const T *edge_next, const T *agg,
+                           const T *dedge_next, T *dedge_prev, T *dpq, T *dnp3, T *dc2pre, int C, int B,
+                           const Graph &g, Dims d, const PassW<T> &w, const PassW<T> *gw, hipStream_t st) {
   const int lg = d.FeP / 4;
   const PassW<T> gwv = gw ? *gw : w;
   const int want = gw ? 1 : 0;
   const int64_t threads = (int64_t)C * g.E * lg;
-  if (threads == 0) return;
+  if (threads == 0) return hipSuccess;
   const unsigned blocks = (unsigned)((threads + 255) / 256);
   // dnp3's Wk block is accumulated atomically by every variant; dpq only by the variants that scatter
   // into it (the two-pass kernel writes every row of both halves exactly once)
@@ -1585,14 +1594,19 @@ void launch_edge_bwd(const T *pq, const T *np3, const T *c2pre, const T *edge_ne
     (void)hipMemsetAsync(dpq, 0, (size_t)C * g.E * 4 * d.FeP * sizeof(T), st);
   static const bool simple = getenv("RN_POTGNN_BWD_SIMPLE") && atoi(getenv("RN_POTGNN_BWD_SIMPLE")) != 0;
   bool done = false;
+  hipError_t err = hipSuccess;
   if (!simple && agg) {
     switch (d.FeP) {
-      case 16: done = launch_edge_bwd_tile<16, T>(pq, np3, c2pre, edge_next, agg, dedge_next, dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want, st); break;
-      case 32: done = launch_edge_bwd_tile<32, T>(pq, np3, c2pre, edge_next, agg, dedge_next, dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want, st); break;
-      case 64: done = launch_edge_bwd_tile<64, T>(pq, np3, c2pre, edge_next, agg, dedge_next, dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want, st); break;
-      case 128: done = launch_edge_bwd_tile<128, T>(pq, np3, c2pre, edge_next, agg, dedge_next, dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want, st); break;
+      case 16: done = launch_edge_bwd_tile<16, T>(pq, np3, c2pre, edge_next, agg, dedge_next, dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want, st, &err); break;
+      case 32: done = launch_edge_bwd_tile<32, T>(pq, np3, c2pre, edge_next, agg, dedge_next, dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want, st, &err); break;
+      case 64: done = launch_edge_bwd_tile<64, T>(pq, np3, c2pre, edge_next, agg, dedge_next, dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want, st, &err); break;
+      case 128: done = launch_edge_bwd_tile<128, T>(pq, np3, c2pre, edge_next, agg, dedge_next, dedge_prev, dpq, dnp3, dc2pre, C, B, g, d, w, gwv, want, st, &err); break;
     }
   }
+  if (err != hipSuccess) return err;
+  // the status of the launches themselves: what was tolerated before them (memsets, occupancy queries) is cleared inside
+  // launch_edge_bwd_tile, right in front of its launch, or here in front of the per-row kernel
+  if (!done) (void)hipGetLastError();
 #define CALL(LGV)                                                                                    \
   if (!done)                                                                                         \
     edge_bwd_simple_kernel<LGV, T><<<blocks, 256, 0, st>>>(pq, np3, c2pre, edge_next, dedge_next,    \
@@ -1601,15 +1615,16 @@ void launch_edge_bwd(const T *pq, const T *np3, const T *c2pre, const T *edge_ne
   q_gather_kernel<LGV, T><<<(unsigned)(((int64_t)C * g.N * lg + 255) / 256), 256, 0, st>>>(dpq, dnp3, C, g)
   RN_LG_SWITCH(d.FeP, CALL)
 #undef CALL
+  return hipGetLastError();
 }
-template void launch_edge_bwd<float>(const float *, const float *, const float *, const float *,
-                                     const float *, const float *, float *, float *, float *, float *,
-                                     int, int, const Graph &, Dims, const PassW<float> &,
-                                     const PassW<float> *, hipStream_t);
-template void launch_edge_bwd<double>(const double *, const double *, const double *, const double *,
-                                      const double *, const double *, double *, double *, double *,
-                                      double *, int, int, const Graph &, Dims, const PassW<double> &,
-                                      const PassW<double> *, hipStream_t);
+template hipError_t launch_edge_bwd<float>(const float *, const float *, const float *, const float *,
+                                           const float *, const float *, float *, float *, float *, float *,
+                                           int, int, const Graph &, Dims, const PassW<float> &,
+                                           const PassW<float> *, hipStream_t);
+template hipError_t launch_edge_bwd<double>(const double *, const double *, const double *, const double *,
+                                            const double *, const double *, double *, double *, double *,
+                                            double *, int, int, const Graph &, Dims, const PassW<double> &,
+                                            const PassW<double> *, hipStream_t);
 
 template <typename T>
 void launch_prod_bwd(const T *dprod, const T *node, T *dnode, int C, int B, const Graph &g, Dims d,

@@ -69,6 +69,78 @@ def sparse_fixture(name, frames=5, seed=0):
     return {"lattice": lattice, "positions": positions, "atomic_numbers": np.asarray(zs), "pos_batch": pos_batch}, cutoff
 
 
+# ----------------------------------------------------------------------------- dense and uneven graphs
+DENSE_CUTOFF = 3.0
+BLOB_RING_ATOMS = 66
+BLOB_ATOMS = {"blob_gas": 56, "blob_ring": BLOB_RING_ATOMS}
+BLOB_SEEDS = {"blob_gas": 11, "blob_ring": 12}
+HUB_SEEDS = {"hub_cap128": 30, "hub_cap64": 88}  # (chosen for the gap around the cutoff: most seeds leave a pair within 1e-3 A of it)
+HUB_SHELL = {"hub_cap128": 71, "hub_cap64": 147}  # the out-degree caps at FeP = 128 and at FeP = 64 (DESIGN.md "Limits")
+
+
+def dense_structures():
+    """name -> (lattice, fractional positions, atomic numbers, cutoff): four deterministic structures in the 14 A box of
+    ``sparse_structures()`` at a cutoff of 3.0 A (under half the box: no pair wraps) whose graphs are dense and very uneven.
+    ``blob_gas`` / ``blob_ring``: a ball of radius 1.4 A holding 56 / BLOB_RING_ATOMS atoms (a complete graph) among fourteen
+    two- and three-atom molecules, the atom order shuffled so that every 16-atom group mixes the ball's degree with degree
+    1 - 2; ``blob_ring`` is the smallest ball whose 64-wide plan keeps the fused path while the role-specialised
+    EdgeBlock's ring refuses it.  ``hub_cap128`` / ``hub_cap64``: one atom at the centre of 71 / 147 atoms on a sphere of
+    radius 2.95 A, in the middle of the atom order: its degree is exactly the largest the library accepts at a padded edge
+    width of 128 / 64.  ``DENSE_PROPERTIES`` pins each graph; tests/test_host_logic.py asserts it, that the float32 and the
+    float64 edge lists agree and that no pair distance lies within 1e-3 A of the cutoff."""
+    lattice = sparse_structures()["dimer"][0]
+    inverse = np.linalg.inv(lattice)
+    centre = np.array([0.5, 0.5, 0.5]) @ lattice
+    out = {}
+    for name, ball in BLOB_ATOMS.items():
+        rng = np.random.default_rng(BLOB_SEEDS[name])
+        cart = []
+        while len(cart) < ball:  # uniform in the ball, no two atoms closer than 0.4 A
+            x = rng.uniform(-1.4, 1.4, size=3)
+            if np.linalg.norm(x) <= 1.4 and all(np.linalg.norm(x - y) >= 0.4 for y in cart):
+                cart.append(x)
+        cart = [centre + x for x in cart]
+        zs = [22] * ball
+        # the molecules sit on the 3 x 3 x 3 grid of cell thirds whose centre site is the ball, on the twenty sites that
+        # share no face with it: 6 A and more from the ball's centre, 4 A and more from each other
+        sites = [(i, j, k) for i in range(3) for j in range(3) for k in range(3) if (i != 1) + (j != 1) + (k != 1) >= 2]
+        for m, site in enumerate(sites[:14]):
+            o = (np.array(site) / 3.0 + 1.0 / 6.0) @ lattice - [0.4, 0.4, 0.0]
+            atoms = [o, o + [0.96, 0.04 * m, 0.0], o + [-0.24, 0.93, 0.02 * m]][:2 + m % 2]
+            cart += atoms
+            zs += [8, 1, 1][:len(atoms)]
+        order = np.random.default_rng(13).permutation(len(zs))
+        out[name] = (lattice, (np.array(cart)[order] @ inverse) % 1.0, [zs[i] for i in order], DENSE_CUTOFF)
+    for name, shell in HUB_SHELL.items():
+        # a golden-angle spiral over the sphere (neighbours 0.5 A and more apart), each point moved by N(0, 0.05) along it
+        i = np.arange(shell) + 0.5
+        polar, azimuth = np.arccos(1 - 2 * i / shell), np.pi * (1 + 5 ** 0.5) * i
+        u = np.stack([np.sin(polar) * np.cos(azimuth), np.sin(polar) * np.sin(azimuth), np.cos(polar)], axis=1)
+        u += np.random.default_rng(HUB_SEEDS[name]).normal(scale=0.05, size=u.shape)
+        cart = centre + 2.95 * u / np.linalg.norm(u, axis=1)[:, None]
+        half = shell // 2
+        cart = np.vstack([cart[:half], [centre], cart[half:]])
+        out[name] = (lattice, (cart @ inverse) % 1.0, [8] * half + [22] + [8] * (shell - half), DENSE_CUTOFF)
+    return out
+
+
+# N, E, T, smallest and largest degree: from the oracle's graph code (tests/test_host_logic.py compares)
+DENSE_PROPERTIES = {
+    "blob_gas": dict(N=91, E=3136, T=166362, min_degree=1, max_degree=55),
+    "blob_ring": dict(N=101, E=4346, T=274602, min_degree=1, max_degree=65),
+    "hub_cap128": dict(N=72, E=1400, T=28582, min_degree=17, max_degree=71),
+    "hub_cap64": dict(N=148, E=5754, T=229990, min_degree=35, max_degree=147),
+}
+
+
+def dense_fixture(name, frames=3, seed=0):
+    """``sparse_fixture`` for one of ``dense_structures()``."""
+    lattice, positions, zs, cutoff = dense_structures()[name]
+    rng = np.random.default_rng(2000 + seed)
+    pos_batch = positions[None] + rng.normal(scale=2e-3, size=(frames,) + positions.shape)
+    return {"lattice": lattice, "positions": positions, "atomic_numbers": np.asarray(zs), "pos_batch": pos_batch}, cutoff
+
+
 # ----------------------------------------------------------------------------- graph plans (rn_potgnn_debug_plan)
 PLAN_WIDTHS = ((5, 14), (16, 16), (20, 48), (32, 64), (64, 64), (50, 40), (64, 16), (128, 128))
 PLAN_FIXTURES = ("triclinic20", "rocksalt64_parity", "rocksalt64_perf", "tio2_gnn_test")

@@ -243,8 +243,8 @@ def test_model_copies_and_pickles_carry_host_state_only():
 
 def test_documented_size_limits_raise_not_implemented():
     """The two limits of the device model (DESIGN.md "Limits"): embedding sizes above 128, and
-    more outgoing edges per atom than one LDS tile holds (149 at Fe = 64; the reference's
-    ``radius_graph_pbc`` keeps one edge per ordered atom pair, so this needs > 149 atoms inside
+    more outgoing edges per atom than one LDS tile holds in float64 (147 at Fe = 64; the reference's
+    ``radius_graph_pbc`` keeps one edge per ordered atom pair, so this needs > 147 atoms inside
     the cutoff sphere).  Both are refused at model creation with NotImplementedError, before
     any device work."""
     from bench import rocksalt
@@ -261,9 +261,9 @@ def test_documented_size_limits_raise_not_implemented():
     dense = PotGNN(ReferenceStructure(list(zs), lattice, ref), 7.9, 64, 64, 1, 0.0, 5.0, *unit)
     assert dense.num_edges / dense.num_atoms > 149
     with pytest.raises(NotImplementedError,
-                       match=r"outgoing edges; more than 149 per atom is unsupported for size_edge_embedding=64"):
+                       match=r"outgoing edges; more than 147 per atom is unsupported for size_edge_embedding=64"):
         dense.calc_polarizabilities(ref[None])
-    # the same graph is accepted at a width whose rows fit (590 per atom at Fe <= 16): creation then
+    # the same graph is accepted at a width whose rows fit (554 per atom at Fe <= 16): creation then
     # proceeds to the device probe, which is what fails on a machine without a GPU
     import torch
     if not torch.cuda.is_available():
@@ -792,6 +792,173 @@ def test_sparse_structures_keep_their_degenerate_graphs_and_get_a_plan():
     assert degree[0] == 0 and degree[1] == 14 and degree[16] == 0 and degree[2:16].min() == 3 and degree[2:16].max() == 8
 
 
+# ----------------------------------------------------------------------------- dense and uneven graphs
+CU_LDS_BYTES = 160 * 1024
+LDS_FAMILIES = ("edge_agg", "edge_bwd", "edge_narrow", "node_tiled", "edge_ps", "node_atom", "node_fused")
+DEGREE_CAPS = {16: 554, 32: 292, 64: 147, 128: 71}  # padded edge width -> most out-edges per atom (DESIGN.md "Limits")
+
+
+def _plan_lds(lib, shape, ea, eb, types, num_cus=256):
+    """``rn_potgnn_debug_plan_lds``: (status, family -> (float32 bytes, float64 bytes), error text)."""
+    n, e, k, fn, fe = shape
+    cfg = _lib.Config(n, e, k, fn, fe, 2, -1.0, 0, 0)
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    out, count = np.full(2 * len(LDS_FAMILIES), -1, dtype=np.int64), ctypes.c_size_t(0)
+    rc = lib.rn_potgnn_debug_plan_lds(ctypes.byref(cfg), p(ea), p(eb), p(types), num_cus, p(out), out.size, ctypes.byref(count))
+    if rc != _lib.RN_OK:
+        return rc, None, lib.rn_potgnn_last_error(None).decode()
+    assert count.value == out.size and np.all(out >= 0)
+    return rc, {f: (int(out[2 * i]), int(out[2 * i + 1])) for i, f in enumerate(LDS_FAMILIES)}, ""
+
+
+def _dense_graph(name):
+    """(edge_a, edge_b, atom types, species) of one of ``dense_structures()``, by the product's host graph code."""
+    from tests.helpers import dense_structures
+    lattice, positions, zs, cutoff = dense_structures()[name]
+    edges = G.radius_graph_pbc(lattice, positions, cutoff)
+    tmap = G.atom_type_map(zs)
+    ea, eb = (np.ascontiguousarray(x, dtype=np.int32) for x in edges)
+    return ea, eb, np.ascontiguousarray(tmap[np.asarray(zs)], dtype=np.int32), int((tmap >= 0).sum())
+
+
+def _dense_plan(lib, name, fn, fe):
+    from tests.plan_worker import debug_plan
+    ea, eb, types, k = _dense_graph(name)
+    return _parse_plan(debug_plan(lib, (len(types), len(ea), k, fn, fe), ea, eb, types, 256), len(types), len(ea))
+
+
+def _planned_edge_width(lib, fn, fe):
+    """The padded edge width the library plans a model of these widths at: FeP of ``rn_potgnn_debug_plan`` on a two-atom graph."""
+    from tests.plan_worker import debug_plan
+    ea, eb = np.array([0, 1], dtype=np.int32), np.array([1, 0], dtype=np.int32)
+    return int(debug_plan(lib, (2, 2, 1, fn, fe), ea, eb, np.zeros(2, dtype=np.int32), 256)[1])
+
+
+def _star_ring(degree):
+    """Atom 0 joined to atoms 1 .. degree, both ways, and those joined in a ring: a hub of that degree among atoms of
+    degree 3, which the greedy tile walks pack many to a tile."""
+    leaves = np.arange(1, degree + 1)
+    after, before = leaves % degree + 1, (leaves - 2) % degree + 1
+    pairs = np.concatenate([np.stack([np.zeros(degree, dtype=np.int64), leaves], 1), np.stack([leaves, np.zeros(degree, dtype=np.int64)], 1),
+                            np.stack([leaves, after], 1), np.stack([leaves, before], 1)])
+    pairs = np.unique(pairs, axis=0)  # (sorted by (a, b))
+    return pairs[:, 0].astype(np.int32), pairs[:, 1].astype(np.int32), np.zeros(degree + 1, dtype=np.int32)
+
+
+def test_dense_structures_keep_their_pinned_graphs():
+    """tests/helpers.py ``dense_structures()`` -- what tests/test_dense_graphs_gpu.py runs on: N, E, T and the smallest and
+    largest degree are the pinned ones; the hubs' degrees are exactly the caps of the widths they are named after; the
+    float32 and the float64 edge lists agree, and no pair distance lies within 1e-3 A of the cutoff (the frames' noise is
+    2e-3 of a cell edge in fractional terms only on paper: the graph is frozen from the reference positions); the
+    product's graph code equals the oracle's bit for bit."""
+    from oracle import potgnn_oracle as O
+    from tests.helpers import BLOB_ATOMS, DENSE_PROPERTIES, HUB_SHELL, dense_structures
+    structures = dense_structures()
+    assert list(structures) == list(DENSE_PROPERTIES) == ["blob_gas", "blob_ring", "hub_cap128", "hub_cap64"]
+    assert HUB_SHELL == {"hub_cap128": DEGREE_CAPS[128], "hub_cap64": DEGREE_CAPS[64]}
+    for name, (lattice, positions, zs, cutoff) in structures.items():
+        n = len(zs)
+        assert cutoff == 3.0 and cutoff < 0.5 * min(np.linalg.norm(np.linalg.inv(lattice), axis=0) ** -1)  # (under half of every cell height)
+        edges = G.radius_graph_pbc(lattice, positions, cutoff)
+        np.testing.assert_array_equal(edges, G.radius_graph_pbc(lattice, positions, cutoff, dtype=np.float64), err_msg=name)
+        f = positions[None] - positions[:, None]
+        dist = np.linalg.norm((f - np.round(f)) @ lattice, axis=-1)[np.triu_indices(n, 1)]
+        assert np.abs(dist - cutoff).min() > 1e-3, (name, np.abs(dist - cutoff).min())
+        trip = G.reference_order_triplets(edges, n)
+        degree = np.bincount(edges[0], minlength=n)
+        np.testing.assert_array_equal(degree, np.bincount(edges[1], minlength=n), err_msg=name)
+        got = dict(N=n, E=edges.shape[1], T=len(trip[2]), min_degree=int(degree.min()), max_degree=int(degree.max()))
+        assert got == DENSE_PROPERTIES[name], (name, got)
+        o_edges, o_trip, o_map = O.build_topology(lattice, positions, zs, cutoff)
+        np.testing.assert_array_equal(edges, o_edges.numpy()[1:], err_msg=name)
+        for mine, ref in zip(trip, o_trip):
+            np.testing.assert_array_equal(mine, ref.numpy(), err_msg=name)
+        np.testing.assert_array_equal(G.atom_type_map(zs), o_map.numpy(), err_msg=name)
+        if name in BLOB_ATOMS:  # every 16-atom group mixes the ball's degree with the molecules'
+            for i in range(0, n - 15, 16):
+                assert degree[i:i + 16].max() == got["max_degree"] and degree[i:i + 16].min() <= 2, (name, i)
+        else:  # the hub sits in the middle of the atom order
+            assert int(degree.argmax()) == HUB_SHELL[name] // 2 and np.sort(degree)[-2] < degree.max() // 2
+
+
+def test_dense_structures_reach_the_planner_branches_they_are_there_for():
+    """The planner's size-dependent branches, by name, on geometric graphs that kernels then run on (the ``ragged`` cases
+    above are graphs no geometry produces): the role-specialised ring refusing a graph with the fused path on; the
+    atom-owning NodeBlock refused by the 1.2x rule; one-atom tiles at the degree cap; a narrow tile above 128 rows (the
+    four-wave form); the reverse EdgeBlock with and without a partition of its own."""
+    lib = _lib.load()
+    ring = _dense_plan(lib, "blob_ring", 64, 64)
+    assert ring["use_fused"] == 1 and ring["use_ps"] == 0 and len(ring["pt"][0]) == 0
+    assert _dense_plan(lib, "blob_ring", 5, 14)["use_narrow"] == 1
+    from tests.helpers import BLOB_ATOMS, dense_structures
+    import tests.helpers as H
+    smaller = dict(BLOB_ATOMS, blob_ring=BLOB_ATOMS["blob_ring"] - 1)  # (the smallest such ball: one atom fewer and the ring takes it)
+    try:
+        H.BLOB_ATOMS, kept = smaller, H.BLOB_ATOMS
+        assert _dense_plan(lib, "blob_ring", 64, 64)["use_ps"] == 1
+    finally:
+        H.BLOB_ATOMS = kept
+    assert dense_structures()["blob_ring"][1].shape[0] == BLOB_ATOMS["blob_ring"] + 35
+
+    gas = _dense_plan(lib, "blob_gas", 64, 64)
+    assert gas["use_fused"] == 1 and gas["use_ps"] == 1 and gas["use_node_fused"] == 1 and len(gas["bt"][0]) == 0
+    assert gas["pt_back"] == 3 and gas["pt"][1] == (58, 58, 4)  # (DESIGN.md quotes the lookahead)
+    deg_in = np.diff(gas["in_ptr"])
+    rounds_atom = sum(int(deg_in[i:i + 16].max()) for i in range(0, len(deg_in), 16))
+    rounds_row = int(((np.diff(gas["in_ptr"][gas["nt"][0]]) + 15) // 16).sum())
+    assert gas["na_num"] == 0 and rounds_atom > 1.2 * rounds_row, (rounds_atom, rounds_row)
+
+    for fn, fe in ((40, 100), (64, 128)):
+        hub = _dense_plan(lib, "hub_cap128", fn, fe)
+        assert (hub["FnP"], hub["FeP"]) == (64, 128) and hub["tile"][1] == (71, 71, 1) and len(hub["tile"][0]) == 73
+    assert _dense_plan(lib, "hub_cap128", 64, 64)["use_ps"] == 1
+    cap64 = _dense_plan(lib, "hub_cap64", 64, 64)
+    assert cap64["tile"][1] == (147, 147, 1) and len(cap64["tile"][0]) == 149 and cap64["use_fused"] == 0 and len(cap64["bt"][0]) == 0
+    assert _dense_plan(lib, "hub_cap64", 24, 20)["head"].tolist() == cap64["head"].tolist()  # (widened onto the same plan)
+    narrow = _dense_plan(lib, "hub_cap64", 5, 14)
+    assert narrow["use_narrow"] == 1 and narrow["tile"][1][:2] == (147, 147) and narrow["tile"][1][2] > 1 and len(narrow["bt"][0]) > 0
+    assert _dense_plan(lib, "blob_gas", 5, 14)["tile"][1][0] <= 128  # (the two-wave form next to it)
+
+
+def test_every_planned_kernel_fits_the_compute_unit():
+    """Accepted => fits: for every graph ``rn_potgnn_create`` accepts, each kernel family of the plan asks for at most the
+    163840 bytes of LDS a CU has, in float32 and in float64 -- by ``rn_potgnn_debug_plan_lds``, which calls the kernels' own
+    footprint functions.  Over the dense structures at every width pair of ``PLAN_WIDTHS`` plus 24/20, 40/50 and 40/100, and
+    over a star-plus-ring graph whose hub's degree runs over [cap - 4, cap] of each padded width (its low-degree atoms
+    share tiles: a partition's maxima mix the hub's rows with another tile's atoms, which the planner answers with
+    one-atom tiles).  One more edge than the cap is refused with RN_ERR_UNSUPPORTED at the PLANNED width: 24 / 20 runs 64
+    wide, so 148 neighbours are refused there although 20 pads to 32."""
+    from tests.helpers import DENSE_PROPERTIES, PLAN_WIDTHS
+    lib = _lib.load()
+    planned = {w: _planned_edge_width(lib, *w) for w in PLAN_WIDTHS + ((24, 20), (40, 50), (40, 100), (8, 20))}
+    assert planned[(24, 20)] == 64 and planned[(8, 20)] == 32 and planned[(40, 100)] == 128 and planned[(5, 14)] == 16
+    for name, props in DENSE_PROPERTIES.items():
+        ea, eb, types, k = _dense_graph(name)
+        for fn, fe in PLAN_WIDTHS + ((24, 20), (40, 50), (40, 100)):
+            rc, lds, text = _plan_lds(lib, (len(types), len(ea), k, fn, fe), ea, eb, types)
+            if props["max_degree"] > DEGREE_CAPS[planned[(fn, fe)]]:
+                assert rc == _lib.RN_ERR_UNSUPPORTED and f"more than {DEGREE_CAPS[planned[(fn, fe)]]} per atom" in text, (name, fn, fe, text)
+                continue
+            assert rc == _lib.RN_OK, (name, fn, fe, text)
+            assert lds["edge_agg"][1] > 0 and max(max(v) for v in lds.values()) <= CU_LDS_BYTES, (name, fn, fe, lds)
+    for (fn, fe), fep in (((5, 14), 16), ((64, 16), 16), ((8, 20), 32), ((64, 64), 64), ((24, 20), 64), ((40, 100), 128), ((128, 128), 128)):
+        cap = DEGREE_CAPS[fep]
+        for degree in range(cap - 4, cap + 1):
+            ea, eb, types = _star_ring(degree)
+            rc, lds, text = _plan_lds(lib, (degree + 1, len(ea), 1, fn, fe), ea, eb, types)
+            assert planned[(fn, fe)] == fep and rc == _lib.RN_OK, (fn, fe, degree, text)
+            assert max(max(v) for v in lds.values()) <= CU_LDS_BYTES, (fn, fe, degree, lds)
+        assert lds["edge_agg"][1] > CU_LDS_BYTES - (2 * fep * 8 + 36), (fn, fe, lds)  # (at the cap: one more row would not fit)
+        ea, eb, types = _star_ring(cap + 1)
+        rc, lds, text = _plan_lds(lib, (cap + 2, len(ea), 1, fn, fe), ea, eb, types)
+        assert rc == _lib.RN_ERR_UNSUPPORTED, (fn, fe, lds)
+        assert text == f"atom 0 has {cap + 1} outgoing edges; more than {cap} per atom is unsupported for size_edge_embedding={fe}"
+    # a directed graph with more in-edges than out-edges at one atom: the destination tables count too
+    ea = np.arange(1, 7001, dtype=np.int32)
+    rc, _, text = _plan_lds(lib, (7001, 7000, 1, 64, 64), ea, np.zeros(7000, dtype=np.int32), np.zeros(7001, dtype=np.int32))
+    assert rc == _lib.RN_ERR_UNSUPPORTED and "7000 incoming edges" in text and "163840 available" in text, text
+
+
 def test_debug_plan_rejects_what_create_rejects():
     """The bad inputs of ``test_create_rejects_bad_arguments_without_touching_the_gpu`` (and the documented size limits)
     through ``rn_potgnn_debug_plan``: the same status codes and texts, from the same code."""
@@ -821,12 +988,12 @@ def test_debug_plan_rejects_what_create_rejects():
     assert rc == _lib.RN_ERR_INVALID_ARGUMENT and text.startswith(b"reference graph has no edges")
     cfg.num_edges, cfg.num_atoms = 2, 0
     assert plan(cfg, ea, eb) == (_lib.RN_ERR_INVALID_ARGUMENT, b"invalid configuration (non-positive size)")
-    # more out-edges than one LDS tile holds: 75 from one atom at Fe = 128 (74 fit)
+    # more out-edges than one LDS tile holds: 75 from one atom at Fe = 128 (71 fit)
     many = _lib.Config(80, 75, 1, 8, 128, 1, -1.0, 0, 0)
     star_a, star_b, star_ty = np.zeros(75, dtype=np.int32), np.arange(1, 76, dtype=np.int32), np.zeros(80, dtype=np.int32)
     rc, text = plan(many, star_a, star_b, star_ty)
     assert rc == _lib.RN_ERR_UNSUPPORTED
-    assert text == b"atom 0 has 75 outgoing edges; more than 74 per atom is unsupported for size_edge_embedding=128"
+    assert text == b"atom 0 has 75 outgoing edges; more than 71 per atom is unsupported for size_edge_embedding=128"
     # the same texts come from rn_potgnn_create
     h, lat = ctypes.c_void_p(), np.eye(3)
     n = lib.rn_potgnn_weight_count(ctypes.byref(many))
