@@ -637,6 +637,34 @@ int rn_potgnn_debug_plan(const rn_potgnn_config *cfg, const int32_t *edge_a, con
 int rn_potgnn_debug_plan_lds(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
                              const int32_t *atom_types, int32_t num_cus, int64_t *out, size_t capacity, size_t *count);
 
+/*
+ * Host-only (no device is touched, none is needed): the packed weight blob rn_potgnn_create / rn_potgnn_set_weights would
+ * make of the state-dict-ordered `weights` for a model of this configuration, at the padded widths the library plans it
+ * at under the RN_POTGNN_* knobs of the environment (csrc/weight_layout.hpp; no graph is needed).  cfg, weights and
+ * num_weights are validated as rn_potgnn_create validates them (same status codes and texts through
+ * rn_potgnn_last_error(NULL)).  Written, each *count entries long:
+ *   packed   the float32 host master copy, derived entries included: the layout rn_potgnn_gradient_buffer exposes
+ *   mask     1 where an entry is a trainable parameter (what rn_potgnn_adam_step updates), else 0
+ *   writers  (optional, may be NULL) low nibble = state-dict elements stored at the entry, high nibble = derived ranges
+ *            (transposed / centred copies, folded constants, prescale pairs, the second copy of readout bias 0) covering it
+ * and flags[1 + num_message_passes]: flags[0] = the weights pass the split-f16 range guard (bit 4 of
+ * rn_potgnn_config_flags is its negation), flags[1 + p] = pass p's triplet loop may take the folded-gate form.
+ * RN_OK also means that the three ranges rn_potgnn_adam_step downloads in one piece each are contiguous in the layout.
+ * When packed, mask or flags is NULL or capacity < *count nothing is written and the call returns
+ * RN_ERR_INVALID_ARGUMENT with *count set.
+ */
+int rn_potgnn_debug_pack_weights(const rn_potgnn_config *cfg, const float *weights, size_t num_weights, float *packed,
+                                 unsigned char *mask, unsigned char *writers, int32_t *flags, size_t capacity, size_t *count);
+
+/*
+ * Host-only inverse: a packed blob of num_packed entries (the *count of rn_potgnn_debug_pack_weights) back into state-dict
+ * order, as rn_potgnn_get_weights (buffers != 0: the state dict's buffers -- Gaussian offsets, BatchNorm running
+ * statistics -- keep their values) and the gradient download of rn_potgnn_train_backward (buffers == 0: zeros there) do
+ * it.  *count = rn_potgnn_weight_count(cfg); the out == NULL / capacity protocol is the one above.
+ */
+int rn_potgnn_debug_unpack_weights(const rn_potgnn_config *cfg, const float *packed, size_t num_packed, int buffers,
+                                   float *out, size_t capacity, size_t *count);
+
 /* Number of edge triplets T of the frozen graph. */
 int64_t rn_potgnn_num_triplets(const rn_potgnn *h);
 

@@ -2,16 +2,17 @@
 //
 // Planning -- validation of the create arguments, the CSRs, the atom tiles of every kernel family and the choice of the
 // family -- is host-only code in graph_plan.hip (rn_potgnn_debug_plan runs it without a device); this file uploads the plan.
+// The packed weight layout -- where each state-dict tensor lands, the derived entries, the trainable mask and the decisions
+// read off the packed values -- is host-only code in weight_layout.hip (rn_potgnn_debug_pack_weights); this file uploads the blob.
 // A handle owns: the frozen graph (CSR both ways, node tiles, triplet offsets), the
-// weights re-laid-out for the kernels (transposed, [filter|core] halves padded to a
-// power-of-two width, concatenated Linear layers split into per-operand blocks), and
+// weights re-laid-out for the kernels (weight_layout.hpp), and
 // per-"lane" device workspaces (a lane = a HIP stream).  An evaluation walks the frames in
 // chunks (hundreds to thousands of frames: large launches amortise launch gaps and tails).
 // The fused pipeline (kernels_fused.hip) uses one lane; the unfused one alternates chunks
 // between two lanes so that the HBM-bound projections of one chunk overlap the VALU-bound
 // aggregation of the other (run_pair).
 //
-// In file order: weight packing and upload; ForwardIO (what an evaluation reads and writes, sliced per chunk in one place)
+// In file order: weight upload and the flags read off the weights; ForwardIO (what an evaluation reads and writes, sliced per chunk in one place)
 // and ChunkRun (one chunk's stages on one lane); forward_device and the reverse pass with their users (Jacobian, input
 // gradients, atom groups, training); then the C entries.  The entries share their argument checks (check_batch,
 // check_train_batch, check_pending, check_types), their staging (stage, stage_lattices, stage_types, lazy_stream,
@@ -35,6 +36,7 @@
 #include "../../include/rn_potgnn.h"
 #include "graph_plan.hpp"
 #include "kernels.hpp"
+#include "weight_layout.hpp"
 
 using namespace rn;
 
@@ -79,37 +81,6 @@ enum KernelId {
 const char *kKernelNames[K_COUNT] = {
     "geom_rbf", "node_init", "proj_node", "proj_edge_c1", "node_agg", "proj_edge_c3",
     "proj_c2", "edge_agg", "readout_mlp", "readout_reduce"};
-
-// Host-side packed weights, one flat array + offsets; uploaded per precision.
-struct PackedLayout {
-  // setup inputs (unpadded)
-  size_t emb, W2, b2, W4, b4, b0, bn_w, bn_b, bn_rm, bn_rv;
-  size_t offsets;  // [FeP]
-  struct Pass {
-    size_t c1_WnT, c1_WeT, c1_bias, c1n_g, c1n_b, fin_g, fin_b;
-    size_t c2_WT, c2_bias, c2n1_g, c2n1_b, c2n2_g, c2n2_b;
-    size_t c3_WnT, c3_nshift, c3_WeT, c3n1_g, c3n1_b, c3n2_g, c3n2_b;
-    size_t c3n1_gs, c3n1_bs;  // c3_norm_1 with the gate's exp2 scale folded in (-log2e | 2 log2e): narrow kernels
-    size_t c2n1_gs, c2n1_bs, c1n_gs, c1n_bs;  // the same for c2_norm_1 and c1_norm (narrow kernels)
-    size_t mfma_scale;        // [8] split-f16 prescales (s, 1/s): c1_WeT | W4 | W5 | c2_WT (kernels.hpp: mfma_prescale)
-    size_t t_c3We, t_c3Wn, t_c2W, t_c1We, t_c1Wn;  // transposed copies [N][K] (reverse pass)
-    // copies of c3_linear / c2_linear centred over their real output columns (kernels_edge_ps.hip) and the
-    // split-f16 prescales (s, 1/s) of W4 | W5 | c2 in that form
-    size_t c3_WeT_c, c3_WnT_c, c3_nshift_c, c2_WT_c, c2_bias_c, mfma_scale_c;
-    size_t c1_WnT_c, c1_WeT_c, c1_bias_c;  // c1_linear centred over its 2 Fn output columns (fused NodeBlock)
-  };
-  std::vector<Pass> pass;
-  size_t W0T, W3T, b3, W5T, b5, ones, b0p, t_W0, t_W3, t_W5;
-  size_t ro_mfma_scale;  // [8] split-f16 prescales (s, 1/s): W0T | W3T | W5T
-  // device-computed
-  size_t node_table, scale0, shift0;
-  size_t total = 0;
-  size_t take(size_t n) {
-    size_t o = total;
-    total += (n + 3) & ~size_t(3);  // keep 16-byte alignment for float4 loads
-    return o;
-  }
-};
 
 template <typename T>
 struct Lane {
@@ -249,303 +220,6 @@ void set_error(rn_potgnn *h, const char *fmt, ...) {
   }
 }
 
-// ----------------------------------------------------------------------------- packing
-// Column of the padded [filter | core] layout for original output row r of a Linear /
-// LayerNorm of logical width 2F (first F rows = filter, last F = core; _gnn.py:143).
-inline int gated_col(int r, int F, int FP) { return r < F ? r : FP + (r - F); }
-
-// The weight blocks that enter a split-f16 matrix product and where their (s, 1/s) pair lives.
-struct MfmaScaleOp {
-  size_t src;
-  int K, N, ld;
-  size_t dst;
-};
-std::vector<MfmaScaleOp> mfma_scale_ops(const rn_potgnn *h) {
-  const PackedLayout &L = h->lay;
-  const int FnP = h->d.FnP, FeP = h->d.FeP, HP = std::max(FeP, 32);
-  std::vector<MfmaScaleOp> ops;
-  for (const auto &q : L.pass) {
-    ops.push_back({q.c1_WeT, FeP, 2 * FnP, 2 * FnP, q.mfma_scale});
-    ops.push_back({q.c3_WeT, FeP, 2 * FeP, 4 * FeP, q.mfma_scale + 2});            // W4: destination-edge part
-    ops.push_back({q.c3_WeT + 2 * FeP, FeP, 2 * FeP, 4 * FeP, q.mfma_scale + 4});  // W5: source-edge part
-    ops.push_back({q.c2_WT, FnP, 2 * FeP, 2 * FeP, q.mfma_scale + 6});
-  }
-  ops.push_back({L.W0T, FeP, HP, HP, L.ro_mfma_scale});
-  ops.push_back({L.W3T, HP, HP, HP, L.ro_mfma_scale + 2});
-  ops.push_back({L.W5T, HP, 32, 32, L.ro_mfma_scale + 4});
-  return ops;
-}
-
-// The centred copies: (source, destination, rows, columns) of every matrix / bias vector whose output columns feed a
-// LayerNorm over a [filter | core] row in the role-specialised EdgeBlock.  LayerNorm(x) = LayerNorm(x - mean x), and
-// the row mean of a Linear's output is itself linear in the input, so subtracting from every weight row (and from
-// the bias) its mean over the real output columns makes the projections come out with zero row mean.
-struct CentreOp {
-  size_t src, dst;
-  int K, N;
-  int F, FP;  // the [filter | core] blocks are 2 FP columns wide, the first F of each half real
-};
-std::vector<CentreOp> centre_ops(const rn_potgnn *h) {
-  const int FnP = h->d.FnP, FeP = h->d.FeP;
-  std::vector<CentreOp> ops;
-  for (const auto &q : h->lay.pass) {
-    const int Fn = h->d.Fn, Fe = h->d.Fe;
-    ops.push_back({q.c3_WeT, q.c3_WeT_c, FeP, 4 * FeP, Fe, FeP});
-    ops.push_back({q.c3_WnT, q.c3_WnT_c, FnP, 6 * FeP, Fe, FeP});
-    ops.push_back({q.c3_nshift, q.c3_nshift_c, 1, 6 * FeP, Fe, FeP});
-    ops.push_back({q.c2_WT, q.c2_WT_c, FnP, 2 * FeP, Fe, FeP});
-    ops.push_back({q.c2_bias, q.c2_bias_c, 1, 2 * FeP, Fe, FeP});
-    ops.push_back({q.c1_WnT, q.c1_WnT_c, FnP, 2 * FnP, Fn, FnP});
-    ops.push_back({q.c1_WeT, q.c1_WeT_c, FeP, 2 * FnP, Fn, FnP});
-    ops.push_back({q.c1_bias, q.c1_bias_c, 1, 2 * FnP, Fn, FnP});
-  }
-  return ops;
-}
-std::vector<MfmaScaleOp> centred_scale_ops(const rn_potgnn *h) {
-  const int FnP = h->d.FnP, FeP = h->d.FeP;
-  std::vector<MfmaScaleOp> ops;
-  for (const auto &q : h->lay.pass) {
-    ops.push_back({q.c3_WeT_c, FeP, 2 * FeP, 4 * FeP, q.mfma_scale_c});
-    ops.push_back({q.c3_WeT_c + 2 * FeP, FeP, 2 * FeP, 4 * FeP, q.mfma_scale_c + 2});
-    ops.push_back({q.c2_WT_c, FnP, 2 * FeP, 2 * FeP, q.mfma_scale_c + 4});
-    ops.push_back({q.c1_WeT_c, FeP, 2 * FnP, 2 * FnP, q.mfma_scale_c + 6});
-  }
-  return ops;
-}
-
-void pack_weights(rn_potgnn *h, const float *w) {
-  const int K = h->cfg.num_atom_types, Fn = h->d.Fn, Fe = h->d.Fe, FnP = h->d.FnP,
-            FeP = h->d.FeP, P = h->cfg.num_message_passes;
-  PackedLayout &L = h->lay;
-  L = PackedLayout();
-  L.emb = L.take((size_t)K * Fn);
-  L.W2 = L.take((size_t)Fn * Fn);
-  L.b2 = L.take(Fn);
-  L.W4 = L.take((size_t)Fn * Fn);
-  L.b4 = L.take(Fn);
-  L.offsets = L.take(FeP);
-  L.pass.resize(P);
-  for (auto &p : L.pass) {
-    p.c1_WnT = L.take((size_t)FnP * 2 * FnP);
-    p.c1_WeT = L.take((size_t)FeP * 2 * FnP);
-    p.c1_bias = L.take(2 * FnP);
-    p.c1n_g = L.take(2 * FnP);
-    p.c1n_b = L.take(2 * FnP);
-    p.fin_g = L.take(FnP);
-    p.fin_b = L.take(FnP);
-    p.c2_WT = L.take((size_t)FnP * 2 * FeP);
-    p.c2_bias = L.take(2 * FeP);
-    p.c2n1_g = L.take(2 * FeP);
-    p.c2n1_b = L.take(2 * FeP);
-    p.c2n2_g = L.take(FeP);
-    p.c2n2_b = L.take(FeP);
-    p.c3_WnT = L.take((size_t)FnP * 6 * FeP);
-    p.c3_nshift = L.take(6 * FeP);
-    p.c3_WeT = L.take((size_t)FeP * 4 * FeP);
-    p.c3n1_g = L.take(2 * FeP);
-    p.c3n1_b = L.take(2 * FeP);
-    p.c3n2_g = L.take(FeP);
-    p.c3n2_b = L.take(FeP);
-    p.c3n1_gs = L.take(2 * FeP);
-    p.c3n1_bs = L.take(2 * FeP);
-    p.c2n1_gs = L.take(2 * FeP);
-    p.c2n1_bs = L.take(2 * FeP);
-    p.c1n_gs = L.take(2 * FnP);
-    p.c1n_bs = L.take(2 * FnP);
-    p.mfma_scale = L.take(8);
-    p.mfma_scale_c = L.take(8);  // (right behind mfma_scale: one copy fetches both after a device-resident step)
-    p.t_c3We = L.take((size_t)4 * FeP * FeP);
-    p.t_c3Wn = L.take((size_t)6 * FeP * FnP);
-    p.t_c2W = L.take((size_t)2 * FeP * FnP);
-    p.t_c1We = L.take((size_t)2 * FnP * FeP);
-    p.t_c1Wn = L.take((size_t)2 * FnP * FnP);
-    p.c3_WeT_c = L.take((size_t)FeP * 4 * FeP);
-    p.c3_WnT_c = L.take((size_t)FnP * 6 * FeP);
-    p.c3_nshift_c = L.take(6 * FeP);
-    p.c2_WT_c = L.take((size_t)FnP * 2 * FeP);
-    p.c2_bias_c = L.take(2 * FeP);
-    p.c1_WnT_c = L.take((size_t)FnP * 2 * FnP);
-    p.c1_WeT_c = L.take((size_t)FeP * 2 * FnP);
-    p.c1_bias_c = L.take(2 * FnP);
-  }
-  const int HP = std::max(FeP, 32);  // readout hidden width: projections emit 32-column tiles
-  L.W0T = L.take((size_t)FeP * HP);
-  L.b0 = L.take(Fe);
-  L.bn_w = L.take(Fe);
-  L.bn_b = L.take(Fe);
-  L.bn_rm = L.take(Fe);
-  L.bn_rv = L.take(Fe);
-  L.W3T = L.take((size_t)HP * HP);
-  L.b3 = L.take(HP);
-  L.W5T = L.take((size_t)HP * 32);
-  L.b5 = L.take(32);
-  L.ones = L.take(HP);
-  L.b0p = L.take(HP);  // bias of readout Linear 0, padded (training-mode forward)
-  L.t_W0 = L.take((size_t)HP * FeP);
-  L.t_W3 = L.take((size_t)HP * HP);
-  L.t_W5 = L.take((size_t)32 * HP);
-  L.ro_mfma_scale = L.take(8);
-  L.node_table = L.take((size_t)K * FnP);
-  L.scale0 = L.take(HP);
-  L.shift0 = L.take(HP);
-
-  std::vector<float> &o = h->packed;
-  o.assign(L.total, 0.0f);
-  const float *c = w;  // cursor over the state_dict-ordered blob
-  auto copy = [&](size_t dst, size_t n) {
-    std::memcpy(&o[dst], c, n * sizeof(float));
-    c += n;
-  };
-  copy(L.emb, (size_t)K * Fn);
-  copy(L.W2, (size_t)Fn * Fn);
-  copy(L.b2, Fn);
-  copy(L.W4, (size_t)Fn * Fn);
-  copy(L.b4, Fn);
-  copy(L.offsets, Fe);  // "_edge_embedding.offset"
-  // node blocks (all passes) come first in the state dict, then edge blocks
-  for (int p = 0; p < P; ++p) {
-    auto &q = L.pass[p];
-    const float *W = c;  // c1_linear.weight [2Fn, Fn+Fe]
-    for (int r = 0; r < 2 * Fn; ++r) {
-      const int col = gated_col(r, Fn, FnP);
-      for (int k = 0; k < Fn; ++k) o[q.c1_WnT + (size_t)k * 2 * FnP + col] = W[r * (Fn + Fe) + k];
-      for (int k = 0; k < Fe; ++k)
-        o[q.c1_WeT + (size_t)k * 2 * FnP + col] = W[r * (Fn + Fe) + Fn + k];
-    }
-    c += (size_t)2 * Fn * (Fn + Fe);
-    for (int r = 0; r < 2 * Fn; ++r) o[q.c1_bias + gated_col(r, Fn, FnP)] = c[r];
-    c += 2 * Fn;
-    for (int r = 0; r < 2 * Fn; ++r) o[q.c1n_g + gated_col(r, Fn, FnP)] = c[r];
-    c += 2 * Fn;
-    for (int r = 0; r < 2 * Fn; ++r) o[q.c1n_b + gated_col(r, Fn, FnP)] = c[r];
-    c += 2 * Fn;
-    copy(q.fin_g, Fn);
-    copy(q.fin_b, Fn);
-  }
-  for (int p = 0; p < P; ++p) {
-    auto &q = L.pass[p];
-    const float *W2 = c;  // c2_linear.weight [2Fe, Fn]
-    for (int r = 0; r < 2 * Fe; ++r) {
-      const int col = gated_col(r, Fe, FeP);
-      for (int k = 0; k < Fn; ++k) o[q.c2_WT + (size_t)k * 2 * FeP + col] = W2[r * Fn + k];
-    }
-    c += (size_t)2 * Fe * Fn;
-    for (int r = 0; r < 2 * Fe; ++r) o[q.c2_bias + gated_col(r, Fe, FeP)] = c[r];
-    c += 2 * Fe;
-    const float *W3 = c;  // c3_linear.weight [2Fe, 3Fn+2Fe]: [n_i | n_j | n_k | e_slot5 | e_slot6]
-    const int ld = 3 * Fn + 2 * Fe;
-    for (int r = 0; r < 2 * Fe; ++r) {
-      const int col = gated_col(r, Fe, FeP);
-      for (int blk = 0; blk < 3; ++blk)
-        for (int k = 0; k < Fn; ++k)
-          o[q.c3_WnT + (size_t)k * 6 * FeP + blk * 2 * FeP + col] = W3[r * ld + blk * Fn + k];
-      for (int blk = 0; blk < 2; ++blk)
-        for (int k = 0; k < Fe; ++k)
-          o[q.c3_WeT + (size_t)k * 4 * FeP + blk * 2 * FeP + col] =
-              W3[r * ld + 3 * Fn + blk * Fe + k];
-    }
-    c += (size_t)2 * Fe * ld;
-    for (int r = 0; r < 2 * Fe; ++r) o[q.c3_nshift + 2 * FeP + gated_col(r, Fe, FeP)] = c[r];
-    c += 2 * Fe;
-    for (int r = 0; r < 2 * Fe; ++r) o[q.c2n1_g + gated_col(r, Fe, FeP)] = c[r];
-    c += 2 * Fe;
-    for (int r = 0; r < 2 * Fe; ++r) o[q.c2n1_b + gated_col(r, Fe, FeP)] = c[r];
-    c += 2 * Fe;
-    for (int r = 0; r < 2 * Fe; ++r) o[q.c3n1_g + gated_col(r, Fe, FeP)] = c[r];
-    c += 2 * Fe;
-    for (int r = 0; r < 2 * Fe; ++r) o[q.c3n1_b + gated_col(r, Fe, FeP)] = c[r];
-    c += 2 * Fe;
-    copy(q.c2n2_g, Fe);
-    copy(q.c2n2_b, Fe);
-    copy(q.c3n2_g, Fe);
-    copy(q.c3n2_b, Fe);
-    for (int k = 0; k < FeP; ++k) {  // sigmoid(f) tanh(c) through exp2: exp2(-log2e f), exp2(2 log2e c)
-      o[q.c3n1_gs + k] = -1.4426950408889634f * o[q.c3n1_g + k];
-      o[q.c3n1_bs + k] = -1.4426950408889634f * o[q.c3n1_b + k];
-      o[q.c3n1_gs + FeP + k] = 2.0f * 1.4426950408889634f * o[q.c3n1_g + FeP + k];
-      o[q.c3n1_bs + FeP + k] = 2.0f * 1.4426950408889634f * o[q.c3n1_b + FeP + k];
-      o[q.c2n1_gs + k] = -1.4426950408889634f * o[q.c2n1_g + k];
-      o[q.c2n1_bs + k] = -1.4426950408889634f * o[q.c2n1_b + k];
-      o[q.c2n1_gs + FeP + k] = 2.0f * 1.4426950408889634f * o[q.c2n1_g + FeP + k];
-      o[q.c2n1_bs + FeP + k] = 2.0f * 1.4426950408889634f * o[q.c2n1_b + FeP + k];
-    }
-    for (int k = 0; k < FnP; ++k) {
-      o[q.c1n_gs + k] = -1.4426950408889634f * o[q.c1n_g + k];
-      o[q.c1n_bs + k] = -1.4426950408889634f * o[q.c1n_b + k];
-      o[q.c1n_gs + FnP + k] = 2.0f * 1.4426950408889634f * o[q.c1n_g + FnP + k];
-      o[q.c1n_bs + FnP + k] = 2.0f * 1.4426950408889634f * o[q.c1n_b + FnP + k];
-    }
-  }
-  {  // readout
-    const float *W0 = c;
-    for (int r = 0; r < Fe; ++r)
-      for (int k = 0; k < Fe; ++k) o[L.W0T + (size_t)k * HP + r] = W0[r * Fe + k];
-    c += (size_t)Fe * Fe;
-    copy(L.b0, Fe);
-    std::memcpy(&o[L.b0p], &o[L.b0], Fe * sizeof(float));
-    copy(L.bn_w, Fe);
-    copy(L.bn_b, Fe);
-    copy(L.bn_rm, Fe);
-    copy(L.bn_rv, Fe);
-    const float *W3 = c;
-    for (int r = 0; r < Fe; ++r)
-      for (int k = 0; k < Fe; ++k) o[L.W3T + (size_t)k * HP + r] = W3[r * Fe + k];
-    c += (size_t)Fe * Fe;
-    copy(L.b3, Fe);
-    const float *W5 = c;
-    for (int r = 0; r < 12; ++r)
-      for (int k = 0; k < Fe; ++k) o[L.W5T + (size_t)k * 32 + r] = W5[r * Fe + k];
-    c += (size_t)12 * Fe;
-    copy(L.b5, 12);
-  }
-  for (int i = 0; i < HP; ++i) o[L.ones + i] = 1.0f;
-  for (const MfmaScaleOp &m : mfma_scale_ops(h)) {  // power-of-two prescales of the split-f16 products
-    float mx = 0.0f;
-    for (int k = 0; k < m.K; ++k)
-      for (int n = 0; n < m.N; ++n) mx = std::max(mx, std::fabs(o[m.src + (size_t)k * m.ld + n]));
-    const float sc = mfma_prescale(mx);
-    o[m.dst] = sc;
-    o[m.dst + 1] = 1.0f / sc;
-  }
-  for (const CentreOp &c : centre_ops(h)) {  // row-centred copies (float64 means; padded columns stay zero)
-    const int bw = 2 * c.FP;
-    for (int k = 0; k < c.K; ++k)
-      for (int b = 0; b < c.N / bw; ++b) {
-        const size_t base = (size_t)k * c.N + (size_t)b * bw;
-        double sum = 0;
-        for (int hh = 0; hh < 2; ++hh)
-          for (int col = 0; col < c.F; ++col) sum += (double)o[c.src + base + hh * c.FP + col];
-        const double mean = sum / (2.0 * c.F);
-        for (int hh = 0; hh < 2; ++hh)
-          for (int col = 0; col < c.FP; ++col)
-            o[c.dst + base + hh * c.FP + col] = col < c.F ? (float)((double)o[c.src + base + hh * c.FP + col] - mean) : 0.0f;
-      }
-  }
-  for (const MfmaScaleOp &m : centred_scale_ops(h)) {
-    float mx = 0.0f;
-    for (int k = 0; k < m.K; ++k)
-      for (int n = 0; n < m.N; ++n) mx = std::max(mx, std::fabs(o[m.src + (size_t)k * m.ld + n]));
-    const float sc = mfma_prescale(mx);
-    o[m.dst] = sc;
-    o[m.dst + 1] = 1.0f / sc;
-  }
-  // transposed copies: src [K][N] (row stride N) -> dst [N][K]
-  auto transpose = [&](size_t src, int Kd, int Nd, size_t dst) {
-    for (int k = 0; k < Kd; ++k)
-      for (int n = 0; n < Nd; ++n) o[dst + (size_t)n * Kd + k] = o[src + (size_t)k * Nd + n];
-  };
-  for (auto &q : L.pass) {
-    transpose(q.c3_WeT, FeP, 4 * FeP, q.t_c3We);
-    transpose(q.c3_WnT, FnP, 6 * FeP, q.t_c3Wn);
-    transpose(q.c2_WT, FnP, 2 * FeP, q.t_c2W);
-    transpose(q.c1_WeT, FeP, 2 * FnP, q.t_c1We);
-    transpose(q.c1_WnT, FnP, 2 * FnP, q.t_c1Wn);
-  }
-  transpose(L.W0T, FeP, HP, L.t_W0);
-  transpose(L.W3T, HP, HP, L.t_W3);
-  transpose(L.W5T, HP, 32, L.t_W5);
-}
-
 // Frames per device work chunk in precision T.  The workspace budget is counted in bytes, so
 // the float64 lanes (created on first use, next to the float32 ones) take half the frames.
 bool lean_workspace(const rn_potgnn *h);
@@ -595,72 +269,20 @@ size_t per_structure_elems(const rn_potgnn *h, bool lean) {
          (lean ? 0 : E * 4 * FeP);
 }
 
-// May the fused kernels run their matrix products as split-f16 MFMAs (device_utils.hpp)?
-// Weights: always -- each block is prescaled by a power of two into f16's normal range (mfma_prescale),
-// so only a non-finite weight refuses.  Activations are split unscaled, which is exact to 22 bits while
-// they stay well inside f16's range: edge rows (Gaussian basis, then tanh outputs), updated node rows
-// and their products are bounded by 1 by construction; the two hidden layers of the readout MLP
-// (shifted softplus, unbounded above) are bounded here from the weights, for |edge| <= 1:
-//   |h1_n| <= |scale0_n| sum_k |W0[n][k]| + |shift0_n|,   |h2_n| <= B1 sum_k |W3[n][k]| + |b3_n|.
-// Beyond 3e4 (f16 overflows at 65504) the handle falls back to the exact-f32 MFMA instantiations.
-bool mfma_f16_range_ok(const rn_potgnn *h) {
-  const PackedLayout &L = h->lay;
-  const float *o = h->packed.data();
-  const int Fe = h->d.Fe, HP = std::max(h->d.FeP, 32);
-  // While the device weights are ahead of `packed` (device-resident training) only the readout block, c3_norm_1 and the
-  // prescale pairs have been fetched: the finiteness of the weight blocks is then read off the pairs, which the device
-  // refresh sets to NaN for a block with a non-finite entry (kernels_train.hip, kind 2)
-  for (const MfmaScaleOp &m : mfma_scale_ops(h)) {
-    if (!std::isfinite(o[m.dst]) || !std::isfinite(o[m.dst + 1])) return false;
-    if (h->host_stale) continue;
-    for (int k = 0; k < m.K; ++k)
-      for (int n = 0; n < m.N; ++n)
-        if (!std::isfinite(o[m.src + (size_t)k * m.ld + n])) return false;
-  }
-  for (const MfmaScaleOp &m : centred_scale_ops(h))
-    if (!std::isfinite(o[m.dst]) || !std::isfinite(o[m.dst + 1])) return false;
-  const double ln2 = 0.6931471805599453;
-  double b1 = ln2, b2 = ln2;
-  for (int n = 0; n < Fe; ++n) {  // BatchNorm(eval) folded as setup_kernel does
-    const double sc = (double)o[L.bn_w + n] / std::sqrt((double)o[L.bn_rv + n] + 1e-5);
-    const double sh = ((double)o[L.b0 + n] - (double)o[L.bn_rm + n]) * sc + (double)o[L.bn_b + n];
-    double sum = 0;
-    for (int k = 0; k < Fe; ++k) sum += std::fabs((double)o[L.W0T + (size_t)k * HP + n]);
-    b1 = std::max(b1, std::fabs(sc) * sum + std::fabs(sh));
-  }
-  for (int n = 0; n < Fe; ++n) {
-    double sum = 0;
-    for (int k = 0; k < Fe; ++k) sum += std::fabs((double)o[L.W3T + (size_t)k * HP + n]);
-    b2 = std::max(b2, sum * b1 + std::fabs((double)o[L.b3 + n]));
-  }
-  return std::isfinite(b1) && std::isfinite(b2) && b1 <= 3.0e4 && b2 <= 3.0e4;
-}
 void refresh_mfma_mode(rn_potgnn *h) {
-  const bool ok = mfma_f16_range_ok(h);
+  const bool ok = mfma_f16_range_ok(h->lay, h->packed.data(), h->host_stale);
   h->mfma_f16 = h->mfma_f16_requested && ok;
   h->mfma_range_fallback = h->mfma_f16_requested && !ok;
 }
 
 // Per pass: may the EdgeBlock's triplet loop fold c3_norm_1's scale into its operands and
-// drop the gate's overflow clamp (edge_agg_kernel, FASTG)?  Needs every gamma of a real
-// column away from zero (the loop divides by it) and the gate arguments provably small:
-// a LayerNorm output is at most sqrt(2Fe - 1) in magnitude.
+// drop the gate's overflow clamp (edge_agg_kernel, FASTG; folded_gate_ok decides from the weights)?
 template <typename T>
 void refresh_pass_flags(rn_potgnn *h) {
   Precision<T> &P = prec<T>(h);
-  const PackedLayout &L = h->lay;
-  const int Fe = h->d.Fe, FeP = h->d.FeP;
   const bool off = getenv("RN_POTGNN_NO_FASTG") && atoi(getenv("RN_POTGNN_NO_FASTG")) != 0;
-  for (size_t p = 0; p < L.pass.size() && p < P.pass.size(); ++p) {
-    const float *gam = h->packed.data() + L.pass[p].c3n1_g, *bet = h->packed.data() + L.pass[p].c3n1_b;
-    const double xmax = std::sqrt(2.0 * Fe) * 1.02;
-    bool ok = !off;
-    for (int half = 0; half < 2 && ok; ++half)
-      for (int k = 0; k < Fe && ok; ++k) {
-        const double g = std::fabs((double)gam[half * FeP + k]), b = std::fabs((double)bet[half * FeP + k]);
-        const double arg = (g * xmax + b) * 2.0 * 1.4426950408889634;
-        ok = std::isfinite(g) && std::isfinite(b) && g >= 1e-5 && arg < 60.0;
-      }
+  for (size_t p = 0; p < h->lay.pass.size() && p < P.pass.size(); ++p) {
+    const bool ok = !off && folded_gate_ok(h->lay, h->packed.data(), (int)p);
     // bit 0: fused EdgeBlock kernel; bit 1: unfused edge_agg_kernel -- there only with a
     // single lane: its 170 registers per lane shut the other lane's projection workgroups
     // out of the CU (150 do not), which costs more than the shorter loop gains
@@ -709,43 +331,13 @@ void ensure_precision(rn_potgnn *h) {
   T lat[9];
   for (int i = 0; i < 9; ++i) lat[i] = (T)h->lattice[i];
   stage<T>(P.lattice, lat, sizeof(lat));
-  P.pass.resize(L.pass.size());
-  for (size_t p = 0; p < L.pass.size(); ++p) {
-    const auto &q = L.pass[p];
-    PassW<T> &o = P.pass[p];
-    o.c1_WnT = w + q.c1_WnT;
-    o.c1_WeT = w + q.c1_WeT;
-    o.c1_bias = w + q.c1_bias;
-    o.c1_norm = {w + q.c1n_g, w + q.c1n_b};
-    o.final_norm = {w + q.fin_g, w + q.fin_b};
-    o.c2_WT = w + q.c2_WT;
-    o.c2_bias = w + q.c2_bias;
-    o.c2_norm_1 = {w + q.c2n1_g, w + q.c2n1_b};
-    o.c2_norm_2 = {w + q.c2n2_g, w + q.c2n2_b};
-    o.c3_WnT = w + q.c3_WnT;
-    o.c3_nshift = w + q.c3_nshift;
-    o.c3_WeT = w + q.c3_WeT;
-    o.c3_norm_1 = {w + q.c3n1_g, w + q.c3n1_b};
-    o.c3_norm_2 = {w + q.c3n2_g, w + q.c3n2_b};
-    o.c3_norm_1s = {w + q.c3n1_gs, w + q.c3n1_bs};
-    o.c2_norm_1s = {w + q.c2n1_gs, w + q.c2n1_bs};
-    o.c1_norm_s = {w + q.c1n_gs, w + q.c1n_bs};
-    o.mfma_scale = w + q.mfma_scale;
-    o.c3_WeT_c = w + q.c3_WeT_c;
-    o.c3_WnT_c = w + q.c3_WnT_c;
-    o.c3_nshift_c = w + q.c3_nshift_c;
-    o.c2_WT_c = w + q.c2_WT_c;
-    o.c2_bias_c = w + q.c2_bias_c;
-    o.mfma_scale_c = w + q.mfma_scale_c;
-    o.c1_WnT_c = w + q.c1_WnT_c;
-    o.c1_WeT_c = w + q.c1_WeT_c;
-    o.c1_bias_c = w + q.c1_bias_c;
-  }
+  WeightViews<T> v = bind_weights<T>(L, w);
+  P.pass = std::move(v.pass);
   refresh_pass_flags<T>(h);
-  P.ro = {w + L.W0T, w + L.scale0, w + L.shift0, w + L.W3T, w + L.b3, w + L.W5T, w + L.b5, w + L.ro_mfma_scale};
-  P.offsets = w + L.offsets;
-  P.node_table = w + L.node_table;
-  P.ones = w + L.ones;
+  P.ro = v.ro;
+  P.offsets = v.offsets;
+  P.node_table = v.node_table;
+  P.ones = v.ones;
 
   const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges, S = chunk_frames<T>(h);
   const size_t FnP = h->d.FnP, FeP = h->d.FeP;
@@ -1681,67 +1273,6 @@ void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_
   hand_back(h, user, P.lanes, 1, true);
 }
 
-// ---- device-resident optimisation step: which entries of the packed blob are parameters, which are
-// functions of parameters (and how to recompute them on the device)
-
-std::vector<DerivedOp> derived_ops(const rn_potgnn *h, int *first_stage = nullptr) {
-  const PackedLayout &L = h->lay;
-  const int FnP = h->d.FnP, FeP = h->d.FeP, Fe = h->d.Fe, HP = std::max(FeP, 32);
-  std::vector<DerivedOp> ops;
-  auto transpose = [&](size_t src, int K, int N, size_t dst) { ops.push_back({0, K, N, 1.0f, src, dst}); };
-  auto scaled = [&](size_t src, int n, float sc, size_t dst) { ops.push_back({1, n, 1, sc, src, dst}); };
-  for (const auto &q : L.pass) {
-    transpose(q.c3_WeT, FeP, 4 * FeP, q.t_c3We);
-    transpose(q.c3_WnT, FnP, 6 * FeP, q.t_c3Wn);
-    transpose(q.c2_WT, FnP, 2 * FeP, q.t_c2W);
-    transpose(q.c1_WeT, FeP, 2 * FnP, q.t_c1We);
-    transpose(q.c1_WnT, FnP, 2 * FnP, q.t_c1Wn);
-    scaled(q.c3n1_g, FeP, -1.4426950408889634f, q.c3n1_gs);
-    scaled(q.c3n1_b, FeP, -1.4426950408889634f, q.c3n1_bs);
-    scaled(q.c3n1_g + FeP, FeP, 2.0f * 1.4426950408889634f, q.c3n1_gs + FeP);
-    scaled(q.c3n1_b + FeP, FeP, 2.0f * 1.4426950408889634f, q.c3n1_bs + FeP);
-    scaled(q.c2n1_g, FeP, -1.4426950408889634f, q.c2n1_gs);
-    scaled(q.c2n1_b, FeP, -1.4426950408889634f, q.c2n1_bs);
-    scaled(q.c2n1_g + FeP, FeP, 2.0f * 1.4426950408889634f, q.c2n1_gs + FeP);
-    scaled(q.c2n1_b + FeP, FeP, 2.0f * 1.4426950408889634f, q.c2n1_bs + FeP);
-    scaled(q.c1n_g, FnP, -1.4426950408889634f, q.c1n_gs);
-    scaled(q.c1n_b, FnP, -1.4426950408889634f, q.c1n_bs);
-    scaled(q.c1n_g + FnP, FnP, 2.0f * 1.4426950408889634f, q.c1n_gs + FnP);
-    scaled(q.c1n_b + FnP, FnP, 2.0f * 1.4426950408889634f, q.c1n_bs + FnP);
-  }
-  transpose(L.W0T, FeP, HP, L.t_W0);
-  transpose(L.W3T, HP, HP, L.t_W3);
-  transpose(L.W5T, HP, 32, L.t_W5);
-  scaled(L.b0p, Fe, 1.0f, L.b0);  // the bias of readout Linear 0 lives twice (eval fold / training forward)
-  for (const MfmaScaleOp &m : mfma_scale_ops(h)) ops.push_back({2, m.K, m.N, (float)m.ld, m.src, m.dst});
-  for (const CentreOp &c : centre_ops(h)) ops.push_back({3, c.K, c.N, 1.0f, c.src, c.dst, c.F, c.FP});
-  if (first_stage) *first_stage = (int)ops.size();
-  // second launch: the prescales of the centred copies read what the first launch wrote
-  for (const MfmaScaleOp &m : centred_scale_ops(h)) ops.push_back({2, m.K, m.N, (float)m.ld, m.src, m.dst});
-  return ops;
-}
-
-// 1 where a packed entry is a trainable parameter: pack a state dict of ones, then drop the buffers
-// and every derived range
-std::vector<unsigned char> trainable_mask(rn_potgnn *h) {
-  std::vector<float> ones(rn_potgnn_weight_count(&h->cfg), 1.0f);
-  const std::vector<float> keep = h->packed;
-  pack_weights(h, ones.data());
-  std::vector<unsigned char> mask(h->packed.size());
-  for (size_t i = 0; i < mask.size(); ++i) mask[i] = h->packed[i] != 0.0f;
-  h->packed = keep;
-  const PackedLayout &L = h->lay;
-  const int HP = std::max(h->d.FeP, 32);
-  auto clear = [&](size_t o, size_t n) { std::fill(mask.begin() + o, mask.begin() + o + n, (unsigned char)0); };
-  for (const DerivedOp &op : derived_ops(h))
-    clear(op.dst, op.kind == 2 ? 2 : (size_t)op.K * ((op.kind == 0 || op.kind == 3) ? op.N : 1));
-  clear(L.ones, HP);
-  clear(L.offsets, h->d.FeP);  // buffers of the state dict: Gaussian offsets, BatchNorm running statistics
-  clear(L.bn_rm, h->d.Fe);
-  clear(L.bn_rv, h->d.Fe);
-  return mask;
-}
-
 // refresh `packed` (and the float64 copy, when it exists) from the device weights
 void sync_host(rn_potgnn *h) {
   if (!h->host_stale) return;
@@ -1923,9 +1454,6 @@ inline void train_forward_device(rn_potgnn *h, const double *d_pos, int S, const
 }
 
 template <typename T>
-void unpack_grads(const rn_potgnn *h, const T *gp, T *out, bool buffers);
-
-template <typename T>
 void train_backward(rn_potgnn *h, const T *dvec6, T *grads /* null: leave the gradients on the device */,
                     double *host_dpos = nullptr /* [S][N][3] or null */, double *host_dlat = nullptr /* [S][9] or null */) {
   Precision<T> &P = prec<T>(h);
@@ -1954,7 +1482,7 @@ void train_backward(rn_potgnn *h, const T *dvec6, T *grads /* null: leave the gr
   if (!grads) return;
   std::vector<T> gp(h->lay.total);
   HIP_TRY(hipMemcpy(gp.data(), P.grad.p, gp.size() * sizeof(T), hipMemcpyDeviceToHost));
-  unpack_grads<T>(h, gp.data(), grads, false);
+  unpack_weights<T>(h->lay, gp.data(), grads, false);
 }
 
 // Reverse pass of a pending train_forward(_device) with the cotangents [S][6] in a DEVICE buffer; the gradients stay in HBM
@@ -1979,84 +1507,6 @@ inline void train_backward_device(rn_potgnn *h, const float *d_dvec6, hipStream_
   hand_back(h, user, P.lanes, 1, false);
   h->train_S = 0;
   h->grads_on_device = true;
-}
-
-// inverse of pack_weights for a gradient blob in the packed layout -> state_dict order
-template <typename T>
-void unpack_grads(const rn_potgnn *h, const T *gp, T *out, bool buffers /* true: gp holds WEIGHTS */) {
-  const int K = h->cfg.num_atom_types, Fn = h->d.Fn, Fe = h->d.Fe, FnP = h->d.FnP, FeP = h->d.FeP,
-            P = h->cfg.num_message_passes;
-  const int HP = std::max(FeP, 32);
-  const PackedLayout &L = h->lay;
-  T *c = out;
-  auto copy = [&](size_t src, size_t n) {
-    std::memcpy(c, gp + src, n * sizeof(T));
-    c += n;
-  };
-  auto zeros = [&](size_t n) {
-    std::memset(c, 0, n * sizeof(T));
-    c += n;
-  };
-  auto buffer = [&](size_t src, size_t n) {  // a non-trainable entry: zero gradient / its value
-    if (buffers) copy(src, n);
-    else zeros(n);
-  };
-  copy(L.emb, (size_t)K * Fn);
-  copy(L.W2, (size_t)Fn * Fn);
-  copy(L.b2, Fn);
-  copy(L.W4, (size_t)Fn * Fn);
-  copy(L.b4, Fn);
-  buffer(L.offsets, Fe);  // "_edge_embedding.offset" is a buffer
-  for (int p = 0; p < P; ++p) {
-    const auto &q = L.pass[p];
-    for (int r = 0; r < 2 * Fn; ++r) {
-      const int col = gated_col(r, Fn, FnP);
-      for (int k = 0; k < Fn; ++k) *c++ = gp[q.c1_WnT + (size_t)k * 2 * FnP + col];
-      for (int k = 0; k < Fe; ++k) *c++ = gp[q.c1_WeT + (size_t)k * 2 * FnP + col];
-    }
-    for (int r = 0; r < 2 * Fn; ++r) *c++ = gp[q.c1_bias + gated_col(r, Fn, FnP)];
-    for (int r = 0; r < 2 * Fn; ++r) *c++ = gp[q.c1n_g + gated_col(r, Fn, FnP)];
-    for (int r = 0; r < 2 * Fn; ++r) *c++ = gp[q.c1n_b + gated_col(r, Fn, FnP)];
-    copy(q.fin_g, Fn);
-    copy(q.fin_b, Fn);
-  }
-  for (int p = 0; p < P; ++p) {
-    const auto &q = L.pass[p];
-    for (int r = 0; r < 2 * Fe; ++r) {
-      const int col = gated_col(r, Fe, FeP);
-      for (int k = 0; k < Fn; ++k) *c++ = gp[q.c2_WT + (size_t)k * 2 * FeP + col];
-    }
-    for (int r = 0; r < 2 * Fe; ++r) *c++ = gp[q.c2_bias + gated_col(r, Fe, FeP)];
-    for (int r = 0; r < 2 * Fe; ++r) {
-      const int col = gated_col(r, Fe, FeP);
-      for (int blk = 0; blk < 3; ++blk)
-        for (int k = 0; k < Fn; ++k) *c++ = gp[q.c3_WnT + (size_t)k * 6 * FeP + blk * 2 * FeP + col];
-      for (int blk = 0; blk < 2; ++blk)
-        for (int k = 0; k < Fe; ++k) *c++ = gp[q.c3_WeT + (size_t)k * 4 * FeP + blk * 2 * FeP + col];
-    }
-    for (int r = 0; r < 2 * Fe; ++r) *c++ = gp[q.c3_nshift + 2 * FeP + gated_col(r, Fe, FeP)];
-    for (int r = 0; r < 2 * Fe; ++r) *c++ = gp[q.c2n1_g + gated_col(r, Fe, FeP)];
-    for (int r = 0; r < 2 * Fe; ++r) *c++ = gp[q.c2n1_b + gated_col(r, Fe, FeP)];
-    for (int r = 0; r < 2 * Fe; ++r) *c++ = gp[q.c3n1_g + gated_col(r, Fe, FeP)];
-    for (int r = 0; r < 2 * Fe; ++r) *c++ = gp[q.c3n1_b + gated_col(r, Fe, FeP)];
-    copy(q.c2n2_g, Fe);
-    copy(q.c2n2_b, Fe);
-    copy(q.c3n2_g, Fe);
-    copy(q.c3n2_b, Fe);
-  }
-  for (int r = 0; r < Fe; ++r)
-    for (int k = 0; k < Fe; ++k) *c++ = gp[L.W0T + (size_t)k * HP + r];
-  copy(L.b0p, Fe);
-  copy(L.bn_w, Fe);
-  copy(L.bn_b, Fe);
-  buffer(L.bn_rm, Fe);  // running_mean
-  buffer(L.bn_rv, Fe);  // running_var
-  for (int r = 0; r < Fe; ++r)
-    for (int k = 0; k < Fe; ++k) *c++ = gp[L.W3T + (size_t)k * HP + r];
-  copy(L.b3, Fe);
-  for (int r = 0; r < 12; ++r)
-    for (int k = 0; k < Fe; ++k) *c++ = gp[L.W5T + (size_t)k * 32 + r];
-  copy(L.b5, 12);
 }
 
 // Every entry point that touches a handle runs inside guarded(): calls on ONE handle are serialised by the handle's own
@@ -2196,14 +1646,11 @@ extern "C" {
 const char *rn_potgnn_version(void) { return "ramannoodle_amd-potgnn 0.1 (gfx950)"; }
 
 size_t rn_potgnn_weight_count(const rn_potgnn_config *c) {
-  if (!c) return 0;
-  const size_t K = c->num_atom_types, Fn = c->size_node_embedding, Fe = c->size_edge_embedding,
-               P = c->num_message_passes;
-  size_t n = K * Fn + 2 * (Fn * Fn + Fn) + Fe;
-  n += P * (2 * Fn * (Fn + Fe) + 2 * Fn + 2 * (2 * Fn) + 2 * Fn);
-  n += P * (2 * Fe * Fn + 2 * Fe + 2 * Fe * (3 * Fn + 2 * Fe) + 2 * Fe + 4 * (2 * Fe) + 4 * Fe);
-  n += (Fe * Fe + Fe) + 4 * Fe + (Fe * Fe + Fe) + (12 * Fe + 12);
-  return n;
+  try {
+    return state_dict_count(c);
+  } catch (const std::exception &) {  // (a pass count no table fits in memory for)
+    return 0;
+  }
 }
 
 const char *rn_potgnn_last_error(const rn_potgnn *h) {
@@ -2325,7 +1772,8 @@ int rn_potgnn_create(const rn_potgnn_config *cfg, const int32_t *edge_a, const i
     std::memcpy(ms + 9, hp->stdv, sizeof(hp->stdv));
     hp->d_mean_std.ensure(sizeof(ms));
     HIP_TRY(hipMemcpy(hp->d_mean_std.p, ms, sizeof(ms), hipMemcpyHostToDevice));
-    pack_weights(hp, weights);
+    hp->lay = layout_weights(hp->cfg, hp->d);
+    pack_weights(hp->lay, weights, hp->packed);
     refresh_mfma_mode(hp);
     hp->ps_fail.ensure(2048);  // [0] the failure word; timing builds (RN_PS_TIMING) keep their cycle counters from byte 64 on
     HIP_TRY(hipMemset(hp->ps_fail.p, 0, 2048));
@@ -2386,6 +1834,79 @@ int rn_potgnn_debug_plan_lds(const rn_potgnn_config *cfg, const int32_t *edge_a,
   } catch (const std::bad_alloc &) {
     set_error(nullptr, "host allocation failed");
     return RN_ERR_OUT_OF_MEMORY;
+  }
+}
+
+// The packed layout of a model of `cfg` alone (no graph), after the configuration checks of rn_potgnn_create.
+static int debug_layout(const rn_potgnn_config *cfg, bool others_null, const size_t *num_weights, PackedLayout &L) {
+  std::string invalid;
+  const int rc = validate_config(cfg, others_null, num_weights, invalid);
+  if (rc != RN_OK) {
+    set_error(nullptr, "%s", invalid.c_str());
+    return rc;
+  }
+  L = layout_weights(*cfg, plan_dims(*cfg, read_plan_knobs()));
+  return RN_OK;
+}
+static int debug_failed(const std::exception &e) {
+  const bool memory = dynamic_cast<const std::bad_alloc *>(&e) != nullptr;
+  set_error(nullptr, memory ? "host allocation failed" : "internal error: %s", e.what());
+  return memory ? RN_ERR_OUT_OF_MEMORY : RN_ERR_HIP;
+}
+
+int rn_potgnn_debug_pack_weights(const rn_potgnn_config *cfg, const float *weights, size_t num_weights, float *packed,
+                                 unsigned char *mask, unsigned char *writers, int32_t *flags, size_t capacity, size_t *count) {
+  if (!count) return RN_ERR_INVALID_ARGUMENT;
+  *count = 0;
+  try {
+    PackedLayout L;
+    if (const int rc = debug_layout(cfg, !weights, &num_weights, L); rc != RN_OK) return rc;
+    *count = L.total;
+    if (!packed || !mask || !flags || capacity < L.total) {
+      set_error(nullptr, "out holds %zu values, the packed blob has %zu", packed && mask && flags ? capacity : (size_t)0, L.total);
+      return RN_ERR_INVALID_ARGUMENT;
+    }
+    std::vector<float> o;
+    pack_weights(L, weights, o);
+    std::memcpy(packed, o.data(), o.size() * sizeof(float));
+    const std::vector<unsigned char> m = trainable_mask(L);
+    std::memcpy(mask, m.data(), m.size());
+    if (writers) {
+      const std::vector<unsigned char> w = packed_writers(L);
+      std::memcpy(writers, w.data(), w.size());
+    }
+    flags[0] = mfma_f16_range_ok(L, o.data(), false);
+    for (int p = 0; p < L.P; ++p) {
+      flags[1 + p] = folded_gate_ok(L, o.data(), p);
+      (void)L.c3_norm_1(p), (void)L.mfma_scales(p);  // (throw when the layout broke what rn_potgnn_adam_step fetches in one piece)
+    }
+    (void)L.readout();
+    return RN_OK;
+  } catch (const std::exception &e) {
+    return debug_failed(e);
+  }
+}
+
+int rn_potgnn_debug_unpack_weights(const rn_potgnn_config *cfg, const float *packed, size_t num_packed, int buffers,
+                                   float *out, size_t capacity, size_t *count) {
+  if (!count) return RN_ERR_INVALID_ARGUMENT;
+  *count = 0;
+  try {
+    PackedLayout L;
+    if (const int rc = debug_layout(cfg, !packed, nullptr, L); rc != RN_OK) return rc;
+    *count = L.weight_count();
+    if (num_packed != L.total) {
+      set_error(nullptr, "packed has %zu floats, expected %zu", num_packed, L.total);
+      return RN_ERR_INVALID_ARGUMENT;
+    }
+    if (!out || capacity < L.weight_count()) {
+      set_error(nullptr, "out holds %zu values, the state dict has %zu", out ? capacity : (size_t)0, L.weight_count());
+      return RN_ERR_INVALID_ARGUMENT;
+    }
+    unpack_weights<float>(L, packed, out, buffers != 0);
+    return RN_OK;
+  } catch (const std::exception &e) {
+    return debug_failed(e);
   }
 }
 
@@ -2798,13 +2319,13 @@ int rn_potgnn_raman_tensors_analytic(rn_potgnn *h, const double *ref_positions,
 }
 
 int rn_potgnn_set_weights(rn_potgnn *h, const float *weights, size_t num_weights) {
-  if (!h || !weights || num_weights != rn_potgnn_weight_count(&h->cfg)) {
+  if (!h || !weights || num_weights != h->lay.weight_count()) {
     set_error(h, "invalid arguments to set_weights");
     return RN_ERR_INVALID_ARGUMENT;
   }
   return guarded(h, [&]() {
     HIP_TRY(hipDeviceSynchronize());
-    pack_weights(h, weights);
+    pack_weights(h->lay, weights, h->packed);
     refresh_mfma_mode(h);
     h->host_stale = false;
     h->grads_on_device = false;
@@ -3017,10 +2538,10 @@ int rn_potgnn_adam_step(rn_potgnn *h, double lr, double beta1, double beta2, dou
       h->adam_v.ensure(n * sizeof(float));
       HIP_TRY(hipMemset(h->adam_m.p, 0, n * sizeof(float)));
       HIP_TRY(hipMemset(h->adam_v.p, 0, n * sizeof(float)));
-      const std::vector<unsigned char> mask = trainable_mask(h);
+      const std::vector<unsigned char> mask = trainable_mask(L);
       h->trainable_mask.ensure(mask.size());
       HIP_TRY(hipMemcpy(h->trainable_mask.p, mask.data(), mask.size(), hipMemcpyHostToDevice));
-      const std::vector<DerivedOp> ops = derived_ops(h, &h->derived_first_stage);
+      const std::vector<DerivedOp> ops = derived_ops(L, &h->derived_first_stage);
       h->derived_ops.ensure(ops.size() * sizeof(DerivedOp));
       HIP_TRY(hipMemcpy(h->derived_ops.p, ops.data(), ops.size() * sizeof(DerivedOp), hipMemcpyHostToDevice));
       h->num_derived_ops = (int)ops.size();
@@ -3041,17 +2562,17 @@ int rn_potgnn_adam_step(rn_potgnn *h, double lr, double beta1, double beta2, dou
     {
       std::vector<long long> seg;
       long long total = 0;
-      auto add = [&](size_t src, size_t n) {
-        seg.push_back((long long)src);
+      auto add = [&](Span s) {
+        seg.push_back((long long)s.begin);
         seg.push_back(total);
-        seg.push_back((long long)n);
-        total += (long long)n;
+        seg.push_back((long long)s.count);
+        total += (long long)s.count;
       };
-      for (const auto &q : L.pass) {
-        add(q.c3n1_g, 4 * (size_t)h->d.FeP);  // scale then shift, adjacent in the packed layout
-        add(q.mfma_scale, 16);                // + mfma_scale_c
+      for (int p = 0; p < L.P; ++p) {
+        add(L.c3_norm_1(p));    // the folded-gate criterion reads gamma and beta
+        add(L.mfma_scales(p));  // the prescale pairs double as finiteness flags
       }
-      add(L.W0T, L.b5 + 32 - L.W0T);          // W0T .. b5, contiguous in the layout
+      add(L.readout());
       if (h->step_seg.bytes < seg.size() * sizeof(long long)) {
         h->step_seg.ensure(seg.size() * sizeof(long long));
         HIP_TRY(hipMemcpy(h->step_seg.p, seg.data(), seg.size() * sizeof(long long), hipMemcpyHostToDevice));
@@ -3080,13 +2601,13 @@ int rn_potgnn_adam_step(rn_potgnn *h, double lr, double beta1, double beta2, dou
 }
 
 int rn_potgnn_get_weights(rn_potgnn *h, float *weights, size_t num_weights) {
-  if (!h || !weights || num_weights != rn_potgnn_weight_count(&h->cfg)) {
+  if (!h || !weights || num_weights != h->lay.weight_count()) {
     set_error(h, "invalid arguments to get_weights");
     return RN_ERR_INVALID_ARGUMENT;
   }
   return guarded(h, [&]() {
     sync_host(h);
-    unpack_grads<float>(h, h->packed.data(), weights, true);
+    unpack_weights<float>(h->lay, h->packed.data(), weights, true);
   });
 }
 

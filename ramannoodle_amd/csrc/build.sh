@@ -11,14 +11,14 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function ${R
 bdir="build${tag:+_$tag}"
 mkdir -p "$here/$bdir"
 pids=()
-hip_srcs="api graph_plan kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group spectrum spectrum_polarized spectrum_partial spectrum_segments spectrum_ensemble"
+hip_srcs="api graph_plan weight_layout kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group spectrum spectrum_polarized spectrum_partial spectrum_segments spectrum_ensemble"
 objs=()
 for f in $hip_srcs; do
   o="$here/$bdir/$(basename "$f").o"
   objs+=("$o")
   if [ ! -f "$o" ] || [ "$here/$f.hip" -nt "$o" ] || [ "$here/fused_common.hpp" -nt "$o" ] || \
      [ "$here/kernels.hpp" -nt "$o" ] || [ "$here/device_utils.hpp" -nt "$o" ] || \
-     [ "$here/graph_plan.hpp" -nt "$o" ] || \
+     [ "$here/graph_plan.hpp" -nt "$o" ] || [ "$here/weight_layout.hpp" -nt "$o" ] || \
      [ "$here/spectrum_common.hpp" -nt "$o" ] || [ "$here/spectrum_segment_core.hpp" -nt "$o" ] || \
      [ "$here/../../include/rn_potgnn.h" -nt "$o" ]; then
     extra=""

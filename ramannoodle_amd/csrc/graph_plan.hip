@@ -379,9 +379,8 @@ size_t max_out_degree(Dims d) {
   return deg;
 }
 
-int validate_create_args(const rn_potgnn_config *cfg_in, const int32_t *edge_a, const int32_t *edge_b, const int32_t *atom_types,
-                         bool others_null, const size_t *num_weights, std::string &error) {
-  if (!cfg_in || !atom_types || others_null || (cfg_in->num_edges > 0 && (!edge_a || !edge_b))) {
+int validate_config(const rn_potgnn_config *cfg_in, bool others_null, const size_t *num_weights, std::string &error) {
+  if (!cfg_in || others_null) {
     error = "null argument";
     return RN_ERR_INVALID_ARGUMENT;
   }
@@ -406,6 +405,15 @@ int validate_create_args(const rn_potgnn_config *cfg_in, const int32_t *edge_a, 
     error = format("weights has %zu floats, expected %zu", *num_weights, rn_potgnn_weight_count(&cfg));
     return RN_ERR_INVALID_ARGUMENT;
   }
+  return RN_OK;
+}
+
+int validate_create_args(const rn_potgnn_config *cfg_in, const int32_t *edge_a, const int32_t *edge_b, const int32_t *atom_types,
+                         bool others_null, const size_t *num_weights, std::string &error) {
+  const bool graph_null = !atom_types || (cfg_in && cfg_in->num_edges > 0 && (!edge_a || !edge_b));
+  if (const int rc = validate_config(cfg_in, others_null || graph_null, num_weights, error); rc != RN_OK) return rc;
+  const rn_potgnn_config &cfg = *cfg_in;
+  const int N = cfg.num_atoms, E = cfg.num_edges;
   for (int e = 0; e < E; ++e) {
     if (edge_a[e] < 0 || edge_a[e] >= N || edge_b[e] < 0 || edge_b[e] >= N || edge_a[e] == edge_b[e]) {
       error = format("edge %d = (%d,%d) is out of range or a self loop", e, edge_a[e], edge_b[e]);

@@ -46,6 +46,8 @@ size_t max_out_degree(Dims d);
 
 // The checks of rn_potgnn_create that need no device, in its order (null arguments, the configuration, the weight count
 // unless `num_weights` is null, the edge list, the atom types, the out-degrees).  RN_OK, or the status with its text in `error`.
+// Its first part, which needs no graph: a null configuration (or `others_null`), the sizes, the widths, the weight count.
+int validate_config(const rn_potgnn_config *cfg, bool others_null, const size_t *num_weights, std::string &error);
 int validate_create_args(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b, const int32_t *atom_types,
                          bool others_null, const size_t *num_weights, std::string &error);
 

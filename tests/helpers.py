@@ -210,3 +210,58 @@ def plan_cases(knobs):
         fn, fe = (64, 64) if seed % 2 == 0 else PLAN_WIDTHS[(seed // 2) % len(PLAN_WIDTHS)]
         add(f"ragged{seed:02d}_{fn}_{fe}", ea, eb, types, k, fn, fe)
     return cases
+
+
+# ----------------------------------------------------------------------------- packed weights (rn_potgnn_debug_pack_weights)
+def state_dict_sizes(k, fn, fe, passes):
+    """(name, element count) of every tensor of a PotGNN state dict, in state-dict order, written out independently of the
+    library's table (csrc/weight_layout.hip): node blocks of all passes first, then the edge blocks, then the readout."""
+    out = [("emb", k * fn), ("W2", fn * fn), ("b2", fn), ("W4", fn * fn), ("b4", fn), ("offset", fe)]
+    for p in range(passes):
+        out += [(f"{p}/c1_w", 2 * fn * (fn + fe)), (f"{p}/c1_b", 2 * fn), (f"{p}/c1n_g", 2 * fn), (f"{p}/c1n_b", 2 * fn),
+                (f"{p}/fin_g", fn), (f"{p}/fin_b", fn)]
+    for p in range(passes):
+        out += [(f"{p}/c2_w", 2 * fe * fn), (f"{p}/c2_b", 2 * fe), (f"{p}/c3_w", 2 * fe * (3 * fn + 2 * fe)), (f"{p}/c3_b", 2 * fe)]
+        out += [(f"{p}/{n}", 2 * fe) for n in ("c2n1_g", "c2n1_b", "c3n1_g", "c3n1_b")]
+        out += [(f"{p}/{n}", fe) for n in ("c2n2_g", "c2n2_b", "c3n2_g", "c3n2_b")]
+    out += [("W0", fe * fe), ("b0", fe), ("bn_w", fe), ("bn_b", fe), ("bn_rm", fe), ("bn_rv", fe), ("W3", fe * fe), ("b3", fe),
+            ("W5", 12 * fe), ("b5", 12)]
+    return out
+
+
+STATE_DICT_BUFFERS = ("offset", "bn_rm", "bn_rv")  # not parameters: Gaussian offsets, BatchNorm running statistics
+WEIGHT_SHAPES = ((1, 1, 1, 1), (3, 5, 14, 2), (2, 16, 16, 1), (2, 20, 40, 2), (2, 8, 64, 1), (3, 64, 64, 4), (1, 100, 128, 1))
+
+
+def state_dict_slices(k, fn, fe, passes):
+    sizes = state_dict_sizes(k, fn, fe, passes)
+    starts = np.concatenate([[0], np.cumsum([n for _, n in sizes])])
+    return {name: slice(int(a), int(b)) for (name, _), a, b in zip(sizes, starts[:-1], starts[1:])}
+
+
+def weight_layout_cases():
+    """(name, (K, Fn, Fe, P), float32 state-dict blob): seeded normal blobs at WEIGHT_SHAPES, then at (2, 64, 64, 2) a tame
+    blob on which the split-f16 range guard and the folded gate both hold ("flags_base": weights 0.1 N(0,1), LayerNorm
+    gammas and the running variance near 1) and three variants that each flip one decision."""
+    cases = []
+    for i, shape in enumerate(WEIGHT_SHAPES):
+        n = sum(size for _, size in state_dict_sizes(*shape))
+        cases.append(("normal_%d_%d_%d_%d" % shape, shape, np.random.default_rng(100 + i).normal(size=n).astype(np.float32)))
+    shape = (2, 64, 64, 2)
+    at = state_dict_slices(*shape)
+    base = (0.1 * np.random.default_rng(200).normal(size=max(s.stop for s in at.values()))).astype(np.float32)
+    for name, s in at.items():
+        if name.endswith("_g") or name in ("bn_w", "bn_rv"):
+            base[s] = 1.0 + np.abs(base[s])
+    cases.append(("flags_base", shape, base))
+    inf = base.copy()
+    inf[at["1/c2_w"].start + 77] = np.inf  # a non-finite weight: the range guard refuses
+    cases.append(("flags_c2_inf", shape, inf))
+    wide = base.copy()
+    wide[at["W0"]] *= 1e3  # |h1| <= ~5e3, |h2| <= ~5e3 * 5e3: beyond the 3e4 bound, the handle falls back
+    wide[at["W3"]] *= 1e3
+    cases.append(("flags_readout_bound", shape, wide))
+    gamma = base.copy()
+    gamma[at["1/c3n1_g"].start + 64 + 5] = 1e-6  # a real core-half gamma of pass 1 the loop cannot divide by
+    cases.append(("flags_small_gamma", shape, gamma))
+    return cases

@@ -1033,3 +1033,176 @@ def test_committed_profile_records_are_fresh():
         assert bench.committed_profile("edge_ps_traffic.json", 256, 4608, 64, 64) is None
     finally:
         bench.PROFILE_ROUNDS = older
+
+
+# ----------------------------------------------------------------------------- packed weight layout
+_PACKED_GOLDEN = os.path.join(ROOT, "tests", "golden", "packed_weights.npz")
+_PACKED_CACHE = {}
+
+
+def _weight_cfg(shape):
+    k, fn, fe, passes = shape
+    return _lib.Config(4, 2, k, fn, fe, passes, -1.0, 0, 0)
+
+
+def _pack(shape, blob):
+    """``rn_potgnn_debug_pack_weights``: (packed, mask, writers, flags), size query first."""
+    lib, cfg, count = _lib.load(), _weight_cfg(shape), ctypes.c_size_t(0)
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    rc = lib.rn_potgnn_debug_pack_weights(ctypes.byref(cfg), p(blob), blob.size, None, None, None, None, 0, ctypes.byref(count))
+    assert rc == _lib.RN_ERR_INVALID_ARGUMENT and count.value > 0, lib.rn_potgnn_last_error(None)
+    n = count.value
+    packed, mask, writers = np.full(n, 7, dtype=np.float32), np.full(n, 7, dtype=np.uint8), np.full(n, 7, dtype=np.uint8)
+    flags = np.full(1 + shape[3], 7, dtype=np.int32)
+    rc = lib.rn_potgnn_debug_pack_weights(ctypes.byref(cfg), p(blob), blob.size, p(packed), p(mask), p(writers), p(flags), n,
+                                          ctypes.byref(count))
+    assert rc == _lib.RN_OK and count.value == n, lib.rn_potgnn_last_error(None)
+    return packed, mask, writers, flags
+
+
+def _unpack(shape, packed, buffers):
+    lib, cfg, count = _lib.load(), _weight_cfg(shape), ctypes.c_size_t(0)
+    out = np.full(lib.rn_potgnn_weight_count(ctypes.byref(cfg)), 7, dtype=np.float32)
+    rc = lib.rn_potgnn_debug_unpack_weights(ctypes.byref(cfg), ctypes.c_void_p(packed.ctypes.data), packed.size, int(buffers),
+                                            ctypes.c_void_p(out.ctypes.data), out.size, ctypes.byref(count))
+    assert rc == _lib.RN_OK and count.value == out.size, lib.rn_potgnn_last_error(None)
+    return out
+
+
+def _packed_cases():
+    """name -> (shape, blob, packed, mask, writers, flags), packed once for the tests below."""
+    from tests.helpers import weight_layout_cases
+    if not _PACKED_CACHE:
+        for name, shape, blob in weight_layout_cases():
+            _PACKED_CACHE[name] = (shape, blob) + _pack(shape, blob)
+    return _PACKED_CACHE
+
+
+def _digest(packed):
+    import hashlib
+    canon = packed.copy()
+    canon[np.isnan(canon)] = np.nan  # one NaN pattern: a centred copy of an infinite weight is inf - inf
+    return np.frombuffer(hashlib.sha256(canon.tobytes()).digest(), dtype=np.uint8)
+
+
+def test_packed_weights_match_the_parent_commit():
+    """The host-only packer (csrc/weight_layout.hip) writes, bit for bit, the packed blob, the trainable mask and the flags
+    (split-f16 range guard; folded gate per pass) that ``pack_weights``, ``trainable_mask``, ``mfma_f16_range_ok`` and the
+    loop of ``refresh_pass_flags`` in csrc/api.hip produced before they moved out of it.  tests/golden/packed_weights.npz was
+    recorded from that parent commit (b687cbc), not from this code: a throw-away harness (not committed) compiled the
+    parent's function text, unchanged, around a minimal handle and ran it on a CPU over tests/helpers.py
+    ``weight_layout_cases`` (profiles/weight_layout_ab.txt: the commit, the harness, the cases, the file size).  A packed
+    blob of the product shape is 3 MB of incompressible floats, so the file keeps the blob itself for the three narrow
+    shapes and a SHA-256 of its bytes for every case; masks and flags are kept in full."""
+    golden = np.load(_PACKED_GOLDEN)
+    cases = _packed_cases()
+    assert sorted({k.split("/")[0] for k in golden.files}) == sorted(cases)
+    kept = 0
+    for name, (shape, blob, packed, mask, writers, flags) in cases.items():
+        np.testing.assert_array_equal(mask, golden[name + "/mask"], err_msg=name)
+        np.testing.assert_array_equal(flags, golden[name + "/flags"], err_msg=name)
+        if name + "/packed" in golden.files:
+            np.testing.assert_array_equal(packed, golden[name + "/packed"], err_msg=name)
+            kept += 1
+        np.testing.assert_array_equal(_digest(packed), golden[name + "/sha256"], err_msg=name)
+    assert kept == 3
+    # the three flag cases each flip one decision of the tame blob they start from
+    flags = {name: list(c[5]) for name, c in cases.items()}
+    assert flags["flags_base"] == [1, 1, 1] and flags["flags_c2_inf"] == [0, 1, 1]
+    assert flags["flags_readout_bound"] == [0, 1, 1] and flags["flags_small_gamma"] == [1, 1, 0]
+
+
+def test_unpack_inverts_pack():
+    """``unpack(pack(w)) == w`` exactly with the buffers switch on (``rn_potgnn_get_weights``); with it off (a gradient
+    download) the state dict's buffers come back as zeros and every parameter is still exact."""
+    from tests.helpers import STATE_DICT_BUFFERS, state_dict_slices
+    for name, (shape, blob, packed, mask, writers, flags) in _packed_cases().items():
+        np.testing.assert_array_equal(_unpack(shape, packed, True), blob, err_msg=name)
+        want = blob.copy()
+        for key, s in state_dict_slices(*shape).items():
+            if key in STATE_DICT_BUFFERS:
+                want[s] = 0.0
+        assert np.count_nonzero(want != blob) > 0
+        np.testing.assert_array_equal(_unpack(shape, packed, False), want, err_msg=name)
+
+
+def test_packed_layout_is_consistent_with_itself():
+    """Per shape: the mask has one 1 per parameter element of the state dict; no packed entry is reached by two state-dict
+    elements, by two derived ranges, or by both (readout bias 0 is scattered into its padded copy and the plain one is
+    derived from it, so not even that pair overlaps); every state-dict element is stored exactly once; and RN_OK itself
+    says that the three ranges ``rn_potgnn_adam_step`` fetches in one piece are contiguous (``PackedLayout::c3_norm_1``,
+    ``mfma_scales``, ``readout`` throw otherwise)."""
+    from tests.helpers import STATE_DICT_BUFFERS, state_dict_sizes
+    lib = _lib.load()
+    for name, (shape, blob, packed, mask, writers, flags) in _packed_cases().items():
+        count = lib.rn_potgnn_weight_count(ctypes.byref(_weight_cfg(shape)))
+        buffers = sum(n for key, n in state_dict_sizes(*shape) if key in STATE_DICT_BUFFERS)
+        assert count == blob.size and buffers == 3 * shape[2]
+        assert set(np.unique(mask)) <= {0, 1} and int(mask.sum()) == count - buffers, name
+        scattered, derived = writers & 15, writers >> 4
+        assert scattered.max() == 1 and int(scattered.sum()) == count, name
+        assert derived.max() == 1 and not np.any((scattered > 0) & (derived > 0)), name
+        assert np.all(scattered[mask == 1] == 1)
+        # an entry nobody writes is padding (zero), the row of ones, or device-computed (zero on the host)
+        idle = packed[(scattered == 0) & (derived == 0)]
+        assert np.all((idle == 0.0) | (idle == 1.0)), name
+
+
+def test_weight_count_matches_the_reference_state_dict(golden):
+    """``rn_potgnn_weight_count`` -- the sum over the library's table of state-dict tensors -- equals the element count of
+    the state dict the reference model itself wrote into the fixture: every floating-point tensor of it (its one integer
+    entry, BatchNorm's step counter ``num_batches_tracked``, is no weight; the Python layer keeps it)."""
+    name, g = golden
+    hp = g["hp"]
+    k = int((G.atom_type_map(g["atomic_numbers"]) >= 0).sum())
+    cfg = _lib.Config(len(g["atomic_numbers"]), 2, k, int(hp[1]), int(hp[2]), int(hp[3]), -1.0, 0, 0)
+    sd = {key: g[key] for key in g.files if key.startswith("sd/")}
+    assert [key for key, v in sd.items() if v.dtype.kind != "f"] == ["sd/_to_polarizability_embedding.1.num_batches_tracked"]
+    assert _lib.load().rn_potgnn_weight_count(ctypes.byref(cfg)) == sum(v.size for v in sd.values() if v.dtype.kind == "f")
+
+
+def test_debug_weight_entries_reject_what_create_rejects():
+    """Null pointers, a wrong weight count and an unsupported width through ``rn_potgnn_debug_pack_weights`` /
+    ``rn_potgnn_debug_unpack_weights``: the status codes and texts of ``rn_potgnn_create``, from the same code."""
+    lib = _lib.load()
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    cfg, count = _weight_cfg((2, 8, 8, 1)), ctypes.c_size_t(0)
+    n = lib.rn_potgnn_weight_count(ctypes.byref(cfg))
+    w = np.zeros(n, dtype=np.float32)
+    packed, _, _, _ = _pack((2, 8, 8, 1), w)
+    mask, flags, out = np.zeros(packed.size, dtype=np.uint8), np.zeros(2, dtype=np.int32), np.zeros(n, dtype=np.float32)
+
+    def pack(cfg_ref, weights, num):
+        rc = lib.rn_potgnn_debug_pack_weights(cfg_ref, weights, num, p(packed), p(mask), None, p(flags), packed.size,
+                                              ctypes.byref(count))
+        return rc, lib.rn_potgnn_last_error(None)
+
+    def unpack(cfg_ref, blob, num, capacity=out.size):
+        rc = lib.rn_potgnn_debug_unpack_weights(cfg_ref, blob, num, 1, p(out), capacity, ctypes.byref(count))
+        return rc, lib.rn_potgnn_last_error(None)
+
+    assert pack(None, p(w), n) == (_lib.RN_ERR_INVALID_ARGUMENT, b"null argument")
+    assert pack(ctypes.byref(cfg), None, n) == (_lib.RN_ERR_INVALID_ARGUMENT, b"null argument")
+    assert unpack(None, p(packed), packed.size) == (_lib.RN_ERR_INVALID_ARGUMENT, b"null argument")
+    assert unpack(ctypes.byref(cfg), None, packed.size) == (_lib.RN_ERR_INVALID_ARGUMENT, b"null argument")
+    assert lib.rn_potgnn_debug_pack_weights(ctypes.byref(cfg), p(w), n, p(packed), p(mask), None, p(flags), packed.size, None) \
+        == _lib.RN_ERR_INVALID_ARGUMENT
+    text = b"weights has %d floats, expected %d" % (n - 1, n)
+    assert pack(ctypes.byref(cfg), p(w), n - 1) == (_lib.RN_ERR_INVALID_ARGUMENT, text)
+    # the same text comes from rn_potgnn_create
+    ea, eb, ty, lat, h = np.array([0, 1], dtype=np.int32), np.array([1, 0], dtype=np.int32), np.zeros(4, dtype=np.int32), \
+        np.eye(3), ctypes.c_void_p()
+    rc = lib.rn_potgnn_create(ctypes.byref(cfg), p(ea), p(eb), p(ty), p(lat), p(w), n - 1, p(lat), p(lat), ctypes.byref(h))
+    assert rc == _lib.RN_ERR_INVALID_ARGUMENT and lib.rn_potgnn_last_error(None) == text
+    wide = _weight_cfg((2, 200, 8, 1))
+    text = b"embedding sizes above 128 are not supported (Fn=200, Fe=8)"
+    assert pack(ctypes.byref(wide), p(w), n) == (_lib.RN_ERR_UNSUPPORTED, text)
+    assert unpack(ctypes.byref(wide), p(packed), packed.size) == (_lib.RN_ERR_UNSUPPORTED, text)
+    none = _weight_cfg((2, 8, 8, 0))
+    assert pack(ctypes.byref(none), p(w), n) == (_lib.RN_ERR_INVALID_ARGUMENT, b"invalid configuration (non-positive size)")
+    # a packed blob of the wrong length, and the size query of the inverse
+    rc, text = unpack(ctypes.byref(cfg), p(packed), packed.size - 4)
+    assert rc == _lib.RN_ERR_INVALID_ARGUMENT and text == b"packed has %d floats, expected %d" % (packed.size - 4, packed.size)
+    rc, _ = unpack(ctypes.byref(cfg), p(packed), packed.size, capacity=n - 1)
+    assert rc == _lib.RN_ERR_INVALID_ARGUMENT and count.value == n
+    assert unpack(ctypes.byref(cfg), p(packed), packed.size)[0] == _lib.RN_OK
