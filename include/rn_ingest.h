@@ -12,6 +12,13 @@
  * N rows of which the first three whitespace-separated tokens are parsed as Python `float`
  * does; reading ends silently at the first label line that is empty or starts with whitespace
  * (that is how the reference detects the end of the file); anything else is an invalid file.
+ * An addition to the reference: variable-cell runs (VASP ISIF=3) repeat the header before every
+ * configuration.  What stands where a label is expected and is not the end signal is tried as a
+ * whole header (comment, one-token scale, three 3-token vectors, symbols, counts, then a label);
+ * when all of it parses the frame records its own lattice.  The line after a label is a row of
+ * three numbers or another label, never a one-token scale, so no label is taken for a header.  Symbols or
+ * counts that differ from the first header's make that frame an invalid file; anything that does
+ * not parse as a header stays an unrecognised label.
  * Frames are indexed when the file is opened and parsed on demand, in parallel, straight into
  * the caller's (possibly pinned) buffer, so that parsing chunk k+1 overlaps evaluating chunk k.
  */
@@ -55,6 +62,16 @@ int rn_xdatcar_species(const rn_xdatcar *h, int32_t index, char *symbol, int32_t
  */
 int rn_xdatcar_read(rn_xdatcar *h, int64_t first, int64_t count, double *positions, uint8_t *cartesian,
                     int num_threads);
+
+/* 1 when a header was found before a configuration other than the first (a lattice per frame), else 0. */
+int rn_xdatcar_variable_cell(const rn_xdatcar *h);
+
+/*
+ * The lattices of frames [first, first + count) -> lattices[count][9]: row-major 3x3 in Angstrom,
+ * multiplied by the scale factor of the header they come from.  A frame without a header of its own
+ * has the lattice of the last header before it (in a fixed-cell file: the one of rn_xdatcar_info).
+ */
+int rn_xdatcar_read_lattices(const rn_xdatcar *h, int64_t first, int64_t count, double *lattices);
 
 /* Message of the last failure on `h`, in the reference's wording (valid until the next call). */
 const char *rn_xdatcar_last_error(const rn_xdatcar *h);

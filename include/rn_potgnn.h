@@ -188,6 +188,37 @@ int rn_potgnn_forward_device_f64(rn_potgnn *h, const double *d_positions, int64_
                                  void *stream, int synchronize);
 
 /*
+ * Variable-cell evaluation (an addition: the reference's calc_polarizabilities knows one fixed cell): the three entries
+ * above with a lattice PER FRAME, for NPT runs, heating ramps and pressure scans.
+ *   lattices / d_lattices  f64[S*9], row-major, rows = lattice vectors in Angstrom, not modified.
+ * Frame s is evaluated in lattices[s] exactly as PotGNN.forward evaluates sample s in lattice[s] (_gnn.py:603-611: the
+ * minimum-image fractional displacements are mapped to Cartesian with it; the graph topology stays the reference
+ * structure's).  Float32 runs cast the lattices to float32 before any arithmetic, as forward casts its lattice argument;
+ * use_float64 != 0 runs the kernels instantiated for double on the lattices as given.
+ * A NULL lattices pointer is exactly the fixed-cell entry (rn_potgnn_calc_polarizabilities / _f64, _to_device,
+ * rn_potgnn_forward_device / _f64), bit for bit.
+ *
+ * rn_potgnn_calc_polarizabilities_cells: host positions and lattices -> host alpha f64[S*9].  Float32: each piece's
+ * lattices are cast into the page-locked piece that holds its float32 positions and copied with them (36 more bytes a
+ * frame).
+ * rn_potgnn_calc_polarizabilities_cells_to_device: host positions and lattices -> d_alpha device f64[S*9], float32
+ * arithmetic, with every ordering guarantee of rn_potgnn_calc_polarizabilities_to_device; the float32 lattices this call
+ * still reads sit in a device buffer of their own, next to the positions.  Both host arrays may be reused on return.
+ * rn_potgnn_forward_cells_device: device positions and lattices -> d_alpha device f64[S*9]; `stream` and `synchronize`
+ * as for rn_potgnn_forward_device.  d_lattices must stay untouched until the work has finished.
+ *
+ * The host entries check the lattices before any device work: a non-finite entry or a determinant of zero (within
+ * rounding: |det| <= 1e-12 |a| |b| |c|) returns RN_ERR_INVALID_ARGUMENT and the message names the first offending frame.  The device entry cannot look at its
+ * lattices without waiting for the device and does not: a non-finite lattice gives a non-finite alpha for that frame.
+ */
+int rn_potgnn_calc_polarizabilities_cells(rn_potgnn *h, const double *positions, const double *lattices, int64_t S,
+                                          int use_float64, double *alpha);
+int rn_potgnn_calc_polarizabilities_cells_to_device(rn_potgnn *h, const double *positions, const double *lattices,
+                                                    int64_t S, double *d_alpha, void *stream);
+int rn_potgnn_forward_cells_device(rn_potgnn *h, const double *d_positions, const double *d_lattices, int64_t S,
+                                   int use_float64, double *d_alpha, void *stream, int synchronize);
+
+/*
  * Replaces PotGNN.forward for host callers (_gnn.py:617-665, eval mode):
  * host f64 positions -> host f32[S*6] standardised 6-vectors.
  */
@@ -368,12 +399,27 @@ int rn_potgnn_forward_vjp_device(rn_potgnn *h, const double *d_lattices, const i
  * fits in returns RN_ERR_OUT_OF_MEMORY.  A pending train_forward is discarded.  Work is ordered after `stream`, `stream`
  * waits for it and is synchronised once at the end.
  *
+ * rn_potgnn_group_increments_cells_device: the same for a variable cell.  d_lattices device f64[S][9] (row-major, rows =
+ * lattice vectors; NULL: exactly the entry above) -> d_out device f64[S-1][G+1][9].  In a deforming cell alpha(x, L) also
+ * changes with L at fixed fractional positions, so the increments gain a CELL CHANNEL, the last one:
+ *   d_out[t][g] = sum_{i in g} 1/2 (J_i(x_t, L_t) + J_i(x_{t+1}, L_{t+1})) . dx_{t,i}                    g < G
+ *   d_out[t][G] = 1/2 (J_L(x_t, L_t) + J_L(x_{t+1}, L_{t+1})) : (L_{t+1} - L_t),   J_L = d alpha / d L  [3][3] per entry
+ * and sum over all G + 1 channels = alpha(x_{t+1}, L_{t+1}) - alpha(x_t, L_t) + O(3rd order).  Every Jacobian row is
+ * taken at its frame's own lattice; J_L comes out of the same reverse pass (geom_input_bwd_kernel's dlat rows) and is
+ * carried over chunk boundaries with the position rows (6 * 9 more doubles a frame, counted against workspace_limit).
+ * The cell channel is a kernel of its own: one wave per step, a fixed summation order, no atomics; with a constant
+ * lattice it is exactly 0.  Float32 runs evaluate at the lattices cast to float32 and take L_{t+1} - L_t in float64.
+ * The cell counts as a group: 1 <= G <= 15, else RN_ERR_INVALID_ARGUMENT.  The lattices are not inspected (device memory).
+ *
  * rn_potgnn_partial_raman_tensors: host pointers ref_positions f64[N*3], displacements f64[M][N][3] -> raman
  * f64[M][G][9], R[m][g] = 2 sum_{i in g} J_i(ref) . d_{m,i} (the factor 2 of rn_potgnn_raman_tensors_analytic, so that
  * sum_g R[m][g] is that entry's tensor): one float64 Jacobian at the reference positions, then the same contraction kernel.
  */
 int rn_potgnn_group_increments_device(rn_potgnn *h, const double *d_positions, int64_t S, const int32_t *labels, int G,
                                       int use_float64, size_t workspace_limit, double *d_out, void *stream);
+int rn_potgnn_group_increments_cells_device(rn_potgnn *h, const double *d_positions, const double *d_lattices, int64_t S,
+                                            const int32_t *labels, int G, int use_float64, size_t workspace_limit,
+                                            double *d_out, void *stream);
 int rn_potgnn_partial_raman_tensors(rn_potgnn *h, const double *ref_positions, const double *displacements, int64_t M,
                                     const int32_t *labels, int G, double *raman);
 int rn_potgnn_train_backward_inputs(rn_potgnn *h, const float *dvec6, float *grads, double *dpos, double *dlat);

@@ -51,6 +51,9 @@ SIGNATURES = {
     "rn_potgnn_calc_polarizabilities": (C.c_int, [_P, _P, C.c_int64, _P]),
     "rn_potgnn_calc_polarizabilities_f64": (C.c_int, [_P, _P, C.c_int64, _P]),
     "rn_potgnn_calc_polarizabilities_to_device": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "rn_potgnn_calc_polarizabilities_cells": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P]),
+    "rn_potgnn_calc_polarizabilities_cells_to_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
+    "rn_potgnn_forward_cells_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, C.c_int]),
     "rn_potgnn_forward_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int]),
     "rn_potgnn_forward_device_f64": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int]),
     "rn_potgnn_calc_polarizabilities_async": (C.c_int, [_P, _P, C.c_int64, _P]),
@@ -81,6 +84,8 @@ SIGNATURES = {
     "rn_potgnn_train_backward_f64": (C.c_int, [_P, _P, _P]),
     "rn_potgnn_forward_vjp_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int, _P, _P, _P]),
     "rn_potgnn_group_increments_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_size_t, _P, _P]),
+    "rn_potgnn_group_increments_cells_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_size_t, _P,
+                                                          _P]),
     "rn_potgnn_partial_raman_tensors": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, _P]),
     "rn_potgnn_train_backward_inputs": (C.c_int, [_P, _P, _P, _P, _P]),
     "rn_potgnn_train_backward_inputs_device": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -124,6 +129,8 @@ SIGNATURES = {
     "rn_xdatcar_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32)]),
     "rn_xdatcar_species": (C.c_int, [_P, C.c_int32, C.c_char_p, C.POINTER(C.c_int32)]),
     "rn_xdatcar_read": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int]),
+    "rn_xdatcar_variable_cell": (C.c_int, [_P]),
+    "rn_xdatcar_read_lattices": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
     "rn_xdatcar_last_error": (C.c_char_p, [_P]),
     "rn_vasprun_open": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "rn_vasprun_close": (None, [_P]),

@@ -168,6 +168,7 @@ struct rn_potgnn {
     // with kernels that still read them, and the other host entries fill io_pos from the null stream, which does not
     // wait for the handle's non-blocking streams.
     DeviceBuf pos;
+    DeviceBuf lat;  // the float32 lattices of a variable-cell call [S][9], under the same rules
     hipEvent_t caller = nullptr;  // the to-device entry: the caller's stream up to the call
     char *out_pin = nullptr;  // the result (+ the EdgeBlock's time-out word) of the synchronous host entry
     size_t out_bytes = 0;
@@ -202,6 +203,9 @@ struct rn_potgnn {
   std::vector<int32_t> grp_labels;
   int grp_G = 0;
   DeviceBuf grp_csr, grp_jac, grp_disp, grp_out;
+  // variable-cell calls: the lattice rows of the Jacobian [frames][6][9], a trajectory's lattices in the arithmetic of a
+  // float32 run (group increments), the float32 lattices of rn_potgnn_forward_cells_device
+  DeviceBuf grp_jl, grp_lat, cells_lat;
 };
 
 namespace {
@@ -1211,9 +1215,9 @@ bool set_group_labels(rn_potgnn *h, const int32_t *labels, int G) {
 // cotangent rows per frame (their per-edge Cartesian cotangents and Jacobian rows included) of F frames, plus one frame of
 // Jacobian rows carried over, within `limit` bytes; 0 when not even one frame fits.
 template <typename T>
-int group_frames(const rn_potgnn *h, size_t limit) {
+int group_frames(const rn_potgnn *h, size_t limit, bool cells = false) {
   const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges;
-  const size_t rows = 6 * N * 3 * sizeof(double);
+  const size_t rows = (6 * N * 3 + (cells ? 6 * 9 : 0)) * sizeof(double);  // (a variable cell: the lattice rows too)
   const size_t per = (tape_elems(h) + per_structure_elems(h, false) + 6 * reverse_elems(h) + 36) * sizeof(T) +
                      6 * E * 3 * sizeof(double) + rows;
   if (limit < per + rows) return 0;
@@ -1221,9 +1225,11 @@ int group_frames(const rn_potgnn *h, size_t limit) {
 }
 
 // d vec6_c / d x of s frames (device float64 [s][N][3]) -> d_jac device float64 [s][6][N][3]: the taped forward on lane 0
-// and one reverse pass with six one-hot cotangent rows per frame (geom_input_bwd_kernel: every entry written, no atomics)
+// and one reverse pass with six one-hot cotangent rows per frame (geom_input_bwd_kernel: every entry written, no atomics).
+// d_lat (device T [s][9], or null: the reference structure's lattice): each frame is evaluated and differentiated at its
+// own lattice; d_jl (or null) then receives d vec6_c / d L, float64 [s][6][9].
 template <typename T>
-void jacobian_rows(rn_potgnn *h, const double *d_pos, int s, double *d_jac) {
+void jacobian_rows(rn_potgnn *h, const double *d_pos, int s, double *d_jac, const T *d_lat = nullptr, double *d_jl = nullptr) {
   Precision<T> &P = prec<T>(h);
   if (P.eye_frames < s) {
     std::vector<T> eye((size_t)s * 36, (T)0);
@@ -1236,22 +1242,27 @@ void jacobian_rows(rn_potgnn *h, const double *d_pos, int s, double *d_jac) {
   }
   ForwardIO<T> io;
   io.pos = d_pos;
+  io.lat = d_lat;
   ChunkRun<T> c = taped_forward<T>(h, io, s);
   Reverse<T> rv{s, 6, P.eye_seeds.template as<T>(), nullptr, nullptr, false};
   rv.in_dpos = d_jac;
+  rv.in_dlat = d_jl;
   reverse_pass<T>(h, c, rv);
 }
 
 // Trapezoid increments of the S frames d_pos (device float64 [S][N][3]) per atom group -> d_out [S-1][G][9], in chunks
 // of F steps whose Jacobian rows overlap by one frame (the last frame's rows are carried into the next chunk).  Ordered
 // after `user`; `user` waits for the work and is synchronised once at the end.
+// d_lat (device float64 [S][9], or null): a lattice per frame.  The Jacobian rows are then taken at each frame's own
+// lattice (cast to T, as the forward casts it), their lattice rows J_L [6][9] are carried over chunk boundaries with them,
+// and d_out is [S-1][G+1][9]: channel G is the cell's share 1/2 (J_L(t) + J_L(t+1)) : (L_{t+1} - L_t).
 template <typename T>
 void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_t limit, double *d_out,
-                      hipStream_t user) {
+                      hipStream_t user, const double *d_lat = nullptr) {
   ensure_precision<T>(h);
   Precision<T> &P = prec<T>(h);
   const int N = h->g.N;
-  const int F = group_frames<T>(h, limit);
+  const int F = group_frames<T>(h, limit, d_lat != nullptr);
   if (F < 1) throw HipError{hipErrorOutOfMemory, "group_increments: one step does not fit the workspace limit"};
   h->train_S = 0;  // the tape and lane 0 are reused: a pending train_forward is void
   hipStream_t st = P.lanes[0].stream;
@@ -1261,13 +1272,31 @@ void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_
   double *jac = h->grp_jac.as<double>();
   const int *perm = h->grp_csr.as<int>(), *gptr = perm + N;
   const double *sigma = h->d_mean_std.as<double>() + 9;
-  jacobian_rows<T>(h, d_pos, 1, jac);
+  const int out_groups = d_lat ? G + 1 : G;
+  const T *lat = nullptr;  // the lattices as the kernels of this precision read them
+  double *jl = nullptr;
+  if (d_lat) {
+    h->grp_jl.ensure((size_t)(F + 1) * 54 * sizeof(double));
+    jl = h->grp_jl.as<double>();
+    if constexpr (sizeof(T) == 8) {
+      lat = d_lat;
+    } else {
+      h->grp_lat.ensure((size_t)S * 9 * sizeof(T));
+      launch_cast_from_f64<T>(d_lat, h->grp_lat.as<T>(), S * 9, st);
+      lat = h->grp_lat.as<T>();
+    }
+  }
+  jacobian_rows<T>(h, d_pos, 1, jac, lat, jl);
   for (int64_t t0 = 0; t0 < S - 1; t0 += F) {
     const int f = (int)std::min<int64_t>(F, S - 1 - t0);
-    if (t0 > 0) HIP_TRY(hipMemcpyAsync(jac, jac + (int64_t)F * rows, rows * sizeof(double), hipMemcpyDeviceToDevice, st));
-    jacobian_rows<T>(h, d_pos + (t0 + 1) * N * 3, f, jac + rows);
+    if (t0 > 0) {
+      HIP_TRY(hipMemcpyAsync(jac, jac + (int64_t)F * rows, rows * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (jl) HIP_TRY(hipMemcpyAsync(jl, jl + (int64_t)F * 54, 54 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    jacobian_rows<T>(h, d_pos + (t0 + 1) * N * 3, f, jac + rows, lat ? lat + (t0 + 1) * 9 : nullptr, jl ? jl + 54 : nullptr);
     launch_group_increments(jac, rows, d_pos + t0 * N * 3, nullptr, 0.0, f, N, perm, gptr, G, sigma,
-                            d_out + t0 * G * 9, st);
+                            d_out + t0 * out_groups * 9, st, out_groups);
+    if (jl) launch_cell_increments(jl, d_lat + t0 * 9, f, G, out_groups, sigma, d_out + t0 * out_groups * 9, st);
     HIP_TRY(hipGetLastError());
   }
   hand_back(h, user, P.lanes, 1, true);
@@ -1557,6 +1586,30 @@ int check_batch(rn_potgnn *h, int64_t S, std::initializer_list<const void *> nee
     for (const void *p : needed) ok = ok && p;
   if (!ok) return refuse(h, text);
   return S == 0 ? RN_OK : kGo;
+}
+
+// Host lattices [S][9] of a variable-cell call (null: the fixed cell, nothing to check): every entry finite and no
+// determinant of zero -- |det| <= 1e-12 |a| |b| |c|, so that vectors that are dependent up to rounding count as well --
+// before any device work; the text names the first offending frame.
+constexpr double kSingularVolume = 1e-12;  // zero within the rounding of the determinant's nine products (dynamics.py: the same)
+int check_lattices(rn_potgnn *h, const double *lattices, int64_t S) {
+  if (!lattices) return kGo;
+  for (int64_t s = 0; s < S; ++s) {
+    const double *L = lattices + s * 9;
+    for (int i = 0; i < 9; ++i)
+      if (!std::isfinite(L[i])) {
+        set_error(h, "lattice of frame %lld has a non-finite entry", (long long)s);
+        return RN_ERR_INVALID_ARGUMENT;
+      }
+    const double det = L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]);
+    double edges = 1.0;  // |a| |b| |c|: the volume of the box the vectors would span at right angles
+    for (int r = 0; r < 3; ++r) edges *= std::sqrt(L[3 * r] * L[3 * r] + L[3 * r + 1] * L[3 * r + 1] + L[3 * r + 2] * L[3 * r + 2]);
+    if (!(std::fabs(det) > kSingularVolume * edges) || !std::isfinite(det)) {
+      set_error(h, "lattice of frame %lld is singular (its determinant is %g)", (long long)s, det);
+      return RN_ERR_INVALID_ARGUMENT;
+    }
+  }
+  return kGo;
 }
 
 int check_types(rn_potgnn *h, const int32_t *atom_types, int64_t S) {
@@ -1973,8 +2026,11 @@ static void cast_to_float(const double *src, float *dst, size_t n) {
 // page-locked staging, and cross PCIe as float32: half the bytes, no pageable copy, and results bit-identical to a float64
 // upload.  The batch goes through in pieces (below: whole work chunks): this thread casts piece k + 1 while piece k crosses
 // PCIe on the copy stream and the kernels of piece k - 1 run on the handle's streams behind h->exec_stream.
-static void staged_forward(rn_potgnn *h, const double *positions, int64_t S, double *d_alpha, bool sync) {
+// `lattices` (host float64 [S][9], or null: the reference structure's): a lattice per frame, cast like the positions -- each
+// piece's lattices are cast into the same page-locked piece, behind its positions, and copied with them.
+static void staged_forward(rn_potgnn *h, const double *positions, const double *lattices, int64_t S, double *d_alpha, bool sync) {
   const size_t per_frame = (size_t)h->cfg.num_atoms * 3;
+  const size_t pin_frame = per_frame + (lattices ? 9 : 0);  // floats of a frame in a page-locked piece
   const int64_t chunk = std::max<int64_t>(1, h->chunk);
   lazy_stream(h->exec_stream);
   lazy_stream(h->copy_stream);
@@ -1996,19 +2052,26 @@ static void staged_forward(rn_potgnn *h, const double *positions, int64_t S, dou
   for (int b = 0; b < 2; ++b)
     if (hs.copied[b]) HIP_TRY(hipEventSynchronize(hs.copied[b]));
   if (hs.done) HIP_TRY(hipStreamWaitEvent(h->copy_stream, hs.done, 0));
-  if (hs.elems < (size_t)piece * per_frame) {
+  if (hs.elems < (size_t)piece * pin_frame) {
     for (int b = 0; b < 2; ++b) {
       if (hs.pin[b]) (void)hipHostFree(hs.pin[b]);
       hs.pin[b] = nullptr;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&hs.pin[b]), (size_t)piece * per_frame * sizeof(float), hipHostMallocDefault));
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&hs.pin[b]), (size_t)piece * pin_frame * sizeof(float), hipHostMallocDefault));
       lazy_event(hs.copied[b]);
     }
-    hs.elems = (size_t)piece * per_frame;
+    hs.elems = (size_t)piece * pin_frame;
   }
   const size_t pos_bytes = (size_t)S * per_frame * sizeof(float);
   if (hs.pos.bytes < pos_bytes && hs.done) HIP_TRY(hipEventSynchronize(hs.done));  // (growing frees what it may still read)
   hs.pos.ensure(pos_bytes);
   float *d_pos32 = hs.pos.as<float>();
+  float *d_lat32 = nullptr;
+  if (lattices) {
+    const size_t lat_bytes = (size_t)S * 9 * sizeof(float);
+    if (hs.lat.bytes < lat_bytes && hs.done) HIP_TRY(hipEventSynchronize(hs.done));
+    hs.lat.ensure(lat_bytes);
+    d_lat32 = hs.lat.as<float>();
+  }
   int b = 0;
   int64_t first = 0;
   static const bool timing = getenv("RN_POTGNN_HOST_TIMING") && atoi(getenv("RN_POTGNN_HOST_TIMING")) != 0;
@@ -2025,10 +2088,16 @@ static void staged_forward(rn_potgnn *h, const double *positions, int64_t S, dou
     t_cast += now() - t1;
     HIP_TRY(hipMemcpyAsync(d_pos32 + first * per_frame, hs.pin[b], (size_t)n * per_frame * sizeof(float), hipMemcpyHostToDevice,
                            h->copy_stream));
+    if (lattices) {
+      float *pin_lat = hs.pin[b] + (size_t)n * per_frame;
+      for (int64_t i = 0; i < n * 9; ++i) pin_lat[i] = (float)lattices[first * 9 + i];
+      HIP_TRY(hipMemcpyAsync(d_lat32 + first * 9, pin_lat, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
+    }
     HIP_TRY(hipEventRecord(hs.copied[b], h->copy_stream));
     HIP_TRY(hipStreamWaitEvent(h->exec_stream, hs.copied[b], 0));
     ForwardIO<float> io;
     io.pos32 = d_pos32 + first * per_frame;
+    io.lat = lattices ? d_lat32 + first * 9 : nullptr;
     io.alpha = d_alpha + first * 9;
     forward_device<float>(h, io, n, h->exec_stream, sync && first + n >= S);
   }
@@ -2063,16 +2132,15 @@ int rn_potgnn_forward_device_f64(rn_potgnn *h, const double *d_positions, int64_
   });
 }
 
-int rn_potgnn_calc_polarizabilities(rn_potgnn *h, const double *positions, int64_t S,
-                                    double *alpha) {
-  if (const int rc = check_batch(h, S, {positions, alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
+// The float32 host-to-host evaluation behind rn_potgnn_calc_polarizabilities and, with lattices, its _cells form.
+static int host_polarizabilities(rn_potgnn *h, const double *positions, const double *lattices, int64_t S, double *alpha) {
   return guarded(h, [&]() {
     const size_t per_frame = (size_t)h->cfg.num_atoms * 3;
     h->io_alpha.ensure((size_t)S * 9 * sizeof(double));
     lazy_stream(h->exec_stream);
     const int64_t chunk = std::max<int64_t>(1, h->chunk);
     static const bool stage_f32 = !(getenv("RN_POTGNN_HOST_F32") && atoi(getenv("RN_POTGNN_HOST_F32")) == 0);
-    if (!stage_f32) {
+    if (!stage_f32 && !lattices) {
       // (the round-5 form, kept for A/B runs: float64 positions, one blocking copy per work chunk)
       h->io_pos.ensure((size_t)S * per_frame * sizeof(double));
       for (int64_t first = 0; first < S; first += chunk) {
@@ -2090,7 +2158,7 @@ int rn_potgnn_calc_polarizabilities(rn_potgnn *h, const double *positions, int64
     // ONE synchronisation per call: the result and the role-specialised EdgeBlock's time-out word come down into page-locked
     // memory behind the kernels (a blocking hipMemcpy each, after a stream synchronisation of its own, was 30 of the ~450 us
     // of a one-structure call: the reference's unchanged Phonons loop makes 2 M of those, dynamics/_phonon.py:93-106)
-    staged_forward(h, positions, S, h->io_alpha.as<double>(), false);
+    staged_forward(h, positions, lattices, S, h->io_alpha.as<double>(), false);
     auto &hs = h->hstage;
     const size_t out_bytes = (size_t)S * 9 * sizeof(double);
     if (hs.out_bytes < out_bytes + 16) {
@@ -2112,8 +2180,24 @@ int rn_potgnn_calc_polarizabilities(rn_potgnn *h, const double *positions, int64
   });
 }
 
-int rn_potgnn_calc_polarizabilities_to_device(rn_potgnn *h, const double *positions, int64_t S, double *d_alpha, void *stream) {
-  if (const int rc = check_batch(h, S, {positions, d_alpha}, "invalid positions / d_alpha / S"); rc != kGo) return rc;
+int rn_potgnn_calc_polarizabilities(rn_potgnn *h, const double *positions, int64_t S,
+                                    double *alpha) {
+  if (const int rc = check_batch(h, S, {positions, alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
+  return host_polarizabilities(h, positions, nullptr, S, alpha);
+}
+
+static int host_polarizabilities_f64(rn_potgnn *h, const double *positions, const double *lattices, int64_t S, double *alpha);
+
+int rn_potgnn_calc_polarizabilities_cells(rn_potgnn *h, const double *positions, const double *lattices, int64_t S,
+                                          int use_float64, double *alpha) {
+  if (const int rc = check_batch(h, S, {positions, alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
+  if (const int rc = check_lattices(h, lattices, S); rc != kGo) return rc;
+  return use_float64 ? host_polarizabilities_f64(h, positions, lattices, S, alpha)
+                     : host_polarizabilities(h, positions, lattices, S, alpha);
+}
+
+static int host_polarizabilities_to_device(rn_potgnn *h, const double *positions, const double *lattices, int64_t S,
+                                           double *d_alpha, void *stream) {
   return guarded(h, [&]() {
     // The evaluation starts behind what the caller queued on `stream` before the call: an earlier reader of d_alpha (the
     // previous all-gather on the same tensor, the last user of a block torch's caching allocator handed out again).
@@ -2122,18 +2206,67 @@ int rn_potgnn_calc_polarizabilities_to_device(rn_potgnn *h, const double *positi
     lazy_event(hs.caller);
     HIP_TRY(hipEventRecord(hs.caller, (hipStream_t)stream));
     HIP_TRY(hipStreamWaitEvent(h->exec_stream, hs.caller, 0));
-    staged_forward(h, positions, S, d_alpha, false);
+    staged_forward(h, positions, lattices, S, d_alpha, false);
     // the caller's stream continues behind the evaluation (e.g. the RCCL all-gather of ramannoodle_amd.parallel)
     HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, hs.done, 0));
   });
 }
 
+int rn_potgnn_calc_polarizabilities_to_device(rn_potgnn *h, const double *positions, int64_t S, double *d_alpha, void *stream) {
+  if (const int rc = check_batch(h, S, {positions, d_alpha}, "invalid positions / d_alpha / S"); rc != kGo) return rc;
+  return host_polarizabilities_to_device(h, positions, nullptr, S, d_alpha, stream);
+}
+
+int rn_potgnn_calc_polarizabilities_cells_to_device(rn_potgnn *h, const double *positions, const double *lattices, int64_t S,
+                                                    double *d_alpha, void *stream) {
+  if (const int rc = check_batch(h, S, {positions, d_alpha}, "invalid positions / d_alpha / S"); rc != kGo) return rc;
+  if (const int rc = check_lattices(h, lattices, S); rc != kGo) return rc;
+  return host_polarizabilities_to_device(h, positions, lattices, S, d_alpha, stream);
+}
+
+int rn_potgnn_forward_cells_device(rn_potgnn *h, const double *d_positions, const double *d_lattices, int64_t S, int use_float64,
+                                   double *d_alpha, void *stream, int synchronize) {
+  if (const int rc = check_batch(h, S, {d_positions, d_alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
+  if (!d_lattices)
+    return use_float64 ? rn_potgnn_forward_device_f64(h, d_positions, S, d_alpha, stream, synchronize)
+                       : rn_potgnn_forward_device(h, d_positions, S, d_alpha, nullptr, stream, synchronize);
+  return guarded(h, [&]() {
+    hipStream_t user = (hipStream_t)stream;
+    if (use_float64) {
+      sync_host(h);  // the float64 copy of the weights is made from the host master copy
+      ForwardIO<double> io;
+      io.pos = d_positions;
+      io.lat = d_lattices;
+      io.alpha = d_alpha;
+      forward_device<double>(h, io, S, user, synchronize != 0);
+      return;
+    }
+    // float32: the lattices are cast on the caller's stream into a buffer of the handle's, behind the kernels of an
+    // earlier call that may still read it (every entry leaves its lanes' `done` recorded behind its last kernel)
+    ensure_precision<float>(h);
+    for (auto &ln : h->f32.lanes)
+      if (ln.done) HIP_TRY(hipStreamWaitEvent(user, ln.done, 0));
+    h->cells_lat.ensure((size_t)S * 9 * sizeof(float));
+    launch_cast_from_f64<float>(d_lattices, h->cells_lat.as<float>(), S * 9, user);
+    ForwardIO<float> io;
+    io.pos = d_positions;
+    io.lat = h->cells_lat.as<float>();
+    io.alpha = d_alpha;
+    forward_device<float>(h, io, S, user, synchronize != 0);
+  });
+}
+
 int rn_potgnn_calc_polarizabilities_f64(rn_potgnn *h, const double *positions, int64_t S, double *alpha) {
   if (const int rc = check_batch(h, S, {positions, alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
+  return host_polarizabilities_f64(h, positions, nullptr, S, alpha);
+}
+
+static int host_polarizabilities_f64(rn_potgnn *h, const double *positions, const double *lattices, int64_t S, double *alpha) {
   return guarded(h, [&]() {
     sync_host(h);  // the float64 copy of the weights is made from the host master copy
     ForwardIO<double> io;
     io.pos = stage<double>(h->io_pos, positions, (size_t)S * h->cfg.num_atoms * 3 * sizeof(double));
+    io.lat = stage_lattices<double>(h, lattices, S);
     h->io_alpha.ensure((size_t)S * 9 * sizeof(double));
     io.alpha = h->io_alpha.as<double>();
     forward_device<double>(h, io, S, nullptr, true);
@@ -2419,6 +2552,28 @@ int rn_potgnn_group_increments_device(rn_potgnn *h, const double *d_positions, i
     const size_t limit = workspace_limit ? workspace_limit : kTapeBudget;
     with_precision(h, use_float64, [&](auto t) {
       group_increments<decltype(t)>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream);
+    });
+  });
+}
+
+int rn_potgnn_group_increments_cells_device(rn_potgnn *h, const double *d_positions, const double *d_lattices, int64_t S,
+                                            const int32_t *labels, int G, int use_float64, size_t workspace_limit,
+                                            double *d_out, void *stream) {
+  if (!d_lattices) return rn_potgnn_group_increments_device(h, d_positions, S, labels, G, use_float64, workspace_limit, d_out, stream);
+  if (!h) return RN_ERR_INVALID_ARGUMENT;
+  if (S < 2 || !d_positions || !labels || !d_out || G < 1 || G + 1 > kMaxGroups) {
+    set_error(h, "invalid arguments to group_increments_cells_device (S < 2, G outside 1..%d -- the cell is one more channel -- "
+                 "or a null pointer)", kMaxGroups - 1);
+    return RN_ERR_INVALID_ARGUMENT;
+  }
+  return guarded(h, [&]() {
+    if (!set_group_labels(h, labels, G)) {
+      set_error(h, "group_increments_cells_device: a label outside [0, G) or an empty group");
+      throw RnInvalid{};
+    }
+    const size_t limit = workspace_limit ? workspace_limit : kTapeBudget;
+    with_precision(h, use_float64, [&](auto t) {
+      group_increments<decltype(t)>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream, d_lattices);
     });
   });
 }

@@ -41,8 +41,13 @@ bool known_symbol(sv s) {
 struct Frame {
   const char *rows;  // first position row
   uint8_t cartesian;
-  uint8_t bad_label;  // unrecognised coordinate format: reading this frame fails
-  std::string label;  // kept only for bad labels (message)
+  uint8_t bad_label;  // unrecognised coordinate format / a header with other atoms: reading this frame fails
+  int32_t cell;       // index into rn_xdatcar::cells: 0 = the first header's lattice
+  std::string label;  // kept only for bad frames (the message)
+};
+
+struct Cell {
+  double lattice[9];
 };
 
 }  // namespace
@@ -56,6 +61,7 @@ struct rn_xdatcar {
   std::vector<long long> counts;
   int32_t num_atoms = 0;
   std::vector<Frame> frames;
+  std::vector<Cell> cells;  // the first header's lattice, then one per header found before a later configuration
   std::string error;
   ~rn_xdatcar() {
     if (data && size) munmap(const_cast<char *>(data), size);
@@ -65,14 +71,23 @@ struct rn_xdatcar {
 
 namespace {
 
-bool parse_header(rn_xdatcar *h, Cursor &c) {
+// What a header holds: comment, one-token scale, three 3-token vectors, symbols, counts.
+struct Header {
+  double lattice[9];
+  std::vector<std::string> symbols;
+  std::vector<long long> counts;
+  long long total = 0;
+};
+
+// Reads a header at `c`; on failure returns false with the reference's wording in `error`.
+bool read_header(Cursor &c, Header &hd, std::string &error) {
   c.readline();  // comment
   Line line = c.readline();
   double scale = 0;
   {
     sv tok[2];
     if (split(line.text, tok, 2) != 1 || !parse_float(tok[0], scale)) {
-      h->error = "scale factor could not be parsed: " + line.as_python();
+      error = "scale factor could not be parsed: " + line.as_python();
       return false;
     }
   }
@@ -84,65 +99,111 @@ bool parse_header(rn_xdatcar *h, Cursor &c) {
     bool ok = n == 3;
     for (int k = 0; k < n && ok; ++k) ok = parse_float(tok[k], v[k]);
     if (!ok) {  // an invalid token fails float(), fewer than three numbers the shape test
-      h->error = "lattice could not be parsed: " + line.as_python();
+      error = "lattice could not be parsed: " + line.as_python();
       return false;
     }
-    for (int k = 0; k < 3; ++k) h->lattice[3 * r + k] = v[k] * scale;
+    for (int k = 0; k < 3; ++k) hd.lattice[3 * r + k] = v[k] * scale;
   }
   line = c.readline();
   const int nsym = count_tokens(line.text);
   if (nsym == 0) {
-    h->error = "no atom symbols found";
+    error = "no atom symbols found";
     return false;
   }
   std::vector<sv> sym((size_t)nsym);
   split(line.text, sym.data(), nsym);
   for (sv s : sym) {
     if (!known_symbol(s)) {
-      h->error = "unrecognized atom symbol: " + std::string(s);
+      error = "unrecognized atom symbol: " + std::string(s);
       return false;
     }
-    h->symbols.emplace_back(s);
+    hd.symbols.emplace_back(s);
   }
   line = c.readline();
   const int ncnt = count_tokens(line.text);
   if (ncnt != nsym) {
-    h->error = "wrong number of ion counts: " + std::to_string(ncnt) + " != " + std::to_string(nsym);
+    error = "wrong number of ion counts: " + std::to_string(ncnt) + " != " + std::to_string(nsym);
     return false;
   }
   std::vector<sv> cnt((size_t)ncnt);
   split(line.text, cnt.data(), ncnt);
-  long long total = 0;
   for (sv s : cnt) {
     long long v;
     if (!parse_int(s, v)) {
-      h->error = "could not parse counts: " + line.as_python();
+      error = "could not parse counts: " + line.as_python();
       return false;
     }
-    h->counts.push_back(v);
-    total += std::max<long long>(v, 0);  // [symbol] * negative == []
+    hd.counts.push_back(v);
+    hd.total += std::max<long long>(v, 0);  // [symbol] * negative == []
   }
-  if (total > (1LL << 30)) {
-    h->error = "could not parse counts: " + line.as_python();
+  if (hd.total > (1LL << 30)) {
+    error = "could not parse counts: " + line.as_python();
     return false;
   }
-  h->num_atoms = (int32_t)total;
   return true;
 }
 
+bool parse_header(rn_xdatcar *h, Cursor &c) {
+  Header hd;
+  if (!read_header(c, hd, h->error)) return false;
+  std::memcpy(h->lattice, hd.lattice, sizeof(h->lattice));
+  h->symbols = std::move(hd.symbols);
+  h->counts = std::move(hd.counts);
+  h->num_atoms = (int32_t)hd.total;
+  Cell first;
+  std::memcpy(first.lattice, h->lattice, sizeof(first.lattice));
+  h->cells.push_back(first);
+  return true;
+}
+
+// The coordinate label at `c` (after an optional selective-dynamics line): its first letter in lower case, 0 at the end.
+char read_label(Cursor &c, Line &label) {
+  label = c.readline();
+  char first = label.text.empty() ? '\0' : (char)(label.text[0] | 0x20);
+  if (first == 's') {  // selective dynamics: the coordinate label follows
+    label = c.readline();
+    first = label.text.empty() ? '\0' : (char)(label.text[0] | 0x20);
+  }
+  return first;
+}
+
+// Variable-cell runs (VASP ISIF=3) repeat the header before every configuration.  What stands where a label is expected
+// and is not the end-of-trajectory signal is first tried as such a header, label included (its comment line is the
+// system's name and may well start with d, c or s): only when all of it parses does the frame take its own lattice.  A
+// label is never mistaken for one -- the line after it is a row of three numbers or another label, not a one-token
+// scale -- and anything else stays the label, good or bad, it always was.
 void index_frames(rn_xdatcar *h, Cursor &c) {
+  int32_t cell = 0;
   for (;;) {
-    Line label = c.readline();
+    Line label;
+    {
+      Cursor peek = c;
+      label = peek.readline();
+    }
     // empty / whitespace-only / leading whitespace: the reference's end-of-trajectory signal
     if (label.text.empty() || is_space(label.text[0])) return;
-    char first = (char)(label.text[0] | 0x20);
-    if (first == 's') {  // selective dynamics: the coordinate label follows
-      label = c.readline();
-      first = label.text.empty() ? '\0' : (char)(label.text[0] | 0x20);
+    char first = '\0';
+    Cursor again = c;
+    Header hd;
+    std::string ignored;
+    if (read_header(again, hd, ignored) && ((first = read_label(again, label)) == 'c' || first == 'd')) {
+      if (hd.symbols != h->symbols || hd.counts != h->counts) {
+        Frame f{again.p, 0, 1, cell, std::string()};
+        f.label = "atom symbols or counts changed in the header of configuration " + std::to_string(h->frames.size() + 1);
+        h->frames.push_back(std::move(f));
+        return;
+      }
+      Cell own;
+      std::memcpy(own.lattice, hd.lattice, sizeof(own.lattice));
+      h->cells.push_back(own);
+      cell = (int32_t)h->cells.size() - 1;
+      c = again;
+    } else {
+      first = read_label(c, label);
     }
-    Frame f{c.p, (uint8_t)(first == 'c'), (uint8_t)(first != 'c' && first != 'd'), std::string()};
+    Frame f{c.p, (uint8_t)(first == 'c'), (uint8_t)(first != 'c' && first != 'd'), cell, std::string()};
     if (f.bad_label) {
-      f.label = label.as_python();
+      f.label = "unrecognized coordinate format: " + label.as_python();
       h->frames.push_back(std::move(f));
       return;  // the reference raises here
     }
@@ -155,7 +216,7 @@ void index_frames(rn_xdatcar *h, Cursor &c) {
 // parses one frame; on failure fills `err` (reference wording) and returns false
 bool parse_frame(const rn_xdatcar *h, const Frame &f, double *out, std::string &err) {
   if (f.bad_label) {
-    err = "unrecognized coordinate format: " + f.label;
+    err = f.label;
     return false;
   }
   Cursor c{f.rows, h->data + h->size};
@@ -287,6 +348,16 @@ int rn_xdatcar_read(rn_xdatcar *h, int64_t first, int64_t count, double *positio
       if (bad_at[(size_t)t] == bad) h->error = errors[(size_t)t];
     return RN_INGEST_INVALID_FILE;
   }
+  return RN_INGEST_OK;
+}
+
+int rn_xdatcar_variable_cell(const rn_xdatcar *h) { return h && h->cells.size() > 1 ? 1 : 0; }
+
+int rn_xdatcar_read_lattices(const rn_xdatcar *h, int64_t first, int64_t count, double *lattices) {
+  if (!h || first < 0 || count < 0 || first + count > (int64_t)h->frames.size() || (count > 0 && !lattices))
+    return RN_INGEST_INVALID_ARGUMENT;
+  for (int64_t k = 0; k < count; ++k)
+    std::memcpy(lattices + 9 * k, h->cells[(size_t)h->frames[(size_t)(first + k)].cell].lattice, 9 * sizeof(double));
   return RN_INGEST_OK;
 }
 

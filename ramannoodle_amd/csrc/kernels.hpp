@@ -289,10 +289,16 @@ constexpr int kMaxGroups = 16;
 // out[t][g][9] = sigma (.) sum_{i in g} 1/2 (J(t)_i + J(t+1)_i) . dx_{t,i}, J float64 [.][6][N][3] frames `jac_stride`
 // doubles apart (0: one Jacobian for every t); dx = the minimum image of pos[t+1] - pos[t] (pos float64 [steps+1][N][3])
 // or, with `disp` float64 [steps][N][3], disp_scale * disp[t].  perm [N] / gptr [G+1]: the atoms of group g are
-// perm[gptr[g] .. gptr[g+1]).  Written once per entry, no atomics.
+// perm[gptr[g] .. gptr[g+1]).  Written once per entry, no atomics.  out_groups > G: the rows of `out` hold that many
+// channels ([t][out_groups][9]) and the kernel fills the first G (0: G).
 void launch_group_increments(const double *jac, int64_t jac_stride, const double *pos, const double *disp,
                              double disp_scale, int64_t steps, int N, const int *perm, const int *gptr, int G,
-                             const double *sigma, double *out, hipStream_t st);
+                             const double *sigma, double *out, hipStream_t st, int out_groups = 0);
+// The cell's share of a variable-cell step (kernels_group.hip: cell_increment_kernel): for t < `steps`,
+// out[t][channel][9] = sigma (.) 1/2 (J_L(t) + J_L(t+1)) : (lat[t+1] - lat[t]), jl float64 [steps+1][6][9] (the dlat rows of
+// launch_geom_input_bwd for six one-hot cotangents per frame), lat float64 [steps+1][9]; `out` as above.
+void launch_cell_increments(const double *jl, const double *lat, int64_t steps, int channel, int out_groups,
+                            const double *sigma, double *out, hipStream_t st);
 
 // Fused EdgeBlock (kernels_fused.hip): projections + triplet aggregation in one launch.
 // Fused EdgeBlock (kernels_fused.hip): float32, FnP == FeP == 64.  Two workgroups per CU

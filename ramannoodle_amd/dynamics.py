@@ -14,6 +14,24 @@ from ramannoodle_amd.spectrum import MDRamanSpectrum, PhononRamanSpectrum
 from ramannoodle_amd.structure import apply_pbc
 
 
+SINGULAR_VOLUME = 1e-12  # |det L| <= this times |a| |b| |c|: a singular lattice
+
+
+def verify_lattices(lattice_ts, frames: int) -> NDArray[np.float64]:
+    """The lattices of a variable-cell trajectory as float64 ``(frames,3,3)`` (rows = lattice vectors in Angstrom):
+    ``ValueError`` on another shape, a non-finite entry or a singular lattice, naming the first offending frame."""
+    verify_ndarray_shape("lattice_ts", lattice_ts, (frames, 3, 3))
+    lattices = np.array(lattice_ts, dtype=np.float64)
+    bad = np.nonzero(~np.isfinite(lattices).all(axis=(1, 2)))[0]
+    if bad.size:
+        raise ValueError(f"lattice_ts[{bad[0]}] has a non-finite entry")
+    # a determinant of zero, within the rounding of its products (the library's rule: csrc/api.hip, check_lattices)
+    bad = np.nonzero(~(np.abs(np.linalg.det(lattices)) > SINGULAR_VOLUME * np.linalg.norm(lattices, axis=2).prod(axis=1)))[0]
+    if bad.size:
+        raise ValueError(f"lattice_ts[{bad[0]}] is singular")
+    return lattices
+
+
 class Phonons(Dynamics):
     """Harmonic lattice vibrations: wavenumbers ``(M,)`` and fractional displacements
     ``(M,N,3)`` about ``ref_positions`` ``(N,3)`` (``dynamics/_phonon.py:13-108``)."""
@@ -84,11 +102,27 @@ class Phonons(Dynamics):
         return PartialPhononRamanSpectrum(self._wavenumbers, tensors)
 
 
+def _cells(lattice_ts, device=None) -> dict:
+    """The ``lattices`` keyword of a variable-cell run for the model's entries (on ``device``: as a tensor); nothing for
+    a fixed cell, so that models without the keyword keep working."""
+    if lattice_ts is None:
+        return {}
+    if device is None:
+        return {"lattices": lattice_ts}
+    import torch
+    return {"lattices": torch.tensor(lattice_ts, dtype=torch.float64, device=device)}
+
+
 class Trajectory(Dynamics, Sequence):
     """MD trajectory: fractional positions ``(S,N,3)`` (wrapped into the cell on
-    construction) and a timestep in fs (``dynamics/_trajectory.py:16-109``)."""
+    construction) and a timestep in fs (``dynamics/_trajectory.py:16-109``).
 
-    def __init__(self, positions_ts, timestep: float) -> None:
+    ``lattice_ts`` (an addition; the reference knows one fixed cell): ``(S,3,3)``, the lattice of every frame of a
+    variable-cell run (NPT, a heating ramp, a pressure scan), rows = lattice vectors in Angstrom, finite and
+    non-singular.  The spectra then evaluate every frame in its own cell, and the partial spectrum has one more
+    group, the last: the cell (``PotGNN.calc_group_increments_device``).  ``None``: the model's reference cell."""
+
+    def __init__(self, positions_ts, timestep: float, lattice_ts=None) -> None:
         verify_ndarray_shape("positions_ts", positions_ts, (None, None, 3))
         try:
             timestep = float(timestep)
@@ -98,10 +132,16 @@ class Trajectory(Dynamics, Sequence):
             raise ValueError("timestep must be positive")
         self._positions_ts = apply_pbc(positions_ts)
         self._timestep = timestep
+        self._lattice_ts = None if lattice_ts is None else verify_lattices(lattice_ts, len(self._positions_ts))
 
     @property
     def positions_ts(self):
         return self._positions_ts.copy()
+
+    @property
+    def lattice_ts(self):
+        """The lattice of every frame ``(S,3,3)`` (a copy), or ``None`` for a fixed cell."""
+        return None if self._lattice_ts is None else self._lattice_ts.copy()
 
     @property
     def timestep(self) -> float:
@@ -123,8 +163,9 @@ class Trajectory(Dynamics, Sequence):
                                      (None, polarizability_model.num_atoms, 3))
                 positions = torch.tensor(self._positions_ts, dtype=torch.float64,
                                          device=f"cuda:{polarizability_model.device_index}")
-                return DeviceMDRamanSpectrum(evaluate(positions), self._timestep)
-            polarizability_ts = polarizability_model.calc_polarizabilities(self._positions_ts)
+                return DeviceMDRamanSpectrum(evaluate(positions, **_cells(self._lattice_ts, positions.device)),
+                                             self._timestep)
+            polarizability_ts = polarizability_model.calc_polarizabilities(self._positions_ts, **_cells(self._lattice_ts))
         except ValueError as exc:
             raise ValueError("polarizability_model and trajectory are incompatible") from exc
         return MDRamanSpectrum(polarizability_ts, self._timestep)
@@ -145,7 +186,7 @@ class Trajectory(Dynamics, Sequence):
             verify_ndarray_shape("positions_ts", self._positions_ts, (None, polarizability_model.num_atoms, 3))
             positions = torch.tensor(self._positions_ts, dtype=torch.float64,
                                      device=f"cuda:{polarizability_model.device_index}")
-            result = increments(positions, groups)
+            result = increments(positions, groups, **_cells(self._lattice_ts, positions.device))
         except ValueError as exc:
             raise ValueError(f"polarizability_model and trajectory are incompatible: {exc}") from exc
         if on_device:
@@ -167,7 +208,9 @@ class Trajectory(Dynamics, Sequence):
 class TrajectoryEnsemble:
     """Several MD trajectories of one system (an addition): independent runs whose spectra are averaged, for example
     NVE branches started from NVT snapshots.  ``trajectories``: a sequence of ``Trajectory`` sharing a timestep and an
-    atom count.  All frames of all runs go through the model in one batch; the spectra never join a run to the next."""
+    atom count.  All frames of all runs go through the model in one batch; the spectra never join a run to the next.
+    Either every run has a lattice per frame (``Trajectory.lattice_ts``) or none has; the lattices are joined as the
+    frames are."""
 
     def __init__(self, trajectories) -> None:
         trajectories = list(trajectories)
@@ -186,6 +229,12 @@ class TrajectoryEnsemble:
         self._timestep = timesteps[0]
         self._run_lengths = [len(trajectory) for trajectory in trajectories]
         self._positions_ts = np.concatenate([trajectory._positions_ts for trajectory in trajectories], axis=0)
+        with_cells = [trajectory._lattice_ts is not None for trajectory in trajectories]
+        if any(with_cells) and not all(with_cells):
+            raise ValueError("either every trajectory has a lattice per frame or none has: trajectories "
+                             f"{[i for i, w in enumerate(with_cells) if not w]} have none")
+        self._lattice_ts = (np.concatenate([trajectory._lattice_ts for trajectory in trajectories], axis=0)
+                            if all(with_cells) else None)
 
     @property
     def trajectories(self):
@@ -221,8 +270,9 @@ class TrajectoryEnsemble:
                                      (None, polarizability_model.num_atoms, 3))
                 positions = torch.tensor(self._positions_ts, dtype=torch.float64,
                                          device=f"cuda:{polarizability_model.device_index}")
-                return DeviceMDRamanEnsemble(evaluate(positions), self._timestep, self._run_lengths)
-            polarizability_ts = polarizability_model.calc_polarizabilities(self._positions_ts)
+                return DeviceMDRamanEnsemble(evaluate(positions, **_cells(self._lattice_ts, positions.device)),
+                                             self._timestep, self._run_lengths)
+            polarizability_ts = polarizability_model.calc_polarizabilities(self._positions_ts, **_cells(self._lattice_ts))
         except ValueError as exc:
             raise ValueError("polarizability_model and trajectory are incompatible") from exc
         return MDRamanEnsemble(self._split(polarizability_ts), self._timestep)
@@ -244,7 +294,7 @@ class TrajectoryEnsemble:
             verify_ndarray_shape("positions_ts", self._positions_ts, (None, polarizability_model.num_atoms, 3))
             positions = torch.tensor(self._positions_ts, dtype=torch.float64,
                                      device=f"cuda:{polarizability_model.device_index}")
-            result = increments(positions, groups)
+            result = increments(positions, groups, **_cells(self._lattice_ts, positions.device))
         except ValueError as exc:
             raise ValueError(f"polarizability_model and trajectory are incompatible: {exc}") from exc
         if on_device:

@@ -52,7 +52,11 @@ def stream_polarizabilities(model, reader, chunk_frames: int = 2000) -> np.ndarr
     bounds = [(lo, min(lo + chunk_frames, total)) for lo in range(0, total, chunk_frames)]
     # the pipelined entry evaluates in float32; under torch.set_default_dtype(float64) the evaluation follows the
     # default dtype as calc_polarizabilities does (_gnn.py:705-710), block by block through the synchronous call
-    pipelined = hasattr(model, "calc_polarizabilities_async") and torch.get_default_dtype() != torch.float64
+    # (a variable-cell file: the pipelined entry has no lattices, so its blocks go through the synchronous call as well,
+    #  each with the lattices of its frames)
+    cells = bool(getattr(reader, "variable_cell", False))
+    pipelined = (hasattr(model, "calc_polarizabilities_async") and torch.get_default_dtype() != torch.float64
+                 and not cells)
     pinned = []
     if pipelined:
         device = model.device_index
@@ -94,6 +98,8 @@ def stream_polarizabilities(model, reader, chunk_frames: int = 2000) -> np.ndarr
             block = buffers[k % len(buffers)][: hi - lo]
             if pipelined:
                 model.calc_polarizabilities_async(block, result[lo:hi])
+            elif cells:
+                result[lo:hi] = model.calc_polarizabilities(block, lattices=reader.read_lattices(lo, hi - lo))
             else:
                 result[lo:hi] = model.calc_polarizabilities(block)
             if worker is not None:

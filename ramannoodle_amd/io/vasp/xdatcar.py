@@ -50,6 +50,8 @@ class XdatcarReader:
         self._lib.rn_xdatcar_info(handle, C.byref(frames), C.byref(atoms), C.c_void_p(lattice.ctypes.data),
                                   C.byref(species))
         self.num_frames, self.num_atoms, self.lattice = frames.value, atoms.value, lattice
+        # a header before a later configuration (VASP ISIF=3): every frame has a lattice of its own
+        self.variable_cell = bool(self._lib.rn_xdatcar_variable_cell(handle))
         self.atomic_symbols: list[str] = []
         for k in range(species.value):
             symbol, count = C.create_string_buffer(8), C.c_int32()
@@ -60,7 +62,8 @@ class XdatcarReader:
              num_threads: int = 0) -> NDArray[np.float64]:
         """Frames ``[first, first+count)`` as ``float64 (count, N, 3)`` fractional positions,
         exactly as the reference returns them (Cartesian frames converted with
-        ``positions @ inv(lattice)``, ``poscar.py:119-120``; no wrapping)."""
+        ``positions @ inv(lattice)``, ``poscar.py:119-120``; no wrapping).  In a variable-cell file a
+        Cartesian frame is converted with its own lattice."""
         count = self.num_frames - first if count is None else count
         shape = (count, self.num_atoms, 3)
         if out is None:
@@ -75,10 +78,25 @@ class XdatcarReader:
         if rc != 0:
             raise ValueError(f"rn_xdatcar_read failed with status {rc} (frames {first}..{first + count})")
         if cartesian[:count].any():
+            if self.variable_cell:
+                lattices = self.read_lattices(first, count)
+                for k in np.nonzero(cartesian[:count])[0]:
+                    out[k] = out[k] @ np.linalg.inv(lattices[k])
+                return out
             inverse = np.linalg.inv(self.lattice)
             for k in np.nonzero(cartesian[:count])[0]:
                 out[k] = out[k] @ inverse
         return out
+
+    def read_lattices(self, first: int = 0, count: int | None = None) -> NDArray[np.float64]:
+        """The lattices of frames ``[first, first+count)`` as ``float64 (count, 3, 3)``, rows = lattice vectors in
+        Angstrom, scale factor applied (``rn_xdatcar_read_lattices``).  A fixed-cell file repeats ``self.lattice``."""
+        count = self.num_frames - first if count is None else count
+        lattices = np.empty((max(count, 0), 3, 3), dtype=np.float64)
+        rc = self._lib.rn_xdatcar_read_lattices(self._handle, first, count, C.c_void_p(lattices.ctypes.data))
+        if rc != 0:
+            raise ValueError(f"rn_xdatcar_read_lattices failed with status {rc} (frames {first}..{first + count})")
+        return lattices
 
     def close(self) -> None:
         if getattr(self, "_handle", None):
@@ -106,9 +124,13 @@ def read_positions_ts(filepath) -> NDArray[np.float64]:
 
 
 def read_trajectory(filepath, timestep: float):
-    """``Trajectory`` from an XDATCAR file; the timestep (fs) is not in the file."""
+    """``Trajectory`` from an XDATCAR file; the timestep (fs) is not in the file.  A variable-cell file (a header before
+    every configuration) gives a ``Trajectory`` with ``lattice_ts``."""
     from ramannoodle_amd.dynamics import Trajectory
-    return Trajectory(read_positions_ts(filepath), timestep)
+    with XdatcarReader(filepath) as reader:
+        if reader.num_frames == 0 or not reader.variable_cell:
+            return Trajectory(read_positions_ts(filepath), timestep)
+        return Trajectory(reader.read(), timestep, reader.read_lattices())
 
 
 def stream_polarizabilities(model, filepath, chunk_frames: int = 2000) -> NDArray[np.float64]:
@@ -116,7 +138,7 @@ def stream_polarizabilities(model, filepath, chunk_frames: int = 2000) -> NDArra
     in memory: a worker thread parses block k+1 (the native reader releases the GIL) while the
     device evaluates block k; with the device model the blocks go through page-locked buffers and
     the pipelined entry point (``ramannoodle_amd.io._stream``).  Positions are wrapped into the
-    cell as ``Trajectory`` does."""
+    cell as ``Trajectory`` does.  The blocks of a variable-cell file are evaluated with their own lattices."""
     from ramannoodle_amd.io._stream import stream_polarizabilities as _stream
     with XdatcarReader(filepath) as reader:
         return _stream(model, reader, chunk_frames)

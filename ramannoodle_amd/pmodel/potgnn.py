@@ -373,10 +373,34 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         verify_ndarray_shape("positions_batch", positions_batch, (None, self.num_atoms, 3))
         return np.ascontiguousarray(positions_batch, dtype=np.float64)
 
+    def _check_lattices(self, lattices, frames: int) -> np.ndarray:
+        """Host lattices of a variable-cell call: ``(S,3,3)``, one per frame, as contiguous float64.  Their values (finite,
+        non-singular) are checked by the library before any device work."""
+        verify_ndarray_shape("lattices", lattices, (frames, 3, 3))
+        return np.ascontiguousarray(lattices, dtype=np.float64)
+
+    def _check_device_lattices(self, lattices, positions: torch.Tensor) -> torch.Tensor:
+        """Device lattices of a variable-cell call: a contiguous float64 ``(S,3,3)`` tensor next to the positions.  Their
+        values are not inspected (that would wait for the device): a non-finite lattice gives a non-finite result."""
+        if not (isinstance(lattices, torch.Tensor) and lattices.is_cuda and lattices.dtype == torch.float64
+                and lattices.is_contiguous()):
+            raise ValueError("lattices must be a contiguous float64 device tensor")
+        if lattices.device != positions.device:
+            raise ValueError(f"lattices live on {lattices.device}, the positions on {positions.device}")
+        if tuple(lattices.shape) != (positions.shape[0], 3, 3):
+            raise ValueError(f"lattices has wrong shape: {tuple(lattices.shape)} != ({positions.shape[0]},3,3)")
+        return lattices
+
     def calc_polarizabilities(self, positions_batch: NDArray[np.float64], dtype=None,
-                              progress: bool = False) -> NDArray[np.float64]:
+                              progress: bool = False, lattices=None) -> NDArray[np.float64]:
         """Polarizabilities ``(S,3,3)`` for fractional positions ``(S,N,3)``
         (``_gnn.py:667-721``): host arrays in, host arrays out.
+
+        ``lattices`` (an addition; ``None`` = the reference structure's cell for every frame, the reference's behaviour):
+        ``(S,3,3)``, one lattice per frame, rows = lattice vectors in Angstrom -- a variable-cell trajectory
+        (``rn_potgnn_calc_polarizabilities_cells``).  Frame ``s`` is evaluated in ``lattices[s]`` as ``forward`` evaluates
+        a sample in its lattice; the graph topology stays the reference structure's.  A non-finite or singular lattice
+        raises ``ValueError`` naming the frame.
 
         ``progress=True`` shows the reference's progress bar (``tqdm``, unit " configs", ``_gnn.py:692,714-717``): the
         batch is then evaluated in blocks through the pipelined entry so that the bar moves; off by default -- one call
@@ -387,10 +411,31 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         caller ran ``torch.set_default_dtype(torch.float64)``; ``torch.float64`` / ``numpy.float64``
         selects the kernels instantiated for ``double`` (``rn_potgnn_calc_polarizabilities_f64``)."""
         pos = self._check_positions(positions_batch)
+        lat = None if lattices is None else self._check_lattices(lattices, pos.shape[0])
         if self.training:  # as the reference does (_gnn.py:686); not walked again per call (the reference's unchanged
             self.eval()    # Phonons loop makes 2 M calls of one structure each, dynamics/_phonon.py:93-106)
         out = np.empty((pos.shape[0], 3, 3), dtype=np.float64)
         handle = self._ensure_handle()
+        if lat is not None:
+            cells = _lib.load().rn_potgnn_calc_polarizabilities_cells
+            use_float64 = int(_wants_float64(dtype))
+            block = pos.shape[0]
+            if progress and pos.shape[0] > 0:
+                from tqdm import tqdm
+                block = max(1, min(pos.shape[0], 2000))
+                progress_bar = tqdm(total=pos.shape[0], unit=" configs")
+            try:
+                for first in range(0, pos.shape[0], max(block, 1)):  # (each block with its own lattices)
+                    n = min(block, pos.shape[0] - first)
+                    rc = cells(handle, _ptr(pos[first:first + n]), _ptr(lat[first:first + n]), n, use_float64,
+                               _ptr(out[first:first + n]))
+                    _lib.check(rc, handle, "rn_potgnn_calc_polarizabilities_cells")
+                    if progress:
+                        progress_bar.update(n)
+            finally:
+                if progress and pos.shape[0] > 0:
+                    progress_bar.close()
+            return out
         if progress and pos.shape[0] > 0:
             from tqdm import tqdm
             entry = (_lib.load().rn_potgnn_calc_polarizabilities_f64 if _wants_float64(dtype)
@@ -441,14 +486,17 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
             _lib.check(rc, self._handle, "rn_potgnn_wait")
 
     def calc_polarizabilities_to_device(self, positions_batch: NDArray[np.float64],
-                                        out: torch.Tensor | None = None) -> torch.Tensor:
+                                        out: torch.Tensor | None = None, lattices=None) -> torch.Tensor:
         """``calc_polarizabilities`` with the result left in HBM (``rn_potgnn_calc_polarizabilities_to_device``): host
         ``float64[S,N,3]`` in, device ``float64[S,3,3]`` out, float32 arithmetic.  The upload is pipelined with the
         kernels (positions cast to float32 while staged: bit-identical results, half the PCIe bytes); torch's current
         stream is ordered behind the evaluation, so the tensor can go straight into a collective, and the evaluation
         behind what was queued on that stream before the call (an earlier reader of ``out``).  ``out``, when given, must
-        be a contiguous ``float64[S,3,3]`` tensor on the model's device."""
+        be a contiguous ``float64[S,3,3]`` tensor on the model's device.  ``lattices``: host ``(S,3,3)``, one lattice per
+        frame as in ``calc_polarizabilities`` (``rn_potgnn_calc_polarizabilities_cells_to_device``); they are staged and
+        ordered like the positions."""
         pos = self._check_positions(positions_batch)
+        lat = None if lattices is None else self._check_lattices(lattices, pos.shape[0])
         self.eval()
         device = torch.device("cuda", self.device_index)
         if out is None:
@@ -457,18 +505,25 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
             _check_out(out, pos.shape[0], self.device_index)
         handle = self._ensure_handle()
         stream = torch.cuda.current_stream(device).cuda_stream
+        if lat is not None:
+            rc = _lib.load().rn_potgnn_calc_polarizabilities_cells_to_device(
+                handle, _ptr(pos), _ptr(lat), pos.shape[0], C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+            _lib.check(rc, handle, "rn_potgnn_calc_polarizabilities_cells_to_device")
+            return out
         rc = _lib.load().rn_potgnn_calc_polarizabilities_to_device(handle, _ptr(pos), pos.shape[0],
                                                                    C.c_void_p(out.data_ptr()), C.c_void_p(stream))
         _lib.check(rc, handle, "rn_potgnn_calc_polarizabilities_to_device")
         return out
 
     def calc_polarizabilities_device(self, positions: torch.Tensor, out: torch.Tensor | None = None,
-                                     synchronize: bool = False, dtype=None) -> torch.Tensor:
+                                     synchronize: bool = False, dtype=None, lattices=None) -> torch.Tensor:
         """Same computation on a device-resident ``float64[S,N,3]`` tensor; returns a device
         ``float64[S,3,3]`` tensor.  Work is enqueued on torch's current stream.  ``dtype`` is the
         arithmetic of the evaluation, resolved exactly as ``calc_polarizabilities`` does: ``None`` follows
         ``torch.get_default_dtype()`` (``_gnn.py:705-710``), ``torch.float64`` runs the kernels instantiated
-        for ``double`` -- so the host, gloo and RCCL paths of ``ramannoodle_amd.parallel`` agree."""
+        for ``double`` -- so the host, gloo and RCCL paths of ``ramannoodle_amd.parallel`` agree.  ``lattices``: a
+        contiguous CUDA float64 ``(S,3,3)`` tensor, one lattice per frame (``rn_potgnn_forward_cells_device``); it must
+        stay untouched until the work has finished, and its values are not inspected."""
         if not (positions.is_cuda and positions.dtype == torch.float64 and positions.is_contiguous()):
             raise ValueError("positions must be a contiguous float64 device tensor")
         if positions.dim() != 3 or tuple(positions.shape[1:]) != (self.num_atoms, 3):
@@ -479,8 +534,16 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
             out = torch.empty((s, 3, 3), dtype=torch.float64, device=positions.device)
         else:
             _check_out(out, s, positions.device.index)
+        if lattices is not None:
+            lattices = self._check_device_lattices(lattices, positions)
         handle = self._ensure_handle()
         stream = torch.cuda.current_stream(positions.device).cuda_stream
+        if lattices is not None:
+            rc = _lib.load().rn_potgnn_forward_cells_device(
+                handle, C.c_void_p(positions.data_ptr()), C.c_void_p(lattices.data_ptr()), s,
+                int(_wants_float64(dtype)), C.c_void_p(out.data_ptr()), C.c_void_p(stream), int(synchronize))
+            _lib.check(rc, handle, "rn_potgnn_forward_cells_device")
+            return out
         if _wants_float64(dtype):
             rc = _lib.load().rn_potgnn_forward_device_f64(
                 handle, C.c_void_p(positions.data_ptr()), s, C.c_void_p(out.data_ptr()), C.c_void_p(stream),
@@ -941,7 +1004,8 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         return group_labels(groups, self._ref_structure.atomic_numbers)
 
     def calc_group_increments_device(self, positions: torch.Tensor, groups, float64: bool = True,
-                                     out: torch.Tensor | None = None, workspace_limit: int = 0) -> torch.Tensor:
+                                     out: torch.Tensor | None = None, workspace_limit: int = 0,
+                                     lattices=None) -> torch.Tensor:
         """Per-group trapezoid increments of the polarizability along a trajectory
         (``rn_potgnn_group_increments_device``): a contiguous float64 CUDA tensor ``(S,N,3)`` of fractional, wrapped
         positions in, a float64 CUDA tensor ``(S-1,G,3,3)`` out,
@@ -949,7 +1013,15 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         mode, ``float64`` or float32 arithmetic) and ``dx`` the minimum image of ``x_{t+1} - x_t``.  ``sum_g out[t]`` is
         ``alpha(x_{t+1}) - alpha(x_t)`` up to the trapezoid error.  ``groups``: ``spectrum.group_labels``.  Ordered on
         torch's current stream.  ``out``, when given, must be a contiguous float64 ``(S-1,G,3,3)`` tensor on the
-        positions' device."""
+        positions' device.
+
+        ``lattices`` (a contiguous CUDA float64 ``(S,3,3)`` tensor, one lattice per frame;
+        ``rn_potgnn_group_increments_cells_device``): a variable cell.  Every ``J`` is then taken at its frame's own lattice
+        and the result is ``(S-1,G+1,3,3)``: **the last group is the cell**,
+        ``out[t,G] = 1/2 (J_L(t) + J_L(t+1)) : (L_{t+1} - L_t)`` with ``J_L = d alpha / d L``, the change of the
+        polarizability because the cell deforms at fixed fractional positions.  The sum over all ``G+1`` channels is
+        ``alpha(t+1) - alpha(t)`` up to the trapezoid error; without the cell channel it is not.  The cell counts as a
+        group: more than 15 atom groups together with lattices raise ``ValueError``."""
         if not (isinstance(positions, torch.Tensor) and positions.is_cuda and positions.dtype == torch.float64
                 and positions.is_contiguous()):
             raise ValueError("positions must be a contiguous float64 device tensor")
@@ -959,7 +1031,13 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         if s < 2:
             raise ValueError(f"group increments need at least two frames, not {s}")
         labels, num_groups = self._group_labels(groups)
-        shape = (s - 1, num_groups, 3, 3)
+        if lattices is not None:
+            lattices = self._check_device_lattices(lattices, positions)
+            from ramannoodle_amd.spectrum import MAX_GROUPS
+            if num_groups + 1 > MAX_GROUPS:
+                raise ValueError(f"{num_groups} atom groups and the cell are more than {MAX_GROUPS} channels: with lattices "
+                                 f"at most {MAX_GROUPS - 1} atom groups")
+        shape = (s - 1, num_groups + (lattices is not None), 3, 3)
         if out is None:
             out = torch.empty(shape, dtype=torch.float64, device=positions.device)
         else:
@@ -976,18 +1054,29 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         self.eval()
         handle = self._ensure_handle()
         stream = torch.cuda.current_stream(positions.device).cuda_stream
+        if lattices is not None:
+            rc = _lib.load().rn_potgnn_group_increments_cells_device(
+                handle, C.c_void_p(positions.data_ptr()), C.c_void_p(lattices.data_ptr()), s, _ptr(labels), num_groups,
+                int(float64), int(workspace_limit), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+            _lib.check(rc, handle, "rn_potgnn_group_increments_cells_device")
+            return out
         rc = _lib.load().rn_potgnn_group_increments_device(
             handle, C.c_void_p(positions.data_ptr()), s, _ptr(labels), num_groups, int(float64), int(workspace_limit),
             C.c_void_p(out.data_ptr()), C.c_void_p(stream))
         _lib.check(rc, handle, "rn_potgnn_group_increments_device")
         return out
 
-    def calc_group_increments(self, positions_ts, groups, float64: bool = True) -> NDArray[np.float64]:
+    def calc_group_increments(self, positions_ts, groups, float64: bool = True, lattices=None) -> NDArray[np.float64]:
         """``calc_group_increments_device`` for host arrays: fractional positions ``(S,N,3)`` in, float64
-        ``(S-1,G,3,3)`` out."""
+        ``(S-1,G,3,3)`` out.  ``lattices``: host ``(S,3,3)``, one lattice per frame; the result is then
+        ``(S-1,G+1,3,3)`` and the last group is the cell.  Non-finite or singular lattices raise ``ValueError``."""
         verify_ndarray_shape("positions_ts", positions_ts, (None, self.num_atoms, 3))
-        positions = torch.tensor(np.asarray(positions_ts, dtype=np.float64), device=f"cuda:{self.device_index}")
-        return self.calc_group_increments_device(positions, groups, float64=float64).cpu().numpy()
+        device = f"cuda:{self.device_index}"
+        if lattices is not None:
+            from ramannoodle_amd.dynamics import verify_lattices
+            lattices = torch.tensor(verify_lattices(lattices, len(positions_ts)), device=device)
+        positions = torch.tensor(np.asarray(positions_ts, dtype=np.float64), device=device)
+        return self.calc_group_increments_device(positions, groups, float64=float64, lattices=lattices).cpu().numpy()
 
     def calc_partial_raman_tensors(self, ref_positions, displacements, groups) -> NDArray[np.float64]:
         """Raman tensors split by atom group, ``(M,G,3,3)``: ``R[m,g] = 2 sum_{i in g} J_i(ref) . d_{m,i}``
