@@ -622,6 +622,52 @@ int rn_md_raman_partial_segments_device(const double *d_increments, int64_t N, i
                                         int64_t K, int average, int device, size_t workspace_limit,
                                         double *intensities, int64_t num_bins, void *stream);
 
+/*
+ * Vibrational density of states (VDOS) of an MD run, whole and by atom group, on the wavenumber axis of the MD Raman
+ * spectra of the same run.  positions: host float64[S][N][3], fractional, wrapped into the cell or not; lattices: host
+ * float64[num_lattices][3][3], rows = lattice vectors, num_lattices = 1 (a fixed cell) or S (a lattice per frame);
+ * masses: host float64[N], finite and positive; labels: host int32[N], the group of each atom in [0, G), 1 <= G <= 16;
+ * starts: host int64[Q], the first frame of each segment of segment_steps = W frames (n = W - 1 steps),
+ * 0 <= starts[q] <= S - W; taper: host float64[n].
+ *   minimum-image step   df[t] = f[t+1] - f[t], df -= rint(df) (round to nearest even)
+ *   Cartesian step       u[t] = df[t] @ M[t], M[t] = lattices[0], or (lattices[t] + lattices[t+1]) / 2 for a lattice per
+ *                        frame (the motion relative to the deforming cell); not divided by the timestep
+ *   segment series       x_{q,i,c}[t] = taper[t] sqrt(masses[i]) u[starts[q] + t][i][c], t = 0..n-1
+ *   row (q, g)           D_{q,g}(f) = sum over the atoms i of group g and c = x, y, z of C(x_{q,i,c})(f), C = the real part
+ *                        of the length-n transform of the positive lags of the autocorrelation (rn_md_raman_intensities'
+ *                        transform of one series), bins 1..num_bins of fftfreq(n), num_bins = ceil(n/2) - 1
+ * computed as P_{q,g}(w) = sum_{i in g, c} |X_{q,i,c}(w)|^2 on the zero-padded length L >= 2n - 1 followed by the back
+ * half of rn_md_raman_segments (inverse transform, positive lags scaled by 1/L, length-n transform, real bins): 3 N
+ * forward FFTs per segment and G back halves.  densities: host float64[Q][G][num_bins] (average = 0) or
+ * float64[G][num_bins] (average = 1: the arithmetic mean over the segments, taken on P before the inverse transform).
+ * The whole-run VDOS is the one segment starts = {0}, segment_steps = S, taper = 1.  Every (row, frequency) is summed by
+ * one thread, segment by segment in table order and atom by atom in ascending index, without atomics: repeated calls
+ * are bit-identical and the order does not depend on the block sizes below.
+ * Checks, before any device work: a null pointer, N < 1, G < 1 or > 16, num_lattices other than 1 or S, segment_steps < 3
+ * or > S, Q < 1, a wrong num_bins, average not 0 or 1, a start out of range, a label outside [0, G), a mass that is not
+ * finite and positive (RN_ERR_INVALID_ARGUMENT each); then hipFFT (RN_ERR_UNSUPPORTED) and the device
+ * (RN_ERR_NO_DEVICE).  workspace_limit (bytes, 0 = 4 GiB) bounds the device memory besides the staged positions and
+ * lattices: atoms and segments go through the forward FFTs in blocks (all atoms of several segments, or some atoms of
+ * one segment) and, when G rows do not fit, the groups in blocks; a limit that one atom of one segment and one row do
+ * not fit in returns RN_ERR_OUT_OF_MEMORY.  Work runs on the null stream; the call returns when the densities are on the
+ * host.
+ */
+int rn_md_vdos(const double *positions, const double *lattices, int64_t num_lattices, int64_t S, int32_t N,
+               const double *masses, const int32_t *labels, int G, int64_t segment_steps, const int64_t *starts,
+               int64_t Q, const double *taper, int average, int device, size_t workspace_limit, double *densities,
+               int64_t num_bins);
+/* The same for positions and lattices already in HBM (device float64[S][N][3] and [num_lattices][3][3], produced on
+ * `stream`): the call synchronises `stream` before it reads them; masses, labels, starts and taper stay host arrays. */
+int rn_md_vdos_device(const double *d_positions, const double *d_lattices, int64_t num_lattices, int64_t S, int32_t N,
+                      const double *masses, const int32_t *labels, int G, int64_t segment_steps, const int64_t *starts,
+                      int64_t Q, const double *taper, int average, int device, size_t workspace_limit,
+                      double *densities, int64_t num_bins, void *stream);
+/* Device time of the phases of the most recent rn_md_vdos / rn_md_vdos_device call (HIP events on the null stream):
+ * millis[4] = series builder, forward FFTs, group power kernel, back half with its copies to the host.  Measured only
+ * while enabled with rn_md_vdos_set_profiling(1); the events cost a few microseconds per launch. */
+int rn_md_vdos_set_profiling(int enabled);
+int rn_md_vdos_phase_times(double *millis);
+
 /* Introspection: bit 0 = the fused EdgeBlock kernel is in use (float32, Fn and Fe padded to
  * 64); bit 1 = every pass takes the folded-LayerNorm-scale triplet loop; bit 2 = the fused
  * kernels' matrix products run as split-f16 MFMA (default; RN_POTGNN_MFMA=f32 at create time

@@ -1,5 +1,5 @@
 // What the on-device MD spectrum reducers share (spectrum.hip, spectrum_polarized.hip, spectrum_partial.hip,
-// spectrum_segments.hip, spectrum_ensemble.hip): the hipFFT loader, the series-length arithmetic, RAII holders for plans and device buffers, the
+// spectrum_segments.hip, spectrum_ensemble.hip, spectrum_vdos.hip): the hipFFT loader, the series-length arithmetic, RAII holders for plans and device buffers, the
 // most-recently-used plan cache, the argument / device check, the host-or-HBM source of a call and the two per-slot
 // kernels of the polarized, partial and segment pipelines.  Each reducer keeps its own signal builder, power /
 // contraction kernel, plans struct, workspace arithmetic and pipeline.

@@ -1,5 +1,6 @@
 // What the segment reducers share (spectrum_segments.hip: segments on a hop grid; spectrum_ensemble.hip: segments from a
-// start table, whole and by atom group): the two power kernels of the whole spectra, the plans and work buffers of one
+// start table, whole and by atom group; spectrum_vdos.hip: the density of states, which takes the plans and the back half):
+// the two power kernels of the whole spectra, the plans and work buffers of one
 // (device, n, series per segment, segments per block, rows per block), the workspace arithmetic that chooses the two
 // block sizes, and the pipeline from the transformed segments to the host rows.  A reducer brings its segment builder
 // (and, for the atom-group form, its own power kernels) and its own PlanCache, so the caches stay apart.
@@ -121,10 +122,11 @@ inline size_t segment_buffer_bytes(int64_t L, int64_t bins, int series, int64_t 
   return (size_t)B * series * L * cz + (size_t)R * L * cz + (size_t)R * bins * sizeof(double);
 }
 
-inline int make_segment_plans(SegmentCache &cache, int device, int64_t n, int series, int B, int R,
-                              SegmentPlans **out) {
+// (Entry: SegmentPlans, or a reducer's extension of it)
+template <class Entry>
+int make_segment_plans(PlanCache<Entry> &cache, int device, int64_t n, int series, int B, int R, Entry **out) {
   const int64_t L = padded_length(n), bins = num_bins(n);
-  SegmentPlans &s = cache.emplace_front();
+  Entry &s = cache.emplace_front();
   s.device = device;
   s.n = n;
   s.L = L;

@@ -113,6 +113,32 @@ def _cells(lattice_ts, device=None) -> dict:
     return {"lattices": torch.tensor(lattice_ts, dtype=torch.float64, device=device)}
 
 
+
+def _vdos_arguments(lattice, lattice_ts, masses, groups, atomic_numbers, atoms: int):
+    """``(lattice, masses, labels, G)`` of ``get_vdos``: the fixed-cell ``lattice`` ``(3,3)`` or the trajectory's own
+    ``lattice_ts`` (exactly one of the two), and ``groups`` resolved through ``spectrum.group_labels``."""
+    from ramannoodle_amd.spectrum import group_labels
+    if lattice_ts is None:
+        if lattice is None:
+            raise ValueError("a fixed-cell trajectory needs lattice (3,3)")
+        verify_ndarray_shape("lattice", np.asarray(lattice), (3, 3))
+        lattice = verify_lattices(np.asarray(lattice)[None], 1)[0]
+    elif lattice is not None:
+        raise ValueError("the trajectory carries a lattice per frame: lattice must be None")
+    else:
+        lattice = lattice_ts
+    if groups is None:
+        return lattice, masses, None, 1
+    if atomic_numbers is None:
+        if isinstance(groups, str):
+            raise ValueError(f"groups = {groups!r} needs atomic_numbers")
+        atomic_numbers = np.zeros(atoms, dtype=np.int64)
+    else:
+        verify_ndarray_shape("atomic_numbers", np.asarray(atomic_numbers), (atoms,))
+    labels, count = group_labels(groups, atomic_numbers)
+    return lattice, masses, labels, count
+
+
 class Trajectory(Dynamics, Sequence):
     """MD trajectory: fractional positions ``(S,N,3)`` (wrapped into the cell on
     construction) and a timestep in fs (``dynamics/_trajectory.py:16-109``).
@@ -192,6 +218,26 @@ class Trajectory(Dynamics, Sequence):
         if on_device:
             return DevicePartialMDRamanSpectrum(result, self._timestep)
         return PartialMDRamanSpectrum(result.cpu().numpy(), self._timestep)
+
+    def get_vdos(self, lattice=None, masses=None, groups=None, atomic_numbers=None, on_device: bool = False,
+                 device: int = 0):
+        """The vibrational density of states of the run (an addition): ``VibrationalDensityOfStates`` of the positions,
+        on the wavenumber axis of ``get_raman_spectrum(...).measure()``.  ``lattice`` ``(3,3)``: required for a fixed
+        cell, ``None`` when the trajectory carries ``lattice_ts`` (either violation is a ``ValueError``); ``masses``
+        ``(N,)``, finite and positive (``None``: unit masses); ``groups``: ``None`` (one group), an integer array
+        ``(N,)`` or ``"species"``, which needs ``atomic_numbers`` (``spectrum.group_labels``).  ``on_device=True``: the
+        positions (and the lattices of a variable-cell run) are put into the HBM of GPU ``device`` and the returned
+        ``DeviceVibrationalDensityOfStates`` reduces them there."""
+        from ramannoodle_amd.spectrum import DeviceVibrationalDensityOfStates, VibrationalDensityOfStates
+        lattice, masses, labels, count = _vdos_arguments(lattice, self._lattice_ts, masses, groups, atomic_numbers,
+                                                         self._positions_ts.shape[1])
+        if not on_device:
+            return VibrationalDensityOfStates(self._positions_ts, self._timestep, lattice, masses, labels, count)
+        import torch
+        positions = torch.tensor(self._positions_ts, dtype=torch.float64, device=f"cuda:{int(device)}")
+        if self._lattice_ts is not None:
+            lattice = torch.tensor(lattice, dtype=torch.float64, device=positions.device)
+        return DeviceVibrationalDensityOfStates(positions, self._timestep, lattice, masses, labels, count)
 
     def __len__(self) -> int:
         return len(self._positions_ts)
@@ -300,3 +346,23 @@ class TrajectoryEnsemble:
         if on_device:
             return DevicePartialMDRamanEnsemble(result, self._timestep, self._run_lengths)
         return PartialMDRamanEnsemble(self._split(result.cpu().numpy(), 1), self._timestep)
+
+    def get_vdos(self, lattice=None, masses=None, groups=None, atomic_numbers=None, on_device: bool = False,
+                 device: int = 0):
+        """``VibrationalDensityOfStatesEnsemble`` of the runs (arguments as ``Trajectory.get_vdos``): the VDOS averaged
+        over the runs, whose segments never read the step from one run to the next.  ``on_device=True``: the joined
+        positions go to the HBM of GPU ``device`` (``DeviceVibrationalDensityOfStatesEnsemble``)."""
+        from ramannoodle_amd.spectrum import (DeviceVibrationalDensityOfStatesEnsemble,
+                                              VibrationalDensityOfStatesEnsemble)
+        lattice, masses, labels, count = _vdos_arguments(lattice, self._lattice_ts, masses, groups, atomic_numbers,
+                                                         self._positions_ts.shape[1])
+        if not on_device:
+            per_run = lattice if self._lattice_ts is None else self._split(lattice)
+            return VibrationalDensityOfStatesEnsemble(self._split(self._positions_ts), self._timestep, per_run, masses,
+                                                      labels, count)
+        import torch
+        positions = torch.tensor(self._positions_ts, dtype=torch.float64, device=f"cuda:{int(device)}")
+        if self._lattice_ts is not None:
+            lattice = torch.tensor(lattice, dtype=torch.float64, device=positions.device)
+        return DeviceVibrationalDensityOfStatesEnsemble(positions, self._timestep, lattice, masses, labels, count,
+                                                        run_lengths=self._run_lengths)

@@ -1237,3 +1237,347 @@ class DevicePartialMDRamanEnsemble(_DeviceResident, PartialMDRamanEnsemble):
         source, stream = self._source(device)
         return _md_partial_segments_on_device(source, self._timestep, weights, width, starts, tau, average, device,
                                               stream=stream)
+
+
+# ----------------------------------------------------------------------------- vibrational density of states
+def _vdos_lattices(lattice, frames: int) -> NDArray[np.float64]:
+    """``lattice`` ``(3,3)`` (a fixed cell) or ``(frames,3,3)`` (a lattice per frame) as float64 ``(1 or frames,3,3)``,
+    rows = lattice vectors in Angstrom; ``ValueError`` on another shape, a non-finite entry or a singular lattice
+    (``dynamics.verify_lattices``)."""
+    from ramannoodle_amd.dynamics import verify_lattices
+    if lattice is None or isinstance(lattice, (str, bytes)):
+        raise get_type_error("lattice", lattice, "ndarray")
+    array = np.asarray(lattice)
+    if array.shape == (3, 3):
+        return verify_lattices(array[None], 1)
+    if array.ndim != 3:
+        raise ValueError(f"lattice has wrong shape: {shape_string(array.shape)} != (3,3) or ({frames},3,3)")
+    return verify_lattices(array, frames)
+
+
+def _vdos_masses(masses, atoms: int) -> NDArray[np.float64]:
+    """``masses`` ``(atoms,)``, finite and positive, as float64; ``None``: unit masses."""
+    if masses is None:
+        return np.ones(atoms)
+    if isinstance(masses, (str, bytes)):
+        raise get_type_error("masses", masses, "ndarray")
+    array = np.asarray(masses)
+    if array.dtype.kind not in "iuf":
+        raise get_type_error("masses", masses, "ndarray of real numbers")
+    if array.shape != (atoms,):
+        raise ValueError(f"masses has wrong shape: {shape_string(array.shape)} != ({atoms},)")
+    array = np.ascontiguousarray(array, dtype=np.float64)
+    if not (np.all(np.isfinite(array)) and np.all(array > 0)):
+        raise ValueError("masses must be finite and positive")
+    return array
+
+
+def _vdos_labels(labels, num_groups, atoms: int) -> tuple[NDArray[np.int32], int]:
+    """``labels`` ``(atoms,)`` in ``[0, num_groups)``, ``1 <= num_groups <= 16``, as int32; ``None``: one group."""
+    if isinstance(num_groups, (bool, np.bool_)) or not isinstance(num_groups, (int, np.integer)):
+        raise get_type_error("num_groups", num_groups, "int")
+    count = int(num_groups)
+    if not 1 <= count <= MAX_GROUPS:
+        raise ValueError(f"invalid num_groups: {count} is not in [1, {MAX_GROUPS}]")
+    if labels is None:
+        if count != 1:
+            raise ValueError(f"num_groups = {count} needs labels")
+        return np.zeros(atoms, dtype=np.int32), 1
+    array = np.asarray(labels)
+    if array.dtype.kind not in "iu":
+        raise ValueError(f"labels must hold integers, not {array.dtype}")
+    if array.shape != (atoms,):
+        raise ValueError(f"labels has wrong shape: {shape_string(array.shape)} != ({atoms},)")
+    if atoms and (array.min() < 0 or array.max() >= count):
+        raise ValueError(f"labels must lie in [0, {count})")
+    return np.ascontiguousarray(array, dtype=np.int32), count
+
+
+def _vdos_steps(positions: NDArray[np.float64], lattices: NDArray[np.float64]) -> NDArray[np.float64]:
+    """The Cartesian minimum-image steps ``u[t] = (df - rint(df)) @ M[t]``, ``df = f[t+1] - f[t]``: ``(S-1,N,3)``.
+    ``M[t]`` is the one lattice, or the midpoint ``(Lat[t] + Lat[t+1]) / 2`` of a lattice per frame."""
+    steps = np.diff(positions, axis=0)
+    steps -= np.rint(steps)
+    if lattices.shape[0] == 1:
+        return steps @ lattices[0]
+    return np.einsum("tik,tkc->tic", steps, 0.5 * (lattices[:-1] + lattices[1:]))
+
+
+def _vdos_host(positions, lattices, masses, labels, num_groups: int, timestep: float, width: int, starts, tau,
+               average: bool):
+    """(wavenumbers, ``D[G][bins]`` or ``D[Q][G][bins]``) on the host, from the definition (``include/rn_potgnn.h``,
+    ``rn_md_vdos``): per segment the zero-padded transforms of the tapered, mass-weighted minimum-image steps of every
+    atom and direction, their power summed per group, its inverse transform, the positive lags and their length-n
+    transform; the mean over the segments is taken on the group powers.  Only the steps of the segments are read."""
+    u = _vdos_steps(np.asarray(positions, dtype=np.float64), lattices) * np.sqrt(masses)[None, :, None]
+    n = width - 1
+    starts = np.asarray(starts, dtype=np.int64)
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    keep = np.flatnonzero(wavenumbers >= 0)[1:]
+    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    atoms = u.shape[1]
+    members = [np.flatnonzero(labels == g) for g in range(num_groups)]
+
+    def finish(power):  # (..., length / 2 + 1) -> (..., bins)
+        lags = np.fft.irfft(power, n=length, axis=-1)[..., :n]
+        return np.real(scipy.fftpack.fft(lags, axis=-1))[..., keep]
+
+    rows = None if average else np.empty((len(starts), num_groups, len(keep)))
+    mean = np.zeros((num_groups, length // 2 + 1))
+    chunk = max(1, _SEGMENT_CHUNK_ELEMENTS // (3 * (length // 2 + 1)))
+    for q, start in enumerate(starts):
+        atom_power = np.empty((atoms, length // 2 + 1))
+        for first in range(0, atoms, chunk):
+            series = u[start:start + n, first:first + chunk] * tau[:, None, None]
+            spectra = np.fft.rfft(series, n=length, axis=0)  # (length / 2 + 1, atoms of the chunk, 3)
+            atom_power[first:first + chunk] = (spectra.real ** 2 + spectra.imag ** 2).sum(axis=2).T
+        power = np.stack([atom_power[index].sum(axis=0) for index in members])
+        if average:
+            mean += power
+        else:
+            rows[q] = finish(power)
+    return wavenumbers[keep], finish(mean / len(starts)) if average else rows
+
+
+def _vdos_on_device(positions, lattices, masses, labels, num_groups: int, timestep: float, width: int, starts, tau,
+                    average: bool, device: int, stream=None, workspace_limit: int = 0):
+    """(wavenumbers, ``D[G][bins]`` or ``D[Q][G][bins]``) from ``rn_md_vdos`` (host positions and lattices) or, with two
+    torch CUDA tensors, ``rn_md_vdos_device`` ordered after ``stream``."""
+    import ctypes as C
+    steps, atoms = int(positions.shape[0]), int(positions.shape[1])
+    if stream is None:
+        lattices = np.ascontiguousarray(lattices, dtype=np.float64)
+        lattice_pointer = lattices.ctypes.data
+    else:
+        lattice_pointer = lattices.data_ptr()
+    masses = np.ascontiguousarray(masses, dtype=np.float64)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    starts, table_args = _table_arguments(starts)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    shape = (num_groups,) if average else (len(starts), num_groups)
+    return _call_md_reducer(
+        "rn_md_vdos", positions, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
+        (C.c_void_p(lattice_pointer), int(lattices.shape[0]), steps, atoms, C.c_void_p(masses.ctypes.data),
+         C.c_void_p(labels.ctypes.data), num_groups, width, *table_args, C.c_void_p(tau.ctypes.data),
+         int(bool(average))), (workspace_limit,))
+
+
+class VibrationalDensityOfStates:
+    """Vibrational density of states (VDOS) of an MD run, whole and by atom group (an addition): which vibrations exist
+    at all, on the wavenumber axis of ``MDRamanSpectrum`` for the same number of frames and timestep, so that the two
+    curves overlay bin for bin.
+
+    ``positions_ts``: fractional positions ``(S,N,3)``, wrapped into the cell or not; ``timestep`` in fs; ``lattice``:
+    ``(3,3)`` (a fixed cell) or ``(S,3,3)`` (a lattice per frame), rows = lattice vectors in Angstrom; ``masses``
+    ``(N,)``, finite and positive (``None``: unit masses); ``labels`` ``(N,)`` integers in ``[0, num_groups)``,
+    ``1 <= num_groups <= 16`` (``None``: one group).
+
+    The step of atom i from frame t to t + 1 is the minimum image ``df - rint(df)`` of ``df = f[t+1] - f[t]`` taken to
+    Cartesian coordinates by the lattice (a lattice per frame: by the midpoint ``(Lat[t] + Lat[t+1]) / 2``, the motion
+    relative to the deforming cell), not divided by the timestep.  ``D[g]`` is the sum over the atoms of group g and the
+    three directions of ``calc_signal_spectrum(sqrt(m_i) u_i,c)`` without the zero bin, so ``D.sum(0)`` is the one-group
+    VDOS and magnitudes scale with the series length as ``MDRamanSpectrum.measure``'s do.  ``device`` (an int) reduces on
+    that GPU (``rn_md_vdos``); ``None`` is the host path."""
+
+    def __init__(self, positions_ts, timestep: float, lattice, masses=None, labels=None, num_groups=1):
+        verify_ndarray_shape("positions_ts", positions_ts, (None, None, 3))
+        self._positions_ts = np.ascontiguousarray(positions_ts, dtype=np.float64)
+        self._set_parameters(self._positions_ts.shape, timestep, lattice, masses, labels, num_groups)
+
+    def _set_parameters(self, shape, timestep, lattice, masses, labels, num_groups) -> None:
+        self._timestep = timestep
+        self._lattices = _vdos_lattices(lattice, int(shape[0]))
+        self._masses = _vdos_masses(masses, int(shape[1]))
+        self._labels, self._num_groups = _vdos_labels(labels, num_groups, int(shape[1]))
+
+    @property
+    def positions_ts(self):
+        return self._positions_ts
+
+    @property
+    def timestep(self) -> float:
+        return self._timestep
+
+    @property
+    def num_groups(self) -> int:
+        return self._num_groups
+
+    def _num_steps(self) -> int:
+        return self._positions_ts.shape[0]
+
+    def _on_device(self, width, starts, tau, average, device: int, workspace_limit: int = 0):
+        return _vdos_on_device(self._positions_ts, self._lattices, self._masses, self._labels, self._num_groups,
+                               self._timestep, width, starts, tau, average, device, workspace_limit=workspace_limit)
+
+    def _reduce(self, width, starts, tau, average, device):
+        if device is not None:
+            return self._on_device(width, starts, tau, bool(average), int(device))
+        return _vdos_host(self.positions_ts, self._lattices, self._masses, self._labels, self._num_groups,
+                          self._timestep, width, starts, tau, bool(average))
+
+    def _segment_table(self, segment_steps, hop, taper):
+        """``(W, tau, starts)`` of ``measure_segments``."""
+        width, hop, tau = segment_plan(self._num_steps(), segment_steps, hop, taper)
+        return width, tau, _segment_starts(self._num_steps(), width, hop)
+
+    def segment_starts(self, segment_steps, hop=None):
+        """The first frame of each of the ``Q = (S - segment_steps) // hop + 1`` segments of ``measure_segments``."""
+        return self._segment_table(segment_steps, hop, "boxcar")[2]
+
+    def measure(self, device=None):
+        """``(wavenumbers, D[G, bins])`` of the whole run: the one boxcar segment of all ``S`` frames."""
+        steps = self._num_steps()
+        width, _, tau = segment_plan(steps, steps, steps, "boxcar")
+        return self._reduce(width, np.zeros(1, dtype=np.int64), tau, True, device)
+
+    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, device=None):
+        """Segment-averaged (Welch) or time-resolved VDOS on ``MDRamanSpectrum.measure_segments``' segments and axis:
+        ``(wavenumbers, D[G, bins])``, the mean over the segments (taken on the power spectra), or with
+        ``average=False`` the rows ``(wavenumbers, D[Q, G, bins])``.  Arguments as ``spectrum.segment_plan``."""
+        width, tau, starts = self._segment_table(segment_steps, hop, taper)
+        return self._reduce(width, starts, tau, average, device)
+
+
+class _DeviceResidentSteps:
+    """Mixin for a VDOS whose positions (and lattices, if per frame) stay in HBM as contiguous float64 CUDA tensors, on
+    the pattern of ``_DeviceResident``: the measurements reduce on the tensors' GPU unless ``host=True``; another
+    ``device`` gets the host copy, which is made on first use."""
+
+    def _set_tensors(self, positions, lattice) -> None:
+        import torch
+        shape = tuple(positions.shape)
+        if len(shape) != 3 or shape[-1] != 3:
+            raise ValueError(f"positions_ts has wrong shape: {shape} != (_,_,3)")
+        if not (positions.is_cuda and positions.is_contiguous() and positions.dtype == torch.float64):
+            raise ValueError("positions_ts must be a contiguous float64 CUDA tensor")
+        self._tensor = positions
+        self._host_copy = None
+        host_lattice = lattice.detach().cpu().numpy() if isinstance(lattice, torch.Tensor) else lattice
+        self._lattice_argument = host_lattice
+        if isinstance(lattice, torch.Tensor) and lattice.is_cuda and lattice.ndim == 3:
+            if not (lattice.is_contiguous() and lattice.dtype == torch.float64 and lattice.device == positions.device):
+                raise ValueError("lattice must be a contiguous float64 CUDA tensor on the positions' GPU")
+            self._lattice_tensor = lattice
+        else:
+            self._lattice_tensor = None  # made from the validated host lattices on first use
+
+    @property
+    def positions_ts(self):
+        if self._host_copy is None:
+            self._host_copy = self._tensor.cpu().numpy()
+        return self._host_copy
+
+    def _num_steps(self) -> int:
+        return self._tensor.shape[0]
+
+    def _device_index(self) -> int:
+        return self._tensor.device.index or 0
+
+    def _on_device(self, width, starts, tau, average, device: int, workspace_limit: int = 0):
+        import torch
+        if device != self._device_index():
+            return _vdos_on_device(self.positions_ts, self._lattices, self._masses, self._labels, self._num_groups,
+                                   self._timestep, width, starts, tau, average, device,
+                                   workspace_limit=workspace_limit)
+        if self._lattice_tensor is None:
+            self._lattice_tensor = torch.tensor(self._lattices, dtype=torch.float64, device=self._tensor.device)
+        stream = torch.cuda.current_stream(self._tensor.device).cuda_stream
+        return _vdos_on_device(self._tensor, self._lattice_tensor, self._masses, self._labels, self._num_groups,
+                               self._timestep, width, starts, tau, average, device, stream=stream,
+                               workspace_limit=workspace_limit)
+
+    def _device_or_host(self, device, host: bool):
+        if host:
+            return None
+        return self._device_index() if device is None else device
+
+    def measure(self, device=None, host=False):
+        """As the base class's ``measure``; reduces on the tensors' GPU unless ``host=True``."""
+        return super().measure(device=self._device_or_host(device, host))
+
+    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, device=None, host=False):
+        """As the base class's ``measure_segments``; reduces on the tensors' GPU unless ``host=True``."""
+        return super().measure_segments(segment_steps, hop, taper, average, device=self._device_or_host(device, host))
+
+
+class DeviceVibrationalDensityOfStates(_DeviceResidentSteps, VibrationalDensityOfStates):
+    """``VibrationalDensityOfStates`` of positions that already sit in HBM for the polarizability evaluation: a
+    contiguous float64 CUDA tensor ``(S,N,3)``, and ``lattice`` as an array or a CUDA tensor ``(3,3)`` / ``(S,3,3)``.
+    The measurements reduce on that GPU (``rn_md_vdos_device``, ordered after torch's current stream) and only the
+    densities travel to the host; ``positions_ts`` copies the positions to the host on first use."""
+
+    def __init__(self, positions_ts_device, timestep: float, lattice, masses=None, labels=None,
+                 num_groups=1):  # pylint: disable=super-init-not-called
+        self._set_tensors(positions_ts_device, lattice)
+        self._set_parameters(tuple(positions_ts_device.shape), timestep, self._lattice_argument, masses, labels,
+                             num_groups)
+
+
+def _joined_lattices(lattice, run_lengths):
+    """The lattice argument of an ensemble: one ``(3,3)`` for all runs, or a sequence of per-run ``(S_r,3,3)``, joined
+    as the frames are."""
+    array = np.asarray(lattice) if not isinstance(lattice, (list, tuple)) else None
+    if array is not None and array.shape == (3, 3):
+        return array
+    parts = [np.asarray(part, dtype=np.float64) for part in lattice]
+    if len(parts) != len(run_lengths) or any(part.shape != (length, 3, 3) for part, length in zip(parts, run_lengths)):
+        raise ValueError("lattice must be (3,3) or one (S_r,3,3) array per run")
+    return np.concatenate(parts, axis=0)
+
+
+class VibrationalDensityOfStatesEnsemble(VibrationalDensityOfStates):
+    """The VDOS averaged over several independent runs of one system: ``runs`` is a sequence of fractional positions
+    ``(S_r,N,3)`` sharing ``timestep``, masses and labels; ``lattice`` is one ``(3,3)`` or a sequence of per-run
+    ``(S_r,3,3)``.  The runs are joined end to end; the joined frames contain one step across each run boundary, which
+    is computed and never read: ``measure_segments`` takes the segments of every run (``ensemble_segment_starts``; rows
+    in run order, ``average=True`` the mean over all of them), ``measure`` the mean of the runs' whole VDOS, defined when
+    the runs have one length."""
+
+    def __init__(self, runs, timestep: float, lattice, masses=None, labels=None,
+                 num_groups=1):  # pylint: disable=super-init-not-called
+        runs = list(runs)
+        if not runs:
+            raise ValueError("an ensemble needs at least one run")
+        for index, run in enumerate(runs):
+            verify_ndarray_shape(f"runs[{index}]", run, (None, runs[0].shape[1], 3))
+        self._run_lengths = [int(run.shape[0]) for run in runs]
+        self._positions_ts = np.ascontiguousarray(np.concatenate(runs, axis=0), dtype=np.float64)
+        self._set_parameters(self._positions_ts.shape, timestep, _joined_lattices(lattice, self._run_lengths), masses,
+                             labels, num_groups)
+
+    @property
+    def run_lengths(self) -> list[int]:
+        return list(self._run_lengths)
+
+    def _segment_table(self, segment_steps, hop, taper):
+        width, hop, tau = segment_plan(min(self._run_lengths), segment_steps, hop, taper)
+        return width, tau, ensemble_segment_starts(self._run_lengths, width, hop)[0]
+
+    def segment_starts(self, segment_steps, hop=None):
+        """``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
+        starts, run_index = ensemble_segment_starts(self._run_lengths, segment_steps, hop)
+        return run_index, starts - _run_offsets(self._run_lengths)[run_index]
+
+    def measure(self, device=None):
+        """The mean of the runs' ``VibrationalDensityOfStates.measure()``: one boxcar segment per run; a ``ValueError``
+        unless the runs have one length (their wavenumbers differ otherwise)."""
+        steps = _equal_run_length(self._run_lengths)
+        width, tau, starts = self._segment_table(steps, steps, "boxcar")
+        return self._reduce(width, starts, tau, True, device)
+
+
+class DeviceVibrationalDensityOfStatesEnsemble(_DeviceResidentSteps, VibrationalDensityOfStatesEnsemble):
+    """``VibrationalDensityOfStatesEnsemble`` whose runs stay in HBM: a sequence of contiguous float64 CUDA tensors
+    ``(S_r,N,3)`` (joined here, on the GPU), or one tensor holding them end to end plus ``run_lengths``.  ``lattice``:
+    ``(3,3)``, or the joined ``(sum S_r,3,3)`` as an array or a CUDA tensor."""
+
+    def __init__(self, runs, timestep: float, lattice, masses=None, labels=None, num_groups=1,
+                 run_lengths=None):  # pylint: disable=super-init-not-called
+        import torch
+        runs, lengths = _joined_tensor("runs", runs, run_lengths, 0)
+        if lengths is None:
+            lengths = [int(run.shape[0]) for run in runs]
+            runs = runs[0] if len(runs) == 1 else torch.cat(runs, dim=0)
+        self._run_lengths = lengths
+        self._set_tensors(runs, lattice)
+        self._set_parameters(tuple(runs.shape), timestep, self._lattice_argument, masses, labels, num_groups)
