@@ -668,6 +668,44 @@ int rn_md_vdos_device(const double *d_positions, const double *d_lattices, int64
 int rn_md_vdos_set_profiling(int enabled);
 int rn_md_vdos_phase_times(double *millis);
 
+/*
+ * Mode-projected VDOS of an MD run: the power spectrum of the run's mass-weighted steps projected onto given vectors
+ * (the harmonic eigenvectors: the normal-mode decomposition of MD), one row per vector, on the axis of rn_md_vdos.
+ * positions, lattices, num_lattices, masses, starts, segment_steps = W (n = W - 1 steps) and taper as for rn_md_vdos;
+ * vectors: host float64[M][N][3], finite, 1 <= M <= 3 N, applied as given (normalisation is the caller's).
+ *   step                 u[t] exactly as in rn_md_vdos (minimum image, then the lattice or the midpoint of two)
+ *   mode series          y_{q,k}[t] = taper[t] sum_{i,c} vectors[k][i][c] sqrt(masses[i]) u[starts[q] + t][i][c], t = 0..n-1
+ *   row (q, k)           D_{q,k}(f) = C(y_{q,k})(f), C as in rn_md_vdos, bins 1..num_bins of fftfreq(n)
+ * computed as P_{q,k}(w) = |Y_{q,k}(w)|^2 on the zero-padded length L >= 2n - 1 followed by the back half of
+ * rn_md_raman_segments: M forward FFTs per segment and M back halves.  densities: host float64[Q][M][num_bins]
+ * (average = 0) or float64[M][num_bins] (average = 1: the arithmetic mean over the segments, taken on P).  Scaling a
+ * vector by c scales its row by c^2; for a complete orthonormal set (M = 3 N) the rows sum to the one-group row of
+ * rn_md_vdos.  The sum over (i, c) has one fixed order (atoms ascending in tiles of 32, four columns at a time) that
+ * does not depend on the block sizes below, and nothing is summed with atomics: repeated calls are bit-identical.
+ * Checks, before any device work: a null pointer, N < 1, M < 1 or > 3 N, num_lattices other than 1 or S,
+ * segment_steps < 3 or > S, Q < 1, a wrong num_bins, average not 0 or 1, a start out of range, a mass that is not
+ * finite and positive, a vector entry that is not finite (RN_ERR_INVALID_ARGUMENT each); then hipFFT
+ * (RN_ERR_UNSUPPORTED) and the device (RN_ERR_NO_DEVICE).  workspace_limit (bytes, 0 = 4 GiB) bounds the device memory
+ * besides the staged positions and lattices: the modes go through in blocks when one segment's M series and M rows do
+ * not fit, the segments in blocks of several; a limit that one series and one row do not fit in returns
+ * RN_ERR_OUT_OF_MEMORY.  Work runs on the null stream; the call returns when the densities are on the host.
+ */
+int rn_md_mode_vdos(const double *positions, const double *lattices, int64_t num_lattices, int64_t S, int32_t N,
+                    const double *masses, const double *vectors, int32_t M, int64_t segment_steps,
+                    const int64_t *starts, int64_t Q, const double *taper, int average, int device,
+                    size_t workspace_limit, double *densities, int64_t num_bins);
+/* The same for positions and lattices already in HBM (device float64[S][N][3] and [num_lattices][3][3], produced on
+ * `stream`): the call synchronises `stream` before it reads them; masses, vectors, starts and taper stay host arrays. */
+int rn_md_mode_vdos_device(const double *d_positions, const double *d_lattices, int64_t num_lattices, int64_t S,
+                           int32_t N, const double *masses, const double *vectors, int32_t M, int64_t segment_steps,
+                           const int64_t *starts, int64_t Q, const double *taper, int average, int device,
+                           size_t workspace_limit, double *densities, int64_t num_bins, void *stream);
+/* Device time of the phases of the most recent rn_md_mode_vdos / rn_md_mode_vdos_device call (HIP events on the null
+ * stream): millis[4] = projection kernel, forward FFTs, power kernel, back half with its copies to the host.  Measured
+ * only while enabled with rn_md_mode_vdos_set_profiling(1). */
+int rn_md_mode_vdos_set_profiling(int enabled);
+int rn_md_mode_vdos_phase_times(double *millis);
+
 /* Introspection: bit 0 = the fused EdgeBlock kernel is in use (float32, Fn and Fe padded to
  * 64); bit 1 = every pass takes the folded-LayerNorm-scale triplet loop; bit 2 = the fused
  * kernels' matrix products run as split-f16 MFMA (default; RN_POTGNN_MFMA=f32 at create time

@@ -129,6 +129,12 @@ SIGNATURES = {
                                     _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_int64, _P]),
     "rn_md_vdos_set_profiling": (C.c_int, [C.c_int]),
     "rn_md_vdos_phase_times": (C.c_int, [_P]),
+    "rn_md_mode_vdos": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, C.c_int64,
+                                  _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_int64]),
+    "rn_md_mode_vdos_device": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P,
+                                         C.c_int64, _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_int64, _P]),
+    "rn_md_mode_vdos_set_profiling": (C.c_int, [C.c_int]),
+    "rn_md_mode_vdos_phase_times": (C.c_int, [_P]),
     # include/rn_ingest.h (host-only trajectory reader)
     "rn_xdatcar_open": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "rn_xdatcar_close": (None, [_P]),

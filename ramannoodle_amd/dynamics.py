@@ -139,6 +139,32 @@ def _vdos_arguments(lattice, lattice_ts, masses, groups, atomic_numbers, atoms: 
     return lattice, masses, labels, count
 
 
+def _mode_vdos_arguments(phonons, lattice, lattice_ts, masses, modes, atoms: int):
+    """``(lattice of the steps, vectors)`` of ``get_mode_vdos``: ``lattice`` ``(3,3)`` is the cell of the phonon
+    calculation and, unless the trajectory carries ``lattice_ts``, of the steps; ``modes`` selects rows of ``phonons``."""
+    from ramannoodle_amd.spectrum import mode_vectors
+    if not isinstance(phonons, Phonons):
+        raise get_type_error("phonons", phonons, "Phonons")
+    if lattice is None:
+        raise ValueError("get_mode_vdos needs lattice (3,3), the cell of the phonon calculation")
+    verify_ndarray_shape("lattice", np.asarray(lattice), (3, 3))
+    lattice = verify_lattices(np.asarray(lattice)[None], 1)[0]
+    displacements = phonons._displacements
+    if displacements.shape[1] != atoms:
+        raise ValueError(f"phonons and trajectory are incompatible: {displacements.shape[1]} atoms != {atoms} atoms")
+    if modes is not None:
+        index = np.asarray(modes)
+        if index.dtype.kind not in "iu" or index.ndim != 1:
+            raise ValueError("modes must be a one-dimensional integer array")
+        if index.size == 0:
+            raise ValueError("modes is empty")
+        if index.min() < 0 or index.max() >= len(displacements):
+            raise ValueError(f"modes must lie in [0, {len(displacements)})")
+        displacements = displacements[index]
+    vectors = mode_vectors(displacements, lattice, np.ones(atoms) if masses is None else masses)
+    return (lattice if lattice_ts is None else lattice_ts), vectors
+
+
 class Trajectory(Dynamics, Sequence):
     """MD trajectory: fractional positions ``(S,N,3)`` (wrapped into the cell on
     construction) and a timestep in fs (``dynamics/_trajectory.py:16-109``).
@@ -238,6 +264,26 @@ class Trajectory(Dynamics, Sequence):
         if self._lattice_ts is not None:
             lattice = torch.tensor(lattice, dtype=torch.float64, device=positions.device)
         return DeviceVibrationalDensityOfStates(positions, self._timestep, lattice, masses, labels, count)
+
+    def get_mode_vdos(self, phonons, lattice, masses=None, modes=None, on_device: bool = False, device: int = 0):
+        """The mode-projected VDOS of the run (an addition): ``ModeVibrationalDensityOfStates`` of the positions and
+        the mass-weighted, normalised eigenvectors of ``phonons`` (``spectrum.mode_vectors``), one row per mode, on the
+        wavenumber axis of ``get_vdos(...).measure()`` and ``get_raman_spectrum(...).measure()``.  ``lattice`` ``(3,3)``,
+        always required, is the cell of the phonon calculation: it takes the displacements to Cartesian coordinates and
+        is the cell of the steps unless the trajectory carries ``lattice_ts``.  ``masses`` ``(N,)`` (``None``: unit
+        masses); ``modes``: an integer index array selecting rows of ``phonons`` (``ValueError`` when empty or out of
+        range).  A ``phonons`` of another atom count is a ``ValueError``.  ``on_device=True``: the positions go to the
+        HBM of GPU ``device`` and the returned ``DeviceModeVibrationalDensityOfStates`` reduces them there."""
+        from ramannoodle_amd.spectrum import DeviceModeVibrationalDensityOfStates, ModeVibrationalDensityOfStates
+        lattice, vectors = _mode_vdos_arguments(phonons, lattice, self._lattice_ts, masses, modes,
+                                                self._positions_ts.shape[1])
+        if not on_device:
+            return ModeVibrationalDensityOfStates(self._positions_ts, self._timestep, lattice, vectors, masses)
+        import torch
+        positions = torch.tensor(self._positions_ts, dtype=torch.float64, device=f"cuda:{int(device)}")
+        if self._lattice_ts is not None:
+            lattice = torch.tensor(lattice, dtype=torch.float64, device=positions.device)
+        return DeviceModeVibrationalDensityOfStates(positions, self._timestep, lattice, vectors, masses)
 
     def __len__(self) -> int:
         return len(self._positions_ts)
@@ -366,3 +412,23 @@ class TrajectoryEnsemble:
             lattice = torch.tensor(lattice, dtype=torch.float64, device=positions.device)
         return DeviceVibrationalDensityOfStatesEnsemble(positions, self._timestep, lattice, masses, labels, count,
                                                         run_lengths=self._run_lengths)
+
+    def get_mode_vdos(self, phonons, lattice, masses=None, modes=None, on_device: bool = False, device: int = 0):
+        """``ModeVibrationalDensityOfStatesEnsemble`` of the runs (arguments as ``Trajectory.get_mode_vdos``): the
+        mode-projected VDOS averaged over the runs, whose segments never read the step from one run to the next.
+        ``on_device=True``: the joined positions go to the HBM of GPU ``device``
+        (``DeviceModeVibrationalDensityOfStatesEnsemble``)."""
+        from ramannoodle_amd.spectrum import (DeviceModeVibrationalDensityOfStatesEnsemble,
+                                              ModeVibrationalDensityOfStatesEnsemble)
+        lattice, vectors = _mode_vdos_arguments(phonons, lattice, self._lattice_ts, masses, modes,
+                                                self._positions_ts.shape[1])
+        if not on_device:
+            per_run = lattice if self._lattice_ts is None else self._split(lattice)
+            return ModeVibrationalDensityOfStatesEnsemble(self._split(self._positions_ts), self._timestep, per_run,
+                                                          vectors, masses)
+        import torch
+        positions = torch.tensor(self._positions_ts, dtype=torch.float64, device=f"cuda:{int(device)}")
+        if self._lattice_ts is not None:
+            lattice = torch.tensor(lattice, dtype=torch.float64, device=positions.device)
+        return DeviceModeVibrationalDensityOfStatesEnsemble(positions, self._timestep, lattice, vectors, masses,
+                                                            run_lengths=self._run_lengths)

@@ -1303,6 +1303,13 @@ def _vdos_steps(positions: NDArray[np.float64], lattices: NDArray[np.float64]) -
     return np.einsum("tik,tkc->tic", steps, 0.5 * (lattices[:-1] + lattices[1:]))
 
 
+def _lag_spectrum(power, n: int, length: int, keep):
+    """The back half of the VDOS paths: power spectra on the padded length ``(..., length / 2 + 1)`` -> the positive lags
+    of the autocorrelation, their length-``n`` transform, the real bins ``keep``: ``(..., bins)``."""
+    lags = np.fft.irfft(power, n=length, axis=-1)[..., :n]
+    return np.real(scipy.fftpack.fft(lags, axis=-1))[..., keep]
+
+
 def _vdos_host(positions, lattices, masses, labels, num_groups: int, timestep: float, width: int, starts, tau,
                average: bool):
     """(wavenumbers, ``D[G][bins]`` or ``D[Q][G][bins]``) on the host, from the definition (``include/rn_potgnn.h``,
@@ -1319,8 +1326,7 @@ def _vdos_host(positions, lattices, masses, labels, num_groups: int, timestep: f
     members = [np.flatnonzero(labels == g) for g in range(num_groups)]
 
     def finish(power):  # (..., length / 2 + 1) -> (..., bins)
-        lags = np.fft.irfft(power, n=length, axis=-1)[..., :n]
-        return np.real(scipy.fftpack.fft(lags, axis=-1))[..., keep]
+        return _lag_spectrum(power, n, length, keep)
 
     rows = None if average else np.empty((len(starts), num_groups, len(keep)))
     mean = np.zeros((num_groups, length // 2 + 1))
@@ -1405,15 +1411,25 @@ class VibrationalDensityOfStates:
     def _num_steps(self) -> int:
         return self._positions_ts.shape[0]
 
+    def _reducer_call(self, positions, lattices, width, starts, tau, average, device: int, **keywords):
+        """The device reduction of ``positions`` and ``lattices`` (host arrays, or CUDA tensors with ``stream=``): what
+        a subclass with another reducer replaces."""
+        return _vdos_on_device(positions, lattices, self._masses, self._labels, self._num_groups, self._timestep, width,
+                               starts, tau, average, device, **keywords)
+
+    def _host_call(self, width, starts, tau, average):
+        """The same reduction on the host."""
+        return _vdos_host(self.positions_ts, self._lattices, self._masses, self._labels, self._num_groups,
+                          self._timestep, width, starts, tau, average)
+
     def _on_device(self, width, starts, tau, average, device: int, workspace_limit: int = 0):
-        return _vdos_on_device(self._positions_ts, self._lattices, self._masses, self._labels, self._num_groups,
-                               self._timestep, width, starts, tau, average, device, workspace_limit=workspace_limit)
+        return self._reducer_call(self._positions_ts, self._lattices, width, starts, tau, average, device,
+                                  workspace_limit=workspace_limit)
 
     def _reduce(self, width, starts, tau, average, device):
         if device is not None:
             return self._on_device(width, starts, tau, bool(average), int(device))
-        return _vdos_host(self.positions_ts, self._lattices, self._masses, self._labels, self._num_groups,
-                          self._timestep, width, starts, tau, bool(average))
+        return self._host_call(width, starts, tau, bool(average))
 
     def _segment_table(self, segment_steps, hop, taper):
         """``(W, tau, starts)`` of ``measure_segments``."""
@@ -1476,15 +1492,13 @@ class _DeviceResidentSteps:
     def _on_device(self, width, starts, tau, average, device: int, workspace_limit: int = 0):
         import torch
         if device != self._device_index():
-            return _vdos_on_device(self.positions_ts, self._lattices, self._masses, self._labels, self._num_groups,
-                                   self._timestep, width, starts, tau, average, device,
-                                   workspace_limit=workspace_limit)
+            return self._reducer_call(self.positions_ts, self._lattices, width, starts, tau, average, device,
+                                      workspace_limit=workspace_limit)
         if self._lattice_tensor is None:
             self._lattice_tensor = torch.tensor(self._lattices, dtype=torch.float64, device=self._tensor.device)
         stream = torch.cuda.current_stream(self._tensor.device).cuda_stream
-        return _vdos_on_device(self._tensor, self._lattice_tensor, self._masses, self._labels, self._num_groups,
-                               self._timestep, width, starts, tau, average, device, stream=stream,
-                               workspace_limit=workspace_limit)
+        return self._reducer_call(self._tensor, self._lattice_tensor, width, starts, tau, average, device,
+                                  stream=stream, workspace_limit=workspace_limit)
 
     def _device_or_host(self, device, host: bool):
         if host:
@@ -1581,3 +1595,173 @@ class DeviceVibrationalDensityOfStatesEnsemble(_DeviceResidentSteps, Vibrational
         self._run_lengths = lengths
         self._set_tensors(runs, lattice)
         self._set_parameters(tuple(runs.shape), timestep, self._lattice_argument, masses, labels, num_groups)
+
+
+# ----------------------------------------------------------------------------- mode-projected VDOS
+def mode_vectors(displacements, lattice, masses) -> NDArray[np.float64]:
+    """The projection vectors of ``ModeVibrationalDensityOfStates`` from the fractional displacements ``(M,N,3)`` of
+    ``Phonons``: taken to Cartesian coordinates with ``lattice`` ``(3,3)`` (rows = lattice vectors), multiplied by
+    ``sqrt(masses[i])`` and normalised to unit norm over ``(N,3)`` per mode: the mass-weighted eigenvectors, orthonormal
+    for a complete harmonic calculation.  ``ValueError`` for a bad shape, a non-finite entry or a mode of zero norm."""
+    displacements = np.asarray(displacements)
+    if displacements.ndim != 3 or displacements.shape[2] != 3 or displacements.dtype.kind not in "iuf":
+        raise ValueError(f"displacements has wrong shape or type: {shape_string(displacements.shape)} != (_,_,3) reals")
+    atoms = displacements.shape[1]
+    lattice = np.asarray(lattice)
+    if lattice.shape != (3, 3):
+        raise ValueError(f"lattice has wrong shape: {shape_string(lattice.shape)} != (3,3)")
+    lattice = _vdos_lattices(lattice, 1)[0]
+    masses = _vdos_masses(masses, atoms)
+    displacements = np.asarray(displacements, dtype=np.float64)
+    if not np.all(np.isfinite(displacements)):
+        raise ValueError("displacements has a non-finite entry")
+    vectors = (displacements @ lattice) * np.sqrt(masses)[None, :, None]
+    norms = np.sqrt((vectors ** 2).sum(axis=(1, 2)))
+    if not np.all(norms > 0):
+        raise ValueError(f"mode {int(np.flatnonzero(~(norms > 0))[0])} has zero norm")
+    return np.ascontiguousarray(vectors / norms[:, None, None])
+
+
+def _mode_vdos_vectors(vectors, atoms: int) -> NDArray[np.float64]:
+    """``vectors`` ``(M,atoms,3)``, finite, ``1 <= M <= 3 atoms``, as contiguous float64."""
+    if vectors is None or isinstance(vectors, (str, bytes)):
+        raise get_type_error("vectors", vectors, "ndarray")
+    array = np.asarray(vectors)
+    if array.dtype.kind not in "iuf":
+        raise get_type_error("vectors", vectors, "ndarray of real numbers")
+    if array.ndim != 3 or array.shape[1:] != (atoms, 3):
+        raise ValueError(f"vectors has wrong shape: {shape_string(array.shape)} != (_,{atoms},3)")
+    if not 1 <= array.shape[0] <= 3 * atoms:
+        raise ValueError(f"invalid number of vectors: {array.shape[0]} is not in [1, {3 * atoms}]")
+    array = np.ascontiguousarray(array, dtype=np.float64)
+    if not np.all(np.isfinite(array)):
+        raise ValueError("vectors has a non-finite entry")
+    return array
+
+
+def _mode_vdos_host(positions, lattices, masses, vectors, timestep: float, width: int, starts, tau, average: bool):
+    """(wavenumbers, ``D[M][bins]`` or ``D[Q][M][bins]``) on the host, from the definition (``include/rn_potgnn.h``,
+    ``rn_md_mode_vdos``): per segment the tapered projections of the mass-weighted minimum-image steps onto the vectors,
+    their zero-padded transforms, the power of each, its inverse transform, the positive lags and their length-n
+    transform; the mean over the segments is taken on the powers.  Only the steps of the segments are read."""
+    u = _vdos_steps(np.asarray(positions, dtype=np.float64), lattices) * np.sqrt(masses)[None, :, None]
+    u = u.reshape(u.shape[0], -1)
+    weights = vectors.reshape(vectors.shape[0], -1)
+    n = width - 1
+    starts = np.asarray(starts, dtype=np.int64)
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    keep = np.flatnonzero(wavenumbers >= 0)[1:]
+    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    modes = weights.shape[0]
+    rows = None if average else np.empty((len(starts), modes, len(keep)))
+    mean = np.zeros((modes, length // 2 + 1))
+    chunk = max(1, _SEGMENT_CHUNK_ELEMENTS // (length // 2 + 1))
+    for q, start in enumerate(starts):
+        power = np.empty((modes, length // 2 + 1))
+        for first in range(0, modes, chunk):
+            series = (u[start:start + n] @ weights[first:first + chunk].T) * tau[:, None]
+            spectra = np.fft.rfft(series, n=length, axis=0)  # (length / 2 + 1, modes of the chunk)
+            power[first:first + chunk] = (spectra.real ** 2 + spectra.imag ** 2).T
+        if average:
+            mean += power
+        else:
+            rows[q] = _lag_spectrum(power, n, length, keep)
+    return wavenumbers[keep], _lag_spectrum(mean / len(starts), n, length, keep) if average else rows
+
+
+def _mode_vdos_on_device(positions, lattices, masses, vectors, timestep: float, width: int, starts, tau, average: bool,
+                         device: int, stream=None, workspace_limit: int = 0):
+    """(wavenumbers, ``D[M][bins]`` or ``D[Q][M][bins]``) from ``rn_md_mode_vdos`` (host positions and lattices) or, with
+    two torch CUDA tensors, ``rn_md_mode_vdos_device`` ordered after ``stream``."""
+    import ctypes as C
+    steps, atoms = int(positions.shape[0]), int(positions.shape[1])
+    if stream is None:
+        lattices = np.ascontiguousarray(lattices, dtype=np.float64)
+        lattice_pointer = lattices.ctypes.data
+    else:
+        lattice_pointer = lattices.data_ptr()
+    masses = np.ascontiguousarray(masses, dtype=np.float64)
+    vectors = np.ascontiguousarray(vectors, dtype=np.float64)
+    starts, table_args = _table_arguments(starts)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    modes = int(vectors.shape[0])
+    shape = (modes,) if average else (len(starts), modes)
+    return _call_md_reducer(
+        "rn_md_mode_vdos", positions, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
+        (C.c_void_p(lattice_pointer), int(lattices.shape[0]), steps, atoms, C.c_void_p(masses.ctypes.data),
+         C.c_void_p(vectors.ctypes.data), modes, width, *table_args, C.c_void_p(tau.ctypes.data),
+         int(bool(average))), (workspace_limit,))
+
+
+class _ModeProjection:
+    """Mixin that replaces the group reduction of a VDOS class by the projection onto ``vectors``: the rows are modes."""
+
+    def _set_vectors(self, vectors) -> None:
+        self._vectors = _mode_vdos_vectors(vectors, self._masses.shape[0])
+
+    @property
+    def num_modes(self) -> int:
+        return self._vectors.shape[0]
+
+    @property
+    def vectors(self):
+        return self._vectors.copy()
+
+    def _reducer_call(self, positions, lattices, width, starts, tau, average, device: int, **keywords):
+        return _mode_vdos_on_device(positions, lattices, self._masses, self._vectors, self._timestep, width, starts, tau,
+                                    average, device, **keywords)
+
+    def _host_call(self, width, starts, tau, average):
+        return _mode_vdos_host(self.positions_ts, self._lattices, self._masses, self._vectors, self._timestep, width,
+                               starts, tau, average)
+
+
+class ModeVibrationalDensityOfStates(_ModeProjection, VibrationalDensityOfStates):
+    """Mode-projected VDOS of an MD run (an addition): the power spectrum of the run's mass-weighted steps projected
+    onto given vectors, one row per vector, on the axis of ``VibrationalDensityOfStates`` and ``MDRamanSpectrum``.  With
+    the harmonic eigenvectors (``mode_vectors`` of ``Phonons.displacements``) this is the normal-mode decomposition of
+    MD: row k peaks at the anharmonic frequency of mode k at the run's temperature and its width is the inverse lifetime.
+
+    ``positions_ts``, ``timestep``, ``lattice`` and ``masses`` as for ``VibrationalDensityOfStates``; ``vectors``
+    ``(M,N,3)``, finite, ``1 <= M <= 3N``, applied as given: ``D[k] = calc_signal_spectrum(y_k)`` without the zero bin,
+    ``y_k[t] = sum_{i,c} vectors[k,i,c] sqrt(m_i) u[t,i,c]`` with the VDOS's step ``u``.  Scaling a vector by c scales
+    its row by c^2; the rows of a complete orthonormal set sum to the one-group VDOS.  ``measure`` returns
+    ``(wavenumbers, D[M, bins])``, ``measure_segments`` that or ``D[Q, M, bins]``.  ``device`` (an int) reduces on that
+    GPU (``rn_md_mode_vdos``); ``None`` is the host path."""
+
+    def __init__(self, positions_ts, timestep: float, lattice, vectors, masses=None):
+        super().__init__(positions_ts, timestep, lattice, masses)
+        self._set_vectors(vectors)
+
+
+class DeviceModeVibrationalDensityOfStates(_DeviceResidentSteps, _ModeProjection, VibrationalDensityOfStates):
+    """``ModeVibrationalDensityOfStates`` of positions that already sit in HBM (``DeviceVibrationalDensityOfStates``'
+    arguments): reduces on that GPU (``rn_md_mode_vdos_device``, ordered after torch's current stream) unless
+    ``host=True``; the mode series never leave the device."""
+
+    def __init__(self, positions_ts_device, timestep: float, lattice, vectors,
+                 masses=None):  # pylint: disable=super-init-not-called
+        self._set_tensors(positions_ts_device, lattice)
+        self._set_parameters(tuple(positions_ts_device.shape), timestep, self._lattice_argument, masses, None, 1)
+        self._set_vectors(vectors)
+
+
+class ModeVibrationalDensityOfStatesEnsemble(_ModeProjection, VibrationalDensityOfStatesEnsemble):
+    """The mode-projected VDOS averaged over several independent runs of one system: ``runs`` and ``lattice`` as for
+    ``VibrationalDensityOfStatesEnsemble``, ``vectors`` as for ``ModeVibrationalDensityOfStates``.  ``measure_segments``
+    takes the segments of every run, ``measure`` is the mean of the runs' whole spectra (runs of one length)."""
+
+    def __init__(self, runs, timestep: float, lattice, vectors, masses=None):
+        super().__init__(runs, timestep, lattice, masses)
+        self._set_vectors(vectors)
+
+
+class DeviceModeVibrationalDensityOfStatesEnsemble(_DeviceResidentSteps, _ModeProjection,
+                                                   VibrationalDensityOfStatesEnsemble):
+    """``ModeVibrationalDensityOfStatesEnsemble`` whose runs stay in HBM (``DeviceVibrationalDensityOfStatesEnsemble``'s
+    arguments)."""
+
+    def __init__(self, runs, timestep: float, lattice, vectors, masses=None,
+                 run_lengths=None):  # pylint: disable=super-init-not-called
+        DeviceVibrationalDensityOfStatesEnsemble.__init__(self, runs, timestep, lattice, masses, run_lengths=run_lengths)
+        self._set_vectors(vectors)
