@@ -723,7 +723,11 @@ int rn_md_mode_vdos_phase_times(double *millis);
  * even enough that it pays; RN_POTGNN_NODE_ATOM=0 at create time keeps node_block_fused_kernel).
  * bit 10 = float32 evaluations keep the edge embedding in HBM as split-f16 operand pairs ([f16 hi x8][f16 lo x8] per eight
  * columns, hi = f16(x), lo = f16(x - hi): the MFMA operand itself, same 256 B per row) between the geometry kernel, the
- * EdgeBlocks, the NodeBlocks and the readout; needs bits 8 and 9; RN_POTGNN_PAIR_ROWS=0 at create time keeps float32 rows. */
+ * EdgeBlocks, the NodeBlocks and the readout; needs bits 8 and 9; RN_POTGNN_PAIR_ROWS=0 at create time keeps float32 rows.
+ * bit 11 = such evaluations compute the EdgeBlock's c2 branch once per atom pair in c2_pairs_kernel (csrc/kernels_c2_pairs.hip)
+ * instead of once per edge inside the EdgeBlock; needs bit 10 and a graph whose pair rows fit the readout's buffer (at most
+ * E / 2 pairs at Fe padded to 64: every edge has its reverse, as in a radius graph; a graph with more unpaired edges keeps the
+ * branch in the EdgeBlock); RN_POTGNN_C2_PAIRS=0 at create time keeps it there always. */
 int rn_potgnn_config_flags(const rn_potgnn *h);
 
 /*
@@ -753,6 +757,17 @@ int rn_potgnn_debug_ps_schedule(const int32_t *rb, const int32_t *re, int32_t nu
  */
 int rn_potgnn_debug_plan(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
                          const int32_t *atom_types, int32_t num_cus, int32_t *out, size_t capacity, size_t *count);
+
+/*
+ * Host-only, validated like rn_potgnn_debug_plan: the atom-pair table of that plan, as int32 values
+ *   NP, pair_of_edge[E], pair_a[NP], pair_b[NP].
+ * Edge d and its reverse rev_edge[d] share the pair pair_of_edge[d]; an edge without a reverse is a pair of its own.  Pairs
+ * are numbered in ascending order of their lower edge id, and pair_a / pair_b are that edge's atoms.  What depends on the
+ * unordered atom pair alone (the EdgeBlock's c2 branch) need be computed once per pair.  *count and
+ * the out == NULL / capacity protocol are those of rn_potgnn_debug_plan.
+ */
+int rn_potgnn_debug_plan_pairs(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
+                               const int32_t *atom_types, int32_t num_cus, int32_t *out, size_t capacity, size_t *count);
 
 /*
  * Host-only, validated like rn_potgnn_debug_plan: the dynamic LDS bytes each kernel family of that plan would ask for, from
@@ -815,6 +830,10 @@ int rn_potgnn_debug_triplets(rn_potgnn *h, int32_t *idx_i, int32_t *idx_j,
  * (only the most recent pass and pass 0... see DESIGN.md: intermediates are kept only
  * when the handle was created with RN_POTGNN_KEEP_STAGES=1 in the environment),
  * 3 = readout embedding [S_c*E,12].  Returns rows written via *rows.
+ * RN_POTGNN_KEEP_STAGES=1 puts the run on float32 edge rows and the readout on the layout stage 3 reads.
+ * RN_POTGNN_KEEP_STAGES=2 keeps stages 1 and 2 only and leaves the run on the kernels it would take without
+ * snapshots (frames are not spread over two lanes, nothing else changes): where its edge rows are split-f16
+ * operand pairs (bit 10 of rn_potgnn_config_flags), stage 2 returns them decoded, x = hi + lo.
  */
 int rn_potgnn_debug_stage(rn_potgnn *h, int stage, int index, float *out,
                           size_t out_capacity, int64_t *rows, int64_t *cols);

@@ -93,6 +93,7 @@ SIGNATURES = {
     "rn_potgnn_debug_triplets": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "rn_potgnn_debug_ps_schedule": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "rn_potgnn_debug_plan": (C.c_int, [C.POINTER(Config), _P, _P, _P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rn_potgnn_debug_plan_pairs": (C.c_int, [C.POINTER(Config), _P, _P, _P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rn_potgnn_debug_plan_lds": (C.c_int, [C.POINTER(Config), _P, _P, _P, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rn_potgnn_debug_pack_weights": (C.c_int, [C.POINTER(Config), _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rn_potgnn_debug_unpack_weights": (C.c_int, [C.POINTER(Config), _P, C.c_size_t, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),

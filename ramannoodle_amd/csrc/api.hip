@@ -76,11 +76,11 @@ struct DeviceBuf {
 
 enum KernelId {
   K_GEOM = 0, K_NODE_INIT, K_PROJ_NODE, K_PROJ_EDGE_C1, K_NODE_AGG, K_PROJ_EDGE_C3, K_PROJ_C2,
-  K_EDGE_AGG, K_READOUT_MLP, K_READOUT_REDUCE, K_COUNT
+  K_EDGE_AGG, K_READOUT_MLP, K_READOUT_REDUCE, K_C2_PAIRS, K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "geom_rbf", "node_init", "proj_node", "proj_edge_c1", "node_agg", "proj_edge_c3",
-    "proj_c2", "edge_agg", "readout_mlp", "readout_reduce"};
+    "proj_c2", "edge_agg", "readout_mlp", "readout_reduce", "c2_pairs"};
 
 template <typename T>
 struct Lane {
@@ -128,10 +128,14 @@ struct rn_potgnn {
   int chunk = 1;
   size_t f64_budget = 0;  // workspace bytes the float64 lanes may take (0: what the float32 lanes were given)
   bool keep_stages = false;
+  bool snap_pairs = false;      // RN_POTGNN_KEEP_STAGES=2: the same snapshots of a run that keeps its kernels (edge rows stay split-f16
+                                // pairs where they would be; rn_potgnn_debug_stage decodes them); stage 3 is not kept
+  bool last_pair_rows = false;  // the last float32 run's edge rows were split-f16 pairs
   bool debug_sync = false;  // RN_POTGNN_DEBUG_SYNC=1: synchronise + check after every kernel
   GraphPlan plan;  // the graph's host arrays, its atom tiles, the kernel family and the lanes (graph_plan.hpp); `g` is its device image
   bool split_projections = true;  // RN_POTGNN_SPLIT_PROJ=0: the forward's stand-alone projections on the exact-f32 MFMA kernel
   bool want_pair_rows = true;   // RN_POTGNN_PAIR_ROWS at create time (ForwardRun::pair_rows decides per run)
+  bool want_c2_pairs = true;    // RN_POTGNN_C2_PAIRS at create time (ChunkRun::c2_pairs decides per run)
   DeviceBuf step_seg, step_stage;  // segments / staging of the one download after a device-resident Adam step
   float *step_host = nullptr;      // its pinned host image
   bool tape_ps = true;          // RN_POTGNN_TAPE_PS: taped float32 runs on the role-specialised EdgeBlock / atom-owning NodeBlock
@@ -266,6 +270,13 @@ bool lean_workspace(const rn_potgnn *h) {
 size_t bufA_width(const rn_potgnn *h, bool lean) {
   return lean ? 32 : std::max<size_t>(std::max(2 * h->d.FnP, 2 * h->d.FeP), 32);
 }
+// The pair kernel's rows [S, NP, FeP] go into the readout's buffer bufA, which nothing touches before the readout: they fit
+// when NP <= E / 2 at FeP = 64 (every edge has its reverse, as in a radius graph), so the workspace and the frames per
+// launch stay what they were.  A graph with unpaired edges beyond that keeps c2 inside the EdgeBlock.
+bool c2_rows_fit(const rn_potgnn *h) {
+  return edge_ps_takes_c2_rows(h->g, true, h->mfma_f16) &&
+         (size_t)h->g.NP * h->d.FeP <= (size_t)h->g.E * bufA_width(h, lean_workspace(h));
+}
 size_t per_structure_elems(const rn_potgnn *h, bool lean) {
   const size_t N = h->cfg.num_atoms, E = h->cfg.num_edges;
   const size_t FnP = h->d.FnP, FeP = h->d.FeP;
@@ -361,7 +372,7 @@ void ensure_precision(rn_potgnn *h) {
     ln.bufA.ensure(S * E * bufA * sizeof(T));
     if (!lean) ln.bufB.ensure(S * E * 4 * FeP * sizeof(T));
   }
-  if (h->keep_stages) {
+  if (h->keep_stages || h->snap_pairs) {
     const int np = h->cfg.num_message_passes + 1;
     P.snap_node.resize(np);
     P.snap_edge.resize(np);
@@ -478,7 +489,7 @@ struct ChunkRun {
   }
   void snapshot(int p) {
     Precision<T> &P = prec<T>(h);
-    if (!h->keep_stages) return;
+    if (!h->keep_stages && !h->snap_pairs) return;
     HIP_TRY(hipMemcpyAsync(P.snap_node[p].p, node[cur], (size_t)MN * h->d.FnP * sizeof(T),
                            hipMemcpyDeviceToDevice, st()));
     HIP_TRY(hipMemcpyAsync(P.snap_edge[p].p, edge[cur], (size_t)ME * h->d.FeP * sizeof(T),
@@ -507,6 +518,7 @@ struct ChunkRun {
       }
       if (!done) launch_geom_rbf<T>(io.pos, S, h->g, lat, lat_stride, P.offsets, gauss, h->d, unit4, edge[0], st(), narrow());
       h->last_in_order = narrow();  // (kernels_narrow.hip: edge rows in (b, a) order; rn_potgnn_debug_stage undoes it)
+      h->last_pair_rows = pair_rows();
     }
     {
       Timer t(h, st(), K_NODE_INIT);
@@ -596,11 +608,19 @@ struct ChunkRun {
   void stage_aggregate(int p) {
     const PassW<T> &w = prec<T>(h).pass[p];
     const int nxt = cur ^ 1;
+    const float *c2_rows = nullptr;
+    if constexpr (sizeof(T) == 4) {
+      if (c2_pairs(w)) {  // the c2 branch once per atom pair, into the readout's buffer (idle until finish())
+        Timer t(h, st(), K_C2_PAIRS);
+        launch_c2_pairs(node[nxt], bufA, S, h->g, h->d, w, st());
+        c2_rows = bufA;
+      }
+    }
     {
       Timer t(h, st(), K_EDGE_AGG);
       if constexpr (sizeof(T) == 4) {
         if (narrow()) launch_edge_narrow(edge[cur], edge[nxt], node[nxt], S, h->g, h->d, w, st());
-        else if (role_split(w)) launch_edge_ps(edge[cur], edge[nxt], node[nxt], np3, tape_agg(p), S, h->g, h->d, w, h->ps_fail.as<int>(), st(), pair_rows(), h->mfma_f16);
+        else if (role_split(w)) launch_edge_ps(edge[cur], edge[nxt], node[nxt], np3, tape_agg(p), S, h->g, h->d, w, h->ps_fail.as<int>(), st(), pair_rows(), h->mfma_f16, c2_rows);
         else if (fused()) edge_unfused_in_blocks(p);
         else HIP_TRY(launch_edge_agg<T>(bufB, np3, bufA, edge[cur], edge[nxt], S, h->g, h->d, w, tape_agg(p), st()));
       } else {
@@ -706,6 +726,14 @@ struct ChunkRun {
     for (const auto &w : prec<T>(h).pass)
       if (!role_split(w)) return false;
     return true;
+  }
+  // The EdgeBlock's c2 branch once per atom pair in a kernel of its own (kernels_c2_pairs.hip) instead of once per edge inside
+  // the role-specialised EdgeBlock: evaluation runs on pair rows with split-f16 products, on a graph whose pair rows fit the
+  // readout's buffer (c2_rows_fit).  Every other run keeps c2 inside the EdgeBlock.  RN_POTGNN_C2_PAIRS=0 at create time:
+  // always.  (rn_potgnn_config_flags bit 11 reports the choice.)
+  bool c2_pairs(const PassW<T> &w) const {
+    if (sizeof(T) != 4 || !h->want_c2_pairs || !role_split(w) || !pair_rows()) return false;
+    return c2_rows_fit(h);
   }
   T *tape_agg(int p) {  // where the EdgeBlock's pre-LayerNorm sums are recorded (taped runs only)
     Precision<T> &P = prec<T>(h);
@@ -834,7 +862,7 @@ void forward_device(rn_potgnn *h, const ForwardIO<T> &io, int64_t S, hipStream_t
   h->train_S = 0;  // lane 0's workspace is about to be overwritten: a pending train_forward is void
   while (done < S) {
     const int64_t left = S - done;
-    if (lanes == 2 && h->interleave && !h->keep_stages && left > 1) {
+    if (lanes == 2 && h->interleave && !h->keep_stages && !h->snap_pairs && left > 1) {
       // split what is left of this round evenly over the two lanes
       const int64_t both = std::min<int64_t>(left, 2 * (int64_t)chunk);
       const int sa = (int)((both + 1) / 2), sb = (int)(both - sa);
@@ -1722,7 +1750,8 @@ static Graph upload(const GraphPlan &plan, DeviceBuf &buf) {
   const size_t o_a = push(plan.edge_a), o_b = push(plan.edge_b), o_op = push(plan.out_ptr),
                o_ip = push(plan.in_ptr), o_ie = push(plan.in_edge), o_at = push(plan.atom_type),
                o_tb = push(plan.tile.begin), o_to = push(plan.trip_off), o_rv = push(plan.rev_edge),
-               o_nt = push(plan.nt.begin), o_bt = push(plan.bt.begin), o_pt = push(plan.pt.begin), o_ipos = push(plan.in_pos);
+               o_nt = push(plan.nt.begin), o_bt = push(plan.bt.begin), o_pt = push(plan.pt.begin), o_ipos = push(plan.in_pos),
+               o_pe = push(plan.pair_of_edge), o_pa = push(plan.pair_a), o_pb = push(plan.pair_b);
   buf.ensure(ints.size() * sizeof(int));
   HIP_TRY(hipMemcpy(buf.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
   const int *base = buf.as<int>();
@@ -1735,6 +1764,9 @@ static Graph upload(const GraphPlan &plan, DeviceBuf &buf) {
   g.in_pos = base + o_ipos;
   g.atom_type = base + o_at;
   g.rev_edge = base + o_rv;
+  g.pair_of_edge = base + o_pe;
+  g.pair_a = base + o_pa;
+  g.pair_b = base + o_pb;
   g.tile_begin = base + o_tb;
   g.trip_off = base + o_to;
   g.nt_begin = base + o_nt;
@@ -1799,7 +1831,8 @@ int rn_potgnn_create(const rn_potgnn_config *cfg, const int32_t *edge_a, const i
   std::memcpy(h->lattice, lattice, sizeof(h->lattice));
   std::memcpy(h->mean, mean, sizeof(h->mean));
   std::memcpy(h->stdv, stddev, sizeof(h->stdv));
-  h->keep_stages = getenv("RN_POTGNN_KEEP_STAGES") && atoi(getenv("RN_POTGNN_KEEP_STAGES")) != 0;
+  h->snap_pairs = getenv("RN_POTGNN_KEEP_STAGES") && atoi(getenv("RN_POTGNN_KEEP_STAGES")) == 2;
+  h->keep_stages = getenv("RN_POTGNN_KEEP_STAGES") && atoi(getenv("RN_POTGNN_KEEP_STAGES")) != 0 && !h->snap_pairs;
   h->debug_sync = getenv("RN_POTGNN_DEBUG_SYNC") && atoi(getenv("RN_POTGNN_DEBUG_SYNC")) != 0;
   if (const char *e = getenv("RN_POTGNN_INTERLEAVE")) h->interleave = atoi(e) != 0;
   if (const char *e = getenv("RN_POTGNN_MFMA")) h->mfma_f16_requested = !(e[0] == 'f' && e[1] == '3');
@@ -1808,6 +1841,7 @@ int rn_potgnn_create(const rn_potgnn_config *cfg, const int32_t *edge_a, const i
   if (const char *e = getenv("RN_POTGNN_TAPE_PS")) h->tape_ps = atoi(e) != 0;
   h->split_projections = getenv("RN_POTGNN_SPLIT_PROJ") ? atoi(getenv("RN_POTGNN_SPLIT_PROJ")) != 0 : true;
   h->want_pair_rows = !(getenv("RN_POTGNN_PAIR_ROWS") && atoi(getenv("RN_POTGNN_PAIR_ROWS")) == 0);
+  h->want_c2_pairs = !(getenv("RN_POTGNN_C2_PAIRS") && atoi(getenv("RN_POTGNN_C2_PAIRS")) == 0);
 
   const PlanKnobs knobs = read_plan_knobs();
   h->d = plan_dims(*cfg, knobs);
@@ -1854,6 +1888,32 @@ int rn_potgnn_debug_plan(const rn_potgnn_config *cfg, const int32_t *edge_a, con
     *count = flat.size();
     if (!out || capacity < flat.size()) {
       set_error(nullptr, "out holds %zu values, the plan has %zu", out ? capacity : (size_t)0, flat.size());
+      return RN_ERR_INVALID_ARGUMENT;
+    }
+    std::memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
+    return RN_OK;
+  } catch (const std::bad_alloc &) {
+    set_error(nullptr, "host allocation failed");
+    return RN_ERR_OUT_OF_MEMORY;
+  }
+}
+
+int rn_potgnn_debug_plan_pairs(const rn_potgnn_config *cfg, const int32_t *edge_a, const int32_t *edge_b,
+                               const int32_t *atom_types, int32_t num_cus, int32_t *out, size_t capacity, size_t *count) {
+  if (!count || num_cus <= 0) return RN_ERR_INVALID_ARGUMENT;
+  *count = 0;
+  std::string invalid;
+  const int rc = validate_create_args(cfg, edge_a, edge_b, atom_types, false, nullptr, invalid);
+  if (rc != RN_OK) {
+    set_error(nullptr, "%s", invalid.c_str());
+    return rc;
+  }
+  try {
+    const PlanKnobs knobs = read_plan_knobs();
+    const std::vector<int32_t> flat = plan_graph(*cfg, plan_dims(*cfg, knobs), edge_a, edge_b, atom_types, num_cus, knobs).flat_pairs();
+    *count = flat.size();
+    if (!out || capacity < flat.size()) {
+      set_error(nullptr, "out holds %zu values, the pair table has %zu", out ? capacity : (size_t)0, flat.size());
       return RN_ERR_INVALID_ARGUMENT;
     }
     std::memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
@@ -2832,6 +2892,8 @@ int rn_potgnn_config_flags(const rn_potgnn *h) {
     flags |= atom ? 512 : 0;
     // bit 10: float32 evaluations keep their edge rows as split-f16 pairs (bits 8 and 9 and the fused readout)
     flags |= (atom && (flags & 256) && h->plan.use_readout_fused && h->want_pair_rows && !h->keep_stages) ? 1024 : 0;
+    // bit 11: such evaluations compute the EdgeBlock's c2 branch once per atom pair (kernels_c2_pairs.hip)
+    flags |= ((flags & 1024) && h->want_c2_pairs && c2_rows_fit(h)) ? 2048 : 0;
   }
   bool fast = !h->f32.pass.empty();
   for (const auto &p : h->f32.pass) fast = fast && !h->plan.use_narrow && (p.c3_fast & (h->plan.use_fused ? 1 : 2));
@@ -2885,8 +2947,8 @@ int rn_potgnn_debug_stage(rn_potgnn *h, int stage, int index, float *out, size_t
     if (stage == 0) {
       src = P.lanes[0].unit4.as<float>(); r = ME; c = 4; ld = 4;
     } else if (stage == 1 || stage == 2) {
-      if (!h->keep_stages || index < 0 || index > h->cfg.num_message_passes)
-        throw HipError{hipErrorInvalidValue, "stage snapshots need RN_POTGNN_KEEP_STAGES=1"};
+      if ((!h->keep_stages && !h->snap_pairs) || index < 0 || index > h->cfg.num_message_passes)
+        throw HipError{hipErrorInvalidValue, "stage snapshots need RN_POTGNN_KEEP_STAGES=1 or 2"};
       if (stage == 1) { src = P.snap_node[index].as<float>(); r = MN; c = h->d.Fn; ld = h->d.FnP; }
       else { src = P.snap_edge[index].as<float>(); r = ME; c = h->d.Fe; ld = h->d.FeP; }
     } else if (stage == 3) {
@@ -2895,6 +2957,18 @@ int rn_potgnn_debug_stage(rn_potgnn *h, int stage, int index, float *out, size_t
       throw HipError{hipErrorInvalidValue, "unknown stage"};
     }
     if ((size_t)(r * c) > out_capacity) throw HipError{hipErrorInvalidValue, "out_capacity too small"};
+    if (stage == 2 && h->snap_pairs && h->last_pair_rows) {  // split-f16 pair rows (kernels.hpp: launch_geom_rbf_pairs): x = hi + lo
+      std::vector<_Float16> raw((size_t)r * 128);
+      HIP_TRY(hipMemcpy(raw.data(), src, raw.size() * sizeof(_Float16), hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < r; ++i)
+        for (int64_t k = 0; k < c; ++k) {
+          const _Float16 *grp = raw.data() + i * 128 + (k >> 3) * 16;  // [hi x8][lo x8] of columns 8 m .. 8 m + 7
+          out[i * c + k] = (float)grp[k & 7] + (float)grp[8 + (k & 7)];
+        }
+      *rows = r;
+      *cols = c;
+      return;
+    }
     HIP_TRY(hipMemcpy2D(out, c * sizeof(float), src, ld * sizeof(float), c * sizeof(float), r,
                         hipMemcpyDeviceToHost));
     if (h->last_in_order && r == ME && stage != 1) {  // per-edge rows of a narrow run: back to edge-id order

@@ -329,6 +329,20 @@ void build_index_arrays(GraphPlan &g) {
     if (it != hi && *it == ad) g.rev_edge[e] = (int)(it - edge_b);
   }
   g.T = g.trip_off[E];
+  // atom pairs: the reverse of an edge with a lower id has its pair already
+  g.pair_of_edge.assign(E, -1);
+  g.pair_a.clear();
+  g.pair_b.clear();
+  for (int e = 0; e < E; ++e) {
+    const int r = g.rev_edge[e];
+    if (r >= 0 && r < e) {
+      g.pair_of_edge[e] = g.pair_of_edge[r];
+    } else {
+      g.pair_of_edge[e] = (int)g.pair_a.size();
+      g.pair_a.push_back(edge_a[e]);
+      g.pair_b.push_back(edge_b[e]);
+    }
+  }
 }
 
 }  // namespace
@@ -502,6 +516,7 @@ GraphPlan plan_graph(const rn_potgnn_config &cfg, Dims d, const int32_t *edge_a,
 Graph GraphPlan::scalars() const {
   Graph s{};
   s.N = N, s.E = E, s.T = T;
+  s.NP = (int)pair_a.size();
   s.num_tiles = tile.num(), s.max_tile_out_rows = tile.max_out_rows, s.max_tile_in_rows = tile.max_in_rows, s.max_tile_nodes = tile.max_nodes;
   s.nt_num = nt.num(), s.nt_max_in_rows = nt.max_in_rows, s.nt_max_nodes = nt.max_nodes, s.nt_narrow = nt_narrow ? 1 : 0;
   s.na_num = na_num, s.na_max_deg = na_max_deg;
@@ -536,6 +551,12 @@ std::vector<int32_t> GraphPlan::flat() const {
   o.insert(o.end(), {nt_narrow ? 1 : 0, na_num, na_max_deg, pt_back, pt_gram, (int32_t)T});
   o.insert(o.end(), {use_fused, 0 /* reserved */, 0 /* reserved */, use_ps, use_narrow, use_node_fused, use_readout_fused, num_lanes});
   for (const std::vector<int> *v : {&out_ptr, &in_ptr, &in_edge, &in_pos, &rev_edge, &trip_off}) o.insert(o.end(), v->begin(), v->end());
+  return o;
+}
+
+std::vector<int32_t> GraphPlan::flat_pairs() const {
+  std::vector<int32_t> o = {(int32_t)pair_a.size()};
+  for (const std::vector<int> *v : {&pair_of_edge, &pair_a, &pair_b}) o.insert(o.end(), v->begin(), v->end());
   return o;
 }
 

@@ -66,6 +66,11 @@ struct GraphPlan {
   std::vector<int> in_edge, in_pos;  // [E] edge ids entering b, ascending; its inverse
   std::vector<int> rev_edge;         // [E] id of (b -> a) or -1
   std::vector<int> trip_off;         // [E+1] exclusive prefix of triplets per destination edge
+  // Atom pairs: edge d and rev_edge[d] share one (what depends on {a_d, b_d} alone -- the EdgeBlock's c2 branch -- need be
+  // computed once per pair).  Pairs are numbered in ascending order of their lower edge id and take
+  // its atoms; an edge without a reverse, or that is its own reverse, is a pair of its own.
+  std::vector<int> pair_of_edge;     // [E] compact pair index
+  std::vector<int> pair_a, pair_b;   // [NP] the two atoms of each pair
   int64_t T = 0;
   Partition tile, nt, bt, pt;        // Graph::tile_begin / nt_ / bt_ / pt_ (kernels.hpp says which kernel each serves)
   bool nt_narrow = false;
@@ -86,6 +91,8 @@ struct GraphPlan {
   std::vector<int64_t> lds_requests() const;
   // The plan as rn_potgnn_debug_plan writes it (include/rn_potgnn.h documents the layout).
   std::vector<int32_t> flat() const;
+  // The pair table as rn_potgnn_debug_plan_pairs writes it: NP, pair_of_edge[E], pair_a[NP], pair_b[NP].
+  std::vector<int32_t> flat_pairs() const;
 };
 
 // The arguments must have passed validate_create_args.  num_cus: compute units of the device the handle will run on.

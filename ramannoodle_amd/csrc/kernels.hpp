@@ -18,6 +18,10 @@ struct Graph {
   const int *in_pos;   // [E]  inverse of in_edge: position of edge e in the (b, a) order
   const int *atom_type;  // [N]
   const int *rev_edge;   // [E]  id of the reverse edge (b -> a), or -1
+  // atom pairs (GraphPlan::pair_of_edge): edge d and rev_edge[d] share pair_of_edge[d]; pair p joins atoms pair_a[p], pair_b[p]
+  int NP;
+  const int *pair_of_edge;  // [E]
+  const int *pair_a, *pair_b;  // [NP]
   // node tiles for the edge-block kernel
   int num_tiles;
   const int *tile_begin;  // [num_tiles+1] node ranges
@@ -334,7 +338,16 @@ bool edge_ps_tile_ok(const int *rb, const int *re, int D, int back, int ring, in
 // `fail`: device int, set to a nonzero code if a bounded spin wait inside the kernel ran out (never in a correct run)
 void launch_edge_ps(const float *edge_in, float *edge_out, const float *node, const float *np3, float *agg_out, int S,
                     const Graph &g, Dims d, const PassW<float> &w, int *fail, hipStream_t st, bool pair_rows = false,
-                    bool f16 = true /* false: exact-f32 MFMA products (float32 rows, no Gram tables) */);
+                    bool f16 = true /* false: exact-f32 MFMA products (float32 rows, no Gram tables) */,
+                    const float *c2_rows = nullptr /* [S, g.NP, 64] from launch_c2_pairs: the kernel computes no c2 branch of its
+                                                      own (pair rows, split-f16 products, eight-lane form without Gram tables) */);
+// may launch_edge_ps take c2 rows for this graph and these options?
+bool edge_ps_takes_c2_rows(const Graph &g, bool pair_rows, bool f16);
+
+// The EdgeBlock's c2 branch once per atom pair (kernels_c2_pairs.hip): out[S, g.NP, 64] float32 = LN(gate(LN(c2_linear(
+// node[pair_b] * node[pair_a])))) on the centred, prescaled c2_linear -- the rows launch_edge_ps takes as `c2_rows`.
+// float32, FnP == FeP == 64, split-f16 products.
+void launch_c2_pairs(const float *node, float *out, int S, const Graph &g, Dims d, const PassW<float> &w, hipStream_t st);
 
 // Device-resident optimisation step (kernels_train.hip); offsets index the packed weight blob.
 struct DerivedOp {

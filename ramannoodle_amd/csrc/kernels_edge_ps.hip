@@ -55,6 +55,7 @@ struct EdgePsArgs {
   const float *np3;   // [S*N, 6FP] = node * centred(Wi | Wj | Wk) + (0 | centred bias | 0)
   float *agg_out;     // optional: the pre-LayerNorm triplet sums [S*E, FP]
   int *fail;          // set when a bounded wait ran out (a protocol bug; the kernel still terminates)
+  const float *c2;    // C2G instantiations: the c2 branch's rows [S, g.NP, FP] (kernels_c2_pairs.hip), else unused
   int S;
   Graph g;
   Dims d;
@@ -329,9 +330,16 @@ __device__ __forceinline__ void ps_publish(unsigned word, unsigned value, int la
 // Gram phase below) instead of a 128-column dot product and a 16-lane reduction per triplet in the consumers' loop
 // F16 = false: every matrix product on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32, RN_POTGNN_MFMA=f32 or the range guard's
 // fallback): f32 weight fragments, f32 operand tiles as they land, no prescales; PRE and GRAM are then false
-template <bool PAD, bool PRE, bool GRAM, bool F16 = true>
+// C2G: the c2 branch's rows are GIVEN (EdgePsArgs::c2, one row per atom pair from kernels_c2_pairs.hip: edge d and its reverse
+// share it).  The producers then hold no c2 weight, request three rows per step instead of five (no node[b], no node[a]),
+// split nothing and multiply a third less; the consumers drop the c2 block of their prologue and read their sixteen columns
+// of the pair's row behind the loop, next to the residual.  The signalling is unchanged.  Evaluation runs on pair rows only
+// (F16 && PRE && !GRAM, the eight-lane form); every other instantiation keeps c2 in the kernel.
+template <bool PAD, bool PRE, bool GRAM, bool F16 = true, bool C2G = false>
 __global__ __launch_bounds__(PS_THREADS) void edge_block_ps_kernel(EdgePsArgs a) {
   static_assert(F16 || (!PRE && !GRAM), "the exact-f32 instantiation keeps float32 rows and the in-loop cross term");
+  static_assert(!C2G || (F16 && PRE && !GRAM && RN_PS_LG8), "c2 rows are taken by the pair-row, eight-lane form only");
+  constexpr int NREQ = C2G ? 3 : 5;  // LDS-DMA requests of a producer step: what the counted wait of the node terms leaves outstanding
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int NRT = GRAM ? PS_NRT_GRAM : PS_NRT, RING = NRT * 16;
   constexpr bool LG8 = RN_PS_LG8 && !GRAM;  // eight-lane destination groups (below)
@@ -454,13 +462,13 @@ __global__ __launch_bounds__(PS_THREADS) void edge_block_ps_kernel(EdgePsArgs a)
     WaveB<F16> bW4, bW5, bWc;
     bW4.load(a.w.c3_WeT_c, 4 * FP, colbase, l15, quad, s4);
     bW5.load(a.w.c3_WeT_c + 2 * FP, 4 * FP, colbase, l15, quad, s5);
-    bWc.load(a.w.c2_WT_c, 2 * FP, colbase, l15, quad, sc2);
+    if constexpr (!C2G) bWc.load(a.w.c2_WT_c, 2 * FP, colbase, l15, quad, sc2);
     const float qscale = uni(inv5 * inv5 / (float)(2 * a.d.Fe));  // |q|^2 / 2Fe from the prescaled accumulators
 
     // LDS-DMA of a step's operand rows: wave w brings rows 4w..4w+3 of every tile; slot (row, piece p) receives
-    // global piece p ^ row (the XOR swizzle load_split_a undoes).  Always the same five requests -- a step without
-    // destinations or with fewer source tiles re-fetches a valid row into a tile nobody reads -- so that every
-    // step is one instruction sequence.
+    // global piece p ^ row (the XOR swizzle load_split_a undoes).  Always the same NREQ requests (five; three when the c2
+    // rows are given: no node[b], no node[a]) -- a step without destinations or with fewer source tiles re-fetches a valid
+    // row into a tile nobody reads -- so that every step is one instruction sequence.
     auto request = [&](const PsStep &st, int buf, int ln) {
       const int row = 4 * wave + (ln >> 4);
       const int piece = ((ln & 15) ^ row) & 15;
@@ -476,8 +484,10 @@ __global__ __launch_bounds__(PS_THREADS) void edge_block_ps_kernel(EdgePsArgs a)
       const float *eb1 = a.edge_in + (int64_t)(sg + min(st.tu1, nunits - 1) * nsg) * g.E * FP;
       const unsigned r0 = (unsigned)(eo0 + min(st.tt0 * 16 + row, R - 1)), r1 = (unsigned)(eo0 + min(st.tt1 * 16 + row, R - 1));
       dma16(eb + ((unsigned)de * FP + 4 * piece), dst);
-      dma16(nb + ((unsigned)db * FP + 4 * piece), dst + PS_TILE);
-      dma16(nb + ((unsigned)da * FP + 4 * piece), na_tile + wave * 256);
+      if constexpr (!C2G) {
+        dma16(nb + ((unsigned)db * FP + 4 * piece), dst + PS_TILE);
+        dma16(nb + ((unsigned)da * FP + 4 * piece), na_tile + wave * 256);
+      }
       dma16(eb0 + (r0 * FP + 4 * piece), dst + 2 * PS_TILE);
       dma16(eb1 + (r1 * FP + 4 * piece), dst + 3 * PS_TILE);
     };
@@ -495,12 +505,14 @@ __global__ __launch_bounds__(PS_THREADS) void edge_block_ps_kernel(EdgePsArgs a)
         write_pair(tb + 2 * PS_TILE * 4, row, phys, v);
         write_pair(tb + 3 * PS_TILE * 4, row, phys, w);
       }
-      lds_read2(sa + PS_TILE * 4, atile_a + (unsigned)(2 * PS_BUF + wave * 256 + ln * 4) * 4u, u, v);
-      if constexpr (F16) {
-        write_pair(tb + PS_TILE * 4, row, phys, u * v);
-      } else {  // (float32 tiles: the product replaces node[b]'s slot as it is)
-        const f32x4 pr = u * v;
-        lds_write4(sa + PS_TILE * 4, float4{pr[0], pr[1], pr[2], pr[3]});
+      if constexpr (!C2G) {
+        lds_read2(sa + PS_TILE * 4, atile_a + (unsigned)(2 * PS_BUF + wave * 256 + ln * 4) * 4u, u, v);
+        if constexpr (F16) {
+          write_pair(tb + PS_TILE * 4, row, phys, u * v);
+        } else {  // (float32 tiles: the product replaces node[b]'s slot as it is)
+          const f32x4 pr = u * v;
+          lds_write4(sa + PS_TILE * 4, float4{pr[0], pr[1], pr[2], pr[3]});
+        }
       }
     };
     static_assert(PS_MAXNEW == 2, "split_landed / request are written for two source tiles per step");
@@ -526,8 +538,8 @@ __global__ __launch_bounds__(PS_THREADS) void edge_block_ps_kernel(EdgePsArgs a)
       // node terms of this step's destinations: four 16-byte loads per lane, issued now and added to the product where that is
       // finished (`seeds_landed` below) -- in flight under the split, the sync, the next requests and the first MFMAs; the
       // source tile's two follow when the P' registers are free, in flight under the c2 and Q' products.
-      // Inline assembly: the compiler would wait for a load it can see with vmcnt(0) at its first use, i.e. for the five
-      // LDS-DMA requests issued after it as well; in order, "all but the five youngest" is exactly these loads.
+      // Inline assembly: the compiler would wait for a load it can see with vmcnt(0) at its first use, i.e. for the NREQ
+      // LDS-DMA requests issued after it as well; in order, "all but the NREQ youngest" is exactly these loads.
       f32x4 kP[2], jP[2], qS[2];
       const float *q_src;  // this lane's node term of the step's first source tile: requested when the P' registers are free
       int ringrow0;
@@ -559,17 +571,17 @@ __global__ __launch_bounds__(PS_THREADS) void edge_block_ps_kernel(EdgePsArgs a)
       // ---- B: request the next step's rows (its buffer and the node[a] tile are free: every producer is past step k - 1)
       PS_TICK(3);
       ln = launder(ln);
-      // Always five requests, also after the last step (its own rows again, into the buffer nobody will read): the wait below
+      // Always NREQ requests, also after the last step (its own rows again, into the buffer nobody will read): the wait below
       // is then ONE statement on one path.  With two variants behind a branch the compiler copied the loaded registers into
       // the merge point's registers in front of one of the waits -- i.e. before the data was there.
       if (!(RN_PS_PROBE & 32)) request(have_next ? nxt : cur, buf ^ 1, ln);
-      // the node terms are there once at most the five requests above are outstanding
+      // the node terms are there once at most the NREQ requests above are outstanding
       // (the product's accumulators are operands too: the wait stays BEHIND the MFMAs it is meant to be covered by)
       auto seeds_landed = [&](f32x4 (&acc)[2]) {
         if (RN_PS_PROBE & 32)
           asm volatile("s_waitcnt vmcnt(0)" : "+v"(kP[0]), "+v"(kP[1]), "+v"(jP[0]), "+v"(jP[1]), "+v"(acc[0]), "+v"(acc[1])::"memory");
         else
-          asm volatile("s_waitcnt vmcnt(5)" : "+v"(kP[0]), "+v"(kP[1]), "+v"(jP[0]), "+v"(jP[1]), "+v"(acc[0]), "+v"(acc[1])::"memory");
+          asm volatile("s_waitcnt vmcnt(%6)" : "+v"(kP[0]), "+v"(kP[1]), "+v"(jP[0]), "+v"(jP[1]), "+v"(acc[0]), "+v"(acc[1]) : "n"(NREQ) : "memory");
       };
       // Every load issued in assembly is waited for on EVERY path, by a statement that names its registers: a register that
       // is loaded and then never read (a step without destinations, a step without a source tile) would be free for the
@@ -612,7 +624,7 @@ __global__ __launch_bounds__(PS_THREADS) void edge_block_ps_kernel(EdgePsArgs a)
         asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qS[0]) : "v"(q_src) : "memory");
         asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qS[1]) : "v"(q_src + 16) : "memory");
       }
-      if (cur.has_dest) {
+      if constexpr (!C2G) if (cur.has_dest) {
         f32x4 accC[2];
         if constexpr (F16) {
           f16x8 ah[2], al[2];
@@ -861,8 +873,11 @@ __global__ __launch_bounds__(PS_THREADS) void edge_block_ps_kernel(EdgePsArgs a)
       // ---- c2: gate(LayerNorm(c2_linear(node[b]*node[a]))) -> LayerNorm   (_gnn.py:223-228), before the loop: the round's
       // P' / c2 buffers then go back to the producers.  Zero-mean pre-activation row (centred weights), exact zeros in its
       // padded columns: its variance is the plain sum of squares (in the weights' prescale: eps scaled).
+      // (C2G: the branch was computed once per atom pair by kernels_c2_pairs.hip; the row is read behind the loop)
       Vec4<float> c2v[2];
-      {
+      int c2pair = 0;  // C2G: the destination's atom pair (one register across the loop)
+      if constexpr (C2G) c2pair = g.pair_of_edge[d_edge[i]];
+      if constexpr (!C2G) {
         const float *crow = bufC + ((int)(gr & 1u) * PS_ND + slot) * LDQ;
         Vec4<float> xf[2], xc[2];
         float q = 0.f;
@@ -978,6 +993,11 @@ __global__ __launch_bounds__(PS_THREADS) void edge_block_ps_kernel(EdgePsArgs a)
         } else {
           old4[j] = *reinterpret_cast<const f32x4 *>(a.edge_in + drow * FP + cj);
         }
+      }
+      if constexpr (C2G) {  // this lane's sixteen columns of the pair's c2 row, requested with the residual
+        const float *crow = a.c2 + ((int64_t)(sg + u * nsg) * g.NP + c2pair) * FP;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) c2v[j] = load4<float>(crow + 4 * l7 + 32 * j);
       }
       // this wave no longer reads the ring rows of round gr; arrivals ordered by round (see the sixteen-lane form)
       poisoned |= (ps_wait_ge(sync_a + ((gr & 1u) ? C_RD1 : C_RD0), CPR * (gr >> 1), sync_a + C_READY, a.fail, 6) & PS_FAILBIT) != 0;
@@ -1355,10 +1375,16 @@ bool edge_ps_tile_ok(const int *rb, const int *re, int D, int back, int ring, in
   return true;
 }
 
+bool edge_ps_takes_c2_rows(const Graph &g, bool pair_rows, bool f16) {
+  return RN_PS_LG8 != 0 && f16 && pair_rows && g.pt_gram == 0 && g.NP > 0;
+}
+
 void launch_edge_ps(const float *edge_in, float *edge_out, const float *node, const float *np3, float *agg_out, int S,
-                    const Graph &g, Dims d, const PassW<float> &w, int *fail, hipStream_t st, bool pair_rows, bool f16) {
+                    const Graph &g, Dims d, const PassW<float> &w, int *fail, hipStream_t st, bool pair_rows, bool f16,
+                    const float *c2_rows) {
   if (S == 0 || g.E == 0) return;
-  EdgePsArgs a{edge_in, edge_out, node, np3, agg_out, fail, S, g, d, w};
+  if (!edge_ps_takes_c2_rows(g, pair_rows, f16)) c2_rows = nullptr;
+  EdgePsArgs a{edge_in, edge_out, node, np3, agg_out, fail, c2_rows, S, g, d, w};
   const bool gram = g.pt_gram != 0 && f16;
   if (!f16) pair_rows = false;
   const size_t lds = ps_lds(g.pt_max_out_rows, g.pt_max_in_rows, gram).total;
@@ -1368,6 +1394,9 @@ void launch_edge_ps(const float *edge_in, float *edge_out, const float *node, co
                                   : (pad ? &edge_block_ps_kernel<true, false, true> : &edge_block_ps_kernel<false, false, true>))
                      : (pair_rows ? (pad ? &edge_block_ps_kernel<true, true, false> : &edge_block_ps_kernel<false, true, false>)
                                   : (pad ? &edge_block_ps_kernel<true, false, false> : &edge_block_ps_kernel<false, false, false>));
+#if RN_PS_LG8
+  if (c2_rows) kern = pad ? &edge_block_ps_kernel<true, true, false, true, true> : &edge_block_ps_kernel<false, true, false, true, true>;
+#endif
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   static int cus = 0;
   if (cus == 0) {

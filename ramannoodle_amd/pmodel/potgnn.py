@@ -1144,7 +1144,7 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
                 "split_f16_mfma": bool(flags & 4), "narrow_kernels": bool(flags & 8),
                 "mfma_range_fallback": bool(flags & 16),
                 "role_split_edge_block": bool(flags & 256), "atom_owning_node_block": bool(flags & 512),
-                "split_f16_pair_rows": bool(flags & 1024)}
+                "split_f16_pair_rows": bool(flags & 1024), "c2_per_atom_pair": bool(flags & 2048)}
 
     def set_profiling(self, mode: int) -> None:
         """0 = off, 1 = HIP-event timing of every kernel launch, 100+k = kernel k only."""
