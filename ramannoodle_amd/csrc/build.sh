@@ -20,6 +20,7 @@ for f in $hip_srcs; do
      [ "$here/kernels.hpp" -nt "$o" ] || [ "$here/device_utils.hpp" -nt "$o" ] || \
      [ "$here/graph_plan.hpp" -nt "$o" ] || [ "$here/weight_layout.hpp" -nt "$o" ] || \
      [ "$here/spectrum_common.hpp" -nt "$o" ] || [ "$here/spectrum_segment_core.hpp" -nt "$o" ] || \
+     [ "$here/spectrum_steps.hpp" -nt "$o" ] || \
      [ "$here/../../include/rn_potgnn.h" -nt "$o" ]; then
     extra=""
     # (the two kernels with hand-counted vmcnt waits keep their assembly listing for tools/check_ps_isa.py, below)

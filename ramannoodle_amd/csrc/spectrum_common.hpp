@@ -1,8 +1,10 @@
 // What the on-device MD spectrum reducers share (spectrum.hip, spectrum_polarized.hip, spectrum_partial.hip,
-// spectrum_segments.hip, spectrum_ensemble.hip, spectrum_vdos.hip): the hipFFT loader, the series-length arithmetic, RAII holders for plans and device buffers, the
-// most-recently-used plan cache, the argument / device check, the host-or-HBM source of a call and the two per-slot
-// kernels of the polarized, partial and segment pipelines.  Each reducer keeps its own signal builder, power /
-// contraction kernel, plans struct, workspace arithmetic and pipeline.
+// spectrum_segments.hip, spectrum_ensemble.hip, spectrum_vdos.hip, spectrum_mode_vdos.hip): the hipFFT loader, the
+// series-length arithmetic, RAII holders for plans and device buffers, the most-recently-used plan cache, the argument /
+// device check, the host-or-HBM source of a call and the two per-slot kernels of the polarized, partial and segment
+// pipelines.  The three whole-run reducers each keep their own signal builder, power / contraction kernel, plans struct,
+// workspace arithmetic and pipeline; the segment reducers (the last four files) share those through
+// spectrum_segment_core.hpp, and the two that read positions share their front end through spectrum_steps.hpp.
 //
 // Two decisions that hold for every reducer:
 //  * Buffer sizing.  A buffer that `workspace_limit` counts (the weights, the taper, the polarized output block, and the fixed
@@ -10,11 +12,11 @@
 //    cached entry never holds more than the limit of the call that uses it.  The staged copies of a host input
 //    (`alpha`, `incr`) are outside the accounting by rn_potgnn.h's own words and use Fit::kGrowOnly.
 //  * Shrink and retry.  The polarized reducer shrinks G (pairs per group, then balanced over ceil(21/G) groups), the
-//    partial reducer shrinks B (rows per block, capped by the row count) and the segment reducer shrinks B and R
-//    (segments and rows per block) together, as do the start-table reducers of spectrum_ensemble.hip through the same
-//    spectrum_segment_core.hpp; they differ in the key, the balancing, the
-//    per-slot cost and what the leftover bytes are used for, and share only "make, measure the work areas, drop".
-//    So each keeps its own loop over the shared cache and arithmetic below.
+//    partial reducer shrinks B (rows per block, capped by the row count) and the segment reducers shrink B and R
+//    (segments and rows per block) together.  The three differ in the key, the balancing, the per-slot cost and what
+//    the leftover bytes are used for, and share only "make, measure the work areas, drop": the polarized and the partial
+//    reducer each keep their own loop over the shared cache and arithmetic below.  The segment reducers have one loop,
+//    get_segment_plans of spectrum_segment_core.hpp, which takes the block chooser as a callable.
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>

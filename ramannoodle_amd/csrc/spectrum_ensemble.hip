@@ -34,7 +34,6 @@ using rn::kMaxGroups;
 
 constexpr int kPairTile = 8;  // rows per thread of the atom-group power kernels (blockIdx.y)
 constexpr int kFormSize = kComponents * kComponents;
-constexpr int64_t kMaxTableSegments = (int64_t)1 << 31;
 
 // build_segments_kernel of spectrum_segments.hip with the segment's first step read from starts[q0 + b]
 __global__ void build_segments_at_kernel(const double *__restrict__ alpha, const double *__restrict__ tau, int64_t n,
@@ -186,24 +185,6 @@ __global__ void __launch_bounds__(kPowerThreads)
 
 PlanCache<SegmentPlans> g_ensemble_cache;  // apart from the caches of the other four reducers
 
-// the checks both entry pairs make before any device work, after their own pointers and sizes: W frames per segment of
-// a series of `frames` frames, Q starts, each with 0 <= starts[q] <= frames - W
-int check_table(int64_t frames, int64_t W, const int64_t *starts, int64_t Q, int64_t K, int average, int64_t bins) {
-  if (K < 1 || K > ((int64_t)1 << 40)) return RN_ERR_INVALID_ARGUMENT;
-  if (W < 3 || W > frames || Q < 1 || Q > kMaxTableSegments) return RN_ERR_INVALID_ARGUMENT;
-  if (bins != num_bins(W - 1) || (average != 0 && average != 1)) return RN_ERR_INVALID_ARGUMENT;
-  for (int64_t q = 0; q < Q; ++q)
-    if (starts[q] < 0 || starts[q] > frames - W) return RN_ERR_INVALID_ARGUMENT;
-  return RN_OK;
-}
-
-// the start table -> s.starts
-int upload_starts(SegmentPlans &s, const int64_t *starts, int64_t Q) {
-  if (int rc = s.starts.ensure((size_t)Q * sizeof(int64_t))) return rc;
-  return hipMemcpy(s.starts.ptr, starts, (size_t)Q * sizeof(int64_t), hipMemcpyHostToDevice) == hipSuccess ? RN_OK
-                                                                                                             : RN_ERR_HIP;
-}
-
 // the bytes of a call besides its blocks: the taper, the weights and the start table
 size_t base_bytes(int64_t n, int64_t K, int64_t Q) {
   return (size_t)n * sizeof(double) + (size_t)K * kPairs * sizeof(double) + (size_t)Q * sizeof(int64_t);
@@ -217,7 +198,8 @@ int md_raman_segments_at(Source src, int64_t S, int64_t W, const int64_t *starts
   for (const void *q : {(const void *)src.data, (const void *)starts, (const void *)taper, (const void *)weights,
                         (const void *)intensities})
     if (!q) return RN_ERR_INVALID_ARGUMENT;
-  int rc = check_table(S, W, starts, Q, K, average, bins);
+  if (K < 1 || K > ((int64_t)1 << 40)) return RN_ERR_INVALID_ARGUMENT;
+  int rc = check_table(S, W, starts, Q, average, bins);
   if (rc != RN_OK) return rc;
   const int64_t n = W - 1;
   rc = check_call({src.data, taper, weights, intensities}, n, bins, device);
@@ -232,7 +214,7 @@ int md_raman_segments_at(Source src, int64_t S, int64_t W, const int64_t *starts
   SegmentPlans &s = *sp;
   if ((rc = src.on_device(s.source, (size_t)S * 9 * sizeof(double), &d_alpha)) != RN_OK) return rc;
   if ((rc = upload_taper_and_weights(s, taper, weights, K)) != RN_OK) return rc;
-  if ((rc = upload_starts(s, starts, Q)) != RN_OK) return rc;
+  if ((rc = upload(s.starts, starts, (size_t)Q)) != RN_OK) return rc;
   auto build = [&](int64_t q0, int count) {
     build_segments_at_kernel<<<dim3(blocks_of_256(s.L), (unsigned)s.B), 256>>>(
         d_alpha, s.tau.as<const double>(), s.n, s.L, s.starts.as<const int64_t>(), q0, count,
@@ -249,7 +231,8 @@ int md_raman_partial_segments(Source src, int64_t N, int G, int64_t W, const int
                         (const void *)intensities})
     if (!q) return RN_ERR_INVALID_ARGUMENT;
   if (G < 1 || G > kMaxGroups || N < 1 || N > (int64_t)1 << 40) return RN_ERR_INVALID_ARGUMENT;
-  int rc = check_table(N + 1, W, starts, Q, K, average, bins);  // N increments join N + 1 frames
+  if (K < 1 || K > ((int64_t)1 << 40)) return RN_ERR_INVALID_ARGUMENT;
+  int rc = check_table(N + 1, W, starts, Q, average, bins);  // N increments join N + 1 frames
   if (rc != RN_OK) return rc;
   const int64_t n = W - 1;
   rc = check_call({src.data, taper, weights, intensities}, n, bins, device);
@@ -266,7 +249,7 @@ int md_raman_partial_segments(Source src, int64_t N, int G, int64_t W, const int
   SegmentPlans &s = *sp;
   if ((rc = src.on_device(s.source, (size_t)N * G * 9 * sizeof(double), &d_incr)) != RN_OK) return rc;
   if ((rc = upload_taper_and_weights(s, taper, weights, K)) != RN_OK) return rc;
-  if ((rc = upload_starts(s, starts, Q)) != RN_OK) return rc;
+  if ((rc = upload(s.starts, starts, (size_t)Q)) != RN_OK) return rc;
   auto *x = s.x.as<hipfftDoubleComplex>(), *p = s.p.as<hipfftDoubleComplex>();
   const auto *w = s.w.as<const double>();
   const unsigned gl = (unsigned)((s.L + kPowerThreads - 1) / kPowerThreads);

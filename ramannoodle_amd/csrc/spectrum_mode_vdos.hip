@@ -41,13 +41,11 @@
 // series = rows = Mb.  Modes are independent, so every row's arithmetic is the same whatever Mb and B are.
 // float64 throughout.  A plan cache of its own, keyed by (device, n, Mb, B, R).  All work runs on the null stream (after
 // a synchronise of the caller's stream in the _device entry).
-// The step arithmetic is a second copy of build_series_kernel's (spectrum_vdos.hip): there a lane owns a step and reads
-// two staged frames from LDS, here a thread owns an atom's eight steps and keeps nine frames in registers, so that the
-// loads overlap the products.  The two share the formulae and not the code; the VDOS kernel is untouched.
-#include <cmath>
-#include <vector>
-
-#include "spectrum_segment_core.hpp"
+// What this reducer shares with spectrum_vdos.hip is in spectrum_steps.hpp: the entry front end, the staging of
+// positions and lattices and the plans entry that holds the staged lattices.  The step arithmetic is written out in
+// both kernels (spectrum_steps.hpp says why): there a lane owns a step and reads two staged frames from LDS, here a
+// thread owns an atom's eight steps and keeps nine frames in registers, so that the loads overlap the products.
+#include "spectrum_steps.hpp"
 
 namespace {
 using namespace rn_spectrum;
@@ -62,7 +60,6 @@ constexpr int kProjectThreads = 256;
 constexpr int kStepsPerThread = kTileSteps / (kProjectThreads / kTileAtoms);  // steps an atom's thread makes per tile
 constexpr int kDiagThreads = 256;
 constexpr int64_t kMaxModesPerBlock = (int64_t)kTileModes * 65535;  // gridDim.y of the projection kernel
-constexpr int64_t kMaxTableSegments = (int64_t)1 << 31;
 
 typedef double f64x4_t __attribute__((ext_vector_type(4)));
 
@@ -215,46 +212,10 @@ __global__ void __launch_bounds__(kDiagThreads)
   *out = make_double2(acc, 0.0);
 }
 
-// the core's plans and buffers (series = rows = Mb; the weighted vectors are in `w`), apart from the other reducers' caches
-SegmentCache g_mode_cache;
-DeviceBuffer g_mode_lattices;  // the staged copy of host lattices (outside the accounting, like `source`); under the mutex
-
-// HIP-event times of the phases of the most recent call, kept only while rn_md_mode_vdos_set_profiling(1) holds.  The
-// shared driver launches the transforms and the back half itself, so a phase lasts from its mark to the next one.
-struct PhaseTimer {
-  bool enabled = false;
-  double millis[4] = {0, 0, 0, 0};  // projection, forward FFTs, power kernel, back half
-  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> spans;
-  bool open = false;
-  void close() {
-    if (enabled && open) (void)hipEventRecord(spans.back().second.second, nullptr);
-    open = false;
-  }
-  void mark(int phase) {
-    if (!enabled) return;
-    close();
-    hipEvent_t a, b;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-    (void)hipEventRecord(a, nullptr);
-    spans.push_back({phase, {a, b}});
-    open = true;
-  }
-  void reset() {
-    for (double &v : millis) v = 0.0;
-  }
-  void collect() {  // after the call's last copy to the host: every event has completed
-    close();
-    (void)hipDeviceSynchronize();
-    for (auto &s : spans) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, s.second.first, s.second.second) == hipSuccess) millis[s.first] += ms;
-      (void)hipEventDestroy(s.second.first);
-      (void)hipEventDestroy(s.second.second);
-    }
-    spans.clear();
-  }
-};
-PhaseTimer g_timer;  // under g_mode_cache.mutex
+// the plans and buffers of spectrum_steps.hpp (series = rows = Mb; the weighted vectors are in `w`), apart from the other
+// reducers' caches
+PlanCache<StepPlans> g_mode_cache;
+PhaseTimer g_timer;  // projection, forward FFTs, power kernel, back half; under g_mode_cache.mutex
 
 // the most modes per block whose series and rows of one segment fit `avail` bytes and the caps of the core; 0: not one
 int64_t modes_per_block(size_t avail, int64_t L, int64_t bins, int64_t M) {
@@ -263,12 +224,6 @@ int64_t modes_per_block(size_t avail, int64_t L, int64_t bins, int64_t M) {
   const int64_t most = std::min<int64_t>(
       {M, kMaxModesPerBlock, kMaxRows, std::max<int64_t>(1, (int64_t)(kMaxBlockBytes / ((size_t)L * cz)))});
   return std::min<int64_t>(most, (int64_t)(avail / per_mode));
-}
-
-template <class T>
-int upload(DeviceBuffer &buffer, const T *host, size_t count) {
-  if (int rc = buffer.ensure(count * sizeof(T))) return rc;
-  return hipMemcpy(buffer.ptr, host, count * sizeof(T), hipMemcpyHostToDevice) == hipSuccess ? RN_OK : RN_ERR_HIP;
 }
 
 // d_pos: device float64[S][N][3], d_lat: device float64[1 or S][9], s.w: vw[M][3N] -> out: host [M][bins] (average) or
@@ -322,33 +277,20 @@ int mode_vdos_on_device(SegmentPlans &s, const double *d_pos, const double *d_la
 int md_mode_vdos(Source pos, Source lat, int64_t num_lattices, int64_t S, int32_t N, const double *masses,
                  const double *vectors, int32_t M, int64_t W, const int64_t *starts, int64_t Q, const double *taper,
                  int average, int device, size_t workspace_limit, double *densities, int64_t bins) {
-  for (const void *q : {(const void *)pos.data, (const void *)lat.data, (const void *)masses, (const void *)vectors,
-                        (const void *)starts, (const void *)taper, (const void *)densities})
-    if (!q) return RN_ERR_INVALID_ARGUMENT;
-  if (N < 1 || M < 1 || (int64_t)M > 3 * (int64_t)N) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 1 || S > ((int64_t)1 << 40) || (num_lattices != 1 && num_lattices != S)) return RN_ERR_INVALID_ARGUMENT;
-  if (W < 3 || W > S || Q < 1 || Q > kMaxTableSegments) return RN_ERR_INVALID_ARGUMENT;
-  if (bins != num_bins(W - 1) || (average != 0 && average != 1)) return RN_ERR_INVALID_ARGUMENT;
-  for (int64_t q = 0; q < Q; ++q)
-    if (starts[q] < 0 || starts[q] > S - W) return RN_ERR_INVALID_ARGUMENT;
-  for (int32_t i = 0; i < N; ++i)
-    if (!(std::isfinite(masses[i]) && masses[i] > 0.0)) return RN_ERR_INVALID_ARGUMENT;
+  if (!vectors || M < 1 || (int64_t)M > 3 * (int64_t)N) return RN_ERR_INVALID_ARGUMENT;
   const int64_t K3 = 3 * (int64_t)N;
   for (int64_t j = 0; j < (int64_t)M * K3; ++j)
     if (!std::isfinite(vectors[j])) return RN_ERR_INVALID_ARGUMENT;
-  const int64_t n = W - 1;
-  int rc = check_call({pos.data, lat.data, taper, densities}, n, bins, device);
+  int64_t n = 0;
+  std::vector<double> sqrt_mass;
+  int rc = begin_step_call(pos, lat, num_lattices, S, N, masses, W, starts, Q, taper, average, device, bins, densities,
+                           &n, &sqrt_mass);
   if (rc != RN_OK || bins == 0) return rc;
-  if ((rc = pos.wait()) != RN_OK || (rc = lat.wait()) != RN_OK) return rc;
 
   // sqrt(m) folded into the vectors, once per call
   std::vector<double> vw((size_t)M * K3);
-  {
-    std::vector<double> sqrt_mass(N);
-    for (int32_t i = 0; i < N; ++i) sqrt_mass[i] = std::sqrt(masses[i]);
-    for (int64_t k = 0; k < M; ++k)
-      for (int64_t j = 0; j < K3; ++j) vw[k * K3 + j] = vectors[k * K3 + j] * sqrt_mass[j / 3];
-  }
+  for (int64_t k = 0; k < M; ++k)
+    for (int64_t j = 0; j < K3; ++j) vw[k * K3 + j] = vectors[k * K3 + j] * sqrt_mass[j / 3];
 
   const int64_t L = padded_length(n);
   const size_t limit = workspace_limit ? workspace_limit : kDefaultWorkspace;
@@ -358,7 +300,7 @@ int md_mode_vdos(Source pos, Source lat, int64_t num_lattices, int64_t S, int32_
   std::lock_guard<std::mutex> lock(g_mode_cache.mutex);
   int64_t most = modes_per_block(limit - base, L, bins, M);
   if (most < 1) return RN_ERR_OUT_OF_MEMORY;
-  SegmentPlans *sp = nullptr;
+  StepPlans *sp = nullptr;
   for (;;) {  // (the plans' work areas may not fit beside the largest block: halve it)
     const int Mb = (int)balanced(M, most);
     rc = get_segment_plans(g_mode_cache, device, n, Mb, Q, Mb, average, limit, base, &sp);
@@ -366,16 +308,14 @@ int md_mode_vdos(Source pos, Source lat, int64_t num_lattices, int64_t S, int32_
     most = (most + 1) / 2;
   }
   if (rc != RN_OK) return rc;
-  SegmentPlans &s = *sp;
+  StepPlans &s = *sp;
   const double *d_pos = nullptr, *d_lat = nullptr;
-  if ((rc = pos.on_device(s.source, (size_t)S * K3 * sizeof(double), &d_pos)) != RN_OK) return rc;
-  if ((rc = lat.on_device(g_mode_lattices, (size_t)num_lattices * 9 * sizeof(double), &d_lat)) != RN_OK) return rc;
-  if ((rc = upload(s.tau, taper, (size_t)n)) != RN_OK || (rc = upload(s.starts, starts, (size_t)Q)) != RN_OK ||
+  if ((rc = stage_step_call(s, pos, lat, num_lattices, S, N, taper, starts, Q, &d_pos, &d_lat)) != RN_OK ||
       (rc = upload(s.w, vw.data(), vw.size())) != RN_OK)
     return rc;
   g_timer.reset();
   rc = mode_vdos_on_device(s, d_pos, d_lat, num_lattices != 1, K3, M, Q, average, densities);
-  if (g_timer.enabled) g_timer.collect();
+  g_timer.collect();
   return rc;
 }
 
@@ -400,15 +340,7 @@ extern "C" int rn_md_mode_vdos_device(const double *d_positions, const double *d
 }
 
 extern "C" int rn_md_mode_vdos_set_profiling(int enabled) {
-  std::lock_guard<std::mutex> lock(g_mode_cache.mutex);
-  g_timer.enabled = enabled != 0;
-  g_timer.reset();
-  return RN_OK;
+  return g_timer.set_profiling(g_mode_cache.mutex, enabled);
 }
 
-extern "C" int rn_md_mode_vdos_phase_times(double *millis) {
-  if (!millis) return RN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lock(g_mode_cache.mutex);
-  std::copy_n(g_timer.millis, 4, millis);
-  return RN_OK;
-}
+extern "C" int rn_md_mode_vdos_phase_times(double *millis) { return g_timer.phase_times(g_mode_cache.mutex, millis); }

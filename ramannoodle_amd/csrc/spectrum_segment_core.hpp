@@ -1,9 +1,12 @@
 // What the segment reducers share (spectrum_segments.hip: segments on a hop grid; spectrum_ensemble.hip: segments from a
-// start table, whole and by atom group; spectrum_vdos.hip: the density of states, which takes the plans and the back half):
-// the two power kernels of the whole spectra, the plans and work buffers of one
-// (device, n, series per segment, segments per block, rows per block), the workspace arithmetic that chooses the two
-// block sizes, and the pipeline from the transformed segments to the host rows.  A reducer brings its segment builder
-// (and, for the atom-group form, its own power kernels) and its own PlanCache, so the caches stay apart.
+// start table, whole and by atom group; spectrum_vdos.hip: the density of states, which takes the plans and the back
+// half; spectrum_mode_vdos.hip: the density of states by mode): the two power kernels of the whole spectra, the plans and
+// work buffers of one (device, n, series per segment, segments per block, rows per block), the workspace arithmetic
+// that chooses the two block sizes, the loop that fits plans of those sizes into a workspace limit (get_segment_plans,
+// for any block chooser), and the pipeline from the transformed segments to the host rows; for the start-table reducers
+// also the check of the table, the upload helper and the phase timer.  A reducer brings its segment builder (and, but
+// for the whole spectra, its own power kernels) and its own PlanCache, so the caches stay apart.  What only the two
+// reducers that read positions share is in spectrum_steps.hpp.
 //
 // A segment is `series` zero-padded real series of length L (6 components; 6 G for G atom groups) and yields `rows` rows
 // (K configurations; K G(G+1)/2 for the atom-group form).  Per block of B segments:
@@ -15,6 +18,9 @@
 // When the rows of pbar do not fit (rows > R), they go through in blocks of R; if the segments do not fit one block either
 // (Q > B), they are transformed again for every block of rows.
 #pragma once
+#include <utility>
+#include <vector>
+
 #include "spectrum_common.hpp"
 
 namespace rn_spectrum {
@@ -24,6 +30,7 @@ constexpr int kRowTile = 16;                              // rows per thread of 
 constexpr int64_t kMaxSegments = 4096;                    // segments per block (gridDim.y of the builder)
 constexpr int64_t kMaxRows = 32768;                       // rows per block (gridDim.y of the slot kernels)
 constexpr size_t kMaxBlockBytes = (size_t)512 << 20;      // x and p are each kept below this
+constexpr int64_t kMaxTableSegments = (int64_t)1 << 31;   // starts of a start table
 
 // Re(X_j conj X_l) of the 21 pairs at one frequency of one segment
 __device__ inline void pair_powers(const hipfftDoubleComplex *__restrict__ x, int64_t L, int64_t b, int64_t f,
@@ -114,7 +121,6 @@ struct SegmentPlans {
   size_t fixed_bytes = 0;  // x + p + out + the plans' work areas
   FftPlan plan_x, plan_inv, plan_n;
 };
-using SegmentCache = PlanCache<SegmentPlans>;
 
 // the bytes of B segments' series and R rows' slots and bins, besides the plans' work areas
 inline size_t segment_buffer_bytes(int64_t L, int64_t bins, int series, int64_t B, int64_t R) {
@@ -177,16 +183,19 @@ inline bool choose_segment_blocks(size_t avail, int64_t L, int64_t bins, int ser
   return true;
 }
 
-// finds or creates the entry whose blocks fit `limit` beside `base` bytes (the taper, the weights, a start table)
-inline int get_segment_plans(SegmentCache &cache, int device, int64_t n, int series, int64_t Q, int64_t rows, int average,
-                             size_t limit, size_t base, SegmentPlans **out) {
+// Finds or creates the entry whose blocks fit `limit` beside `base` bytes (the taper, the weights, a start table, a
+// reducer's own arrays).  choose(avail, &series, &B, &R) sets the block sizes for `avail` bytes, or returns false when
+// not one block fits; it is asked again, with less, while the plans' work areas do not fit beside the buffers.
+template <class Entry, class Choose>
+int get_segment_plans(PlanCache<Entry> &cache, int device, int64_t n, size_t limit, size_t base, Choose choose,
+                      Entry **out) {
   const int64_t L = padded_length(n), bins = num_bins(n);
   if (limit <= base) return RN_ERR_OUT_OF_MEMORY;
   size_t avail = limit - base;
   for (int attempt = 0; attempt < 4; ++attempt) {
-    int B = 0, R = 0;
-    if (!choose_segment_blocks(avail, L, bins, series, Q, rows, average, &B, &R)) return RN_ERR_OUT_OF_MEMORY;
-    SegmentPlans *s = cache.find([&](const SegmentPlans &e) {
+    int series = 0, B = 0, R = 0;
+    if (!choose(avail, &series, &B, &R)) return RN_ERR_OUT_OF_MEMORY;
+    Entry *s = cache.find([&](const Entry &e) {
       return e.device == device && e.n == n && e.series == series && e.B == B && e.R == R;
     });
     if (!s) {
@@ -207,16 +216,97 @@ inline int get_segment_plans(SegmentCache &cache, int device, int64_t n, int ser
   return RN_ERR_OUT_OF_MEMORY;
 }
 
+// ... with choose_segment_blocks: Q segments of `series` series and `rows` rows each
+template <class Entry>
+int get_segment_plans(PlanCache<Entry> &cache, int device, int64_t n, int series, int64_t Q, int64_t rows, int average,
+                      size_t limit, size_t base, Entry **out) {
+  const int64_t L = padded_length(n), bins = num_bins(n);
+  auto choose = [&](size_t avail, int *s, int *B, int *R) {
+    *s = series;
+    return choose_segment_blocks(avail, L, bins, series, Q, rows, average, B, R);
+  };
+  return get_segment_plans(cache, device, n, limit, base, choose, out);
+}
+
+// host[count] -> buffer, sized to fit exactly (a buffer that `workspace_limit` counts); a blocking copy
+template <class T>
+int upload(DeviceBuffer &buffer, const T *host, size_t count) {
+  if (int rc = buffer.ensure(count * sizeof(T))) return rc;
+  return hipMemcpy(buffer.ptr, host, count * sizeof(T), hipMemcpyHostToDevice) == hipSuccess ? RN_OK : RN_ERR_HIP;
+}
+
 // the taper (host [n]) and the weights (host [K][21]) of a call -> s.tau, s.w
 inline int upload_taper_and_weights(SegmentPlans &s, const double *taper, const double *weights, int64_t K) {
-  int rc;
-  if ((rc = s.tau.ensure((size_t)s.n * sizeof(double))) != RN_OK) return rc;
-  if ((rc = s.w.ensure((size_t)K * kPairs * sizeof(double))) != RN_OK) return rc;
-  if (hipMemcpy(s.tau.ptr, taper, (size_t)s.n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(s.w.ptr, weights, (size_t)K * kPairs * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-    return RN_ERR_HIP;
+  if (int rc = upload(s.tau, taper, (size_t)s.n)) return rc;
+  return upload(s.w, weights, (size_t)K * kPairs);
+}
+
+// The checks of a start table, after an entry's own pointers and sizes and before any device work: W frames per
+// segment of a series of `frames` frames, Q starts, each with 0 <= starts[q] <= frames - W.
+inline int check_table(int64_t frames, int64_t W, const int64_t *starts, int64_t Q, int average, int64_t bins) {
+  if (W < 3 || W > frames || Q < 1 || Q > kMaxTableSegments) return RN_ERR_INVALID_ARGUMENT;
+  if (bins != num_bins(W - 1) || (average != 0 && average != 1)) return RN_ERR_INVALID_ARGUMENT;
+  for (int64_t q = 0; q < Q; ++q)
+    if (starts[q] < 0 || starts[q] > frames - W) return RN_ERR_INVALID_ARGUMENT;
   return RN_OK;
 }
+
+// HIP-event times of the four phases of a reducer's most recent call (builder, forward FFTs, power kernel, back half),
+// kept only while profiling is on; one per reducer, under its cache's mutex.  A phase lasts from its mark to the next
+// mark or close, because run_segments launches the transforms and the back half itself.  A reducer that launches
+// everything itself (the VDOS) marks all the same: on the null stream, with nothing between the end of a phase and the
+// next mark, that is the span of a begin / end pair plus one event.
+struct PhaseTimer {
+  bool enabled = false;
+  double millis[4] = {0, 0, 0, 0};
+  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> spans;
+  bool open = false;
+  void close() {
+    if (enabled && open) (void)hipEventRecord(spans.back().second.second, nullptr);
+    open = false;
+  }
+  void mark(int phase) {
+    if (!enabled) return;
+    close();
+    hipEvent_t a, b;
+    if (hipEventCreate(&a) != hipSuccess) return;
+    if (hipEventCreate(&b) != hipSuccess) {
+      (void)hipEventDestroy(a);
+      return;
+    }
+    (void)hipEventRecord(a, nullptr);
+    spans.push_back({phase, {a, b}});
+    open = true;
+  }
+  void reset() {
+    for (double &v : millis) v = 0.0;
+  }
+  void collect() {  // after the call's last copy to the host
+    if (!enabled) return;
+    close();
+    (void)hipDeviceSynchronize();
+    for (auto &s : spans) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, s.second.first, s.second.second) == hipSuccess) millis[s.first] += ms;
+      (void)hipEventDestroy(s.second.first);
+      (void)hipEventDestroy(s.second.second);
+    }
+    spans.clear();
+  }
+  // the bodies of a reducer's two extern "C" profiling entries
+  int set_profiling(std::mutex &mutex, int on) {
+    std::lock_guard<std::mutex> lock(mutex);
+    enabled = on != 0;
+    reset();
+    return RN_OK;
+  }
+  int phase_times(std::mutex &mutex, double *out) {
+    if (!out) return RN_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(mutex);
+    std::copy_n(millis, 4, out);
+    return RN_OK;
+  }
+};
 
 // slots of s.p (powers, `count` of them real) -> out: host float64[count][bins]
 inline int segment_rows_to_host(SegmentPlans &s, int count, double *out) {

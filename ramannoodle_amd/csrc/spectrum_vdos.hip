@@ -33,11 +33,8 @@
 // sizes.  When G rows do not fit either, the groups go through in blocks and the series are transformed again for each.
 // float64 throughout.  A plan cache of its own, keyed by (device, n, 3 A, B, slots).  All work runs on the null stream
 // (after a synchronise of the caller's stream in the _device entry).
-#include <cmath>
-#include <vector>
-
 #include "kernels.hpp"
-#include "spectrum_segment_core.hpp"
+#include "spectrum_steps.hpp"
 
 namespace {
 using namespace rn_spectrum;
@@ -50,7 +47,6 @@ constexpr int kTileStride = kTileCols + 1;      // LDS row stride in doubles (od
 constexpr int kBuilderThreads = 256;
 constexpr int kGroupPowerThreads = 64;          // one wave per workgroup: L / 64 workgroups per slot
 constexpr int64_t kMaxAtomsPerBlock = (int64_t)kTileAtoms * 65535;  // gridDim.y of the builder
-constexpr int64_t kMaxTableSegments = (int64_t)1 << 31;
 
 // segment b = blockIdx.z of the block (segments q0 .. q0+count-1), atoms a0 .. a0+ac-1 (slot a - a0 of the A slots):
 // x[b][a - a0][c][t] = tau[t] sqrt_mass[a] u[starts[q0+b] + t][a][c] for t < n; zero for n <= t < L and for b >= count
@@ -146,42 +142,12 @@ __global__ void __launch_bounds__(kGroupPowerThreads)
   *out = make_double2(acc, 0.0);
 }
 
-// the core's plans and buffers (series = 3 A) and what this reducer adds to them
-struct VdosPlans : SegmentPlans {
-  DeviceBuffer lattices;  // the staged copy of host lattices (outside the accounting, like `source`)
-  DeviceBuffer list;      // atom indices sorted by group, int32[N]; the square roots of the masses are in `w`
+// the plans and buffers of spectrum_steps.hpp (series = 3 A) and what this reducer adds to them
+struct VdosPlans : StepPlans {
+  DeviceBuffer list;  // atom indices sorted by group, int32[N]; the square roots of the masses are in `w`
 };
 PlanCache<VdosPlans> g_vdos_cache;  // apart from the caches of the other reducers
-
-// HIP-event times of the phases of the most recent call, kept only while rn_md_vdos_set_profiling(1) holds
-struct PhaseTimer {
-  bool enabled = false;
-  double millis[4] = {0, 0, 0, 0};  // builder, forward FFTs, power kernel, back half
-  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> spans;
-  void begin(int phase) {
-    if (!enabled) return;
-    hipEvent_t a, b;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-    (void)hipEventRecord(a, nullptr);
-    spans.push_back({phase, {a, b}});
-  }
-  void end() {
-    if (enabled && !spans.empty()) (void)hipEventRecord(spans.back().second.second, nullptr);
-  }
-  void reset() {
-    for (double &v : millis) v = 0.0;
-  }
-  void collect() {  // after the call's last copy to the host: every event has completed
-    for (auto &s : spans) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, s.second.first, s.second.second) == hipSuccess) millis[s.first] += ms;
-      (void)hipEventDestroy(s.second.first);
-      (void)hipEventDestroy(s.second.second);
-    }
-    spans.clear();
-  }
-};
-PhaseTimer g_timer;  // under g_vdos_cache.mutex
+PhaseTimer g_timer;                 // builder, forward FFTs, power kernel, back half; under g_vdos_cache.mutex
 
 // A atoms and B segments per block and the slots of p (groups per block gr: slots = gr, or B gr for average = 0) for
 // `avail` bytes; false when one atom of one segment and one row do not fit
@@ -210,49 +176,6 @@ bool choose_vdos_blocks(size_t avail, int64_t L, int64_t bins, int64_t N, int G,
     b = std::min<int64_t>({b, (int64_t)(avail / (per_segment + (size_t)groups * per_row)), rows_most / groups});
   *B = (int)balanced(Q, std::max<int64_t>(1, b));
   return true;
-}
-
-size_t vdos_buffer_bytes(int64_t L, int64_t bins, int64_t A, int B, int slots) {
-  return segment_buffer_bytes(L, bins, (int)(3 * A), B, slots);
-}
-
-// finds or creates the entry whose blocks fit `limit` beside `base` bytes (the taper, the start table, the atom arrays)
-int get_vdos_plans(int device, int64_t n, int64_t N, int G, int64_t Q, int average, size_t limit, size_t base,
-                   int *groups_per_block, VdosPlans **out) {
-  const int64_t L = padded_length(n), bins = num_bins(n);
-  if (limit <= base) return RN_ERR_OUT_OF_MEMORY;
-  size_t avail = limit - base;
-  for (int attempt = 0; attempt < 4; ++attempt) {
-    int64_t A = 0;
-    int B = 0, gr = 0;
-    if (!choose_vdos_blocks(avail, L, bins, N, G, Q, average, &A, &B, &gr)) return RN_ERR_OUT_OF_MEMORY;
-    const int series = (int)(3 * A), slots = average ? gr : B * gr;
-    VdosPlans *s = g_vdos_cache.find([&](const VdosPlans &e) {
-      return e.device == device && e.n == n && e.series == series && e.B == B && e.R == slots;
-    });
-    if (!s) {
-      int rc = make_segment_plans(g_vdos_cache, device, n, series, B, slots, &s);
-      if (rc != RN_OK) return rc;
-    }
-    if (s->fixed_bytes + base <= limit) {
-      g_vdos_cache.trim();
-      *groups_per_block = gr;
-      *out = s;
-      return RN_OK;
-    }
-    // the plans' work areas do not fit beside the buffers: they shrink with the blocks, so set their bytes aside
-    const size_t work = s->fixed_bytes - vdos_buffer_bytes(L, bins, A, B, slots);
-    g_vdos_cache.drop_front();
-    if (limit - base <= work) return RN_ERR_OUT_OF_MEMORY;
-    avail = std::min(avail - 1, limit - base - work);
-  }
-  return RN_ERR_OUT_OF_MEMORY;
-}
-
-template <class T>
-int upload(DeviceBuffer &buffer, const T *host, size_t count) {
-  if (int rc = buffer.ensure(count * sizeof(T))) return rc;
-  return hipMemcpy(buffer.ptr, host, count * sizeof(T), hipMemcpyHostToDevice) == hipSuccess ? RN_OK : RN_ERR_HIP;
 }
 
 // d_pos: device float64[S][N][3], d_lat: device float64[1 or S][9] -> out: host [G][bins] (average) or [Q][G][bins]
@@ -285,26 +208,22 @@ int vdos_on_device(VdosPlans &s, int groups_per_block, const double *d_pos, cons
         }
         if (!any && !first) continue;  // none of the block's atoms is in these groups
         if (any) {
-          g_timer.begin(0);
+          g_timer.mark(0);
           build_series_kernel<<<dim3(tiles_t, (unsigned)((ac + kTileAtoms - 1) / kTileAtoms), (unsigned)B),
                                 kBuilderThreads>>>(d_pos, d_lat, per_frame, N, s.w.as<const double>(),
                                                    s.tau.as<const double>(), s.n, L, s.starts.as<const int64_t>(), q0,
                                                    count, a0, ac, A, x);
-          g_timer.end();
-          g_timer.begin(1);
-          const bool ok = s.plan_x.exec(x, HIPFFT_FORWARD);
-          g_timer.end();
-          if (!ok) return RN_ERR_HIP;
+          g_timer.mark(1);
+          if (!s.plan_x.exec(x, HIPFFT_FORWARD)) return RN_ERR_HIP;
         }
-        g_timer.begin(2);
+        g_timer.mark(2);
         group_power_kernel<<<dim3(power_x, (unsigned)s.R), kGroupPowerThreads>>>(
             x, L, A, a0, any ? count : 0, s.list.as<const int32_t>(), ranges, g0, gc, average,
             average ? 1.0 / (double)Q : 1.0, first, p);
-        g_timer.end();
         first = false;
       }
       if (average) continue;
-      g_timer.begin(3);
+      g_timer.mark(3);
       if (gc == G) {
         rc = segment_rows_to_host(s, count * G, out + q0 * G * bins);
       } else {
@@ -313,13 +232,13 @@ int vdos_on_device(VdosPlans &s, int groups_per_block, const double *d_pos, cons
         for (int b = 0; rc == RN_OK && b < count; ++b)
           std::copy_n(rows.data() + (size_t)b * gc * bins, (size_t)gc * bins, out + ((q0 + b) * G + g0) * bins);
       }
-      g_timer.end();
+      g_timer.close();
       if (rc != RN_OK) return rc;
     }
     if (average) {
-      g_timer.begin(3);
+      g_timer.mark(3);
       rc = segment_rows_to_host(s, gc, out + (int64_t)g0 * bins);
-      g_timer.end();
+      g_timer.close();
       if (rc != RN_OK) return rc;
     }
   }
@@ -330,23 +249,14 @@ int vdos_on_device(VdosPlans &s, int groups_per_block, const double *d_pos, cons
 int md_vdos(Source pos, Source lat, int64_t num_lattices, int64_t S, int32_t N, const double *masses,
             const int32_t *labels, int G, int64_t W, const int64_t *starts, int64_t Q, const double *taper, int average,
             int device, size_t workspace_limit, double *densities, int64_t bins) {
-  for (const void *q : {(const void *)pos.data, (const void *)lat.data, (const void *)masses, (const void *)labels,
-                        (const void *)starts, (const void *)taper, (const void *)densities})
-    if (!q) return RN_ERR_INVALID_ARGUMENT;
-  if (N < 1 || G < 1 || G > kMaxGroups) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 1 || S > ((int64_t)1 << 40) || (num_lattices != 1 && num_lattices != S)) return RN_ERR_INVALID_ARGUMENT;
-  if (W < 3 || W > S || Q < 1 || Q > kMaxTableSegments) return RN_ERR_INVALID_ARGUMENT;
-  if (bins != num_bins(W - 1) || (average != 0 && average != 1)) return RN_ERR_INVALID_ARGUMENT;
-  for (int64_t q = 0; q < Q; ++q)
-    if (starts[q] < 0 || starts[q] > S - W) return RN_ERR_INVALID_ARGUMENT;
+  if (!labels || G < 1 || G > kMaxGroups) return RN_ERR_INVALID_ARGUMENT;
   for (int32_t i = 0; i < N; ++i)
     if (labels[i] < 0 || labels[i] >= G) return RN_ERR_INVALID_ARGUMENT;
-  for (int32_t i = 0; i < N; ++i)
-    if (!(std::isfinite(masses[i]) && masses[i] > 0.0)) return RN_ERR_INVALID_ARGUMENT;
-  const int64_t n = W - 1;
-  int rc = check_call({pos.data, lat.data, taper, densities}, n, bins, device);
+  int64_t n = 0;
+  std::vector<double> sqrt_mass;
+  int rc = begin_step_call(pos, lat, num_lattices, S, N, masses, W, starts, Q, taper, average, device, bins, densities,
+                           &n, &sqrt_mass);
   if (rc != RN_OK || bins == 0) return rc;
-  if ((rc = pos.wait()) != RN_OK || (rc = lat.wait()) != RN_OK) return rc;
 
   // the atoms sorted by group, stably: ascending index within a group
   std::vector<int> group_begin(G + 1, 0);
@@ -357,8 +267,6 @@ int md_vdos(Source pos, Source lat, int64_t num_lattices, int64_t S, int32_t N, 
     std::vector<int> next(group_begin.begin(), group_begin.end() - 1);
     for (int32_t i = 0; i < N; ++i) list[next[labels[i]]++] = i;
   }
-  std::vector<double> sqrt_mass(N);
-  for (int32_t i = 0; i < N; ++i) sqrt_mass[i] = std::sqrt(masses[i]);
 
   const size_t limit = workspace_limit ? workspace_limit : kDefaultWorkspace;
   const size_t base = (size_t)n * sizeof(double) + (size_t)Q * sizeof(int64_t) +
@@ -366,22 +274,24 @@ int md_vdos(Source pos, Source lat, int64_t num_lattices, int64_t S, int32_t N, 
   std::lock_guard<std::mutex> lock(g_vdos_cache.mutex);
   VdosPlans *sp = nullptr;
   int groups_per_block = 0;
-  rc = get_vdos_plans(device, n, N, G, Q, average, limit, base, &groups_per_block, &sp);
-  if (rc != RN_OK) return rc;
+  const int64_t L = padded_length(n);
+  auto choose = [&](size_t avail, int *series, int *B, int *slots) {
+    int64_t A = 0;
+    if (!choose_vdos_blocks(avail, L, bins, N, G, Q, average, &A, B, &groups_per_block)) return false;
+    *series = (int)(3 * A);
+    *slots = average ? groups_per_block : *B * groups_per_block;
+    return true;
+  };
+  if ((rc = get_segment_plans(g_vdos_cache, device, n, limit, base, choose, &sp)) != RN_OK) return rc;
   VdosPlans &s = *sp;
   const double *d_pos = nullptr, *d_lat = nullptr;
-  if ((rc = pos.on_device(s.source, (size_t)S * N * 3 * sizeof(double), &d_pos)) != RN_OK) return rc;
-  if ((rc = lat.on_device(s.lattices, (size_t)num_lattices * 9 * sizeof(double), &d_lat)) != RN_OK) return rc;
-  if ((rc = upload(s.tau, taper, (size_t)n)) != RN_OK || (rc = upload(s.starts, starts, (size_t)Q)) != RN_OK ||
+  if ((rc = stage_step_call(s, pos, lat, num_lattices, S, N, taper, starts, Q, &d_pos, &d_lat)) != RN_OK ||
       (rc = upload(s.w, sqrt_mass.data(), (size_t)N)) != RN_OK || (rc = upload(s.list, list.data(), (size_t)N)) != RN_OK)
     return rc;
   g_timer.reset();
   rc = vdos_on_device(s, groups_per_block, d_pos, d_lat, num_lattices != 1, N, list, group_begin, G, Q, average,
                       densities);
-  if (g_timer.enabled) {
-    (void)hipDeviceSynchronize();
-    g_timer.collect();
-  }
+  g_timer.collect();
   return rc;
 }
 
@@ -403,16 +313,6 @@ extern "C" int rn_md_vdos_device(const double *d_positions, const double *d_latt
                  labels, G, segment_steps, starts, Q, taper, average, device, workspace_limit, densities, num_bins);
 }
 
-extern "C" int rn_md_vdos_set_profiling(int enabled) {
-  std::lock_guard<std::mutex> lock(g_vdos_cache.mutex);
-  g_timer.enabled = enabled != 0;
-  g_timer.reset();
-  return RN_OK;
-}
+extern "C" int rn_md_vdos_set_profiling(int enabled) { return g_timer.set_profiling(g_vdos_cache.mutex, enabled); }
 
-extern "C" int rn_md_vdos_phase_times(double *millis) {
-  if (!millis) return RN_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lock(g_vdos_cache.mutex);
-  std::copy_n(g_timer.millis, 4, millis);
-  return RN_OK;
-}
+extern "C" int rn_md_vdos_phase_times(double *millis) { return g_timer.phase_times(g_vdos_cache.mutex, millis); }

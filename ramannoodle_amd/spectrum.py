@@ -1345,10 +1345,11 @@ def _vdos_host(positions, lattices, masses, labels, num_groups: int, timestep: f
     return wavenumbers[keep], finish(mean / len(starts)) if average else rows
 
 
-def _vdos_on_device(positions, lattices, masses, labels, num_groups: int, timestep: float, width: int, starts, tau,
-                    average: bool, device: int, stream=None, workspace_limit: int = 0):
-    """(wavenumbers, ``D[G][bins]`` or ``D[Q][G][bins]``) from ``rn_md_vdos`` (host positions and lattices) or, with two
-    torch CUDA tensors, ``rn_md_vdos_device`` ordered after ``stream``."""
+def _step_reducer_on_device(entry: str, positions, lattices, masses, rows, count: int, timestep: float, width: int,
+                            starts, tau, average: bool, device: int, stream, workspace_limit: int):
+    """What ``rn_md_vdos`` and ``rn_md_mode_vdos`` share, argument for argument: ``rows`` is the reducer's own array, already
+    contiguous and typed (the labels; the vectors), ``count`` the number of rows it yields per segment (G; M).  Host
+    positions and lattices, or two torch CUDA tensors and the ``_device`` entry ordered after ``stream``."""
     import ctypes as C
     steps, atoms = int(positions.shape[0]), int(positions.shape[1])
     if stream is None:
@@ -1357,15 +1358,23 @@ def _vdos_on_device(positions, lattices, masses, labels, num_groups: int, timest
     else:
         lattice_pointer = lattices.data_ptr()
     masses = np.ascontiguousarray(masses, dtype=np.float64)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
     starts, table_args = _table_arguments(starts)
     tau = np.ascontiguousarray(tau, dtype=np.float64)
-    shape = (num_groups,) if average else (len(starts), num_groups)
+    shape = (count,) if average else (len(starts), count)
     return _call_md_reducer(
-        "rn_md_vdos", positions, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
+        entry, positions, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
         (C.c_void_p(lattice_pointer), int(lattices.shape[0]), steps, atoms, C.c_void_p(masses.ctypes.data),
-         C.c_void_p(labels.ctypes.data), num_groups, width, *table_args, C.c_void_p(tau.ctypes.data),
-         int(bool(average))), (workspace_limit,))
+         C.c_void_p(rows.ctypes.data), count, width, *table_args, C.c_void_p(tau.ctypes.data), int(bool(average))),
+        (workspace_limit,))
+
+
+def _vdos_on_device(positions, lattices, masses, labels, num_groups: int, timestep: float, width: int, starts, tau,
+                    average: bool, device: int, stream=None, workspace_limit: int = 0):
+    """(wavenumbers, ``D[G][bins]`` or ``D[Q][G][bins]``) from ``rn_md_vdos`` (host positions and lattices) or, with two
+    torch CUDA tensors, ``rn_md_vdos_device`` ordered after ``stream``."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    return _step_reducer_on_device("rn_md_vdos", positions, lattices, masses, labels, num_groups, timestep, width,
+                                   starts, tau, average, device, stream, workspace_limit)
 
 
 class VibrationalDensityOfStates:
@@ -1673,24 +1682,9 @@ def _mode_vdos_on_device(positions, lattices, masses, vectors, timestep: float, 
                          device: int, stream=None, workspace_limit: int = 0):
     """(wavenumbers, ``D[M][bins]`` or ``D[Q][M][bins]``) from ``rn_md_mode_vdos`` (host positions and lattices) or, with
     two torch CUDA tensors, ``rn_md_mode_vdos_device`` ordered after ``stream``."""
-    import ctypes as C
-    steps, atoms = int(positions.shape[0]), int(positions.shape[1])
-    if stream is None:
-        lattices = np.ascontiguousarray(lattices, dtype=np.float64)
-        lattice_pointer = lattices.ctypes.data
-    else:
-        lattice_pointer = lattices.data_ptr()
-    masses = np.ascontiguousarray(masses, dtype=np.float64)
     vectors = np.ascontiguousarray(vectors, dtype=np.float64)
-    starts, table_args = _table_arguments(starts)
-    tau = np.ascontiguousarray(tau, dtype=np.float64)
-    modes = int(vectors.shape[0])
-    shape = (modes,) if average else (len(starts), modes)
-    return _call_md_reducer(
-        "rn_md_mode_vdos", positions, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
-        (C.c_void_p(lattice_pointer), int(lattices.shape[0]), steps, atoms, C.c_void_p(masses.ctypes.data),
-         C.c_void_p(vectors.ctypes.data), modes, width, *table_args, C.c_void_p(tau.ctypes.data),
-         int(bool(average))), (workspace_limit,))
+    return _step_reducer_on_device("rn_md_mode_vdos", positions, lattices, masses, vectors, int(vectors.shape[0]),
+                                   timestep, width, starts, tau, average, device, stream, workspace_limit)
 
 
 class _ModeProjection:

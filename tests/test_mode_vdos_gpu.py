@@ -131,6 +131,36 @@ def test_repeated_calls_are_bit_identical_and_rows_follow_the_table():
     np.testing.assert_array_equal(_reduce(case, False, starts=case[-1][::-1].copy()), rows[::-1])
 
 
+def _phase_times(lib):
+    millis = (C.c_double * 4)(-1.0, -1.0, -1.0, -1.0)
+    assert lib.rn_md_mode_vdos_phase_times(millis) == _lib.RN_OK
+    return np.array(millis)
+
+
+@pytest.mark.parametrize("average", (True, False))
+def test_phase_times_are_kept_only_while_profiling(average):
+    """Several mode blocks of one segment, so that every phase runs more than once per call."""
+    lib = _lib.load()
+    case = _blocking_case()
+    limit = 64 * 8 + len(case[-1]) * 8 + 65 * 3 * 130 * 8 + 20 * (128 * 16 + 128 * 16 + 31 * 8)
+    plain = _reduce(case, average, limit)
+    np.testing.assert_array_equal(_phase_times(lib), np.zeros(4))
+    assert lib.rn_md_mode_vdos_set_profiling(1) == _lib.RN_OK
+    try:
+        t0 = time.perf_counter()
+        profiled = _reduce(case, average, limit)
+        wall_ms = 1e3 * (time.perf_counter() - t0)
+        millis = _phase_times(lib)
+    finally:
+        assert lib.rn_md_mode_vdos_set_profiling(0) == _lib.RN_OK
+    np.testing.assert_array_equal(profiled, plain)
+    print(f"projection, forward FFTs, power, back half: {millis} ms; the call took {wall_ms:.3f} ms")
+    assert np.isfinite(millis).all() and np.all(millis > 0)
+    assert millis.sum() <= wall_ms
+    np.testing.assert_array_equal(_phase_times(lib), np.zeros(4))
+    assert lib.rn_md_mode_vdos_phase_times(None) == _lib.RN_ERR_INVALID_ARGUMENT
+
+
 def test_raw_entry_checks():
     lib = _lib.load()
     steps, atoms, modes, width = 20, 4, 5, 9

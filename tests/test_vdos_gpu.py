@@ -120,6 +120,36 @@ def test_repeated_calls_are_bit_identical():
         np.testing.assert_array_equal(_reduce(case, average), first)
 
 
+def _phase_times(lib):
+    millis = (C.c_double * 4)(-1.0, -1.0, -1.0, -1.0)
+    assert lib.rn_md_vdos_phase_times(millis) == _lib.RN_OK
+    return np.array(millis)
+
+
+@pytest.mark.parametrize("average", (True, False))
+def test_phase_times_are_kept_only_while_profiling(average):
+    """Several atom blocks of one segment, so that every phase runs more than once per call."""
+    lib = _lib.load()
+    case = _blocking_case()
+    limit = 64 * 8 + len(case[-1]) * 8 + 130 * 12 + 2 * (128 * 16 + 31 * 8) + 40 * (3 * 128 * 16)
+    plain = _reduce(case, average, limit)
+    np.testing.assert_array_equal(_phase_times(lib), np.zeros(4))
+    assert lib.rn_md_vdos_set_profiling(1) == _lib.RN_OK
+    try:
+        t0 = time.perf_counter()
+        profiled = _reduce(case, average, limit)
+        wall_ms = 1e3 * (time.perf_counter() - t0)
+        millis = _phase_times(lib)
+    finally:
+        assert lib.rn_md_vdos_set_profiling(0) == _lib.RN_OK
+    np.testing.assert_array_equal(profiled, plain)
+    print(f"builder, forward FFTs, power, back half: {millis} ms; the call took {wall_ms:.3f} ms")
+    assert np.isfinite(millis).all() and np.all(millis > 0)
+    assert millis.sum() <= wall_ms
+    np.testing.assert_array_equal(_phase_times(lib), np.zeros(4))
+    assert lib.rn_md_vdos_phase_times(None) == _lib.RN_ERR_INVALID_ARGUMENT
+
+
 def test_single_segment_and_start_table():
     f, lattice, masses, labels = _run(50, 5, 3)
     vdos = VibrationalDensityOfStates(f, DT, lattice, masses, labels, 3)
