@@ -422,6 +422,43 @@ int rn_potgnn_group_increments_cells_device(rn_potgnn *h, const double *d_positi
                                             double *d_out, void *stream);
 int rn_potgnn_partial_raman_tensors(rn_potgnn *h, const double *ref_positions, const double *displacements, int64_t M,
                                     const int32_t *labels, int G, double *raman);
+/*
+ * Phonon-mode decomposition (ModeMDRamanSpectrum): the trapezoid increments of the entries above, split by phonon mode
+ * instead of by atom group.  disp (D) and proj (P) are float64[M][N][3]: D[m] is the fractional displacement of a unit
+ * amplitude of mode m and P[m] its dual in fractional coordinates (spectrum.mode_projectors), so that for a complete
+ * orthonormal set sum_m D[m][i][a] P[m][j][b] = delta_ij delta_ab.  With J_c(t) = d vec6_c / d x at frame t (the rows
+ * [frame][6][N][3] of the group entries' reverse pass, component order xx, yy, zz, xy, xz, yz), map = {0,3,4,3,1,5,4,5,2}
+ * and sigma the de-standardisation:
+ *   dx_t           = x_{t+1} - x_t - round(x_{t+1} - x_t)
+ *   a_c[t][m]      = sum_{i,r} 1/2 (J_c(t) + J_c(t+1))[i][r] D[m][i][r]
+ *   q[t][m]        = sum_{i,r} P[m][i][r] dx_t[i][r]
+ *   out[t][m][3r+s] = sigma[3r+s] a_{map(r,s)}[t][m] q[t][m]                                            m < M
+ *   out[t][M]      = total[t] - sum_{m<M} out[t][m] (ascending m), total[t] = the one-group increment   (the REST, optional)
+ * and, with a lattice per frame, one more channel, the cell channel of rn_potgnn_group_increments_cells_device,
+ * unchanged: the channels are [modes..., rest?, cell?] and their sum is the sum over all atom groups.  For a complete
+ * set the rest is round-off.  D and P belong to the lattice of the phonon calculation even when the cell varies: the
+ * identity above is a change of basis in fractional space.  The seven sums over (i, r) run on the float64 matrix pipe
+ * (csrc/kernels_mode.hip: 16 steps x 64 modes per workgroup, 3N in ascending tiles of 32) in one fixed order that does not
+ * depend on the chunking, without atomics: for given Jacobian rows repeated calls are bit-identical.
+ *
+ * rn_potgnn_mode_contract_device: handle-free, the contraction alone.  d_jac device f64[frames][6][N][3], d_positions
+ * device f64[frames][N][3], d_disp / d_proj device f64[M][N][3], sigma host f64[9] -> d_out device
+ * f64[frames-1][out_channels][9]: channels 0..M-1 and, with rest = 1, channel M are written, the others left alone.
+ * Runs on `stream` of the current device and synchronises it before it returns.  RN_ERR_INVALID_ARGUMENT, before any
+ * device work: a null pointer, frames < 2, N < 1, M < 1 (or > 64 * 65535), rest not 0 or 1, out_channels < M + rest.
+ *
+ * rn_potgnn_mode_increments_device: d_positions device f64[S][N][3], d_lattices device f64[S][9] or NULL, disp / proj HOST
+ * f64[M][N][3] (finite, else RN_ERR_INVALID_ARGUMENT; any M >= 1: there is no cap at 3N, a caller may project on vectors
+ * of their own) -> d_out device f64[S-1][M + rest + (d_lattices != NULL)][9].  Chunks, the one-frame carry-over, the
+ * stream ordering and workspace_limit are those of rn_potgnn_group_increments_device (the two share the loop); D and P
+ * are uploaded once per call and count against workspace_limit.
+ */
+int rn_potgnn_mode_contract_device(const double *d_jac, int64_t frames, const double *d_positions, int32_t N,
+                                   const double *d_disp, const double *d_proj, int32_t M, const double *sigma, int rest,
+                                   int out_channels, double *d_out, void *stream);
+int rn_potgnn_mode_increments_device(rn_potgnn *h, const double *d_positions, const double *d_lattices, int64_t S,
+                                     const double *disp, const double *proj, int32_t M, int rest, int use_float64,
+                                     size_t workspace_limit, double *d_out, void *stream);
 int rn_potgnn_train_backward_inputs(rn_potgnn *h, const float *dvec6, float *grads, double *dpos, double *dlat);
 int rn_potgnn_train_backward_inputs_device(rn_potgnn *h, const float *d_dvec6, double *d_dpos, double *d_dlat,
                                            void *stream);
@@ -705,6 +742,40 @@ int rn_md_mode_vdos_device(const double *d_positions, const double *d_lattices, 
  * only while enabled with rn_md_mode_vdos_set_profiling(1). */
 int rn_md_mode_vdos_set_profiling(int enabled);
 int rn_md_mode_vdos_phase_times(double *millis);
+
+/*
+ * Many-channel MD Raman spectra: the self-spectrum of every channel of a set of increments (the phonon modes of
+ * rn_potgnn_mode_increments_device) and the spectrum of their sum, per segment of a start table.  increments: host
+ * float64[N][C][9], C >= 1 (unbounded: the pair spectra of rn_md_raman_partial_segments stop at 16 groups, these
+ * diagonal ones do not); N, segment_steps = W (n = W - 1 increments), starts, taper, weights and K as for
+ * rn_md_raman_partial_segments.
+ *   row (q, k, c), c < C   rn_md_raman_partial_segments' I_k[g][g] taken on channel c alone (the self-spectrum)
+ *   row (q, k, C)          the same form of the increments summed over all channels, in ascending channel order per
+ *                          (step, entry): the whole spectrum
+ * so that row C - sum_c row c is the interference between channels.  intensities: host float64[Q][K][C+1][num_bins]
+ * (average = 0) or float64[K][C+1][num_bins] (average = 1: the mean over the segments, taken on the contracted power
+ * spectra in table order by one thread per (row, frequency)).  The summed channel goes through the same kernels as one
+ * more channel; channels are independent, so repeated calls and different blockings are bit-identical and a channel of
+ * zeros gives rows that are exactly zero.  Checks, their order and the return codes are those of
+ * rn_md_raman_partial_segments, with C >= 1 in place of 1 <= G <= 16.  workspace_limit (bytes, 0 = 4 GiB) bounds the
+ * device memory besides the staged increments: the channels go through in blocks when one segment's 6 (C + 1) series and
+ * K (C + 1) rows do not fit, the segments in blocks of several; a limit that one channel of one segment and one row do
+ * not fit in returns RN_ERR_OUT_OF_MEMORY.  Work runs on the null stream; the call returns when the intensities are on
+ * the host.
+ */
+int rn_md_raman_modes(const double *increments, int64_t N, int C, int64_t segment_steps, const int64_t *starts,
+                      int64_t Q, const double *taper, const double *weights, int64_t K, int average, int device,
+                      size_t workspace_limit, double *intensities, int64_t num_bins);
+/* The same for increments already in HBM (d_increments: device float64[N][C][9], produced on `stream`): the call
+ * synchronises `stream` before it reads them; only the intensities travel to the host. */
+int rn_md_raman_modes_device(const double *d_increments, int64_t N, int C, int64_t segment_steps, const int64_t *starts,
+                             int64_t Q, const double *taper, const double *weights, int64_t K, int average, int device,
+                             size_t workspace_limit, double *intensities, int64_t num_bins, void *stream);
+/* Device time of the phases of the most recent rn_md_raman_modes / rn_md_raman_modes_device call (HIP events on the null
+ * stream): millis[4] = segment builder, forward FFTs, power kernel, back half with its copies to the host.  Measured
+ * only while enabled with rn_md_raman_modes_set_profiling(1). */
+int rn_md_raman_modes_set_profiling(int enabled);
+int rn_md_raman_modes_phase_times(double *millis);
 
 /* Introspection: bit 0 = the fused EdgeBlock kernel is in use (float32, Fn and Fe padded to
  * 64); bit 1 = every pass takes the folded-LayerNorm-scale triplet loop; bit 2 = the fused

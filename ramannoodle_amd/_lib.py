@@ -87,6 +87,10 @@ SIGNATURES = {
     "rn_potgnn_group_increments_cells_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_size_t, _P,
                                                           _P]),
     "rn_potgnn_partial_raman_tensors": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, _P]),
+    "rn_potgnn_mode_contract_device": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int, C.c_int,
+                                                 _P, _P]),
+    "rn_potgnn_mode_increments_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int, C.c_int,
+                                                   C.c_size_t, _P, _P]),
     "rn_potgnn_train_backward_inputs": (C.c_int, [_P, _P, _P, _P, _P]),
     "rn_potgnn_train_backward_inputs_device": (C.c_int, [_P, _P, _P, _P, _P]),
     "rn_potgnn_num_triplets": (C.c_int64, [_P]),
@@ -136,6 +140,12 @@ SIGNATURES = {
                                          C.c_int64, _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_int64, _P]),
     "rn_md_mode_vdos_set_profiling": (C.c_int, [C.c_int]),
     "rn_md_mode_vdos_phase_times": (C.c_int, [_P]),
+    "rn_md_raman_modes": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int, C.c_int,
+                                    C.c_size_t, _P, C.c_int64]),
+    "rn_md_raman_modes_device": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int,
+                                           C.c_int, C.c_size_t, _P, C.c_int64, _P]),
+    "rn_md_raman_modes_set_profiling": (C.c_int, [C.c_int]),
+    "rn_md_raman_modes_phase_times": (C.c_int, [_P]),
     # include/rn_ingest.h (host-only trajectory reader)
     "rn_xdatcar_open": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "rn_xdatcar_close": (None, [_P]),

@@ -207,6 +207,7 @@ struct rn_potgnn {
   std::vector<int32_t> grp_labels;
   int grp_G = 0;
   DeviceBuf grp_csr, grp_jac, grp_disp, grp_out;
+  DeviceBuf mode_vectors;  // rn_potgnn_mode_increments_device: D [M][N][3] | P [M][N][3]
   // variable-cell calls: the lattice rows of the Jacobian [frames][6][9], a trajectory's lattices in the arithmetic of a
   // float32 run (group increments), the float32 lattices of rn_potgnn_forward_cells_device
   DeviceBuf grp_jl, grp_lat, cells_lat;
@@ -1278,29 +1279,29 @@ void jacobian_rows(rn_potgnn *h, const double *d_pos, int s, double *d_jac, cons
   reverse_pass<T>(h, c, rv);
 }
 
-// Trapezoid increments of the S frames d_pos (device float64 [S][N][3]) per atom group -> d_out [S-1][G][9], in chunks
-// of F steps whose Jacobian rows overlap by one frame (the last frame's rows are carried into the next chunk).  Ordered
-// after `user`; `user` waits for the work and is synchronised once at the end.
+// The loop every increment entry shares: the S frames d_pos (device float64 [S][N][3]) go through in chunks of F steps
+// whose Jacobian rows overlap by one frame (the last frame's rows are carried into the next chunk), and
+// contract(jac, pos, f, out, st) launches the contraction of a chunk's f steps (jac [f+1][6][N][3], pos the chunk's first
+// frame, out its first step's row of d_out [S-1][out_channels][9]) on lane 0's stream.  Ordered after `user`; `user` waits
+// for the work and is synchronised once at the end.
 // d_lat (device float64 [S][9], or null): a lattice per frame.  The Jacobian rows are then taken at each frame's own
 // lattice (cast to T, as the forward casts it), their lattice rows J_L [6][9] are carried over chunk boundaries with them,
-// and d_out is [S-1][G+1][9]: channel G is the cell's share 1/2 (J_L(t) + J_L(t+1)) : (L_{t+1} - L_t).
-template <typename T>
-void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_t limit, double *d_out,
-                      hipStream_t user, const double *d_lat = nullptr) {
+// and channel `cell_channel` of d_out is the cell's share 1/2 (J_L(t) + J_L(t+1)) : (L_{t+1} - L_t).
+template <typename T, class Contract>
+void chunked_increments(rn_potgnn *h, const double *d_pos, int64_t S, size_t limit, int out_channels, int cell_channel,
+                        double *d_out, hipStream_t user, const double *d_lat, const char *too_small, Contract contract) {
   ensure_precision<T>(h);
   Precision<T> &P = prec<T>(h);
   const int N = h->g.N;
   const int F = group_frames<T>(h, limit, d_lat != nullptr);
-  if (F < 1) throw HipError{hipErrorOutOfMemory, "group_increments: one step does not fit the workspace limit"};
+  if (F < 1) throw HipError{hipErrorOutOfMemory, too_small};
   h->train_S = 0;  // the tape and lane 0 are reused: a pending train_forward is void
   hipStream_t st = P.lanes[0].stream;
   behind_caller(h, user, P.lanes, 1);
   const int64_t rows = (int64_t)6 * N * 3;
   h->grp_jac.ensure((size_t)(F + 1) * rows * sizeof(double));
   double *jac = h->grp_jac.as<double>();
-  const int *perm = h->grp_csr.as<int>(), *gptr = perm + N;
   const double *sigma = h->d_mean_std.as<double>() + 9;
-  const int out_groups = d_lat ? G + 1 : G;
   const T *lat = nullptr;  // the lattices as the kernels of this precision read them
   double *jl = nullptr;
   if (d_lat) {
@@ -1322,12 +1323,60 @@ void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_
       if (jl) HIP_TRY(hipMemcpyAsync(jl, jl + (int64_t)F * 54, 54 * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     jacobian_rows<T>(h, d_pos + (t0 + 1) * N * 3, f, jac + rows, lat ? lat + (t0 + 1) * 9 : nullptr, jl ? jl + 54 : nullptr);
-    launch_group_increments(jac, rows, d_pos + t0 * N * 3, nullptr, 0.0, f, N, perm, gptr, G, sigma,
-                            d_out + t0 * out_groups * 9, st, out_groups);
-    if (jl) launch_cell_increments(jl, d_lat + t0 * 9, f, G, out_groups, sigma, d_out + t0 * out_groups * 9, st);
+    contract(jac, d_pos + t0 * N * 3, f, d_out + t0 * out_channels * 9, st);
+    if (jl) launch_cell_increments(jl, d_lat + t0 * 9, f, cell_channel, out_channels, sigma, d_out + t0 * out_channels * 9, st);
     HIP_TRY(hipGetLastError());
   }
   hand_back(h, user, P.lanes, 1, true);
+}
+
+// Trapezoid increments per atom group -> d_out [S-1][G][9], or, with a lattice per frame, [S-1][G+1][9]: channel G is
+// the cell's share.
+template <typename T>
+void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_t limit, double *d_out,
+                      hipStream_t user, const double *d_lat = nullptr) {
+  const int N = h->g.N;
+  const int *perm = h->grp_csr.as<int>(), *gptr = perm + N;
+  const double *sigma = h->d_mean_std.as<double>() + 9;
+  const int out_groups = d_lat ? G + 1 : G;
+  chunked_increments<T>(h, d_pos, S, limit, out_groups, G, d_out, user, d_lat,
+                        "group_increments: one step does not fit the workspace limit",
+                        [&](const double *jac, const double *pos, int f, double *out, hipStream_t st) {
+                          launch_group_increments(jac, (int64_t)6 * N * 3, pos, nullptr, 0.0, f, N, perm, gptr, G, sigma,
+                                                  out, st, out_groups);
+                        });
+}
+
+// The contraction of one chunk of Jacobian rows with M modes (both mode entries): channels 0 .. M-1 and, with `rest`,
+// channel M of out [frames-1][out_channels][9]; everything a device pointer.
+void mode_contract(const double *jac, int64_t frames, const double *pos, int N, const double *disp, const double *proj,
+                   int M, const double *sigma, bool rest, int out_channels, double *out, hipStream_t st) {
+  launch_mode_increments(jac, pos, frames - 1, N, disp, proj, M, sigma, out_channels, out, st);
+  if (rest) launch_mode_rest(jac, pos, frames - 1, N, M, sigma, out_channels, out, st);
+}
+
+// Trapezoid increments per phonon mode -> d_out [S-1][M + rest (+ 1)][9]: the modes, the rest and, with a lattice per
+// frame, the cell.  disp / proj: host [M][N][3], uploaded once and counted against `limit`.
+template <typename T>
+void mode_increments(rn_potgnn *h, const double *d_pos, int64_t S, const double *disp, const double *proj, int M,
+                     bool rest, size_t limit, double *d_out, hipStream_t user, const double *d_lat) {
+  const int N = h->g.N;
+  const size_t bytes = (size_t)M * N * 3 * sizeof(double);
+  if (limit <= 2 * bytes) throw HipError{hipErrorOutOfMemory, "mode_increments: the modes do not fit the workspace limit"};
+  ensure_precision<T>(h);
+  HIP_TRY(hipStreamSynchronize(prec<T>(h).lanes[0].stream));  // (an earlier call may still read the old modes)
+  h->mode_vectors.ensure(2 * bytes);
+  double *d_disp = h->mode_vectors.as<double>(), *d_proj = d_disp + (size_t)M * N * 3;
+  HIP_TRY(hipMemcpy(d_disp, disp, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_proj, proj, bytes, hipMemcpyHostToDevice));
+  const double *sigma = h->d_mean_std.as<double>() + 9;
+  const int channels = M + (rest ? 1 : 0);
+  const int out_channels = channels + (d_lat ? 1 : 0);
+  chunked_increments<T>(h, d_pos, S, limit - 2 * bytes, out_channels, channels, d_out, user, d_lat,
+                        "mode_increments: one step does not fit the workspace limit",
+                        [&](const double *jac, const double *pos, int f, double *out, hipStream_t st2) {
+                          mode_contract(jac, (int64_t)f + 1, pos, N, d_disp, d_proj, M, sigma, rest, out_channels, out, st2);
+                        });
 }
 
 // refresh `packed` (and the float64 copy, when it exists) from the device weights
@@ -2634,6 +2683,46 @@ int rn_potgnn_group_increments_cells_device(rn_potgnn *h, const double *d_positi
     const size_t limit = workspace_limit ? workspace_limit : kTapeBudget;
     with_precision(h, use_float64, [&](auto t) {
       group_increments<decltype(t)>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream, d_lattices);
+    });
+  });
+}
+
+int rn_potgnn_mode_contract_device(const double *d_jac, int64_t frames, const double *d_positions, int32_t N,
+                                   const double *d_disp, const double *d_proj, int32_t M, const double *sigma, int rest,
+                                   int out_channels, double *d_out, void *stream) {
+  if (!d_jac || !d_positions || !d_disp || !d_proj || !sigma || !d_out) return RN_ERR_INVALID_ARGUMENT;
+  if (frames < 2 || N < 1 || M < 1 || M > kMaxModes || (rest != 0 && rest != 1)) return RN_ERR_INVALID_ARGUMENT;
+  if ((int64_t)out_channels < (int64_t)M + rest) return RN_ERR_INVALID_ARGUMENT;
+  return guarded(nullptr, [&]() {
+    hipStream_t st = (hipStream_t)stream;
+    DeviceBuf d_sigma;
+    d_sigma.ensure(9 * sizeof(double));
+    HIP_TRY(hipMemcpyAsync(d_sigma.p, sigma, 9 * sizeof(double), hipMemcpyHostToDevice, st));
+    mode_contract(d_jac, frames, d_positions, N, d_disp, d_proj, M, d_sigma.as<double>(), rest != 0, out_channels, d_out, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));  // (sigma's copy is freed on return)
+  });
+}
+
+int rn_potgnn_mode_increments_device(rn_potgnn *h, const double *d_positions, const double *d_lattices, int64_t S,
+                                     const double *disp, const double *proj, int32_t M, int rest, int use_float64,
+                                     size_t workspace_limit, double *d_out, void *stream) {
+  if (!h) return RN_ERR_INVALID_ARGUMENT;
+  if (S < 2 || !d_positions || !disp || !proj || !d_out || M < 1 || M > kMaxModes || (rest != 0 && rest != 1)) {
+    set_error(h, "invalid arguments to mode_increments_device (S < 2, M outside 1..%d, rest not 0 or 1 or a null pointer)",
+              kMaxModes);
+    return RN_ERR_INVALID_ARGUMENT;
+  }
+  const size_t entries = (size_t)M * h->g.N * 3;
+  for (size_t j = 0; j < entries; ++j)
+    if (!std::isfinite(disp[j]) || !std::isfinite(proj[j])) {
+      set_error(h, "mode_increments_device: a non-finite entry in disp or proj");
+      return RN_ERR_INVALID_ARGUMENT;
+    }
+  return guarded(h, [&]() {
+    const size_t limit = workspace_limit ? workspace_limit : kTapeBudget;
+    with_precision(h, use_float64, [&](auto t) {
+      mode_increments<decltype(t)>(h, d_positions, S, disp, proj, M, rest != 0, limit, d_out, (hipStream_t)stream, d_lattices);
     });
   });
 }

@@ -303,6 +303,18 @@ void launch_group_increments(const double *jac, int64_t jac_stride, const double
 // launch_geom_input_bwd for six one-hot cotangents per frame), lat float64 [steps+1][9]; `out` as above.
 void launch_cell_increments(const double *jl, const double *lat, int64_t steps, int channel, int out_groups,
                             const double *sigma, double *out, hipStream_t st);
+// Phonon-mode contraction (kernels_mode.hip: mode_increment_kernel, float64 MFMA): for steps t < `steps` and modes m < M,
+// out[t][m][3r+s] = sigma[3r+s] a_{map(r,s)}[t][m] q[t][m], a_c = 1/2 (J_c(t) + J_c(t+1)) . disp[m], q = proj[m] . dx_t;
+// jac float64 [steps+1][6][N][3], pos float64 [steps+1][N][3], disp / proj float64 [M][N][3], M <= kMaxModes, out
+// float64 [steps][out_channels][9] with out_channels >= M.  Written once per entry, no atomics.
+constexpr int kMaxModes = 64 * 65535;  // gridDim.y of mode_increment_kernel
+void launch_mode_increments(const double *jac, const double *pos, int64_t steps, int N, const double *disp,
+                            const double *proj, int M, const double *sigma, int out_channels, double *out,
+                            hipStream_t st);
+// The rest channel (kernels_mode.hip: mode_rest_kernel), after launch_mode_increments on the same stream:
+// out[t][M] = the one-group increment of launch_group_increments - sum_{m<M} out[t][m] (ascending m); out_channels > M.
+void launch_mode_rest(const double *jac, const double *pos, int64_t steps, int N, int M, const double *sigma,
+                      int out_channels, double *out, hipStream_t st);
 
 // Fused EdgeBlock (kernels_fused.hip): projections + triplet aggregation in one launch.
 // Fused EdgeBlock (kernels_fused.hip): float32, FnP == FeP == 64.  Two workgroups per CU

@@ -1,9 +1,9 @@
 // What the on-device MD spectrum reducers share (spectrum.hip, spectrum_polarized.hip, spectrum_partial.hip,
-// spectrum_segments.hip, spectrum_ensemble.hip, spectrum_vdos.hip, spectrum_mode_vdos.hip): the hipFFT loader, the
+// spectrum_segments.hip, spectrum_ensemble.hip, spectrum_vdos.hip, spectrum_mode_vdos.hip, spectrum_modes.hip): the hipFFT loader, the
 // series-length arithmetic, RAII holders for plans and device buffers, the most-recently-used plan cache, the argument /
 // device check, the host-or-HBM source of a call and the two per-slot kernels of the polarized, partial and segment
 // pipelines.  The three whole-run reducers each keep their own signal builder, power / contraction kernel, plans struct,
-// workspace arithmetic and pipeline; the segment reducers (the last four files) share those through
+// workspace arithmetic and pipeline; the segment reducers (the last five files) share those through
 // spectrum_segment_core.hpp, and the two that read positions share their front end through spectrum_steps.hpp.
 //
 // Two decisions that hold for every reducer:

@@ -33,7 +33,6 @@ using namespace rn_spectrum;
 using rn::kMaxGroups;
 
 constexpr int kPairTile = 8;  // rows per thread of the atom-group power kernels (blockIdx.y)
-constexpr int kFormSize = kComponents * kComponents;
 
 // build_segments_kernel of spectrum_segments.hip with the segment's first step read from starts[q0 + b]
 __global__ void build_segments_at_kernel(const double *__restrict__ alpha, const double *__restrict__ tau, int64_t n,
@@ -75,38 +74,6 @@ __global__ void build_group_segments_kernel(const double *__restrict__ incr, con
 #pragma unroll
   for (int c = 0; c < kComponents; ++c)
     x[(((int64_t)b * G + g) * kComponents + c) * L + t] = make_double2(s[c], 0.0);
-}
-
-// the forms M_k of the tile's `nr` rows (row r0 + i has k = (r / pairs) % K) from the packed weights: diagonal as is,
-// off-diagonal halved, as partial_contract_kernel unpacks them
-__device__ inline void load_forms(const double *__restrict__ w, int64_t r0, int nr, int pairs, int64_t K, double *ms) {
-  for (int i = threadIdx.x; i < nr * kPairs; i += blockDim.x) {
-    const int row = i / kPairs, q = i % kPairs;
-    const int64_t k = ((r0 + row) / pairs) % K;
-    int a, b;
-    upper_pair(q, kComponents, a, b);
-    const double v = w[k * kPairs + q];
-    ms[row * kFormSize + a * kComponents + b] = a == b ? v : 0.5 * v;
-    ms[row * kFormSize + b * kComponents + a] = a == b ? v : 0.5 * v;
-  }
-}
-
-__device__ inline void load_group(const hipfftDoubleComplex *__restrict__ x, int64_t L, hipfftDoubleComplex *v) {
-#pragma unroll
-  for (int c = 0; c < kComponents; ++c) v[c] = x[c * L];
-}
-
-// sum_{c,e} m[c][e] Re(a_c conj b_e), summed as partial_contract_kernel sums it
-__device__ inline double contract_groups(const double *m, const hipfftDoubleComplex *a, const hipfftDoubleComplex *b) {
-  double v = 0.0;
-#pragma unroll
-  for (int c = 0; c < kComponents; ++c) {
-    double row = 0.0;
-#pragma unroll
-    for (int e = 0; e < kComponents; ++e) row = fma(m[c * kComponents + e], a[c].x * b[e].x + a[c].y * b[e].y, row);
-    v += row;
-  }
-  return v;
 }
 
 // average = 0.  Slot j of the sub-block (rows r0 .. r0+count-1 of the segment block, row r = (b K + k) pairs + pair):

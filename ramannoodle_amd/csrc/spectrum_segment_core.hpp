@@ -1,6 +1,7 @@
 // What the segment reducers share (spectrum_segments.hip: segments on a hop grid; spectrum_ensemble.hip: segments from a
 // start table, whole and by atom group; spectrum_vdos.hip: the density of states, which takes the plans and the back
-// half; spectrum_mode_vdos.hip: the density of states by mode): the two power kernels of the whole spectra, the plans and
+// half; spectrum_mode_vdos.hip: the density of states by mode; spectrum_modes.hip: the self-spectra of many channels of
+// increments): the two power kernels of the whole spectra, the plans and
 // work buffers of one (device, n, series per segment, segments per block, rows per block), the workspace arithmetic
 // that chooses the two block sizes, the loop that fits plans of those sizes into a workspace limit (get_segment_plans,
 // for any block chooser), and the pipeline from the transformed segments to the host rows; for the start-table reducers
@@ -109,6 +110,41 @@ static __global__ void __launch_bounds__(kPowerThreads)
 #pragma unroll
   for (int i = 0; i < kRowTile; ++i)
     if (i0 + i < slots) pbar[(int64_t)(i0 + i) * L + f] = make_double2(acc[i], 0.0);
+}
+
+constexpr int kFormSize = kComponents * kComponents;
+
+// What the power kernels of the atom-group and the channel reducers share (spectrum_ensemble.hip, spectrum_modes.hip).
+// The forms M_k of the tile's `nr` rows (row r0 + i has k = (r / pairs) % K) from the packed weights: diagonal as is,
+// off-diagonal halved, as partial_contract_kernel unpacks them
+__device__ inline void load_forms(const double *__restrict__ w, int64_t r0, int nr, int pairs, int64_t K, double *ms) {
+  for (int i = threadIdx.x; i < nr * kPairs; i += blockDim.x) {
+    const int row = i / kPairs, q = i % kPairs;
+    const int64_t k = ((r0 + row) / pairs) % K;
+    int a, b;
+    upper_pair(q, kComponents, a, b);
+    const double v = w[k * kPairs + q];
+    ms[row * kFormSize + a * kComponents + b] = a == b ? v : 0.5 * v;
+    ms[row * kFormSize + b * kComponents + a] = a == b ? v : 0.5 * v;
+  }
+}
+
+__device__ inline void load_group(const hipfftDoubleComplex *__restrict__ x, int64_t L, hipfftDoubleComplex *v) {
+#pragma unroll
+  for (int c = 0; c < kComponents; ++c) v[c] = x[c * L];
+}
+
+// sum_{c,e} m[c][e] Re(a_c conj b_e), summed as partial_contract_kernel sums it
+__device__ inline double contract_groups(const double *m, const hipfftDoubleComplex *a, const hipfftDoubleComplex *b) {
+  double v = 0.0;
+#pragma unroll
+  for (int c = 0; c < kComponents; ++c) {
+    double row = 0.0;
+#pragma unroll
+    for (int e = 0; e < kComponents; ++e) row = fma(m[c * kComponents + e], a[c].x * b[e].x + a[c].y * b[e].y, row);
+    v += row;
+  }
+  return v;
 }
 
 // plans + work buffers of one (device, n, series, B, R)

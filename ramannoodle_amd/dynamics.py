@@ -285,6 +285,44 @@ class Trajectory(Dynamics, Sequence):
             lattice = torch.tensor(lattice, dtype=torch.float64, device=positions.device)
         return DeviceModeVibrationalDensityOfStates(positions, self._timestep, lattice, vectors, masses)
 
+    def get_mode_raman_spectrum(self, polarizability_model: PolarizabilityModel, phonons, lattice=None, masses=None,
+                                modes=None, rest: bool = True, on_device: bool = False):
+        """Phonon-mode decomposition of the spectrum (an addition): ``ModeMDRamanSpectrum`` of the per-mode trapezoid
+        increments of the polarizability (``PotGNN.calc_mode_increments``): which mode makes which peak of the MD
+        spectrum, and how much of it is interference between modes.  ``phonons``, ``masses`` and ``modes`` as for
+        ``get_mode_vdos``; ``lattice`` ``(3,3)`` is the cell of the phonon calculation (``None``: the model's reference
+        lattice).  ``rest=True`` adds a channel for what the chosen modes leave out, so that the channels sum to the
+        whole increment; a variable-cell trajectory gains the cell channel, the last.  ``on_device=True``: the
+        increments stay in HBM and the returned ``DeviceModeMDRamanSpectrum`` reduces them there.  Needs a model with
+        ``calc_mode_increments_device`` (the device PotGNN); there is no fallback."""
+        from ramannoodle_amd.spectrum import (DeviceModeMDRamanSpectrum, ModeMDRamanSpectrum, _projectors_of_vectors,
+                                              _vdos_masses)
+        increments = getattr(polarizability_model, "calc_mode_increments_device", None)
+        if increments is None:
+            raise TypeError(f"{type(polarizability_model).__name__} has no calc_mode_increments_device: mode spectra "
+                            "need the Jacobian of the model (the device PotGNN)")
+        atoms = self._positions_ts.shape[1]
+        if lattice is None:
+            lattice = getattr(polarizability_model, "ref_lattice", None)
+            if lattice is None:
+                raise ValueError("get_mode_raman_spectrum needs lattice (3,3): the model has no ref_lattice")
+        # (the cell of the steps is not needed: the projection happens in fractional coordinates)
+        _, vectors = _mode_vdos_arguments(phonons, lattice, None, masses, modes, atoms)
+        displacements, projectors = _projectors_of_vectors(vectors, np.asarray(lattice, dtype=np.float64),
+                                                           _vdos_masses(masses, atoms))
+        import torch
+        try:
+            verify_ndarray_shape("positions_ts", self._positions_ts, (None, polarizability_model.num_atoms, 3))
+            positions = torch.tensor(self._positions_ts, dtype=torch.float64,
+                                     device=f"cuda:{polarizability_model.device_index}")
+            result = increments(positions, displacements, projectors, rest=rest,
+                                **_cells(self._lattice_ts, positions.device))
+        except ValueError as exc:
+            raise ValueError(f"polarizability_model and trajectory are incompatible: {exc}") from exc
+        if on_device:
+            return DeviceModeMDRamanSpectrum(result, self._timestep)
+        return ModeMDRamanSpectrum(result.cpu().numpy(), self._timestep)
+
     def __len__(self) -> int:
         return len(self._positions_ts)
 

@@ -252,6 +252,11 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         return int(self._ref_edge_indexes.shape[1])
 
     @property
+    def ref_lattice(self) -> np.ndarray:
+        """The lattice of the reference structure, float64 ``(3,3)`` (rows = lattice vectors; a copy)."""
+        return np.array(self._ref_structure.lattice, dtype=np.float64)
+
+    @property
     def num_atoms(self) -> int:
         return int(self._ref_structure.num_atoms)
 
@@ -1003,6 +1008,34 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         from ramannoodle_amd.spectrum import group_labels
         return group_labels(groups, self._ref_structure.atomic_numbers)
 
+    def _increments_frames(self, positions, what: str) -> int:
+        """The frame count of the device positions of an increments entry, after their checks."""
+        if not (isinstance(positions, torch.Tensor) and positions.is_cuda and positions.dtype == torch.float64
+                and positions.is_contiguous()):
+            raise ValueError("positions must be a contiguous float64 device tensor")
+        if positions.dim() != 3 or tuple(positions.shape[1:]) != (self.num_atoms, 3):
+            raise ValueError(f"positions has wrong shape: {tuple(positions.shape)} != (_,{self.num_atoms},3)")
+        if positions.shape[0] < 2:
+            raise ValueError(f"{what} increments need at least two frames, not {positions.shape[0]}")
+        return positions.shape[0]
+
+    @staticmethod
+    def _increments_out(out, positions: torch.Tensor, shape) -> torch.Tensor:
+        """``out`` of an increments entry after its checks, or a new tensor of ``shape`` on the positions' device."""
+        if out is None:
+            return torch.empty(shape, dtype=torch.float64, device=positions.device)
+        if not isinstance(out, torch.Tensor):
+            raise ValueError(f"out must be a torch.Tensor, not {type(out).__name__}")
+        if not out.is_cuda or out.device.index != positions.device.index:
+            raise ValueError(f"out lives on {out.device}, the increments are written on {positions.device}")
+        if out.dtype != torch.float64:
+            raise ValueError(f"out must be float64, not {out.dtype}")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"out has shape {tuple(out.shape)}, the increments are {shape}")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+        return out
+
     def calc_group_increments_device(self, positions: torch.Tensor, groups, float64: bool = True,
                                      out: torch.Tensor | None = None, workspace_limit: int = 0,
                                      lattices=None) -> torch.Tensor:
@@ -1022,14 +1055,7 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         polarizability because the cell deforms at fixed fractional positions.  The sum over all ``G+1`` channels is
         ``alpha(t+1) - alpha(t)`` up to the trapezoid error; without the cell channel it is not.  The cell counts as a
         group: more than 15 atom groups together with lattices raise ``ValueError``."""
-        if not (isinstance(positions, torch.Tensor) and positions.is_cuda and positions.dtype == torch.float64
-                and positions.is_contiguous()):
-            raise ValueError("positions must be a contiguous float64 device tensor")
-        if positions.dim() != 3 or tuple(positions.shape[1:]) != (self.num_atoms, 3):
-            raise ValueError(f"positions has wrong shape: {tuple(positions.shape)} != (_,{self.num_atoms},3)")
-        s = positions.shape[0]
-        if s < 2:
-            raise ValueError(f"group increments need at least two frames, not {s}")
+        s = self._increments_frames(positions, "group")
         labels, num_groups = self._group_labels(groups)
         if lattices is not None:
             lattices = self._check_device_lattices(lattices, positions)
@@ -1037,20 +1063,7 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
             if num_groups + 1 > MAX_GROUPS:
                 raise ValueError(f"{num_groups} atom groups and the cell are more than {MAX_GROUPS} channels: with lattices "
                                  f"at most {MAX_GROUPS - 1} atom groups")
-        shape = (s - 1, num_groups + (lattices is not None), 3, 3)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float64, device=positions.device)
-        else:
-            if not isinstance(out, torch.Tensor):
-                raise ValueError(f"out must be a torch.Tensor, not {type(out).__name__}")
-            if not out.is_cuda or out.device.index != positions.device.index:
-                raise ValueError(f"out lives on {out.device}, the increments are written on {positions.device}")
-            if out.dtype != torch.float64:
-                raise ValueError(f"out must be float64, not {out.dtype}")
-            if tuple(out.shape) != shape:
-                raise ValueError(f"out has shape {tuple(out.shape)}, the increments are {shape}")
-            if not out.is_contiguous():
-                raise ValueError("out must be contiguous")
+        out = self._increments_out(out, positions, (s - 1, num_groups + (lattices is not None), 3, 3))
         self.eval()
         handle = self._ensure_handle()
         stream = torch.cuda.current_stream(positions.device).cuda_stream
@@ -1093,6 +1106,68 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
                                                          num_groups, _ptr(out))
         _lib.check(rc, handle, "rn_potgnn_partial_raman_tensors")
         return out
+
+    # ------------------------------------------------------------------ phonon-mode decomposition
+    def _mode_arrays(self, displacements, projectors):
+        """``displacements`` and ``projectors`` ``(M,N,3)``, finite, as contiguous float64 (``spectrum.mode_projectors``)."""
+        arrays = []
+        for name, value in (("displacements", displacements), ("projectors", projectors)):
+            if value is None or isinstance(value, (str, bytes, torch.Tensor)):
+                raise ValueError(f"{name} must be a host array (M,{self.num_atoms},3)")
+            array = np.asarray(value)
+            if array.dtype.kind not in "iuf":
+                raise ValueError(f"{name} must hold real numbers, not {array.dtype}")
+            if array.ndim != 3 or array.shape[0] < 1 or tuple(array.shape[1:]) != (self.num_atoms, 3):
+                raise ValueError(f"{name} has wrong shape: {tuple(array.shape)} != (_,{self.num_atoms},3)")
+            array = np.ascontiguousarray(array, dtype=np.float64)
+            if not np.all(np.isfinite(array)):
+                raise ValueError(f"{name} has a non-finite entry")
+            arrays.append(array)
+        if arrays[0].shape != arrays[1].shape:
+            raise ValueError(f"displacements {arrays[0].shape} and projectors {arrays[1].shape} differ in shape")
+        return arrays
+
+    def calc_mode_increments_device(self, positions: torch.Tensor, displacements, projectors, rest: bool = True,
+                                    float64: bool = True, out: torch.Tensor | None = None, workspace_limit: int = 0,
+                                    lattices=None) -> torch.Tensor:
+        """Per-mode trapezoid increments of the polarizability along a trajectory (``rn_potgnn_mode_increments_device``):
+        ``calc_group_increments_device`` split by phonon mode instead of by atom group.  ``positions``: a contiguous
+        float64 CUDA tensor ``(S,N,3)``; ``displacements`` and ``projectors``: the host arrays ``(D, P)`` of
+        ``spectrum.mode_projectors``, ``(M,N,3)`` each, any ``M >= 1``.  Out: a float64 CUDA tensor ``(S-1,C,3,3)``,
+        ``out[t,m] = (1/2 (J(x_t) + J(x_{t+1})) . D[m]) (P[m] . dx_t)`` for ``m < M``: the change of the polarizability
+        along mode m times the step's amplitude in mode m, contracted on the float64 matrix pipe.  ``rest=True`` adds
+        channel ``M``, the one-group increment minus the modes' sum (round-off for a complete set, the unselected modes
+        otherwise); ``lattices`` (as for ``calc_group_increments_device``) adds the cell channel, the last.  The
+        channels, ``[modes..., rest?, cell?]``, sum to what the atom groups sum to.  Ordered on torch's current stream;
+        ``out`` as for ``calc_group_increments_device``."""
+        s = self._increments_frames(positions, "mode")
+        disp, proj = self._mode_arrays(displacements, projectors)
+        if lattices is not None:
+            lattices = self._check_device_lattices(lattices, positions)
+        channels = disp.shape[0] + bool(rest) + (lattices is not None)
+        out = self._increments_out(out, positions, (s - 1, channels, 3, 3))
+        self.eval()
+        handle = self._ensure_handle()
+        stream = torch.cuda.current_stream(positions.device).cuda_stream
+        rc = _lib.load().rn_potgnn_mode_increments_device(
+            handle, C.c_void_p(positions.data_ptr()), C.c_void_p(lattices.data_ptr() if lattices is not None else None),
+            s, _ptr(disp), _ptr(proj), disp.shape[0], int(bool(rest)), int(float64), int(workspace_limit),
+            C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, handle, "rn_potgnn_mode_increments_device")
+        return out
+
+    def calc_mode_increments(self, positions_ts, displacements, projectors, rest: bool = True, float64: bool = True,
+                             lattices=None) -> NDArray[np.float64]:
+        """``calc_mode_increments_device`` for host arrays: fractional positions ``(S,N,3)`` in, float64
+        ``(S-1,C,3,3)`` out; ``lattices``: host ``(S,3,3)`` (non-finite or singular lattices raise ``ValueError``)."""
+        verify_ndarray_shape("positions_ts", positions_ts, (None, self.num_atoms, 3))
+        device = f"cuda:{self.device_index}"
+        if lattices is not None:
+            from ramannoodle_amd.dynamics import verify_lattices
+            lattices = torch.tensor(verify_lattices(lattices, len(positions_ts)), device=device)
+        positions = torch.tensor(np.asarray(positions_ts, dtype=np.float64), device=device)
+        return self.calc_mode_increments_device(positions, displacements, projectors, rest=rest, float64=float64,
+                                                lattices=lattices).cpu().numpy()
 
     # ------------------------------------------------------------------ introspection
     @property

@@ -1759,3 +1759,231 @@ class DeviceModeVibrationalDensityOfStatesEnsemble(_DeviceResidentSteps, _ModePr
                  run_lengths=None):  # pylint: disable=super-init-not-called
         DeviceVibrationalDensityOfStatesEnsemble.__init__(self, runs, timestep, lattice, masses, run_lengths=run_lengths)
         self._set_vectors(vectors)
+
+
+# ----------------------------------------------------------------------------- mode-projected MD Raman spectra
+def _projectors_of_vectors(vectors, lattice, masses) -> tuple[NDArray[np.float64], NDArray[np.float64]]:
+    """``(D, P)`` of ``mode_projectors`` from the mass-weighted unit vectors ``e`` ``(M,N,3)`` of ``mode_vectors``."""
+    root = np.sqrt(masses)[None, :, None]
+    displacements = (vectors / root) @ np.linalg.inv(lattice)
+    projectors = root * (vectors @ lattice.T)
+    return np.ascontiguousarray(displacements), np.ascontiguousarray(projectors)
+
+
+def mode_projectors(displacements, lattice, masses) -> tuple[NDArray[np.float64], NDArray[np.float64]]:
+    """The two sets of vectors of ``ModeMDRamanSpectrum`` from the fractional displacements ``(M,N,3)`` of ``Phonons``,
+    a pair of float64 arrays ``(D, P)``, each ``(M,N,3)``.  With ``e = mode_vectors(displacements, lattice, masses)``,
+    the mass-weighted unit eigenvectors: ``D[m,i] = (e[m,i] / sqrt(masses[i])) @ inv(lattice)``, the fractional
+    displacement of a unit amplitude of mode m, and ``P[m,i] = sqrt(masses[i]) * (e[m,i] @ lattice.T)``, the mode's dual
+    in fractional coordinates: ``P[m] . dx`` is the amplitude of mode m in a fractional step ``dx``.  For a complete
+    orthonormal ``e``, ``sum_m D[m,i,a] P[m,j,b] = delta_ij delta_ab``.  ``ValueError`` as ``mode_vectors``."""
+    vectors = mode_vectors(displacements, lattice, masses)
+    return _projectors_of_vectors(vectors, _vdos_lattices(lattice, 1)[0], _vdos_masses(masses, vectors.shape[1]))
+
+
+def _md_modes_host(increments, timestep: float, weights, width: int, starts, tau, average: bool):
+    """(wavenumbers, ``I[K,C+1,bins]`` or ``I[Q,K,C+1,bins]``) on the host, from the definition (``include/rn_potgnn.h``,
+    ``rn_md_raman_modes``): channel ``C`` is the sum of the ``C`` channels; per segment of ``width`` frames starting at
+    frame ``starts[q]`` the zero-padded transforms of the tapered components of increments ``starts[q] .. starts[q] +
+    width - 2`` of each channel, their power contracted with each configuration's form, its inverse transform, the
+    positive lags and their length-n transform; the mean over the segments is taken on the contracted powers."""
+    d = _symmetric_components(np.asarray(increments, dtype=np.float64))  # (N, C, 6)
+    d = np.concatenate([d, d.sum(axis=1, keepdims=True)], axis=1)
+    channels = d.shape[1]
+    n = width - 1
+    starts = np.asarray(starts, dtype=np.int64)
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    keep = np.flatnonzero(wavenumbers >= 0)[1:]
+    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    forms = _weight_forms(weights)
+    count = weights.shape[0]
+    out = None if average else np.empty((len(starts), count, channels, len(keep)))
+    mean = np.zeros((count, channels, length // 2 + 1))
+    chunk = max(1, _SEGMENT_CHUNK_ELEMENTS // ((length // 2 + 1) * 6))  # channels of one segment at once
+    for q, start in enumerate(starts):
+        for first in range(0, channels, chunk):
+            series = d[start:start + n, first:first + chunk] * tau[:, None, None]
+            spectra = np.fft.rfft(series, n=length, axis=0)  # (length / 2 + 1, c, 6)
+            power = np.einsum("kje,fcj,fce->kcf", forms, spectra, np.conj(spectra)).real
+            if average:
+                mean[:, first:first + chunk] += power
+            else:
+                out[q, :, first:first + chunk] = _lag_spectrum(power, n, length, keep)
+    if average:
+        out = _lag_spectrum(mean / len(starts), n, length, keep)
+    return wavenumbers[keep], out
+
+
+def _md_modes_on_device(increments, timestep: float, weights, width: int, starts, tau, average: bool, device: int,
+                        stream=None, workspace_limit: int = 0):
+    """(wavenumbers, uncorrected ``I[K,C+1,bins]`` or ``I[Q,K,C+1,bins]``) from ``rn_md_raman_modes`` (host increments)
+    or, with a torch CUDA tensor, ``rn_md_raman_modes_device`` ordered after ``stream``."""
+    import ctypes as C
+    steps, channels = increments.shape[0], increments.shape[1]
+    weights, weight_args = _weights_arguments(weights)
+    starts, table_args = _table_arguments(starts)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    count = weights.shape[0]
+    shape = (count, channels + 1) if average else (len(starts), count, channels + 1)
+    return _call_md_reducer(
+        "rn_md_raman_modes", increments, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
+        (steps, channels, width, *table_args, C.c_void_p(tau.ctypes.data), *weight_args, int(bool(average))),
+        (workspace_limit,))
+
+
+MAX_SELECTED = MAX_GROUPS - 1  # channels of ModeMDRamanSpectrum.select, beside the channel of all others
+
+
+class ModeMDRamanSpectrum:
+    """Phonon-mode decomposition of an MD spectrum: per-channel polarizability increments ``(S-1,C,3,3)``
+    (``PotGNN.calc_mode_increments``: the modes, then the rest and the cell where present) and a timestep in fs.  Every
+    measurement returns ``(wavenumbers, I[..., C+1, bins])``: row ``c < C`` is the self-spectrum of channel c, what
+    ``PartialMDRamanSpectrum`` calls ``I[g,g]``, and the last row the spectrum of the summed increments, the whole
+    spectrum; ``I[..., C, :] - I[..., :C, :].sum(-2)`` is the interference between channels.  Any number of channels;
+    the cross terms between a few of them come from ``select``.  ``device`` (an int) reduces on that GPU
+    (``rn_md_raman_modes``); arguments and corrections are those of ``PartialMDRamanSpectrum``."""
+
+    def __init__(self, increments, timestep: float):
+        verify_ndarray_shape("increments", increments, (None, None, 3, 3))
+        if increments.shape[1] < 1:
+            raise ValueError("increments has no channel")
+        self._increments = increments
+        self._timestep = timestep
+
+    @property
+    def increments(self):
+        return self._increments
+
+    @property
+    def timestep(self) -> float:
+        return self._timestep
+
+    @property
+    def num_channels(self) -> int:
+        return self._shape()[1]
+
+    def _shape(self):
+        return self.increments.shape
+
+    def _segment_table(self, segment_steps, hop, taper):
+        """``(W, tau, starts)``: the segments of the ``S = N + 1`` frames that the ``N`` increments join."""
+        steps = self._shape()[0] + 1
+        width, hop, tau = segment_plan(steps, segment_steps, hop, taper)
+        return width, tau, _segment_starts(steps, width, hop)
+
+    def _whole_table(self):
+        """The whole run as one boxcar segment."""
+        steps = self._shape()[0]
+        if steps < 2:
+            raise ValueError(_TOO_FEW_STEPS)
+        return steps + 1, np.ones(steps), np.zeros(1, dtype=np.int64)
+
+    def _on_device(self, weights, width, starts, tau, average, device: int):
+        return _md_modes_on_device(self.increments, self._timestep, weights, width, starts, tau, average, device)
+
+    def _reduce(self, weights, table, average, device):
+        """The uncorrected ``(wavenumbers, I[K,C+1,bins] or I[Q,K,C+1,bins])`` of every measurement."""
+        width, tau, starts = table
+        if device is not None:
+            return self._on_device(weights, width, starts, tau, bool(average), int(device))
+        return _md_modes_host(self.increments, self._timestep, weights, width, starts, tau, bool(average))
+
+    def segment_starts(self, segment_steps, hop=None) -> NDArray[np.int64]:
+        """The first frame of each segment of ``measure_segments`` (frame t is where increment t begins)."""
+        return self._segment_table(segment_steps, hop, "boxcar")[2]
+
+    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
+                bose_einstein_correction=False, temperature=300, device=None):
+        """``(wavenumbers, I[C+1,bins])`` of ``measure()``'s ``45 a^2 + 7 gamma^2`` over the whole run."""
+        _require_polycrystalline(orientation)
+        wavenumbers, intensities = self._reduce(_measure_weights(), self._whole_table(), True, device)
+        return wavenumbers, _apply_corrections(wavenumbers, intensities[0], laser_correction, laser_wavelength,
+                                               bose_einstein_correction, temperature)
+
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False, laser_wavelength=522,
+                          bose_einstein_correction=False, temperature=300, device=None):
+        """``(wavenumbers, I[K,C+1,bins])`` for the configurations of ``polarized_weights``; ``[C+1,bins]`` when no
+        argument has a ``K`` axis."""
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        wavenumbers, intensities = self._reduce(weights, self._whole_table(), True, device)
+        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities[0] if squeeze else intensities
+
+    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
+                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
+                         device=None):
+        """Segment-averaged (Welch) or time-resolved spectra over ``PartialMDRamanSpectrum.measure_segments``' segments:
+        ``(wavenumbers, I[C+1,bins])``, or ``I[Q,C+1,bins]`` with ``average=False``."""
+        _require_polycrystalline(orientation)
+        table = self._segment_table(segment_steps, hop, taper)
+        wavenumbers, intensities = self._reduce(_measure_weights(), table, average, device)
+        return wavenumbers, _apply_corrections(wavenumbers, intensities[..., 0, :, :], laser_correction,
+                                               laser_wavelength, bose_einstein_correction, temperature)
+
+    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
+                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
+                                   bose_einstein_correction=False, temperature=300, device=None):
+        """``measure_segments`` for the configurations of ``polarized_weights``: ``I[K,C+1,bins]``, or
+        ``I[Q,K,C+1,bins]`` with ``average=False``; the ``K`` axis is squeezed when no argument has one."""
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        table = self._segment_table(segment_steps, hop, taper)
+        wavenumbers, intensities = self._reduce(weights, table, average, device)
+        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, intensities[..., 0, :, :] if squeeze else intensities
+
+    def _selection(self, channels) -> NDArray[np.int64]:
+        index = np.asarray(channels)
+        if index.dtype.kind not in "iu" or index.ndim != 1:
+            raise ValueError("channels must be a one-dimensional integer array")
+        if not 1 <= index.size <= MAX_SELECTED:
+            raise ValueError(f"select takes 1 to {MAX_SELECTED} channels, not {index.size}")
+        if index.min() < 0 or index.max() >= self.num_channels:
+            raise ValueError(f"channels must lie in [0, {self.num_channels})")
+        if len(np.unique(index)) != index.size:
+            raise ValueError("channels names a channel twice")
+        return index.astype(np.int64)
+
+    def select(self, channels):
+        """A ``PartialMDRamanSpectrum`` of the chosen ``channels`` (1 to 15 distinct indices, in the order given) plus
+        one last channel holding the sum of all others: its ``I[g,h]`` are the pair spectra of the chosen modes, cross
+        terms included, and its sum over all pairs is the whole spectrum."""
+        index = self._selection(channels)
+        others = np.setdiff1d(np.arange(self.num_channels), index)
+        increments = np.asarray(self.increments)
+        chosen = np.concatenate([increments[:, index], increments[:, others].sum(axis=1, keepdims=True)], axis=1)
+        return PartialMDRamanSpectrum(np.ascontiguousarray(chosen), self._timestep)
+
+
+class DeviceModeMDRamanSpectrum(_DeviceResident, ModeMDRamanSpectrum):
+    """``ModeMDRamanSpectrum`` whose increments stay in HBM (a contiguous float64 CUDA tensor ``(S-1,C,3,3)``): the
+    measurements reduce them on that GPU (``rn_md_raman_modes_device``, ordered after torch's current stream) unless
+    ``host=True``; ``increments`` copies them to the host on first use.  ``select`` returns a
+    ``DevicePartialMDRamanSpectrum``."""
+
+    def __init__(self, increments_device, timestep: float):  # pylint: disable=super-init-not-called
+        self._set_tensor("increments", increments_device, 4, "(_,_,3,3)")
+        if increments_device.shape[1] < 1:
+            raise ValueError("increments has no channel")
+        self._timestep = timestep
+
+    @property
+    def increments(self):
+        return self._host()
+
+    def _shape(self):
+        return tuple(self._tensor.shape)
+
+    def _on_device(self, weights, width, starts, tau, average, device: int):
+        source, stream = self._source(device)
+        return _md_modes_on_device(source, self._timestep, weights, width, starts, tau, average, device, stream=stream)
+
+    def select(self, channels):
+        import torch
+        index = self._selection(channels)
+        others = np.setdiff1d(np.arange(self.num_channels), index)
+        device = self._tensor.device
+        chosen = torch.cat([self._tensor[:, torch.as_tensor(index, device=device)],
+                            self._tensor[:, torch.as_tensor(others, device=device)].sum(dim=1, keepdim=True)], dim=1)
+        return DevicePartialMDRamanSpectrum(chosen.contiguous(), self._timestep)
