@@ -777,6 +777,50 @@ int rn_md_raman_modes_device(const double *d_increments, int64_t N, int C, int64
 int rn_md_raman_modes_set_profiling(int enabled);
 int rn_md_raman_modes_phase_times(double *millis);
 
+/*
+ * Mode-by-mode interference matrices of MD Raman bands: the pair spectra between all C channels of a set of increments,
+ * summed over weighted bins.  increments, N, C (>= 1, unbounded), segment_steps = W (n = W - 1), starts, Q, taper,
+ * weights and K as for rn_md_raman_modes; bin_weights: host float64[B][num_bins], B >= 1, any finite values (a band
+ * indicator times the corrections of its bins).  With I_k[m][n][bin] the segment-averaged pair spectrum of channels m
+ * and n that rn_md_raman_partial_segments (average = 1) would return were there no cap on its groups,
+ *   matrices[b][k][m][n] = sum_bin bin_weights[b][bin] I_k[m][n][bin]
+ * host float64[B][K][C][C]: the full symmetric matrix, the lower triangle a bit-for-bit mirror of the upper.  There is
+ * no summed channel: the band's whole intensity is the sum of all entries, entry (m, m) the band sum of channel m's
+ * self-spectrum and the sum of row m channel m's share of the band with its cross terms.  Always of the segment mean.
+ * The sum over bins is taken on the frequency side (the back half of the reducers is linear in the cross-power: see
+ * csrc/spectrum_mode_matrix.hip), as one float64 matrix product on the matrix pipe.  Every entry is summed in one
+ * order (segments in table order, frequencies ascending) whatever the blocking, without atomics: repeated calls and
+ * different workspace_limits are bit-identical, and a channel of zeros gives a row and a column that are exactly zero.
+ * Checks, their order and the return codes are those of rn_md_raman_modes, with B >= 1 and bin_weights non-null beside
+ * them, and K and B at most 65535 each (grid dimensions).  workspace_limit (bytes, 0 = 4 GiB) bounds the device memory
+ * besides the staged increments: the channels go
+ * through in blocks of whole tiles, the segments in blocks of several; a limit that the series of one segment of one
+ * pair of channel tiles and that pair's entries do not fit in returns RN_ERR_OUT_OF_MEMORY.  Work runs on the null
+ * stream; the call returns when the matrices are on the host.
+ */
+int rn_md_raman_mode_matrix(const double *increments, int64_t N, int C, int64_t segment_steps, const int64_t *starts,
+                            int64_t Q, const double *taper, const double *weights, int64_t K, const double *bin_weights,
+                            int64_t B, int device, size_t workspace_limit, double *matrices, int64_t num_bins);
+/* The same for increments already in HBM (d_increments: device float64[N][C][9], produced on `stream`): the call
+ * synchronises `stream` before it reads them; only the matrices travel to the host. */
+int rn_md_raman_mode_matrix_device(const double *d_increments, int64_t N, int C, int64_t segment_steps,
+                                   const int64_t *starts, int64_t Q, const double *taper, const double *weights,
+                                   int64_t K, const double *bin_weights, int64_t B, int device, size_t workspace_limit,
+                                   double *matrices, int64_t num_bins, void *stream);
+/* Device time of the phases of the most recent rn_md_raman_mode_matrix / rn_md_raman_mode_matrix_device call (HIP
+ * events on the null stream): millis[4] = segment builder, forward FFTs, product kernel, copies of the matrices to the
+ * host.  Measured only while enabled with rn_md_raman_mode_matrix_set_profiling(1). */
+int rn_md_raman_mode_matrix_set_profiling(int enabled);
+int rn_md_raman_mode_matrix_phase_times(double *millis);
+/* Host only (no device is touched): the frequency-side weights that rn_md_raman_mode_matrix derives from bin_weights.
+ * n = segment_steps - 1 >= 2, L the zero-padded transform length (the least power of two >= 2 n - 1), T[bin][f] =
+ * (1/L) sum_{tau=0}^{n-1} cos(2 pi tau (f/L - (bin+1)/n)) and u_b[f] = sum_bin bin_weights[b][bin] T[bin][f]:
+ *   response[b][f] = scale * (u_b[f] + u_b[L - f])  for 0 < f < L/2,   scale * u_b[f]  for f = 0 and f = L/2
+ * the half-spectrum folded, as the series are real.  response: host float64[B][F], F = L/2 + 1 rounded up to a
+ * multiple of 4, the tail zero.  num_bins must be (n + 1) / 2 - 1; RN_ERR_INVALID_ARGUMENT otherwise. */
+int rn_md_raman_mode_matrix_response(int64_t n, const double *bin_weights, int64_t B, int64_t num_bins, double scale,
+                                     double *response);
+
 /* Introspection: bit 0 = the fused EdgeBlock kernel is in use (float32, Fn and Fe padded to
  * 64); bit 1 = every pass takes the folded-LayerNorm-scale triplet loop; bit 2 = the fused
  * kernels' matrix products run as split-f16 MFMA (default; RN_POTGNN_MFMA=f32 at create time

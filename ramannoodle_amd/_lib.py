@@ -146,6 +146,13 @@ SIGNATURES = {
                                            C.c_int, C.c_size_t, _P, C.c_int64, _P]),
     "rn_md_raman_modes_set_profiling": (C.c_int, [C.c_int]),
     "rn_md_raman_modes_phase_times": (C.c_int, [_P]),
+    "rn_md_raman_mode_matrix": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P,
+                                          C.c_int64, C.c_int, C.c_size_t, _P, C.c_int64]),
+    "rn_md_raman_mode_matrix_device": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P,
+                                                 C.c_int64, C.c_int, C.c_size_t, _P, C.c_int64, _P]),
+    "rn_md_raman_mode_matrix_set_profiling": (C.c_int, [C.c_int]),
+    "rn_md_raman_mode_matrix_phase_times": (C.c_int, [_P]),
+    "rn_md_raman_mode_matrix_response": (C.c_int, [C.c_int64, _P, C.c_int64, C.c_int64, C.c_double, _P]),
     # include/rn_ingest.h (host-only trajectory reader)
     "rn_xdatcar_open": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "rn_xdatcar_close": (None, [_P]),

@@ -31,40 +31,7 @@ namespace {
 using namespace rn_spectrum;
 
 constexpr int kChannelTile = 8;           // rows per thread of the power kernels (blockIdx.y)
-constexpr int64_t kMaxChannels = 65535;   // channels per block (gridDim.z of the builder)
 constexpr int64_t kMostChannels = (int64_t)1 << 30;
-
-// segment b of the block, slot cl = blockIdx.z (channel c0 + cl of the C + 1): x[b][cl][j][t] for t < n; zero for
-// n <= t < L, for b >= count and for cl >= cc
-__global__ void build_channel_segments_kernel(const double *__restrict__ incr, const double *__restrict__ tau, int64_t n,
-                                              int64_t L, int64_t C, const int64_t *__restrict__ starts, int64_t q0,
-                                              int count, int64_t c0, int cc, int Cb, hipfftDoubleComplex *__restrict__ x) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int b = blockIdx.y, cl = blockIdx.z;
-  if (t >= L) return;
-  double s[kComponents] = {0, 0, 0, 0, 0, 0};
-  if (t < n && b < count && cl < cc) {
-    const double *a = incr + (starts[q0 + b] + t) * C * 9;
-    double d[9];
-    if (c0 + cl < C) {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) d[i] = a[(c0 + cl) * 9 + i];
-    } else {  // the summed channel
-#pragma unroll
-      for (int i = 0; i < 9; ++i) d[i] = 0.0;
-      for (int64_t c = 0; c < C; ++c)
-#pragma unroll
-        for (int i = 0; i < 9; ++i) d[i] += a[c * 9 + i];
-    }
-    const double w = tau[t];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) d[i] *= w;
-    symmetric_components(d, s);
-  }
-#pragma unroll
-  for (int j = 0; j < kComponents; ++j)
-    x[(((int64_t)b * Cb + cl) * kComponents + j) * L + t] = make_double2(s[j], 0.0);
-}
 
 // average = 0.  Slot j of the sub-block (rows r0 .. r0+count-1 of the segment block, row r = (b K + k) Cb + cl): P_r(f);
 // slots >= count are zeroed.

@@ -1,8 +1,8 @@
 // What the segment reducers share (spectrum_segments.hip: segments on a hop grid; spectrum_ensemble.hip: segments from a
 // start table, whole and by atom group; spectrum_vdos.hip: the density of states, which takes the plans and the back
 // half; spectrum_mode_vdos.hip: the density of states by mode; spectrum_modes.hip: the self-spectra of many channels of
-// increments): the two power kernels of the whole spectra, the plans and
-// work buffers of one (device, n, series per segment, segments per block, rows per block), the workspace arithmetic
+// increments; spectrum_mode_matrix.hip: their band-summed pair spectra, which takes the channel builder, the table
+// check, the upload helper and the phase timer): the two power kernels of the whole spectra, the plans and work buffers of one (device, n, series per segment, segments per block, rows per block), the workspace arithmetic
 // that chooses the two block sizes, the loop that fits plans of those sizes into a workspace limit (get_segment_plans,
 // for any block chooser), and the pipeline from the transformed segments to the host rows; for the start-table reducers
 // also the check of the table, the upload helper and the phase timer.  A reducer brings its segment builder (and, but
@@ -145,6 +145,42 @@ __device__ inline double contract_groups(const double *m, const hipfftDoubleComp
     v += row;
   }
   return v;
+}
+
+constexpr int64_t kMaxChannels = 65535;  // channels per block (gridDim.z of the builder)
+
+// The builder of the channel reducers (spectrum_modes.hip, spectrum_mode_matrix.hip).  Segment b of the block, slot
+// cl = blockIdx.z (channel c0 + cl of the C + 1, channel C being the sum of the C): x[b][cl][j][t] for t < n; zero for
+// n <= t < L, for b >= count and for cl >= cc
+static __global__ void build_channel_segments_kernel(const double *__restrict__ incr, const double *__restrict__ tau,
+                                                     int64_t n, int64_t L, int64_t C,
+                                                     const int64_t *__restrict__ starts, int64_t q0, int count,
+                                                     int64_t c0, int cc, int Cb, hipfftDoubleComplex *__restrict__ x) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y, cl = blockIdx.z;
+  if (t >= L) return;
+  double s[kComponents] = {0, 0, 0, 0, 0, 0};
+  if (t < n && b < count && cl < cc) {
+    const double *a = incr + (starts[q0 + b] + t) * C * 9;
+    double d[9];
+    if (c0 + cl < C) {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) d[i] = a[(c0 + cl) * 9 + i];
+    } else {  // the summed channel
+#pragma unroll
+      for (int i = 0; i < 9; ++i) d[i] = 0.0;
+      for (int64_t c = 0; c < C; ++c)
+#pragma unroll
+        for (int i = 0; i < 9; ++i) d[i] += a[c * 9 + i];
+    }
+    const double w = tau[t];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) d[i] *= w;
+    symmetric_components(d, s);
+  }
+#pragma unroll
+  for (int j = 0; j < kComponents; ++j)
+    x[(((int64_t)b * Cb + cl) * kComponents + j) * L + t] = make_double2(s[j], 0.0);
 }
 
 // plans + work buffers of one (device, n, series, B, R)

@@ -165,6 +165,32 @@ def _mode_vdos_arguments(phonons, lattice, lattice_ts, masses, modes, atoms: int
     return (lattice if lattice_ts is None else lattice_ts), vectors
 
 
+def _mode_increments(polarizability_model, positions_ts, lattice_ts, phonons, lattice, masses, modes, rest):
+    """The per-mode increments of ``get_mode_raman_spectrum`` over the frames ``positions_ts``, a CUDA tensor
+    ``(S-1,C,3,3)`` (``PotGNN.calc_mode_increments_device``)."""
+    from ramannoodle_amd.spectrum import _projectors_of_vectors, _vdos_masses
+    increments = getattr(polarizability_model, "calc_mode_increments_device", None)
+    if increments is None:
+        raise TypeError(f"{type(polarizability_model).__name__} has no calc_mode_increments_device: mode spectra "
+                        "need the Jacobian of the model (the device PotGNN)")
+    atoms = positions_ts.shape[1]
+    if lattice is None:
+        lattice = getattr(polarizability_model, "ref_lattice", None)
+        if lattice is None:
+            raise ValueError("get_mode_raman_spectrum needs lattice (3,3): the model has no ref_lattice")
+    # (the cell of the steps is not needed: the projection happens in fractional coordinates)
+    _, vectors = _mode_vdos_arguments(phonons, lattice, None, masses, modes, atoms)
+    displacements, projectors = _projectors_of_vectors(vectors, np.asarray(lattice, dtype=np.float64),
+                                                       _vdos_masses(masses, atoms))
+    import torch
+    try:
+        verify_ndarray_shape("positions_ts", positions_ts, (None, polarizability_model.num_atoms, 3))
+        positions = torch.tensor(positions_ts, dtype=torch.float64, device=f"cuda:{polarizability_model.device_index}")
+        return increments(positions, displacements, projectors, rest=rest, **_cells(lattice_ts, positions.device))
+    except ValueError as exc:
+        raise ValueError(f"polarizability_model and trajectory are incompatible: {exc}") from exc
+
+
 class Trajectory(Dynamics, Sequence):
     """MD trajectory: fractional positions ``(S,N,3)`` (wrapped into the cell on
     construction) and a timestep in fs (``dynamics/_trajectory.py:16-109``).
@@ -295,30 +321,9 @@ class Trajectory(Dynamics, Sequence):
         whole increment; a variable-cell trajectory gains the cell channel, the last.  ``on_device=True``: the
         increments stay in HBM and the returned ``DeviceModeMDRamanSpectrum`` reduces them there.  Needs a model with
         ``calc_mode_increments_device`` (the device PotGNN); there is no fallback."""
-        from ramannoodle_amd.spectrum import (DeviceModeMDRamanSpectrum, ModeMDRamanSpectrum, _projectors_of_vectors,
-                                              _vdos_masses)
-        increments = getattr(polarizability_model, "calc_mode_increments_device", None)
-        if increments is None:
-            raise TypeError(f"{type(polarizability_model).__name__} has no calc_mode_increments_device: mode spectra "
-                            "need the Jacobian of the model (the device PotGNN)")
-        atoms = self._positions_ts.shape[1]
-        if lattice is None:
-            lattice = getattr(polarizability_model, "ref_lattice", None)
-            if lattice is None:
-                raise ValueError("get_mode_raman_spectrum needs lattice (3,3): the model has no ref_lattice")
-        # (the cell of the steps is not needed: the projection happens in fractional coordinates)
-        _, vectors = _mode_vdos_arguments(phonons, lattice, None, masses, modes, atoms)
-        displacements, projectors = _projectors_of_vectors(vectors, np.asarray(lattice, dtype=np.float64),
-                                                           _vdos_masses(masses, atoms))
-        import torch
-        try:
-            verify_ndarray_shape("positions_ts", self._positions_ts, (None, polarizability_model.num_atoms, 3))
-            positions = torch.tensor(self._positions_ts, dtype=torch.float64,
-                                     device=f"cuda:{polarizability_model.device_index}")
-            result = increments(positions, displacements, projectors, rest=rest,
-                                **_cells(self._lattice_ts, positions.device))
-        except ValueError as exc:
-            raise ValueError(f"polarizability_model and trajectory are incompatible: {exc}") from exc
+        from ramannoodle_amd.spectrum import DeviceModeMDRamanSpectrum, ModeMDRamanSpectrum
+        result = _mode_increments(polarizability_model, self._positions_ts, self._lattice_ts, phonons, lattice, masses,
+                                  modes, rest)
         if on_device:
             return DeviceModeMDRamanSpectrum(result, self._timestep)
         return ModeMDRamanSpectrum(result.cpu().numpy(), self._timestep)
@@ -470,3 +475,19 @@ class TrajectoryEnsemble:
             lattice = torch.tensor(lattice, dtype=torch.float64, device=positions.device)
         return DeviceModeVibrationalDensityOfStatesEnsemble(positions, self._timestep, lattice, vectors, masses,
                                                             run_lengths=self._run_lengths)
+
+    def get_mode_raman_spectrum(self, polarizability_model: PolarizabilityModel, phonons, lattice=None, masses=None,
+                                modes=None, rest: bool = True, on_device: bool = False):
+        """``ModeMDRamanEnsemble`` of the runs' per-mode increments (arguments as
+        ``Trajectory.get_mode_raman_spectrum``), from one ``calc_mode_increments_device`` call over the joined frames:
+        the increments across the run boundaries are computed and never read.  ``on_device=True``: they stay in HBM
+        (``DeviceModeMDRamanEnsemble``).  Needs a model with ``calc_mode_increments_device`` (the device PotGNN); there
+        is no fallback."""
+        from ramannoodle_amd.spectrum import DeviceModeMDRamanEnsemble, ModeMDRamanEnsemble
+        if min(self._run_lengths) < 2:
+            raise ValueError("every trajectory needs at least two frames for its increments")
+        result = _mode_increments(polarizability_model, self._positions_ts, self._lattice_ts, phonons, lattice, masses,
+                                  modes, rest)
+        if on_device:
+            return DeviceModeMDRamanEnsemble(result, self._timestep, self._run_lengths)
+        return ModeMDRamanEnsemble(self._split(result.cpu().numpy(), 1), self._timestep)

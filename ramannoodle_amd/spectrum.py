@@ -180,18 +180,19 @@ def _md_basis_spectra(polarizability_ts: NDArray[np.float64], timestep: float):
 
 
 def _call_md_reducer(entry: str, source, n: int, too_short: str, timestep: float, device: int, stream,
-                     out_shape, args_before=(), args_after=()):
+                     out_shape, args_before=(), args_after=(), bin_axis: bool = True):
     """What every device reduction shares.  ``source`` is a host array (entry ``entry``) or, with ``stream`` set, a
     contiguous float64 CUDA tensor (entry ``entry + "_device"``, ordered after ``stream``); ``n`` is the number of
     differences of the series.  The call is ``entry(source, *args_before, device, *args_after, out, bins[, stream])``
-    with ``out`` a new float64 array ``(*out_shape, bins)``.  Returns ``(wavenumbers, out)``."""
+    with ``out`` a new float64 array ``(*out_shape, bins)``, or ``out_shape`` itself with ``bin_axis=False``.  Returns
+    ``(wavenumbers, out)``."""
     import ctypes as C
 
     from ramannoodle_amd import _lib
     if n < 2:
         raise ValueError(too_short)
     bins = (n + 1) // 2 - 1
-    out = np.empty((*out_shape, bins), dtype=np.float64)
+    out = np.empty((*out_shape, bins) if bin_axis else tuple(out_shape), dtype=np.float64)
     if stream is None:
         source = np.ascontiguousarray(source, dtype=np.float64)
         pointer, tail = source.ctypes.data, ()
@@ -1831,6 +1832,84 @@ def _md_modes_on_device(increments, timestep: float, weights, width: int, starts
         (workspace_limit,))
 
 
+def band_weights(wavenumbers, bands, laser_correction=False, laser_wavelength=522, bose_einstein_correction=False,
+                 temperature=300) -> NDArray[np.float64]:
+    """The weights ``bw[B,bins]`` that sum a spectrum on ``wavenumbers`` ``(bins,)`` over ``bands`` ``(B,2)``, the
+    half-open intervals ``[lo, hi)`` in cm^-1: 1 for a bin inside its band, 0 outside, times the laser and
+    Bose-Einstein corrections of the bin where asked for, so that ``bw @ I`` is the band sums of the corrected rows
+    ``I[..., bins]``.  ``ValueError``: ``bands`` of another shape or with no band, a non-finite edge, ``lo >= hi``, and
+    a band that holds no bin (the message names the band and the bin spacing).  What ``measure_interference`` hands to
+    ``rn_md_raman_mode_matrix``."""
+    wavenumbers = np.asarray(wavenumbers, dtype=np.float64)
+    try:
+        edges = np.asarray(bands, dtype=np.float64)
+    except (TypeError, ValueError) as exc:
+        raise ValueError("bands must be an array (B,2) of band edges in cm^-1") from exc
+    if edges.ndim != 2 or edges.shape[1] != 2 or edges.shape[0] < 1:
+        raise ValueError(f"bands has wrong shape: {shape_string(edges.shape)} != (_,2)")
+    if not np.all(np.isfinite(edges)):
+        raise ValueError("bands has a non-finite edge")
+    for index, (low, high) in enumerate(edges):
+        if low >= high:
+            raise ValueError(f"bands[{index}] is empty: {low:g} >= {high:g}")
+    inside = (wavenumbers[None, :] >= edges[:, :1]) & (wavenumbers[None, :] < edges[:, 1:])
+    for index in np.flatnonzero(~inside.any(axis=1)):
+        spacing = wavenumbers[0]  # (the bins are the multiples of the first)
+        raise ValueError(f"bands[{index}] = [{edges[index, 0]:g}, {edges[index, 1]:g}) cm^-1 holds no bin: the bins are "
+                         f"{spacing:g} cm^-1 apart, from {wavenumbers[0]:g} to {wavenumbers[-1]:g}")
+    weights = _apply_corrections(wavenumbers, inside.astype(np.float64), laser_correction, laser_wavelength,
+                                 bose_einstein_correction, temperature)
+    return np.ascontiguousarray(weights, dtype=np.float64)
+
+
+def _md_mode_matrix_host(increments, timestep: float, weights, width: int, starts, tau, bin_weights):
+    """``A[B,K,C,C]`` on the host, from the definition (``include/rn_potgnn.h``, ``rn_md_raman_mode_matrix``): per
+    segment the zero-padded transforms of the tapered components of each channel, for each pair of channels their
+    cross-power contracted with each configuration's form and averaged over the segments, its inverse transform, the
+    positive lags and their length-n transform (the pair spectra of ``_md_partial_segments_host`` without a cap on the
+    channels), and then the sum over the bins with ``bin_weights``.  Pairs ``m <= n`` are computed and mirrored."""
+    d = _symmetric_components(np.asarray(increments, dtype=np.float64))  # (N, C, 6)
+    channels = d.shape[1]
+    n = width - 1
+    starts = np.asarray(starts, dtype=np.int64)
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    keep = np.flatnonzero(wavenumbers >= 0)[1:]
+    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    forms = _weight_forms(weights)
+    count = weights.shape[0]
+    power = np.zeros((count, channels, channels, length // 2 + 1))  # rows m, columns n >= m
+    for start in starts:
+        spectra = np.fft.rfft(d[start:start + n] * tau[:, None, None], n=length, axis=0)  # (length / 2 + 1, C, 6)
+        for m in range(channels):
+            cross = np.real(spectra[:, m, None, :, None] * np.conj(spectra[:, m:, None, :]))  # (f, n, j, l)
+            power[:, m, m:] += np.einsum("kje,fnje->knf", forms, cross)
+    spectra_of_pairs = _lag_spectrum(power / len(starts), n, length, keep)  # (K, C, C, bins)
+    out = np.einsum("bi,kmni->bkmn", np.asarray(bin_weights, dtype=np.float64), spectra_of_pairs)
+    rows, cols = np.triu_indices(channels, 1)
+    out[:, :, cols, rows] = out[:, :, rows, cols]
+    return out
+
+
+def _md_mode_matrix_on_device(increments, timestep: float, weights, width: int, starts, tau, bin_weights, device: int,
+                              stream=None, workspace_limit: int = 0):
+    """``A[B,K,C,C]`` from ``rn_md_raman_mode_matrix`` (host increments) or, with a torch CUDA tensor,
+    ``rn_md_raman_mode_matrix_device`` ordered after ``stream``."""
+    import ctypes as C
+    steps, channels = increments.shape[0], increments.shape[1]
+    weights, weight_args = _weights_arguments(weights)
+    starts, table_args = _table_arguments(starts)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    bin_weights = np.ascontiguousarray(bin_weights, dtype=np.float64)
+    if bin_weights.ndim != 2 or bin_weights.shape[1] != width // 2 - 1:
+        raise ValueError(f"bin_weights has wrong shape: {shape_string(bin_weights.shape)}")
+    shape = (bin_weights.shape[0], weights.shape[0], channels, channels)
+    _, out = _call_md_reducer(
+        "rn_md_raman_mode_matrix", increments, width - 1, _TOO_FEW_STEPS, timestep, device, stream, shape,
+        (steps, channels, width, *table_args, C.c_void_p(tau.ctypes.data), *weight_args,
+         C.c_void_p(bin_weights.ctypes.data), bin_weights.shape[0]), (workspace_limit,), bin_axis=False)
+    return out
+
+
 MAX_SELECTED = MAX_GROUPS - 1  # channels of ModeMDRamanSpectrum.select, beside the channel of all others
 
 
@@ -1840,8 +1919,10 @@ class ModeMDRamanSpectrum:
     measurement returns ``(wavenumbers, I[..., C+1, bins])``: row ``c < C`` is the self-spectrum of channel c, what
     ``PartialMDRamanSpectrum`` calls ``I[g,g]``, and the last row the spectrum of the summed increments, the whole
     spectrum; ``I[..., C, :] - I[..., :C, :].sum(-2)`` is the interference between channels.  Any number of channels;
-    the cross terms between a few of them come from ``select``.  ``device`` (an int) reduces on that GPU
-    (``rn_md_raman_modes``); arguments and corrections are those of ``PartialMDRamanSpectrum``."""
+    which of them interfere under a peak comes from ``measure_interference``, the matrix of all pair spectra summed
+    over a band, and the pair spectra of a few channels bin by bin from ``select``.  ``device`` (an int) reduces on
+    that GPU (``rn_md_raman_modes``, ``rn_md_raman_mode_matrix``); arguments and corrections are those of
+    ``PartialMDRamanSpectrum``."""
 
     def __init__(self, increments, timestep: float):
         verify_ndarray_shape("increments", increments, (None, None, 3, 3))
@@ -1933,6 +2014,57 @@ class ModeMDRamanSpectrum:
                                          bose_einstein_correction, temperature)
         return wavenumbers, intensities[..., 0, :, :] if squeeze else intensities
 
+    def _matrix_on_device(self, weights, width, starts, tau, bin_weights, device: int):
+        return _md_mode_matrix_on_device(self.increments, self._timestep, weights, width, starts, tau, bin_weights,
+                                         device)
+
+    def _interference(self, weights, bands, segment_steps, hop, taper, corrections, device):
+        """``(bands, A[B,K,C,C])`` of both interference measurements; ``corrections``: the four correction arguments."""
+        if segment_steps is None:
+            width, tau, starts = self._whole_table()
+        else:
+            width, tau, starts = self._segment_table(segment_steps, hop, taper)
+        n = width - 1
+        wavenumbers = (scipy.fftpack.fftfreq(n, self._timestep) * _PER_FS_TO_CM1)[1:(n + 1) // 2]
+        if len(wavenumbers) == 0:
+            raise ValueError(f"segments of {width} frames have no bin to sum over")
+        weights_of_bins = band_weights(wavenumbers, bands, *corrections)
+        if device is not None:
+            matrices = self._matrix_on_device(weights, width, starts, tau, weights_of_bins, int(device))
+        else:
+            matrices = _md_mode_matrix_host(self.increments, self._timestep, weights, width, starts, tau,
+                                            weights_of_bins)
+        return np.array(bands, dtype=np.float64), matrices
+
+    def measure_interference(self, bands, segment_steps=None, hop=None, taper="hann", orientation="polycrystalline",
+                             laser_correction=False, laser_wavelength=522, bose_einstein_correction=False,
+                             temperature=300, device=None):
+        """Which channels interfere under a peak: ``(bands, A[B,C,C])``, the pair spectra between all channels summed
+        over each of ``bands`` ``(B,2)`` (cm^-1, half-open ``[lo, hi)``; ``band_weights``).  ``A[b,m,n]`` is the band
+        sum of what ``PartialMDRamanSpectrum.measure_segments`` calls ``I[m,n]``, for any number of channels:
+        symmetric, ``A[b].sum()`` the band sum of the whole spectrum (the last row of ``measure_segments``),
+        ``np.diagonal(A[b])`` the band sums of the self-spectra and ``A[b].sum(-1)`` each channel's share of the band
+        with its cross terms, shares that add up to the band as the self-spectra do not.  ``segment_steps``, ``hop``
+        and ``taper`` as for ``measure_segments``, always the segment mean; ``segment_steps=None`` is the whole run as
+        one boxcar segment, as ``measure``.  The corrections weight the bins before the sum.  ``device`` (an int)
+        reduces on that GPU (``rn_md_raman_mode_matrix``: one float64 matrix product); ``None`` is the host, from the
+        definition, whose time and memory grow with ``C^2``.  ``ValueError`` for ``bands``: see ``band_weights``."""
+        _require_polycrystalline(orientation)
+        corrections = (laser_correction, laser_wavelength, bose_einstein_correction, temperature)
+        bands, matrices = self._interference(_measure_weights(), bands, segment_steps, hop, taper, corrections, device)
+        return bands, matrices[:, 0]
+
+    def measure_interference_polarized(self, incident, scattered, orientation=None, *, bands, segment_steps=None,
+                                       hop=None, taper="hann", laser_correction=False, laser_wavelength=522,
+                                       bose_einstein_correction=False, temperature=300, device=None):
+        """``measure_interference`` for the configurations of ``polarized_weights``: ``(bands, A[K,B,C,C])``;
+        ``[B,C,C]`` when no argument has a ``K`` axis."""
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        corrections = (laser_correction, laser_wavelength, bose_einstein_correction, temperature)
+        bands, matrices = self._interference(weights, bands, segment_steps, hop, taper, corrections, device)
+        matrices = np.ascontiguousarray(np.swapaxes(matrices, 0, 1))
+        return bands, matrices[0] if squeeze else matrices
+
     def _selection(self, channels) -> NDArray[np.int64]:
         index = np.asarray(channels)
         if index.dtype.kind not in "iu" or index.ndim != 1:
@@ -1956,17 +2088,9 @@ class ModeMDRamanSpectrum:
         return PartialMDRamanSpectrum(np.ascontiguousarray(chosen), self._timestep)
 
 
-class DeviceModeMDRamanSpectrum(_DeviceResident, ModeMDRamanSpectrum):
-    """``ModeMDRamanSpectrum`` whose increments stay in HBM (a contiguous float64 CUDA tensor ``(S-1,C,3,3)``): the
-    measurements reduce them on that GPU (``rn_md_raman_modes_device``, ordered after torch's current stream) unless
-    ``host=True``; ``increments`` copies them to the host on first use.  ``select`` returns a
-    ``DevicePartialMDRamanSpectrum``."""
-
-    def __init__(self, increments_device, timestep: float):  # pylint: disable=super-init-not-called
-        self._set_tensor("increments", increments_device, 4, "(_,_,3,3)")
-        if increments_device.shape[1] < 1:
-            raise ValueError("increments has no channel")
-        self._timestep = timestep
+class _DeviceModeChannels(_DeviceResident):
+    """What the device-resident mode spectra share: the increments stay in HBM as a contiguous float64 CUDA tensor
+    ``(_,C,3,3)`` and every measurement reduces them there, ordered after torch's current stream."""
 
     @property
     def increments(self):
@@ -1979,11 +2103,132 @@ class DeviceModeMDRamanSpectrum(_DeviceResident, ModeMDRamanSpectrum):
         source, stream = self._source(device)
         return _md_modes_on_device(source, self._timestep, weights, width, starts, tau, average, device, stream=stream)
 
-    def select(self, channels):
+    def _matrix_on_device(self, weights, width, starts, tau, bin_weights, device: int):
+        source, stream = self._source(device)
+        return _md_mode_matrix_on_device(source, self._timestep, weights, width, starts, tau, bin_weights, device,
+                                         stream=stream)
+
+    def measure_interference(self, bands, segment_steps=None, hop=None, taper="hann", orientation="polycrystalline",
+                             laser_correction=False, laser_wavelength=522, bose_einstein_correction=False,
+                             temperature=300, device=None, host=False):
+        """As the base class's ``measure_interference``; reduces on the tensor's GPU unless ``host=True``."""
+        return super().measure_interference(bands, segment_steps, hop, taper, orientation, laser_correction,
+                                            laser_wavelength, bose_einstein_correction, temperature,
+                                            device=self._device_or_host(device, host))
+
+    def measure_interference_polarized(self, incident, scattered, orientation=None, *, bands, segment_steps=None,
+                                       hop=None, taper="hann", laser_correction=False, laser_wavelength=522,
+                                       bose_einstein_correction=False, temperature=300, device=None, host=False):
+        """As the base class's ``measure_interference_polarized``; reduces on the tensor's GPU unless ``host=True``."""
+        return super().measure_interference_polarized(
+            incident, scattered, orientation, bands=bands, segment_steps=segment_steps, hop=hop, taper=taper,
+            laser_correction=laser_correction, laser_wavelength=laser_wavelength,
+            bose_einstein_correction=bose_einstein_correction, temperature=temperature,
+            device=self._device_or_host(device, host))
+
+    def _selected_tensor(self, channels):
         import torch
         index = self._selection(channels)
         others = np.setdiff1d(np.arange(self.num_channels), index)
         device = self._tensor.device
         chosen = torch.cat([self._tensor[:, torch.as_tensor(index, device=device)],
                             self._tensor[:, torch.as_tensor(others, device=device)].sum(dim=1, keepdim=True)], dim=1)
-        return DevicePartialMDRamanSpectrum(chosen.contiguous(), self._timestep)
+        return chosen.contiguous()
+
+
+class DeviceModeMDRamanSpectrum(_DeviceModeChannels, ModeMDRamanSpectrum):
+    """``ModeMDRamanSpectrum`` whose increments stay in HBM (a contiguous float64 CUDA tensor ``(S-1,C,3,3)``): the
+    measurements reduce them on that GPU (``rn_md_raman_modes_device``, ``rn_md_raman_mode_matrix_device``, ordered
+    after torch's current stream) unless ``host=True``; ``increments`` copies them to the host on first use.
+    ``select`` returns a ``DevicePartialMDRamanSpectrum``."""
+
+    def __init__(self, increments_device, timestep: float):  # pylint: disable=super-init-not-called
+        self._set_tensor("increments", increments_device, 4, "(_,_,3,3)")
+        if increments_device.shape[1] < 1:
+            raise ValueError("increments has no channel")
+        self._timestep = timestep
+
+    def select(self, channels):
+        return DevicePartialMDRamanSpectrum(self._selected_tensor(channels), self._timestep)
+
+
+class ModeMDRamanEnsemble(ModeMDRamanSpectrum):
+    """Phonon-mode spectra averaged over several runs: ``runs`` is a sequence of per-channel increments
+    ``(S_r-1,C,3,3)`` sharing ``C`` and ``timestep``.  The runs are joined with one zero row between them, so that
+    increment t still belongs to frame t of the joined frames; no segment reads that row.  Every measurement of
+    ``ModeMDRamanSpectrum`` is here: the segment measurements and ``measure_interference`` with ``segment_steps`` take
+    the segments of every run (``ensemble_segment_starts`` of the runs' ``S_r`` frames; rows in run order,
+    ``average=True`` the mean over all of them); ``measure`` / ``measure_polarized`` and ``measure_interference``
+    without ``segment_steps`` the mean over the runs of each run's whole spectrum, one boxcar segment per run, when
+    the runs have one length.  ``device`` (an int) reduces all runs in one call.  ``select`` returns a
+    ``PartialMDRamanEnsemble``."""
+
+    def __init__(self, runs, timestep: float):  # pylint: disable=super-init-not-called
+        runs = list(runs)
+        if not runs:
+            raise ValueError("an ensemble needs at least one run")
+        for index, run in enumerate(runs):
+            verify_ndarray_shape(f"runs[{index}]", run, (None, runs[0].shape[1], 3, 3))
+        if runs[0].shape[1] < 1:
+            raise ValueError("increments has no channel")
+        self._run_lengths = [int(run.shape[0]) + 1 for run in runs]  # frames
+        gap = np.zeros((1, *runs[0].shape[1:]))
+        parts = [part for run in runs for part in (np.asarray(run, dtype=np.float64), gap)][:-1]
+        self._increments = np.concatenate(parts, axis=0)
+        self._timestep = timestep
+
+    @property
+    def run_lengths(self) -> list[int]:
+        """Frames per run (one more than its increments)."""
+        return list(self._run_lengths)
+
+    def _segment_table(self, segment_steps, hop, taper):
+        width, hop, tau = segment_plan(min(self._run_lengths), segment_steps, hop, taper)
+        return width, tau, ensemble_segment_starts(self._run_lengths, width, hop)[0]
+
+    def _whole_table(self):
+        """Each run as one boxcar segment."""
+        steps = _equal_run_length(self._run_lengths)
+        if steps < 3:
+            raise ValueError(_TOO_FEW_STEPS)
+        return self._segment_table(steps, steps, "boxcar")
+
+    def segment_starts(self, segment_steps, hop=None) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
+        """``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
+        starts, run_index = ensemble_segment_starts(self._run_lengths, segment_steps, hop)
+        return run_index, starts - _run_offsets(self._run_lengths)[run_index]
+
+    def select(self, channels):
+        index = self._selection(channels)
+        others = np.setdiff1d(np.arange(self.num_channels), index)
+        increments = np.asarray(self.increments)
+        chosen = np.concatenate([increments[:, index], increments[:, others].sum(axis=1, keepdims=True)], axis=1)
+        bounds = np.cumsum(self._run_lengths)
+        return PartialMDRamanEnsemble([chosen[end - length:end - 1] for length, end in zip(self._run_lengths, bounds)],
+                                      self._timestep)
+
+
+class DeviceModeMDRamanEnsemble(_DeviceModeChannels, ModeMDRamanEnsemble):
+    """``ModeMDRamanEnsemble`` whose increments stay in HBM: a sequence of contiguous float64 CUDA tensors
+    ``(S_r-1,C,3,3)`` (joined here, on the GPU, with a zero row between them), or one tensor ``(sum(S_r)-1,C,3,3)``
+    plus ``run_lengths`` (frames per run), as one batched evaluation of the joined frames writes it: its rows across
+    the run boundaries stand where the zero rows would and are never read.  ``select`` returns a
+    ``DevicePartialMDRamanEnsemble``."""
+
+    def __init__(self, runs, timestep: float, run_lengths=None):  # pylint: disable=super-init-not-called
+        import torch
+        runs, lengths = _joined_tensor("runs", runs, run_lengths, 1)
+        if lengths is None:
+            if not all(isinstance(run, torch.Tensor) for run in runs):
+                raise ValueError("runs must be contiguous float64 CUDA tensors")
+            lengths = [int(run.shape[0]) + 1 for run in runs]
+            gap = runs[0].new_zeros((1, *runs[0].shape[1:]))
+            runs = torch.cat([part for run in runs for part in (run, gap)][:-1], dim=0)
+        self._set_tensor("runs", runs, 4, "(_,_,3,3)")
+        if runs.shape[1] < 1:
+            raise ValueError("increments has no channel")
+        self._run_lengths = lengths
+        self._timestep = timestep
+
+    def select(self, channels):
+        return DevicePartialMDRamanEnsemble(self._selected_tensor(channels), self._timestep, self._run_lengths)
