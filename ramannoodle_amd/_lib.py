@@ -172,6 +172,21 @@ SIGNATURES = {
     "rn_vasprun_last_error": (C.c_char_p, [_P]),
 }
 
+# include/rn_interp.h (the interpolation model; a table of its own: SIGNATURES is the rn_potgnn / rn_md / ingest ABI)
+INTERP_SIGNATURES = {
+    "rn_interp_create": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int, C.POINTER(_P)]),
+    "rn_interp_destroy": (None, [_P]),
+    "rn_interp_last_error": (C.c_char_p, [_P]),
+    "rn_interp_set_mask": (C.c_int, [_P, _P]),
+    "rn_interp_is_symmetric": (C.c_int, [_P]),
+    "rn_interp_calc_polarizabilities": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "rn_interp_forward_device": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "rn_interp_jacobian_device": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "rn_interp_group_increments_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_size_t, _P, _P]),
+    "rn_interp_mode_increments_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int, C.c_size_t, _P, _P]),
+    "rn_interp_partial_raman_tensors": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, _P]),
+}
+
 _lib = None
 
 
@@ -193,7 +208,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(_LIB_PATH)
     except OSError as exc:
         raise DeviceError(f"cannot load {_LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes
@@ -201,12 +216,17 @@ def load() -> C.CDLL:
     return lib
 
 
-def check(rc: int, handle=None, what: str = "device call") -> None:
+def check_interp(rc: int, handle=None, what: str = "device call") -> None:
+    """``check`` for the entries of ``include/rn_interp.h``, whose handles keep their own error text."""
+    check(rc, handle, what, last_error="rn_interp_last_error")
+
+
+def check(rc: int, handle=None, what: str = "device call", last_error: str = "rn_potgnn_last_error") -> None:
     """Map a status code to the exception the reference API contract expects."""
     if rc == RN_OK:
         return
     lib = load()
-    msg = lib.rn_potgnn_last_error(handle)
+    msg = getattr(lib, last_error)(handle)
     text = msg.decode() if msg else ""
     if rc == RN_ERR_INVALID_ARGUMENT:
         raise ValueError(f"{what}: {text}")

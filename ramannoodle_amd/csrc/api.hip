@@ -1218,21 +1218,10 @@ void forward_vjp(rn_potgnn *h, const double *d_lat /* [S][9] or null */, const i
 // CSR permutation in h->grp_csr; rebuilt only when the labels change.  false on a label out of range or an empty group.
 bool set_group_labels(rn_potgnn *h, const int32_t *labels, int G) {
   const int N = h->g.N;
-  std::vector<int32_t> ptr(G + 1, 0);
-  for (int i = 0; i < N; ++i) {
-    if (labels[i] < 0 || labels[i] >= G) return false;
-    ++ptr[labels[i] + 1];
-  }
-  for (int g = 0; g < G; ++g) {
-    if (ptr[g + 1] == 0) return false;
-    ptr[g + 1] += ptr[g];
-  }
+  std::vector<int32_t> csr;
+  if (!group_csr(labels, N, G, csr)) return false;  // (kernels.hpp: shared with the interpolation model's entries)
   if (h->grp_G == G && h->grp_labels.size() == (size_t)N && std::equal(labels, labels + N, h->grp_labels.begin()))
     return true;
-  std::vector<int32_t> csr(N + G + 1);
-  std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-  for (int i = 0; i < N; ++i) csr[fill[labels[i]]++] = i;
-  std::copy(ptr.begin(), ptr.end(), csr.begin() + N);
   h->grp_csr.ensure(csr.size() * sizeof(int32_t));
   HIP_TRY(hipMemcpy(h->grp_csr.p, csr.data(), csr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   h->grp_labels.assign(labels, labels + N);

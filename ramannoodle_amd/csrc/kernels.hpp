@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace rn {
 
@@ -315,6 +316,41 @@ void launch_mode_increments(const double *jac, const double *pos, int64_t steps,
 // out[t][M] = the one-group increment of launch_group_increments - sum_{m<M} out[t][m] (ascending m); out_channels > M.
 void launch_mode_rest(const double *jac, const double *pos, int64_t steps, int N, int M, const double *sigma,
                       int out_channels, double *out, hipStream_t st);
+
+// The interpolation model on the device (kernels_interp.hip; api_interp.hip owns the arrays).  Everything float64:
+// F [J][K3] the basis with the lattice folded in and FT [K3][J] its transpose, ref [K3] the reference positions,
+// alpha_ref [9], poff [J+1] the piece offsets, xs the breakpoints (DOF j's P_j + 1 values start at poff[j] + j),
+// coef [pieces][order+1][9] Taylor coefficients about each piece's left breakpoint (ascending power, zero-padded to the
+// model's highest order `order` in 1..5), scale [J] = 1 - mask, Pmax the largest piece count of a DOF.
+struct InterpModel {
+  const double *F, *FT, *ref, *alpha_ref, *xs, *coef, *scale;
+  const int *poff;
+  int64_t K3;
+  int J, order, Pmax;
+};
+// alpha float64 [S][9] of the frames pos float64 [S][K3] (interp_alpha_kernel): written once per entry, no atomics.
+void launch_interp_alpha(const double *pos, int64_t S, const InterpModel &m, double *alpha, hipStream_t st);
+// Jacobian rows jac float64 [S][6][K3] (component order of launch_group_increments) of the frames pos; g: workspace
+// of S * 6 * J doubles (the scaled spline derivatives).  Two launches on `st`, no atomics.
+void launch_interp_jacobian(const double *pos, int64_t S, const InterpModel &m, double *g, double *jac, hipStream_t st);
+// The atoms bucketed by group for launch_group_increments: csr = perm [N] (ascending atom index within a group) followed
+// by gptr [G+1].  false on a label outside [0, G) or an empty group.  Host only.
+inline bool group_csr(const int32_t *labels, int N, int G, std::vector<int32_t> &csr) {
+  std::vector<int32_t> ptr(G + 1, 0);
+  for (int i = 0; i < N; ++i) {
+    if (labels[i] < 0 || labels[i] >= G) return false;
+    ++ptr[labels[i] + 1];
+  }
+  for (int g = 0; g < G; ++g) {
+    if (ptr[g + 1] == 0) return false;
+    ptr[g + 1] += ptr[g];
+  }
+  csr.assign((size_t)N + G + 1, 0);
+  std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+  for (int i = 0; i < N; ++i) csr[fill[labels[i]]++] = i;
+  std::copy(ptr.begin(), ptr.end(), csr.begin() + N);
+  return true;
+}
 
 // Fused EdgeBlock (kernels_fused.hip): projections + triplet aggregation in one launch.
 // Fused EdgeBlock (kernels_fused.hip): float32, FnP == FeP == 64.  Two workgroups per CU

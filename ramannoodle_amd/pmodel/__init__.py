@@ -1,4 +1,5 @@
-"""Polarizability models (device PotGNN only; see SURVEY.md section 2 for scope)."""
+"""Polarizability models: the device PotGNN and the device interpolation model (a finished model; building one is
+the reference's job)."""
 from ramannoodle_amd.pmodel.potgnn import (  # noqa: F401
     DeviceAdam,
     PotGNN,
@@ -6,7 +7,8 @@ from ramannoodle_amd.pmodel.potgnn import (  # noqa: F401
     polarizability_vectors_to_tensors,
 )
 
+from ramannoodle_amd.pmodel.interpolation import InterpolationModel  # noqa: F401
 from ramannoodle_amd.pmodel.train import train_single_epoch  # noqa: F401
 
-__all__ = ["PotGNN", "DeviceAdam", "train_single_epoch", "polarizability_vectors_to_tensors",
+__all__ = ["PotGNN", "InterpolationModel", "DeviceAdam", "train_single_epoch", "polarizability_vectors_to_tensors",
            "polarizability_tensors_to_vectors"]
