@@ -187,6 +187,15 @@ INTERP_SIGNATURES = {
     "rn_interp_partial_raman_tensors": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, _P]),
 }
 
+# include/rn_lineshape.h (the Lorentzian fits of ramannoodle_amd/lineshape.py; a table of its own, as INTERP_SIGNATURES is)
+LINESHAPE_SIGNATURES = {
+    "rn_lineshape_fit": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
+    "rn_lineshape_fit_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, C.c_int, _P, _P, _P,
+                                          _P]),
+    "rn_lineshape_window_capacity": (C.c_int, []),
+    "rn_lineshape_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 
 
@@ -208,7 +217,8 @@ def load() -> C.CDLL:
         lib = C.CDLL(_LIB_PATH)
     except OSError as exc:
         raise DeviceError(f"cannot load {_LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items()):
+    for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items())
+                                      + list(LINESHAPE_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes

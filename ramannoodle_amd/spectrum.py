@@ -1710,6 +1710,28 @@ class _ModeProjection:
         return _mode_vdos_host(self.positions_ts, self._lattices, self._masses, self._vectors, self._timestep, width,
                                starts, tau, average)
 
+    def fit_peaks(self, centres, half_width, segment_steps=None, hop=None, taper="hann", average=True,
+                  fit_device=None, **measure_keywords):
+        """One Lorentzian per mode row (``lineshape.fit_lorentzians``): row k is fitted on the window
+        ``[centres[k] - half_width, centres[k] + half_width)`` in cm^-1.  The rows are those of ``measure`` (with
+        ``segment_steps=None``: a raw periodogram, whose bins scatter by their own size, so fits belong on segment
+        averages) or of ``measure_segments(segment_steps, hop, taper, average)``; ``measure_keywords`` go to that call.
+        ``centres`` has ``num_modes`` entries, typically ``phonons.wavenumbers[modes]``: ``result.position - centres``
+        is then the anharmonic shift and ``result.lifetime_ps`` the lifetime.  The result's arrays are ``(M,)``, or
+        ``(Q,M)`` with ``average=False``.  ``fit_device`` (an int) fits on that GPU, ``None`` on the host; on the
+        device-resident classes ``None`` is the tensors' GPU, unless ``host=True`` is among the keywords."""
+        from ramannoodle_amd.lineshape import fit_lorentzians, mode_windows
+        windows = mode_windows(centres, half_width)
+        if windows.shape[0] != self.num_modes:
+            raise ValueError(f"centres has wrong shape: {windows.shape[0]} entries for {self.num_modes} modes")
+        if segment_steps is None:
+            wavenumbers, rows = self.measure(**measure_keywords)
+        else:
+            wavenumbers, rows = self.measure_segments(segment_steps, hop, taper, average, **measure_keywords)
+        if fit_device is None and isinstance(self, _DeviceResidentSteps) and not measure_keywords.get("host", False):
+            fit_device = self._device_index()
+        return fit_lorentzians(wavenumbers, rows, np.broadcast_to(windows, rows.shape[:-1] + (2,)), device=fit_device)
+
 
 class ModeVibrationalDensityOfStates(_ModeProjection, VibrationalDensityOfStates):
     """Mode-projected VDOS of an MD run (an addition): the power spectrum of the run's mass-weighted steps projected
