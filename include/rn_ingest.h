@@ -12,6 +12,10 @@
  * N rows of which the first three whitespace-separated tokens are parsed as Python `float`
  * does; reading ends silently at the first label line that is empty or starts with whitespace
  * (that is how the reference detects the end of the file); anything else is an invalid file.
+ * Lines end as in a file Python opened in text mode (universal newlines): at "\n", at "\r\n" and at a
+ * lone "\r"; a message that quotes a line ends in "\n" wherever one of the three stood.
+ * tests/test_ingest_mutants.py holds both readers to the reference on every prefix and on seeded
+ * one-byte edits of small files (tests/golden/{xdatcar,vasprun}/mutants.npz).
  * An addition to the reference: variable-cell runs (VASP ISIF=3) repeat the header before every
  * configuration.  What stands where a label is expected and is not the end signal is tried as a
  * whole header (comment, one-token scale, three 3-token vectors, symbols, counts, then a label);
@@ -87,6 +91,26 @@ const char *rn_xdatcar_last_error(const rn_xdatcar *h);
  * The document is tokenised once when it is opened (ill-formed XML -> RN_INGEST_INVALID_FILE with
  * the reference's "root xml element could not be found"); frames are parsed on demand, in
  * parallel, into the caller's buffer, like rn_xdatcar_read.
+ * What counts as ill-formed, as the parser behind the reference's ElementTree decides it:
+ *   - a '&' in character data or in an attribute value that does not start one of the five
+ *     predefined entities or a decimal / hexadecimal reference to a character XML allows;
+ *     "]]>" in character data;
+ *   - "<!" in content that opens neither a comment nor a CDATA section, "--" inside a comment, a
+ *     CDATA section or DOCTYPE outside its place (content / once in the prolog);
+ *   - a processing instruction without a name as its target, or with the target "xml" anywhere
+ *     but as the XML declaration at the very start (after an optional byte-order mark);
+ *   - an XML declaration that is not version, then optionally encoding, then optionally
+ *     standalone="yes|no", each after white space and quoted; an encoding of UTF-16 (the bytes are
+ *     not).  An encoding name that is none of UTF-8, US-ASCII, ISO-8859-1 or a single-byte codec
+ *     Python knows (latin1, ISO-8859-n, cp125x, ...) is refused with "unknown encoding: NAME"
+ *     (the reference dies of a LookupError there);
+ *   - a tag or attribute name that does not start with a letter, '_' or a byte above 0x7F, or that
+ *     carries a namespace prefix other than xml: (none is ever bound); an attribute without white
+ *     space before it, without '=' or quotes, with '<' in its value, or given twice.
+ * References are replaced in the text of rows and of POTIM and in name="..." before they are used
+ * (name="P&#79;TIM" is POTIM); a float() failure quotes the token as Python's repr does.
+ * Not checked: that bytes above 0x7F form UTF-8, control characters, Unicode white space or digits
+ * brought in by character references, declared namespaces and entities.
  */
 typedef struct rn_vasprun rn_vasprun; /* opaque */
 

@@ -32,7 +32,7 @@ for f in $hip_srcs; do
 done
 for f in ingest ingest_vasprun; do
   if [ ! -f "$here/$bdir/$f.o" ] || [ "$here/$f.cpp" -nt "$here/$bdir/$f.o" ] || \
-     [ "$here/ingest_common.hpp" -nt "$here/$bdir/$f.o" ] || \
+     [ "$here/ingest_common.hpp" -nt "$here/$bdir/$f.o" ] || [ "$here/ingest_internal.hpp" -nt "$here/$bdir/$f.o" ] || \
      [ "$here/../../include/rn_ingest.h" -nt "$here/$bdir/$f.o" ]; then
     g++ -O3 -std=c++17 -fPIC -Wall -pthread -c "$here/$f.cpp" -o "$here/$bdir/$f.o" &
     pids+=($!)

@@ -19,6 +19,7 @@
 
 #include "../../include/rn_ingest.h"
 #include "ingest_common.hpp"
+#include "ingest_internal.hpp"
 
 namespace {
 
@@ -56,6 +57,7 @@ struct rn_xdatcar {
   int fd = -1;
   const char *data = nullptr;
   size_t size = 0;
+  bool mapped = false;  // data is this handle's mapping of the file (rn_xdatcar_open), else the caller's text
   double lattice[9] = {0};
   std::vector<std::string> symbols;
   std::vector<long long> counts;
@@ -64,7 +66,7 @@ struct rn_xdatcar {
   std::vector<Cell> cells;  // the first header's lattice, then one per header found before a later configuration
   std::string error;
   ~rn_xdatcar() {
-    if (data && size) munmap(const_cast<char *>(data), size);
+    if (mapped && size) munmap(const_cast<char *>(data), size);
     if (fd >= 0) close(fd);
   }
 };
@@ -234,6 +236,14 @@ bool parse_frame(const rn_xdatcar *h, const Frame &f, double *out, std::string &
   return true;
 }
 
+// Parses the header of the text h->data[0, h->size) and indexes its frames.
+int index_text(rn_xdatcar *h) {
+  Cursor c{h->data, h->data + h->size};
+  if (!parse_header(h, c)) return RN_INGEST_INVALID_FILE;
+  index_frames(h, c);
+  return RN_INGEST_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -258,13 +268,20 @@ int rn_xdatcar_open(const char *path, rn_xdatcar **out) {
       return RN_INGEST_FILE_NOT_FOUND;
     }
     h->data = static_cast<const char *>(m);
+    h->mapped = true;
     (void)madvise(m, h->size, MADV_SEQUENTIAL);
   }
   *out = h;
-  Cursor c{h->data, h->data + h->size};
-  if (!parse_header(h, c)) return RN_INGEST_INVALID_FILE;
-  index_frames(h, c);
-  return RN_INGEST_OK;
+  return index_text(h);
+}
+
+int rn_xdatcar_open_text(const char *text, size_t size, rn_xdatcar **out) {
+  if ((!text && size) || !out) return RN_INGEST_INVALID_ARGUMENT;
+  rn_xdatcar *h = new rn_xdatcar();
+  h->data = text;
+  h->size = size;
+  *out = h;
+  return index_text(h);
 }
 
 void rn_xdatcar_close(rn_xdatcar *h) { delete h; }
@@ -292,7 +309,7 @@ int rn_xdatcar_read(rn_xdatcar *h, int64_t first, int64_t count, double *positio
   if (!h || first < 0 || count < 0 || first + count > (int64_t)h->frames.size() || (count > 0 && !positions))
     return RN_INGEST_INVALID_ARGUMENT;
   if (count == 0) return RN_INGEST_OK;
-  {
+  if (h->mapped) {
     // Map the block's pages in one call: faulting them in one by one from many threads
     // serialises on the address-space lock (measured: no speed-up from threads at all).
     const char *b = h->frames[(size_t)first].rows;

@@ -1,6 +1,10 @@
 // Text helpers shared by the trajectory readers (ingest.cpp: XDATCAR, ingest_vasprun.cpp:
 // vasprun.xml): Python-compatible whitespace splitting and float()/int() parsing.
 #pragma once
+#if defined(__SSE2__)
+#include <emmintrin.h>
+#endif
+
 #include <charconv>
 #include <cstdint>
 #include <cstdlib>
@@ -18,6 +22,22 @@ inline bool is_space(char c) {
 }
 inline bool is_digit(char c) { return c >= '0' && c <= '9'; }
 
+// The first '\n' or '\r' in [p, end), or end: one pass for both (a row of a trajectory is a few dozen bytes, so the
+// cost of a line is the calls made for it, not the bytes).
+inline const char *line_end(const char *p, const char *end) {
+#if defined(__SSE2__)
+  const __m128i nl = _mm_set1_epi8('\n'), cr = _mm_set1_epi8('\r');
+  for (; end - p >= 16; p += 16) {
+    const __m128i v = _mm_loadu_si128(reinterpret_cast<const __m128i *>(p));
+    const int mask = _mm_movemask_epi8(_mm_or_si128(_mm_cmpeq_epi8(v, nl), _mm_cmpeq_epi8(v, cr)));
+    if (mask) return p + __builtin_ctz((unsigned)mask);
+  }
+#endif
+  for (; p < end; ++p)
+    if (*p == '\n' || *p == '\r') return p;
+  return end;
+}
+
 struct Line {
   sv text;     // without the line terminator
   bool ended;  // a terminator was present (Python's readline() result ends with '\n')
@@ -31,14 +51,18 @@ struct Line {
 struct Cursor {
   const char *p, *end;
   bool at_end() const { return p >= end; }
-  Line readline() {  // '' at EOF, like file.readline()
+  // '' at EOF, like readline() of a file opened in text mode: "\n", "\r\n" and a lone "\r" each end a
+  // line (universal newlines), and the line Python sees then ends in "\n"
+  Line readline() {
     if (p >= end) return {sv(), false};
-    const char *nl = static_cast<const char *>(memchr(p, '\n', (size_t)(end - p)));
-    const char *stop = nl ? nl : end;
-    sv t(p, (size_t)(stop - p));
-    if (nl && !t.empty() && t.back() == '\r') t.remove_suffix(1);  // universal newlines
-    p = nl ? nl + 1 : end;
-    return {t, nl != nullptr};
+    const char *stop = line_end(p, end);
+    const sv t(p, (size_t)(stop - p));
+    if (stop == end) {
+      p = end;
+      return {t, false};
+    }
+    p = (*stop == '\r' && stop + 1 < end && stop[1] == '\n') ? stop + 2 : stop + 1;
+    return {t, true};
   }
 };
 

@@ -77,6 +77,7 @@ class XdatcarReader:
             raise InvalidFileException(self._lib.rn_xdatcar_last_error(self._handle).decode())
         if rc != 0:
             raise ValueError(f"rn_xdatcar_read failed with status {rc} (frames {first}..{first + count})")
+        self.last_cartesian = cartesian[:count]  # which frames of this block the file gave in Cartesian coordinates
         if cartesian[:count].any():
             if self.variable_cell:
                 lattices = self.read_lattices(first, count)
@@ -120,6 +121,15 @@ def read_positions_ts(filepath) -> NDArray[np.float64]:
     with XdatcarReader(filepath) as reader:
         if reader.num_frames == 0:  # np.array([]) in the reference
             return np.array([])
+        if reader.num_atoms == 0:
+            # Counts that add up to no atom: every line is a label.  The reference collects one empty
+            # list per direct frame, (S, 0), and its conversion of a Cartesian frame, [] @ inv(lattice),
+            # fails inside numpy with a ValueError that it lets through: the same expression here.
+            for k in range(reader.num_frames):
+                reader.read(k, 1)  # (an unrecognised label raises here, in the file's order)
+                if reader.last_cartesian[0]:
+                    np.array([]) @ np.linalg.inv(reader.lattice)  # pylint: disable=expression-not-assigned
+            return np.empty((reader.num_frames, 0))
         return reader.read()
 
 

@@ -7,7 +7,11 @@ run on its own test files and on generated variants / malformed documents.  Buil
 Writes ``tests/golden/vasprun/*.xml`` (input data: the reference's ``test/data/TiO2/md_run_vasprun.xml``
 cut to its first 6 MD frames, ``test/data/STO/vasprun.xml`` as is, generated variants) and
 ``tests/golden/vasprun/expected.npz`` (what the reference returned: arrays, or the exception type
-and message, per function).  Fixtures are data; no reference code is copied.
+and message, per function), and ``tests/golden/vasprun/mutants.npz``: the reference's verdict
+(``read_trajectory``, ``read_positions``) on a family of damaged documents (every prefix and seeded
+one-byte edits of five small documents, plus a structured set; ``tests/ingest_mutants.py``,
+``tests/test_ingest_mutants.py``), reproduced bit for bit by every run.  Fixtures are data; no
+reference code is copied.
 """
 from __future__ import annotations
 
@@ -150,3 +154,144 @@ for name, spec in CASES.items():
     print(name, res[:2] if res[0] == "err" else res[1].positions_ts.shape, "|",
           res_p[:3] if res_p[0] == "err" else np.asarray(res_p[1]).shape, "|", res_s[:3] if res_s[0] == "err" else "ref ok")
 np.savez_compressed(os.path.join(OUT, "expected.npz"), **expected)
+
+
+# ----------------------------------------------------------------------------- damaged files (tests/test_ingest_mutants.py)
+# The reference's verdict (read_trajectory and read_positions) on every prefix and on seeded one-byte
+# edits of a few small documents, plus a structured set that holds each known damage class on
+# purpose.  -> vasprun/mutants.npz
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+import tempfile  # noqa: E402
+
+from tests import ingest_mutants as M  # noqa: E402
+
+MUTANT_BASES = ["small", "comments_cdata_entities", "number_forms", "self_closing_row", "one_frame"]
+
+
+def judge(data, scratch):
+    with open(scratch, "wb") as f:
+        f.write(data)
+    out = {}
+    res = attempt(ref.read_trajectory, scratch)
+    out["traj"] = ("ok", res[1].positions_ts, res[1].timestep) if res[0] == "ok" else res
+    res = attempt(ref.read_positions, scratch)
+    out["pos"] = ("ok", np.asarray(res[1], dtype=np.float64), None) if res[0] == "ok" else res
+    return out
+
+
+def structured_xml(base):
+    """(offset, deleted, inserted) splices of `base` (small.xml), one damage class after the other."""
+    out = []
+
+    def at(needle, nth=0, after=False):
+        k = -1
+        for _ in range(nth + 1):
+            k = base.index(needle, k + 1)
+        return k + (len(needle) if after else 0)
+
+    row = at(b"0.46793495")              # a number in a row of the first MD frame (character data)
+    initial = at(b"0.62509547")          # ... and of the initial structure
+    potim = at(b"0.50000000", 1)         # the text of the POTIM element that is read
+    attr = at(b'name="POTIM">  0.5', 1) + len(b'name="P')  # inside that element's attribute value, before "OTIM"
+    gap = at(b" <structure>")            # between two children of the root
+    decl_end = at(b"?>\n", after=True)   # after the XML declaration
+    enc = at(b"ISO-8859-1")
+    end = len(base)
+
+    # references: the five predefined entities, decimal and hexadecimal character references, well and ill formed
+    good_refs = [b"&lt;", b"&gt;", b"&amp;", b"&quot;", b"&apos;", b"&#48;", b"&#x30;", b"&#048;", b"&#x0030;", b"&#x4f;",
+                 b"&#79;", b"&#233;", b"&#x20AC;", b"&#9;", b"&#x10FFFF;"]
+    bad_refs = [b"&", b"& ", b"&;", b"&lt", b"&amp ", b"&AMP;", b"&foo;", b"&#;", b"&#x;", b"&#X30;", b"&#4;", b"&#0;",
+                b"&#x110000;", b"&#xD800;", b"&#xFFFE;", b"&#48", b"&#4 8;", b"&#x3G;", b"&1;", b"&#-48;", b"&lt;;&", b"&&amp;"]
+    for ref_ in good_refs + bad_refs:
+        out.append((row, 1, ref_))        # in place of the leading 0 of a number
+        out.append((attr, 1, ref_))       # in place of the O of name="POTIM"
+        out.append((potim, 1, ref_))
+    for ref_ in (b"&#48;", b"&amp;", b"&", b"&#4;"):
+        out.append((initial, 1, ref_))
+        out.append((gap, 0, ref_))        # between elements, inside the root
+        out.append((end, 0, ref_))        # after the root
+        out.append((decl_end, 0, ref_))   # before the root
+    # comments
+    for text in (b"<!-- a -- b -->", b"<!-- a --->", b"<!---->", b"<!--->", b"<!-- - -->", b"<!-- <v> & -->", b"<!- a -->",
+                 b"<!-- a --", b"<! -- a -->"):
+        for where in (row, gap, decl_end, end):
+            out.append((where, 0, text))
+    # "]]>" in character data, CDATA sections
+    for text in (b"]]>", b"]]", b"]>", b"]]&gt;", b"] ]>", b"<![CDATA[]]>", b"<![CDATA[ 0.5 ]]>", b"<![CDATA[<v>&amp;]]>",
+                 b"<![CDATA[]]]]>", b"<![CDATA[ ]]", b"<![cdata[ ]]>", b"<![CDATA [ ]]>", b"<![CDATA[ ]]><![CDATA[ ]]>"):
+        for where in (row, potim, gap):
+            out.append((where, 0, text))
+    out.append((decl_end, 0, b"<![CDATA[ ]]>"))
+    out.append((end, 0, b"<![CDATA[ ]]>"))
+    # attributes
+    tag = at(b'<i name="POTIM">  0.5', 1)
+    for text in (b'<i name="POTIM" name="POTIM">', b'<i type="x" type="y" name="POTIM">', b'<i name="POTIM" nam="x">',
+                 b'<i name="PO<TIM">', b'<i name="PO>TIM">', b'<i name="PO&lt;TIM">', b"<i name='POTIM'>", b"<i name='PO\"TIM'>",
+                 b'<i name="POTIM\'>', b"<i name=POTIM>", b'<i name ="POTIM">', b'<i name= "POTIM">', b'<i name\n=\n"POTIM">',
+                 b'<i type="x"name="POTIM">', b'<i name="POTIM"type="x">', b'<i name="POTIM" >', b'<i name="POTIM"/>',
+                 b'<i name="POTIM" / >', b'<i name=" POTIM">', b'<i name="POTIM\n">', b'<i name="PO\tTIM">', b'<i 0name="POTIM">',
+                 b'<i -name="POTIM">', b'<i .name="POTIM">', b'<i _name="POTIM">', b'<i na.me-0="POTIM">', b'<i name>',
+                 b'<i name="POTIM" x>', b'<i a:b="1" name="POTIM">', b'<i xml:lang="en" name="POTIM">', b'<i name="POTIM"',
+                 b'<i\nname="POTIM"\n>', b'< i name="POTIM">', b'<0i name="POTIM">', b'<i name="">', b'<i name="POTIM" name2="POTIM">'):
+        out.append((tag, len(b'<i name="POTIM">'), text))
+    out.append((at(b"<v> 4.0", 1), 3, b'<v a="1" a="2">'))
+    out.append((at(b"<v> 4.0", 1), 3, b"<a:v>"))
+    out.append((at(b"</incar>"), len(b"</incar>"), b"</incar >"))
+    out.append((at(b"</incar>"), len(b"</incar>"), b"</ incar>"))
+    out.append((at(b"</incar>"), len(b"</incar>"), b'</incar a="1">'))
+    # processing instructions
+    for text in (b"<?x?>", b"<?x y?>", b"<?x y ?> ?>", b"<? x?>", b"<?0x?>", b"<?x", b"<?x y>", b"<?xml version=\"1.0\"?>",
+                 b"<?XML y?>", b"<?xmlx y?>", b"<?x?y?>"):
+        for where in (decl_end, row, gap, end):
+            out.append((where, 0, text))
+    # DOCTYPE
+    for text in (b"<!DOCTYPE modeling>", b"<!DOCTYPE modeling SYSTEM \"m.dtd\">", b"<!DOCTYPE modeling [ <!ELEMENT modeling ANY> ]>",
+                 b"<!doctype modeling>", b"<!DOCTYPE>", b"<!DOCTYPE modeling", b"<!DOCTYPE modeling><!DOCTYPE modeling>",
+                 b"<!ELEMENT modeling ANY>"):
+        for where in (decl_end, gap, end):
+            out.append((where, 0, text))
+    # byte-order mark, what may precede the declaration
+    for text in (b"\xef\xbb\xbf", b"\xef\xbb\xbf\xef\xbb\xbf", b"\xef\xbb\xbf ", b" ", b"\n", b"<!-- c -->", b"\xef\xbb"):
+        out.append((0, 0, text))
+    out.append((0, decl_end, b""))                      # no declaration at all
+    out.append((0, decl_end, b"\xef\xbb\xbf"))          # a mark and no declaration
+    # the declaration: encoding names, known, unknown and misspelt; its other parts
+    for name in (b"ISO-859-1", b"klingon", b"latin1", b"latin-1", b"iso-8859-1", b"ISO-8859-15", b"ISO-8859-12", b"UTF-8", b"utf-8",
+                 b"utf8", b"US-ASCII", b"ascii", b"UTF-16", b"utf-16", b"cp1252", b"", b"8859", b"ISO 8859-1", b"ISO-8859-1 "):
+        out.append((enc, len(b"ISO-8859-1"), name))
+    for text in (b'<?xml version="1.0"?>', b'<?xml version="1.1" encoding="ISO-8859-1"?>', b"<?xml version='1.0' encoding='ISO-8859-1'?>",
+                 b'<?xml encoding="ISO-8859-1"?>', b'<?xml encoding="ISO-8859-1" version="1.0"?>', b'<?xml version="1.0" standalone="yes"?>',
+                 b'<?xml version="1.0" standalone="maybe"?>', b'<?xml version="1.0" standalone="no" encoding="UTF-8"?>',
+                 b'<?xml version="1.0" encoding="UTF-8" standalone="no" ?>', b'<?xml version = "1.0" ?>', b'<?xml version="1.0"encoding="UTF-8"?>',
+                 b'<?xml version="1.0" encoding="UTF-8"', b'<?xml?>', b'<?xml ?>', b'<?xml version=1.0?>', b'<?xml version="1.0" x="y"?>',
+                 b'<?xml version="">', b'<?xml version=""?>', b'<?XML version="1.0"?>', b'<?xml\nversion="1.0"\n?>'):
+        out.append((0, decl_end - 1, text))
+    return out
+
+
+def record_mutants():
+    rec = M.Recorder(["traj", "pos"])
+    scratch = os.path.join(tempfile.mkdtemp(), "vasprun.xml")
+    bases = {}
+    for seed, name in enumerate(MUTANT_BASES):
+        with open(os.path.join(OUT, f"{name}.xml"), "rb") as f:
+            bases[name] = f.read()
+        for op, offset, arg in M.family(bases[name], M.XML_ALPHABET, seed + 101):
+            data = M.apply(bases[name], op, offset, arg)
+            rec.add(rec.base(name), op, offset, arg, data, judge(data, scratch))
+    structured = structured_xml(bases["small"])
+    for offset, deleted, inserted in structured:
+        data = bases["small"][:offset] + inserted + bases["small"][offset + deleted:]
+        rec.add(rec.base("small"), M.SPLICE, offset, rec.splice(deleted, inserted), data, judge(data, scratch))
+    rec.save(os.path.join(OUT, "mutants.npz"))
+    print(f"mutants: {len(rec.rows)} cases ({len(structured)} structured)")
+    for kind in rec.kinds:
+        counts = rec.counts(kind)
+        print(f"mutants: {kind}: {counts}")
+        assert min(counts[k] for k in ("returned", "InvalidFileException", "ValueError")) >= 50, "lopsided family: widen it"
+    largest = max(os.path.getsize(os.path.join(OUT, n)) for n in os.listdir(OUT) if n != "mutants.npz")
+    assert os.path.getsize(os.path.join(OUT, "mutants.npz")) < largest, "mutants.npz must stay below the largest fixture"
+
+
+record_mutants()
