@@ -196,6 +196,16 @@ LINESHAPE_SIGNATURES = {
     "rn_lineshape_last_error": (C.c_char_p, []),
 }
 
+# include/rn_quasiharmonic.h (the covariance moments of ramannoodle_amd/quasiharmonic.py; a table of its own as well)
+QH_SIGNATURES = {
+    "rn_qh_moments": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P]),
+    "rn_qh_moments_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "rn_qh_chunk_frames": (C.c_int, []),
+    "rn_qh_set_profiling": (C.c_int, [C.c_int]),
+    "rn_qh_phase_times": (C.c_int, [_P]),
+    "rn_qh_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 
 
@@ -218,7 +228,7 @@ def load() -> C.CDLL:
     except OSError as exc:
         raise DeviceError(f"cannot load {_LIB_PATH}: {exc}") from exc
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items())
-                                      + list(LINESHAPE_SIGNATURES.items())):
+                                      + list(LINESHAPE_SIGNATURES.items()) + list(QH_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes

@@ -317,6 +317,19 @@ void launch_mode_increments(const double *jac, const double *pos, int64_t steps,
 void launch_mode_rest(const double *jac, const double *pos, int64_t steps, int N, int M, const double *sigma,
                       int out_channels, double *out, hipStream_t st);
 
+// Covariance moments of quasi-harmonic mode analysis (kernels_covariance.hip; include/rn_quasiharmonic.h states them):
+// pos float64 [.][K]; chunks int64 [num_chunks][3] = (first frame, frames, steps) in ascending frames; block_chunks
+// int64 [B + 1], the chunks of block b; ws float64 [covariance_workspace_doubles]; first_ws float64 [num_chunks][K];
+// -> first float64 [B][K], second float64 [B][2][K][K].  All device pointers; B <= 65535 and num_chunks
+// covariance_pairs(K) < 2^31 (the grid).
+constexpr int kCovarianceChunkFrames = 512;  // the frames of a chunk: a multiple of the kernel's k-tile of 16
+int covariance_pairs(int64_t K);
+size_t covariance_workspace_doubles(int64_t K, int64_t num_chunks);
+void launch_covariance_chunks(const double *pos, int64_t K, const double *anchor, const int64_t *chunks,
+                              int64_t num_chunks, double *ws, double *first_ws, hipStream_t st);
+void launch_covariance_reduce(const double *ws, const double *first_ws, int64_t K, const int64_t *block_chunks, int64_t B,
+                              double *first, double *second, hipStream_t st);
+
 // The interpolation model on the device (kernels_interp.hip; api_interp.hip owns the arrays).  Everything float64:
 // F [J][K3] the basis with the lattice folded in and FT [K3][J] its transpose, ref [K3] the reference positions,
 // alpha_ref [9], poff [J+1] the piece offsets, xs the breakpoints (DOF j's P_j + 1 values start at poff[j] + j),

@@ -1,0 +1,220 @@
+// Covariance moments of quasi-harmonic mode analysis (include/rn_quasiharmonic.h; the definition is moments_host of
+// ramannoodle_amd/quasiharmonic.py): per block of frames, the sums of the minimum-image displacements w_t from an anchor,
+// of w_t w_t^T and of s_t s_t^T for the minimum-image steps s_t.
+//
+// covariance_chunk_kernel: two symmetric rank-updates of a K x K matrix (K = 3N) with the frames as the contraction
+// dimension, on v_mfma_f64_16x16x4_f64.  The columns are cut into tiles of kTile = 64, and only the pairs (I, J) of
+// tiles with I >= J are computed (at K = 768: 78 of 144).  The frames of a block are cut into chunks of
+// kCovarianceChunkFrames = 512 (kernels.hpp) so that the grid fills the device; a workgroup (4 waves) owns one pair of
+// one chunk and writes its two 64 x 64 partial sums to a workspace, [chunk][pair][series][64][64].  It walks the chunk
+// in ascending k-tiles of kFrames = 16 frames (4 k-steps of the instruction).  Per k-tile, thread (side = thread / 128: tile I or J; half = thread / 64 % 2; column =
+// thread % 64) loads its column of 9 consecutive frames (8 and the one after them, which both series of the last one
+// need: x_{t+1} is loaded once), and writes 8 displacements and 8 steps to LDS: neither series ever exists in HBM.
+// LDS is [series][side][frame][column] with a row stride of 80 doubles: an operand read (eight bytes a lane) is served
+// in two groups of 32 lanes, two frames (quads) x sixteen columns, whose doubles start at banks 2 l15 and 2 l15 + 32 of
+// the 64 and touch every bank once; the staging writes are contiguous along the columns.  Wave v holds rows 16 v .. 16
+// v + 15 of tile I against the 64 columns of tile J: per series four accumulators of the instruction.  First operand:
+// lane (l15, quad) holds frame 4 ks + quad of column 16 v + l15 of tile I; second operand: the same frame of column
+// 16 c + l15 of tile J; result register j of lane (l15, quad) is row 4 j + quad, column l15 (the layout of
+// mode_increment_kernel, tools/mfma_f64_layout_probe.hip).  The frames of the next k-tile are requested before the
+// products of this one.  The remainders of K, of the frames of a chunk and of its steps are zeros in LDS; loads are
+// unconditional from clamped addresses (a column past K reads column 0, a frame past the chunk's last reads that last
+// one), with the zero selected afterwards: nothing is read past an array.  A diagonal pair stages its tile twice and
+// computes the whole square; the reducing kernel reads its lower triangle only.
+// The pairs with J = 0 also sum the displacements of tile I: the stagers of side 0 add theirs in ascending frames, and
+// the two halves are added (half 0 + half 1) at the end: first_ws[chunk][K].
+//
+// covariance_reduce_kernel: one workgroup per (pair, series, block).  Thread e of 256 owns the elements e + 256 q of the
+// tile and adds the block's chunks in ascending order, from zero.  It writes element (r, c) to second[b][s][I0 + r][J0 +
+// c] and, through a transposing LDS tile (row stride 65), to its mirror [J0 + c][I0 + r]; of a diagonal pair the
+// elements with c <= r and the mirrors of those with c < r: both matrices are symmetric bit for bit.
+// covariance_first_kernel: first[b][j] = the ascending sum of first_ws over the block's chunks.
+// No atomics anywhere: the order of every sum depends on the chunk table, that is on (T, bounds), alone.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kernels.hpp"
+
+namespace rn {
+
+namespace {
+
+constexpr int kTile = 64;                // columns per tile
+constexpr int kFrames = 16;              // frames per k-tile
+constexpr int kStride = kTile + 16;      // LDS row stride in doubles (see the head of this file)
+constexpr int kKSteps = kFrames / 4;     // k-steps of the 16x16x4 instruction per k-tile
+constexpr int kHalfFrames = kFrames / 2; // frames a stager owns per k-tile
+constexpr int kThreads = 256;
+constexpr int kPlane = kFrames * kStride;  // doubles of one (series, side)
+constexpr int kMirrorStride = kTile + 1;
+
+typedef double f64x4_t __attribute__((ext_vector_type(4)));
+
+// pair p of the lower triangle, row-major: (0,0) (1,0) (1,1) (2,0) ..
+__device__ inline void lower_pair(int p, int &I, int &J) {
+  I = 0;
+  while ((I + 1) * (I + 2) / 2 <= p) ++I;
+  J = p - I * (I + 1) / 2;
+}
+
+// chunks: int64 [chunk][3] = (first frame f0, frames nf, steps ns <= nf); the chunk reads frames f0 .. f0 + max(nf - 1, ns)
+__global__ void __launch_bounds__(kThreads)
+    covariance_chunk_kernel(const double *__restrict__ pos, int64_t K, const double *__restrict__ anchor,
+                            const int64_t *__restrict__ chunks, int pairs, double *__restrict__ ws,
+                            double *__restrict__ first_ws) {
+  __shared__ double tile[2 * 2 * kPlane];  // [series][side][frame][column], row stride 80
+  const int chunk = blockIdx.x / pairs, pair = blockIdx.x % pairs;
+  int I, J;
+  lower_pair(pair, I, J);
+  const int64_t f0 = chunks[3 * (int64_t)chunk], nf = chunks[3 * (int64_t)chunk + 1], ns = chunks[3 * (int64_t)chunk + 2];
+  const int64_t last = std::max(nf - 1, ns);  // the last frame the chunk reads, relative to f0
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l15 = lane & 15, quad = lane >> 4;
+
+  // staging: thread (side, half, column) keeps its column of 9 frames in registers
+  const int side = threadIdx.x >> 7, half = (threadIdx.x >> 6) & 1, stage_col = threadIdx.x & 63;
+  const int64_t column = (int64_t)(side ? J : I) * kTile + stage_col;
+  const bool column_live = column < K;
+  const double *source = pos + f0 * K + (column_live ? column : 0);
+  const double origin = anchor[column_live ? column : 0];
+  double staged[kHalfFrames + 1];
+  auto load_tile = [&](int64_t t0) {  // frames t0 + 8 half .. + 8 of the chunk
+#pragma unroll
+    for (int j = 0; j <= kHalfFrames; ++j) {
+      const int64_t t = t0 + half * kHalfFrames + j;
+      staged[j] = source[(t < last ? t : last) * K];
+    }
+  };
+  load_tile(0);
+
+  f64x4_t acc[2][4];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[s][c] = f64x4_t{0.0, 0.0, 0.0, 0.0};
+  const bool sums_first = J == 0 && side == 0;
+  double total = 0.0;
+
+  for (int64_t t0 = 0; t0 < nf; t0 += kFrames) {
+    {
+      double *dst = tile + side * kPlane + (half * kHalfFrames) * kStride + stage_col;
+#pragma unroll
+      for (int j = 0; j < kHalfFrames; ++j) {
+        const int64_t t = t0 + half * kHalfFrames + j;
+        double w = staged[j] - origin;
+        w -= rint(w);
+        double s = staged[j + 1] - staged[j];
+        s -= rint(s);
+        w = column_live && t < nf ? w : 0.0;
+        s = column_live && t < ns ? s : 0.0;
+        if (sums_first) total += w;
+        dst[j * kStride] = w;
+        dst[2 * kPlane + j * kStride] = s;
+      }
+    }
+    __syncthreads();
+    if (t0 + kFrames < nf) load_tile(t0 + kFrames);
+    const double *a = tile + quad * kStride + 16 * wave + l15;       // side 0: tile I
+    const double *b = tile + kPlane + quad * kStride + l15;           // side 1: tile J
+#pragma unroll
+    for (int ks = 0; ks < kKSteps; ++ks) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const double av = a[s * 2 * kPlane + 4 * ks * kStride];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          acc[s][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b[s * 2 * kPlane + 4 * ks * kStride + 16 * c], acc[s][c],
+                                                           0, 0, 0);
+      }
+    }
+    __syncthreads();  // the next k-tile's series are written over these
+  }
+
+  double *out = ws + ((int64_t)chunk * pairs + pair) * (2 * kTile * kTile);
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        out[s * (kTile * kTile) + (16 * wave + 4 * j + quad) * kTile + 16 * c + l15] = acc[s][c][j];
+
+  if (J == 0) {  // (uniform over the workgroup; the loop ended with a barrier)
+    if (side == 0) tile[half * kTile + stage_col] = total;
+    __syncthreads();
+    if (threadIdx.x < kTile && column_live) first_ws[(int64_t)chunk * K + column] = tile[stage_col] + tile[kTile + stage_col];
+  }
+}
+
+// block_chunks: int64 [B + 1], the chunks of block b are block_chunks[b] .. block_chunks[b + 1] - 1; second [B][2][K][K]
+__global__ void __launch_bounds__(kThreads)
+    covariance_reduce_kernel(const double *__restrict__ ws, const int64_t *__restrict__ block_chunks, int pairs, int64_t K,
+                             double *__restrict__ second) {
+  __shared__ double mirror[kTile * kMirrorStride];
+  const int pair = blockIdx.x, series = blockIdx.y;
+  const int64_t block = blockIdx.z;
+  int I, J;
+  lower_pair(pair, I, J);
+  const int64_t c0 = block_chunks[block], c1 = block_chunks[block + 1];
+  double *out = second + (block * 2 + series) * K * K;
+  const int64_t row0 = (int64_t)I * kTile, col0 = (int64_t)J * kTile;
+  for (int q = 0; q < kTile * kTile / kThreads; ++q) {
+    const int e = threadIdx.x + kThreads * q;
+    const int r = e / kTile, c = e % kTile;
+    const double *p = ws + (c0 * pairs + pair) * (2 * kTile * kTile) + series * (kTile * kTile) + e;
+    double sum = 0.0;
+    for (int64_t chunk = c0; chunk < c1; ++chunk) {
+      sum += *p;
+      p += (int64_t)pairs * (2 * kTile * kTile);
+    }
+    mirror[r * kMirrorStride + c] = sum;
+    if (row0 + r < K && col0 + c < K && (I != J || c <= r)) out[(row0 + r) * K + col0 + c] = sum;
+  }
+  __syncthreads();
+  for (int q = 0; q < kTile * kTile / kThreads; ++q) {
+    const int e = threadIdx.x + kThreads * q;
+    const int r = e / kTile, c = e % kTile;  // of the mirrored tile: row in J, column in I
+    if (col0 + r < K && row0 + c < K && (I != J || c > r)) out[(col0 + r) * K + row0 + c] = mirror[c * kMirrorStride + r];
+  }
+}
+
+// first [B][K]
+__global__ void __launch_bounds__(kThreads)
+    covariance_first_kernel(const double *__restrict__ first_ws, const int64_t *__restrict__ block_chunks, int64_t K,
+                            double *__restrict__ first) {
+  const int64_t column = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  const int64_t block = blockIdx.y;
+  if (column >= K) return;
+  double sum = 0.0;
+  for (int64_t chunk = block_chunks[block]; chunk < block_chunks[block + 1]; ++chunk) sum += first_ws[chunk * K + column];
+  first[block * K + column] = sum;
+}
+
+}  // namespace
+
+int covariance_pairs(int64_t K) {
+  const int64_t tiles = (K + kTile - 1) / kTile;
+  return (int)(tiles * (tiles + 1) / 2);
+}
+
+size_t covariance_workspace_doubles(int64_t K, int64_t num_chunks) {
+  return (size_t)num_chunks * (size_t)covariance_pairs(K) * (2 * kTile * kTile);
+}
+
+void launch_covariance_chunks(const double *pos, int64_t K, const double *anchor, const int64_t *chunks,
+                              int64_t num_chunks, double *ws, double *first_ws, hipStream_t st) {
+  const int pairs = covariance_pairs(K);
+  covariance_chunk_kernel<<<(unsigned)(num_chunks * pairs), kThreads, 0, st>>>(pos, K, anchor, chunks, pairs, ws,
+                                                                               first_ws);
+}
+
+void launch_covariance_reduce(const double *ws, const double *first_ws, int64_t K, const int64_t *block_chunks, int64_t B,
+                              double *first, double *second, hipStream_t st) {
+  const int pairs = covariance_pairs(K);
+  covariance_reduce_kernel<<<dim3((unsigned)pairs, 2, (unsigned)B), kThreads, 0, st>>>(ws, block_chunks, pairs, K, second);
+  covariance_first_kernel<<<dim3((unsigned)((K + kThreads - 1) / kThreads), (unsigned)B), kThreads, 0, st>>>(
+      first_ws, block_chunks, K, first);
+}
+
+}  // namespace rn
