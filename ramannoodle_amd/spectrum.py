@@ -179,6 +179,21 @@ def _md_basis_spectra(polarizability_ts: NDArray[np.float64], timestep: float):
     return wavenumbers[keep], basis
 
 
+def _lag_axis(n: int, timestep: float):
+    """What the host reducers of ``n`` differences per segment start from: ``(wavenumbers, keep, length)``, the kept
+    wavenumbers (the positive ones of a length-``n`` transform), their bins and the padded transform length."""
+    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
+    keep = np.flatnonzero(wavenumbers >= 0)[1:]
+    return wavenumbers[keep], keep, 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+
+
+def _lag_spectrum(power, n: int, length: int, keep):
+    """The back half of the host reducers: power spectra on the padded length ``(..., length / 2 + 1)`` -> the positive
+    lags of the autocorrelation, their length-``n`` transform, the real bins ``keep``: ``(..., bins)``."""
+    lags = np.fft.irfft(power, n=length, axis=-1)[..., :n]
+    return np.real(scipy.fftpack.fft(lags, axis=-1))[..., keep]
+
+
 def _call_md_reducer(entry: str, source, n: int, too_short: str, timestep: float, device: int, stream,
                      out_shape, args_before=(), args_after=(), bin_axis: bool = True):
     """What every device reduction shares.  ``source`` is a host array (entry ``entry``) or, with ``stream`` set, a
@@ -340,14 +355,8 @@ def _md_segments_host(polarizability_ts, timestep: float, weights, width: int, h
     n = width - 1
     if starts is None:
         starts = _segment_starts(d.shape[0] + 1, width, hop)
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    keep = np.flatnonzero(wavenumbers >= 0)[1:]
-    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    wavenumbers, keep, length = _lag_axis(n, timestep)
     count = weights.shape[0]
-
-    def finish(power):  # (..., length / 2 + 1) -> (..., bins)
-        lags = np.fft.irfft(power, n=length, axis=-1)[..., :n]
-        return np.real(scipy.fftpack.fft(lags, axis=-1))[..., keep]
 
     rows = None if average else np.empty((len(starts), count, len(keep)))
     mean = np.zeros((count, length // 2 + 1))
@@ -360,8 +369,8 @@ def _md_segments_host(polarizability_ts, timestep: float, weights, width: int, h
         if average:
             mean += power.sum(axis=0)
         else:
-            rows[first:first + chunk] = finish(power)
-    return wavenumbers[keep], finish(mean / len(starts)) if average else rows
+            rows[first:first + chunk] = _lag_spectrum(power, n, length, keep)
+    return wavenumbers, _lag_spectrum(mean / len(starts), n, length, keep) if average else rows
 
 
 def _md_segments_on_device(alpha, timestep: float, weights, width: int, hop: int, tau, average: bool, device: int,
@@ -475,25 +484,346 @@ class PhononRamanSpectrum(RamanSpectrum):
         return self._phonon_wavenumbers, intensities[0] if squeeze else intensities
 
 
-class MDRamanSpectrum(RamanSpectrum):
-    """Spectrum from a polarizability time series ``(S,3,3)`` and a timestep in fs
-    (``spectrum/_raman.py:197-309``)."""
+# ----------------------------------------------------------------------------- the time series of an MD spectrum
+def _run_offsets(run_lengths) -> NDArray[np.int64]:
+    return np.concatenate([[0], np.cumsum(run_lengths)[:-1]]).astype(np.int64)
 
-    def __init__(self, polarizability_ts, timestep: float):
-        verify_ndarray_shape("polarizability_ts", polarizability_ts, (None, 3, 3))
-        self._polarizability_ts = polarizability_ts
-        self._timestep = timestep
+
+def _equal_run_length(run_lengths) -> int:
+    if len(set(run_lengths)) != 1:
+        raise ValueError(f"the mean of the runs' whole spectra needs runs of one length, not {sorted(set(run_lengths))}: "
+                         "use measure_segments")
+    return run_lengths[0]
+
+
+class _Series:
+    """The time series of an MD spectrum class, and the only thing that knows where it lives.
+
+    ``data`` is a host ndarray or a contiguous float64 CUDA tensor, time along the first axis.  Its rows are frames, or
+    with ``increments`` the differences between successive frames (frame t is where increment t begins).
+    ``run_lengths`` is ``None`` for a single run, or the frames of each of several runs joined end to end; runs of
+    increments are joined with one row between them (zeros, or whatever a batched evaluation of the joined frames wrote
+    there), so that increment t still belongs to frame t of the joined frames, and no segment reads that row."""
+
+    def __init__(self, data, run_lengths=None, increments: bool = False):
+        self.data = data
+        self.run_lengths = run_lengths
+        self.increments = increments
+        self._host_copy = None
+        self._whole_table = None
+
+    @classmethod
+    def of_tensor(cls, name: str, tensor, pattern, run_lengths=None, increments: bool = False):
+        """A CUDA tensor shaped like ``pattern`` (``None``: any size), contiguous and float64."""
+        shape = tuple(tensor.shape)
+        if len(shape) != len(pattern) or any(want is not None and have != want for have, want in zip(shape, pattern)):
+            raise ValueError(f"{name} has wrong shape: {shape} != {shape_string(pattern)}")
+        if not (tensor.is_cuda and tensor.is_contiguous() and str(tensor.dtype) == "torch.float64"):
+            raise ValueError(f"{name} must be a contiguous float64 CUDA tensor")
+        return cls(tensor, run_lengths, increments)
+
+    @classmethod
+    def of_runs(cls, runs, trailing, shared_axis: bool, increments: bool = False):
+        """Host runs joined end to end as float64: each ``(S_r, *trailing)``, or with ``shared_axis``
+        ``(S_r, A, *trailing)`` for the first run's ``A``."""
+        runs = list(runs)
+        if not runs:
+            raise ValueError("an ensemble needs at least one run")
+        pattern = (None, runs[0].shape[1], *trailing) if shared_axis else (None, *trailing)
+        for index, run in enumerate(runs):
+            verify_ndarray_shape(f"runs[{index}]", run, pattern)
+        parts = [np.asarray(run, dtype=np.float64) for run in runs]
+        if increments:
+            gap = np.zeros((1, *runs[0].shape[1:]))
+            parts = [part for run in parts for part in (run, gap)][:-1]
+        lengths = [int(run.shape[0]) + int(increments) for run in runs]
+        return cls(np.concatenate(parts, axis=0), lengths, increments)
+
+    @classmethod
+    def of_tensor_runs(cls, name: str, runs, run_lengths, pattern, increments: bool = False, tensors_only: bool = False):
+        """Device runs: a sequence of CUDA tensors, joined here on the GPU, or one tensor holding them end to end with
+        ``run_lengths`` (frames per run; joined increments have ``sum(run_lengths) - 1`` rows)."""
+        import torch
+        if isinstance(runs, torch.Tensor):
+            if run_lengths is None:
+                raise ValueError("runs: one joined tensor needs run_lengths")
+            lengths = [int(length) for length in run_lengths]
+            if not lengths or min(lengths) < 1 or sum(lengths) - int(increments) != runs.shape[0]:
+                raise ValueError(f"runs: run_lengths {lengths} do not add up to the {runs.shape[0]} rows of the tensor")
+            return cls.of_tensor(name, runs, pattern, lengths, increments)
+        if run_lengths is not None:
+            raise ValueError("runs: run_lengths goes with one joined tensor, not with a sequence of runs")
+        runs = list(runs)
+        if not runs:
+            raise ValueError("an ensemble needs at least one run")
+        if tensors_only and not all(isinstance(run, torch.Tensor) for run in runs):
+            raise ValueError("runs must be contiguous float64 CUDA tensors")
+        lengths = [int(run.shape[0]) + int(increments) for run in runs]
+        if increments:
+            gap = runs[0].new_zeros((1, *runs[0].shape[1:]))
+            joined = torch.cat([part for run in runs for part in (run, gap)][:-1], dim=0)
+        else:
+            joined = runs[0] if len(runs) == 1 else torch.cat(runs, dim=0)
+        return cls.of_tensor(name, joined, pattern, lengths, increments)
+
+    # -------------------------------------------------------------------------------------------------- access
+    @property
+    def shape(self) -> tuple:
+        return tuple(self.data.shape)
 
     @property
-    def polarizability_ts(self):
-        return self._polarizability_ts
+    def frames(self) -> int:
+        """Frames of the series, run boundaries included."""
+        return int(self.data.shape[0]) + int(self.increments)
+
+    @property
+    def gpu(self):
+        """The index of the GPU that holds the series, ``None`` for a host array."""
+        if not getattr(self.data, "is_cuda", False):
+            return None
+        return self.data.device.index or 0
+
+    def host(self):
+        """The series as a host array: a tensor is copied on first use."""
+        if self.gpu is None:
+            return self.data
+        if self._host_copy is None:
+            self._host_copy = self.data.cpu().numpy()
+        return self._host_copy
+
+    def source(self, device: int):
+        """``(source, stream)`` of a reduction on ``device``: a tensor on that GPU and torch's current stream there
+        (the ``_device`` entries, ordered after it); otherwise the host array, or the host copy of a tensor on another
+        GPU, and ``None``."""
+        if device != self.gpu:
+            return self.host(), None
+        import torch
+        return self.data, torch.cuda.current_stream(self.data.device).cuda_stream
+
+    def device_or_host(self, device, host: bool):
+        """The ``device=`` argument of a measurement for a device class's ``device=`` / ``host=`` pair: the tensor's GPU
+        unless another is named, or ``None`` (the host path) with ``host=True``."""
+        if host:
+            return None
+        return self.gpu if device is None else device
+
+    # -------------------------------------------------------------------------------------------------- segments
+    def segment_table(self, segment_steps, hop, taper):
+        """``(W, tau, starts)`` (``segment_plan``): the hop grid over a single run, or the segments of every run
+        (``ensemble_segment_starts``), counted in frames of the joined series, none of them across a run boundary."""
+        if self.run_lengths is None:
+            width, hop, tau = segment_plan(self.frames, segment_steps, hop, taper)
+            return width, tau, _segment_starts(self.frames, width, hop)
+        width, hop, tau = segment_plan(min(self.run_lengths), segment_steps, hop, taper)
+        return width, tau, ensemble_segment_starts(self.run_lengths, width, hop)[0]
+
+    def whole_table(self, too_few=None):
+        """The whole run as one boxcar segment, or each of several runs as one: those need one length.  ``too_few``: the
+        message for fewer than three frames, where ``segment_plan``'s is not the caller's."""
+        if self._whole_table is None:
+            frames = self.frames if self.run_lengths is None else _equal_run_length(self.run_lengths)
+            if too_few is not None and frames < 3:
+                raise ValueError(too_few)
+            self._whole_table = self.segment_table(frames, frames, "boxcar")
+        return self._whole_table
+
+    def segment_starts(self, segment_steps, hop=None):
+        """What the classes' ``segment_starts`` return: the first frame of each segment of a single run, or
+        ``(run_index, start_within_run)`` for runs."""
+        if self.run_lengths is None:
+            return self.segment_table(segment_steps, hop, "boxcar")[2]
+        starts, run_index = ensemble_segment_starts(self.run_lengths, segment_steps, hop)
+        return run_index, starts - _run_offsets(self.run_lengths)[run_index]
+
+
+def _held(name: str, value, pattern, increments: bool = False) -> _Series:
+    """The constructor argument of a host class: an array, checked here, or the holder a subclass has made."""
+    if isinstance(value, _Series):
+        return value
+    verify_ndarray_shape(name, value, pattern)
+    return _Series(value, increments=increments)
+
+
+# ----------------------------------------------------------------------------- weight-contracted measurements
+class _ContractedSpectrum:
+    """``measure`` / ``measure_polarized`` of every spectrum that contracts the spectra of component pairs with weights
+    (``polarized_weights``).  ``_whole(weights, device)`` returns the uncorrected ``(wavenumbers, I[K, *rows, bins])``
+    and ``_row_axes`` counts the row axes between ``K`` and the bins: none for a whole spectrum, the ``G,G`` of the
+    atom-group spectra, the ``C+1`` of the mode spectra.  The corrections apply to every row."""
+
+    _row_axes = 0
+
+    def _whole(self, weights, device):
+        raise NotImplementedError
+
+    def _first_configuration(self, intensities):
+        """Drop the ``K`` axis, which stands before the rows."""
+        return intensities[(..., 0) + (slice(None),) * (self._row_axes + 1)]
+
+    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
+                bose_einstein_correction=False, temperature=300, device=None):
+        """``(wavenumbers, I[*rows, bins])`` of ``45 a^2 + 7 gamma^2``, the powder average."""
+        _require_polycrystalline(orientation)
+        wavenumbers, intensities = self._whole(_measure_weights(), device)
+        intensities = _apply_corrections(wavenumbers, self._first_configuration(intensities), laser_correction,
+                                         laser_wavelength, bose_einstein_correction, temperature)
+        return wavenumbers, intensities
+
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False, laser_wavelength=522,
+                          bose_einstein_correction=False, temperature=300, device=None):
+        """``(wavenumbers, I[K, *rows, bins])`` for the configurations of ``polarized_weights``; ``[*rows, bins]`` when
+        no argument has a ``K`` axis."""
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        wavenumbers, intensities = self._whole(weights, device)
+        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, self._first_configuration(intensities) if squeeze else intensities
+
+
+class _ContractedMDSpectrum(_ContractedSpectrum):
+    """The four weight-contracted measurements of the MD Raman classes (whole, atom-group, mode) over the series in
+    ``self._series``.  A class supplies ``_reduce(weights, table, average, device)`` for a segment table
+    ``(W, tau, starts)`` of the holder: the uncorrected ``(wavenumbers, I[K, *rows, bins])``, or
+    ``I[Q, K, *rows, bins]`` with ``average=False``; ``device=None`` is the host path.  ``measure`` /
+    ``measure_polarized`` take the holder's whole table, the segment measurements its segment table."""
+
+    def __init__(self, series: _Series, timestep: float):
+        self._series = series
+        self._timestep = timestep
 
     @property
     def timestep(self) -> float:
         return self._timestep
 
-    def _measure_on_device(self, device: int):
-        return _md_intensities_on_device(self._polarizability_ts, self._timestep, device)
+    def _reduce(self, weights, table, average: bool, device):
+        raise NotImplementedError
+
+    def _whole_table(self):
+        return self._series.whole_table()
+
+    def _whole(self, weights, device):
+        return self._reduce(weights, self._whole_table(), True, device)
+
+    def _segments(self, weights, segment_steps, hop, taper, average, device):
+        return self._reduce(weights, self._series.segment_table(segment_steps, hop, taper), bool(average), device)
+
+    def segment_starts(self, segment_steps, hop=None) -> NDArray[np.int64]:
+        """The first frame of each of the ``Q = (S - segment_steps) // hop + 1`` segments of ``measure_segments``: the
+        time axis of a spectrogram (segment q covers frames ``starts[q] .. starts[q] + segment_steps - 1``; for
+        increments, frame t is where increment t begins)."""
+        return self._series.segment_starts(segment_steps, hop)
+
+    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
+                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
+                         device=None):
+        """Segment-averaged (Welch) or time-resolved spectra of ``measure()``'s ``45 a^2 + 7 gamma^2``: the series is
+        cut into ``Q`` overlapping segments of ``segment_steps`` frames, ``hop`` frames apart (default
+        ``segment_steps // 2``), whose ``segment_steps - 1`` differences are multiplied by ``taper``
+        (``spectrum.segment_plan``; normalised to a mean square of one).  ``average=True`` returns
+        ``(wavenumbers, I[*rows, bins])``, the arithmetic mean over the segments, whose variance falls with ``Q`` where a
+        single periodogram's does not fall with the length of the series; ``average=False`` the rows
+        ``(wavenumbers, I[Q, *rows, bins])``.  No further normalisation is applied: magnitudes scale with the segment
+        length as ``measure()``'s scale with the series length, and the wavenumbers are those of a ``segment_steps``
+        series.  The corrections apply to every row."""
+        _require_polycrystalline(orientation)
+        wavenumbers, intensities = self._segments(_measure_weights(), segment_steps, hop, taper, average, device)
+        intensities = _apply_corrections(wavenumbers, self._first_configuration(intensities), laser_correction,
+                                         laser_wavelength, bose_einstein_correction, temperature)
+        return wavenumbers, intensities
+
+    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
+                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
+                                   bose_einstein_correction=False, temperature=300, device=None):
+        """``measure_segments`` for the configurations of ``measure_polarized`` (``polarized_weights``): intensities
+        ``(K, *rows, bins)``, or ``(Q, K, *rows, bins)`` with ``average=False``; the ``K`` axis is squeezed when no
+        argument has one."""
+        weights, squeeze = polarized_weights(incident, scattered, orientation)
+        wavenumbers, intensities = self._segments(weights, segment_steps, hop, taper, average, device)
+        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature)
+        return wavenumbers, self._first_configuration(intensities) if squeeze else intensities
+
+
+class _Ensemble:
+    """What the classes of several runs add to their single-run class."""
+
+    @property
+    def run_lengths(self) -> list[int]:
+        """Frames per run (for runs of increments, one more than the run's increments)."""
+        return list(self._series.run_lengths)
+
+    def segment_starts(self, segment_steps, hop=None) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
+        """``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
+        return self._series.segment_starts(segment_steps, hop)
+
+
+class _OnDevice:
+    """Mixin for a Raman class whose series stays in HBM as a contiguous float64 CUDA tensor: ``measure`` /
+    ``measure_polarized`` / ``measure_segments`` / ``measure_segments_polarized`` reduce it on the tensor's GPU unless
+    ``host=True``; another ``device`` gets the host copy, which is made on first use."""
+
+    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
+                bose_einstein_correction=False, temperature=300, device=None, host=False):
+        """As the base class's ``measure``; reduces on the tensor's GPU unless ``host=True``."""
+        return super().measure(orientation, laser_correction, laser_wavelength, bose_einstein_correction,
+                               temperature, device=self._series.device_or_host(device, host))
+
+    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False,
+                          laser_wavelength=522, bose_einstein_correction=False, temperature=300, device=None,
+                          host=False):
+        """As the base class's ``measure_polarized``; reduces on the tensor's GPU unless ``host=True`` (the
+        ``_device`` entries: only the intensities leave HBM)."""
+        return super().measure_polarized(incident, scattered, orientation, laser_correction, laser_wavelength,
+                                         bose_einstein_correction, temperature,
+                                         device=self._series.device_or_host(device, host))
+
+    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
+                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
+                         device=None, host=False):
+        """As the base class's ``measure_segments``; reduces on the tensor's GPU unless ``host=True``."""
+        return super().measure_segments(segment_steps, hop, taper, average, orientation, laser_correction,
+                                        laser_wavelength, bose_einstein_correction, temperature,
+                                        device=self._series.device_or_host(device, host))
+
+    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
+                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
+                                   bose_einstein_correction=False, temperature=300, device=None, host=False):
+        """As the base class's ``measure_segments_polarized``; reduces on the tensor's GPU unless ``host=True``."""
+        return super().measure_segments_polarized(
+            incident, scattered, orientation, segment_steps=segment_steps, hop=hop, taper=taper, average=average,
+            laser_correction=laser_correction, laser_wavelength=laser_wavelength,
+            bose_einstein_correction=bose_einstein_correction, temperature=temperature,
+            device=self._series.device_or_host(device, host))
+
+
+# ----------------------------------------------------------------------------- the whole MD spectrum
+class MDRamanSpectrum(_ContractedMDSpectrum, RamanSpectrum):
+    """Spectrum from a polarizability time series ``(S,3,3)`` and a timestep in fs
+    (``spectrum/_raman.py:197-309``).
+
+    ``measure_polarized``: spectra for set incident / scattered polarizations and crystal orientations (an addition).
+    Configuration k's spectrum is ``calc_signal_spectrum(s_k, timestep)`` without the zero bin, on ``measure``'s
+    wavenumbers, for ``s_k(t) = e_s . R da(t) R^T . e_i`` with ``da(t) = alpha(t+1) - alpha(t)``; the symmetric part of
+    ``da`` is used (every model output is exactly symmetric).  Arguments as ``PhononRamanSpectrum.measure_polarized``;
+    under ``"polycrystalline"`` the invariant spectra take the place of ``a^2`` and ``gamma^2``, so
+    ``45 (I_parallel + I_perpendicular)`` is ``measure()``.  Intensities are ``(K, bins)``, or ``(bins,)`` when no
+    argument has a ``K`` axis.  The 21 cross-spectra of the tensor components are computed once and contracted with each
+    configuration's weights (``polarized_weights``); ``device`` (an int) does that on the GPU
+    (``rn_md_raman_polarized``).
+
+    ``measure_segments`` (an addition) is the segment-averaged (Welch) or time-resolved spectrum of ``measure()``:
+    ``(wavenumbers, I[bins])``, or with ``average=False`` the spectrogram ``(wavenumbers, I[Q, bins])``.  Row q is the
+    spectrum of segment q: with ``taper="boxcar"`` it is
+    ``MDRamanSpectrum(alpha[a:a + segment_steps], timestep).measure()`` for ``a = segment_starts(...)[q]``.  ``device``
+    (an int) reduces on that GPU (``rn_md_raman_segments``: the mean is taken before the inverse transform).
+    ``measure_segments_polarized`` returns ``(K, bins)``, or ``(Q, K, bins)`` with ``average=False``."""
+
+    def __init__(self, polarizability_ts, timestep: float):
+        super().__init__(_held("polarizability_ts", polarizability_ts, (None, 3, 3)), timestep)
+
+    @property
+    def polarizability_ts(self):
+        return self._series.host()
 
     def measure(self, orientation="polycrystalline", laser_correction=False,
                 laser_wavelength=522, bose_einstein_correction=False, temperature=300, device=None):
@@ -503,11 +833,12 @@ class MDRamanSpectrum(RamanSpectrum):
         _require_polycrystalline(orientation)
         dt = self._timestep
         if device is not None:
-            wavenumbers, intensities = self._measure_on_device(int(device))
+            source, stream = self._series.source(int(device))
+            wavenumbers, intensities = _md_intensities_on_device(source, dt, int(device), stream)
             intensities = _apply_corrections(wavenumbers, intensities, laser_correction,
                                              laser_wavelength, bose_einstein_correction, temperature)
             return wavenumbers, intensities
-        ad = np.diff(self._polarizability_ts, axis=0)  # d(alpha)/dt up to a constant
+        ad = np.diff(self._series.host(), axis=0)  # d(alpha)/dt up to a constant
 
         def spec(sig):
             return calc_signal_spectrum(sig, dt)[1]
@@ -526,208 +857,48 @@ class MDRamanSpectrum(RamanSpectrum):
                                          laser_wavelength, bose_einstein_correction, temperature)
         return wavenumbers, intensities
 
-    def _polarized_on_device(self, weights, device: int):
-        return _md_polarized_on_device(self._polarizability_ts, self._timestep, weights, device)
-
-    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False,
-                          laser_wavelength=522, bose_einstein_correction=False, temperature=300, device=None):
-        """Spectra for set incident / scattered polarizations and crystal orientations (an addition).
-
-        Configuration k's spectrum is ``calc_signal_spectrum(s_k, timestep)`` without the zero bin, on
-        ``measure``'s wavenumbers, for ``s_k(t) = e_s . R da(t) R^T . e_i`` with
-        ``da(t) = alpha(t+1) - alpha(t)``; the symmetric part of ``da`` is used (every model output is
-        exactly symmetric).  Arguments as ``PhononRamanSpectrum.measure_polarized``; under
-        ``"polycrystalline"`` the invariant spectra take the place of ``a^2`` and ``gamma^2``, so
-        ``45 (I_parallel + I_perpendicular)`` is ``measure()``.  Intensities are ``(K, bins)``, or
-        ``(bins,)`` when no argument has a ``K`` axis.  The 21 cross-spectra of the tensor components are
-        computed once and contracted with each configuration's weights (``polarized_weights``);
-        ``device`` (an int) does that on the GPU (``rn_md_raman_polarized``).
-        """
-        weights, squeeze = polarized_weights(incident, scattered, orientation)
+    def _whole(self, weights, device):
+        """A single run has entries of its own: the 21 cross-spectra of the whole series."""
         if device is not None:
-            wavenumbers, intensities = self._polarized_on_device(weights, int(device))
-        else:
-            wavenumbers, basis = _md_basis_spectra(np.asarray(self._polarizability_ts, dtype=np.float64),
-                                                   self._timestep)
-            intensities = weights @ basis
-        intensities = _apply_corrections(wavenumbers, intensities, laser_correction,
-                                         laser_wavelength, bose_einstein_correction, temperature)
-        return wavenumbers, intensities[0] if squeeze else intensities
-
-    def _num_steps(self) -> int:
-        return self._polarizability_ts.shape[0]
-
-    def _segments_on_device(self, weights, width, hop, tau, average, device: int):
-        return _md_segments_on_device(self._polarizability_ts, self._timestep, weights, width, hop, tau, average, device)
+            source, stream = self._series.source(int(device))
+            return _md_polarized_on_device(source, self._timestep, weights, int(device), stream=stream)
+        wavenumbers, basis = _md_basis_spectra(np.asarray(self._series.host(), dtype=np.float64), self._timestep)
+        return wavenumbers, weights @ basis
 
     def _segments(self, weights, segment_steps, hop, taper, average, device):
-        """The uncorrected ``(wavenumbers, I[K][bins] or I[Q][K][bins])`` of both segment measurements."""
-        width, hop, tau = segment_plan(self._num_steps(), segment_steps, hop, taper)
-        if device is not None:
-            return self._segments_on_device(weights, width, hop, tau, bool(average), int(device))
-        return _md_segments_host(self._polarizability_ts, self._timestep, weights, width, hop, tau, bool(average))
+        """A single run goes to the hop-grid entry (``rn_md_raman_segments``), which builds the table itself."""
+        width, hop, tau = segment_plan(self._series.frames, segment_steps, hop, taper)
+        if device is None:
+            return _md_segments_host(self._series.host(), self._timestep, weights, width, hop, tau, bool(average))
+        source, stream = self._series.source(int(device))
+        return _md_segments_on_device(source, self._timestep, weights, width, hop, tau, bool(average), int(device),
+                                      stream=stream)
 
-    def segment_starts(self, segment_steps, hop=None) -> NDArray[np.int64]:
-        """The first step of each of the ``Q = (S - segment_steps) // hop + 1`` segments of ``measure_segments``: the time
-        axis of a spectrogram (segment q covers steps ``starts[q] .. starts[q] + segment_steps - 1``)."""
-        width, hop, _ = segment_plan(self._num_steps(), segment_steps, hop, "boxcar")
-        return _segment_starts(self._num_steps(), width, hop)
-
-    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
-                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
-                         device=None):
-        """Segment-averaged (Welch) or time-resolved spectrum of ``measure()``'s ``45 a^2 + 7 gamma^2`` (an addition).
-
-        The series is cut into ``Q`` overlapping segments of ``segment_steps`` polarizabilities, ``hop`` steps apart
-        (default ``segment_steps // 2``), whose ``segment_steps - 1`` differences are multiplied by ``taper``
-        (``spectrum.segment_plan``; normalised to a mean square of one).  Row q is the spectrum of segment q: with
-        ``taper="boxcar"`` it is ``MDRamanSpectrum(alpha[a:a + segment_steps], timestep).measure()`` for
-        ``a = segment_starts(...)[q]``.  ``average=True`` returns ``(wavenumbers, I[bins])``, the arithmetic mean of the
-        rows, whose variance falls with ``Q`` where a single periodogram's does not fall with the length of the series;
-        ``average=False`` returns the spectrogram ``(wavenumbers, I[Q, bins])``.  No further normalisation is applied:
-        magnitudes scale with the segment length as ``measure()``'s scale with the series length, and the wavenumbers
-        are those of a ``segment_steps`` series.  The corrections apply to every row.  ``device`` (an int) reduces on
-        that GPU (``rn_md_raman_segments``: the mean is taken before the inverse transform)."""
-        _require_polycrystalline(orientation)
-        wavenumbers, intensities = self._segments(_measure_weights(), segment_steps, hop, taper, average, device)
-        intensities = _apply_corrections(wavenumbers, intensities[..., 0, :], laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities
-
-    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
-                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
-                                   bose_einstein_correction=False, temperature=300, device=None):
-        """``measure_segments`` for the configurations of ``measure_polarized`` (``polarized_weights``): intensities
-        ``(K, bins)``, or ``(Q, K, bins)`` with ``average=False``; the ``K`` axis is squeezed when no argument has one."""
-        weights, squeeze = polarized_weights(incident, scattered, orientation)
-        wavenumbers, intensities = self._segments(weights, segment_steps, hop, taper, average, device)
-        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities[..., 0, :] if squeeze else intensities
+    def _reduce(self, weights, table, average: bool, device):
+        width, tau, starts = table
+        if device is None:
+            return _md_segments_host(self._series.host(), self._timestep, weights, width, None, tau, bool(average),
+                                     starts=starts)
+        source, stream = self._series.source(int(device))
+        return _md_segments_at_on_device(source, self._timestep, weights, width, starts, tau, bool(average), int(device),
+                                         stream=stream)
 
 
-class _DeviceResident:
-    """Mixin for a spectrum whose input stays in HBM as a contiguous float64 CUDA tensor: ``measure`` /
-    ``measure_polarized`` (and, where the base class has them, ``measure_segments`` / ``measure_segments_polarized``)
-    reduce it on the tensor's GPU unless ``host=True``; another ``device`` gets the host copy, which is made on first
-    use."""
-
-    def _set_tensor(self, name: str, tensor, ndim: int, pattern: str) -> None:
-        shape = tuple(tensor.shape)
-        if len(shape) != ndim or shape[-2:] != (3, 3):
-            raise ValueError(f"{name} has wrong shape: {shape} != {pattern}")
-        if not (tensor.is_cuda and tensor.is_contiguous() and str(tensor.dtype) == "torch.float64"):
-            raise ValueError(f"{name} must be a contiguous float64 CUDA tensor")
-        self._tensor = tensor
-        self._host_copy = None
-
-    def _host(self):
-        if self._host_copy is None:
-            self._host_copy = self._tensor.cpu().numpy()
-        return self._host_copy
-
-    def _device_index(self) -> int:
-        return self._tensor.device.index or 0
-
-    def _source(self, device: int):
-        """``(source, stream)`` of a reduction on ``device``: the tensor and the current stream of its GPU, or the
-        host copy and ``None`` when ``device`` is another GPU."""
-        import torch
-        if device != self._device_index():
-            return self._host(), None
-        return self._tensor, torch.cuda.current_stream(self._tensor.device).cuda_stream
-
-    def _device_or_host(self, device, host: bool):
-        """The base classes' ``device=`` argument for this class's ``device=`` / ``host=``."""
-        if host:
-            return None
-        return self._device_index() if device is None else device
-
-    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
-                bose_einstein_correction=False, temperature=300, device=None, host=False):
-        """As the base class's ``measure``; reduces on the tensor's GPU unless ``host=True``."""
-        return super().measure(orientation, laser_correction, laser_wavelength, bose_einstein_correction,
-                               temperature, device=self._device_or_host(device, host))
-
-    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False,
-                          laser_wavelength=522, bose_einstein_correction=False, temperature=300, device=None,
-                          host=False):
-        """As the base class's ``measure_polarized``; reduces on the tensor's GPU unless ``host=True`` (the
-        ``_device`` entries: only the intensities leave HBM)."""
-        return super().measure_polarized(incident, scattered, orientation, laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature,
-                                         device=self._device_or_host(device, host))
-
-    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
-                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
-                         device=None, host=False):
-        """As the base class's ``measure_segments``; reduces on the tensor's GPU unless ``host=True``."""
-        return super().measure_segments(segment_steps, hop, taper, average, orientation, laser_correction,
-                                        laser_wavelength, bose_einstein_correction, temperature,
-                                        device=self._device_or_host(device, host))
-
-    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
-                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
-                                   bose_einstein_correction=False, temperature=300, device=None, host=False):
-        """As the base class's ``measure_segments_polarized``; reduces on the tensor's GPU unless ``host=True``."""
-        return super().measure_segments_polarized(
-            incident, scattered, orientation, segment_steps=segment_steps, hop=hop, taper=taper, average=average,
-            laser_correction=laser_correction, laser_wavelength=laser_wavelength,
-            bose_einstein_correction=bose_einstein_correction, temperature=temperature,
-            device=self._device_or_host(device, host))
-
-
-class DeviceMDRamanSpectrum(_DeviceResident, MDRamanSpectrum):
+class DeviceMDRamanSpectrum(_OnDevice, MDRamanSpectrum):
     """``MDRamanSpectrum`` whose polarizability time series stays where the evaluator wrote it
     (HBM, a contiguous torch CUDA tensor ``float64[S,3,3]``): ``measure`` reduces it on that GPU
     and only the intensities travel to the host.  ``polarizability_ts``
     copies the series to the host on first use, for callers that want the numbers themselves."""
 
-    def __init__(self, polarizability_ts_device, timestep: float):  # pylint: disable=super-init-not-called
-        self._set_tensor("polarizability_ts", polarizability_ts_device, 3, "(_,3,3)")
-        self._timestep = timestep
+    def __init__(self, polarizability_ts_device, timestep: float):
+        super().__init__(_Series.of_tensor("polarizability_ts", polarizability_ts_device, (None, 3, 3)), timestep)
 
     @property
     def _device_ts(self):
-        return self._tensor
-
-    @property
-    def polarizability_ts(self):
-        return self._host()
-
-    @property
-    def _polarizability_ts(self):  # what the host path of MDRamanSpectrum.measure reads
-        return self._host()
-
-    def _measure_on_device(self, device: int):
-        source, stream = self._source(device)
-        return _md_intensities_on_device(source, self._timestep, device, stream)
-
-    def _polarized_on_device(self, weights, device: int):
-        source, stream = self._source(device)
-        return _md_polarized_on_device(source, self._timestep, weights, device, stream=stream)
-
-    def _num_steps(self) -> int:
-        return self._tensor.shape[0]
-
-    def _segments_on_device(self, weights, width, hop, tau, average, device: int):
-        source, stream = self._source(device)
-        return _md_segments_on_device(source, self._timestep, weights, width, hop, tau, average, device, stream=stream)
+        return self._series.data
 
 
-# ----------------------------------------------------------------------------- ensembles of runs
-def _run_offsets(run_lengths) -> NDArray[np.int64]:
-    return np.concatenate([[0], np.cumsum(run_lengths)[:-1]]).astype(np.int64)
-
-
-def _equal_run_length(run_lengths) -> int:
-    if len(set(run_lengths)) != 1:
-        raise ValueError(f"the mean of the runs' whole spectra needs runs of one length, not {sorted(set(run_lengths))}: "
-                         "use measure_segments")
-    return run_lengths[0]
-
-
-class MDRamanEnsemble(MDRamanSpectrum):
+class MDRamanEnsemble(_Ensemble, MDRamanSpectrum):
     """Spectra averaged over several independent runs (an addition): ``runs`` is a sequence of polarizability time
     series ``(S_r,3,3)`` sharing ``timestep`` (fs), for example NVE branches started from NVT snapshots.
 
@@ -735,118 +906,34 @@ class MDRamanEnsemble(MDRamanSpectrum):
     (``ensemble_segment_starts``): ``average=True`` is the mean over all segments of all runs, ``average=False`` gives
     the rows in run order.  No segment crosses a run boundary, where the difference of the joined series is a jump
     that would put a broadband artefact into every bin.  ``measure`` / ``measure_polarized`` are the mean of the runs'
-    whole spectra (the boxcar segment of ``S_r`` steps), defined when the runs have one length.  ``device`` (an int)
-    reduces all runs in one call on that GPU (``rn_md_raman_segments_at``)."""
+    whole spectra (the boxcar segment of ``S_r`` steps), defined when the runs have one length: ``measure`` is the mean
+    of ``MDRamanSpectrum(run, timestep).measure()`` over the runs and ``measure_polarized`` that of the runs'
+    ``measure_polarized``; a ``ValueError`` unless they have one length (their wavenumbers differ otherwise).
+    ``device`` (an int) reduces all runs in one call on that GPU (``rn_md_raman_segments_at``)."""
 
-    def __init__(self, runs, timestep: float):  # pylint: disable=super-init-not-called
-        runs = list(runs)
-        if not runs:
-            raise ValueError("an ensemble needs at least one run")
-        for index, run in enumerate(runs):
-            verify_ndarray_shape(f"runs[{index}]", run, (None, 3, 3))
-        self._run_lengths = [int(run.shape[0]) for run in runs]
-        self._polarizability_ts = np.concatenate([np.asarray(run, dtype=np.float64) for run in runs], axis=0)
-        self._timestep = timestep
+    # runs have no entry of a single series: every measurement is the base's, over the holder's tables
+    measure = _ContractedMDSpectrum.measure
+    _whole = _ContractedMDSpectrum._whole
+    _segments = _ContractedMDSpectrum._segments
 
-    @property
-    def run_lengths(self) -> list[int]:
-        return list(self._run_lengths)
+    def __init__(self, runs, timestep: float):
+        super().__init__(runs if isinstance(runs, _Series) else _Series.of_runs(runs, (3, 3), False), timestep)
 
     @property
     def runs(self):
         """The runs' series, views of the joined ``polarizability_ts``."""
-        bounds = np.cumsum(self._run_lengths)[:-1]
-        return np.split(self._polarizability_ts, bounds, axis=0)
-
-    def _segments_at_on_device(self, weights, width, starts, tau, average, device: int):
-        return _md_segments_at_on_device(self._polarizability_ts, self._timestep, weights, width, starts, tau, average,
-                                         device)
-
-    def _segments(self, weights, segment_steps, hop, taper, average, device):
-        width, hop, tau = segment_plan(min(self._run_lengths), segment_steps, hop, taper)
-        starts, _ = ensemble_segment_starts(self._run_lengths, width, hop)
-        if device is not None:
-            return self._segments_at_on_device(weights, width, starts, tau, bool(average), int(device))
-        return _md_segments_host(self._polarizability_ts, self._timestep, weights, width, hop, tau, bool(average),
-                                 starts=starts)
-
-    def segment_starts(self, segment_steps, hop=None) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
-        """``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
-        starts, run_index = ensemble_segment_starts(self._run_lengths, segment_steps, hop)
-        return run_index, starts - _run_offsets(self._run_lengths)[run_index]
-
-    def _whole(self, weights, device):
-        """The mean over the runs of each run's whole spectrum: one boxcar segment per run."""
-        steps = _equal_run_length(self._run_lengths)
-        return self._segments(weights, steps, steps, "boxcar", True, device)
-
-    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
-                bose_einstein_correction=False, temperature=300, device=None):
-        """The mean of ``MDRamanSpectrum(run, timestep).measure()`` over the runs; a ``ValueError`` unless they have
-        one length (their wavenumbers differ otherwise)."""
-        _require_polycrystalline(orientation)
-        wavenumbers, intensities = self._whole(_measure_weights(), device)
-        intensities = _apply_corrections(wavenumbers, intensities[0], laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities
-
-    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False, laser_wavelength=522,
-                          bose_einstein_correction=False, temperature=300, device=None):
-        """The mean of the runs' ``measure_polarized``; a ``ValueError`` unless they have one length."""
-        weights, squeeze = polarized_weights(incident, scattered, orientation)
-        wavenumbers, intensities = self._whole(weights, device)
-        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities[0] if squeeze else intensities
+        bounds = np.cumsum(self._series.run_lengths)[:-1]
+        return np.split(self._series.host(), bounds, axis=0)
 
 
-def _joined_tensor(name: str, runs, run_lengths, rows_short: int):
-    """``(tensor, run_lengths)`` of a device ensemble: ``runs`` is one CUDA tensor holding the runs end to end, with
-    ``run_lengths`` (steps per run; the tensor has ``sum(run_lengths) - rows_short`` rows), or a sequence of tensors."""
-    import torch
-    if isinstance(runs, torch.Tensor):
-        if run_lengths is None:
-            raise ValueError(f"{name}: one joined tensor needs run_lengths")
-        lengths = [int(length) for length in run_lengths]
-        if not lengths or min(lengths) < 1 or sum(lengths) - rows_short != runs.shape[0]:
-            raise ValueError(f"{name}: run_lengths {lengths} do not add up to the {runs.shape[0]} rows of the tensor")
-        return runs, lengths
-    if run_lengths is not None:
-        raise ValueError(f"{name}: run_lengths goes with one joined tensor, not with a sequence of runs")
-    runs = list(runs)
-    if not runs:
-        raise ValueError("an ensemble needs at least one run")
-    return runs, None
-
-
-class DeviceMDRamanEnsemble(_DeviceResident, MDRamanEnsemble):
+class DeviceMDRamanEnsemble(_OnDevice, MDRamanEnsemble):
     """``MDRamanEnsemble`` whose runs stay in HBM: ``runs`` is a sequence of contiguous float64 CUDA tensors
     ``(S_r,3,3)`` (joined here, on the GPU), or one tensor holding them end to end plus ``run_lengths``, as one batched
     evaluation writes it.  Every measurement reduces on that GPU (``rn_md_raman_segments_at_device``, ordered after
     torch's current stream) unless ``host=True``."""
 
-    def __init__(self, runs, timestep: float, run_lengths=None):  # pylint: disable=super-init-not-called
-        import torch
-        runs, lengths = _joined_tensor("runs", runs, run_lengths, 0)
-        if lengths is None:
-            lengths = [int(run.shape[0]) for run in runs]
-            runs = runs[0] if len(runs) == 1 else torch.cat(runs, dim=0)
-        self._set_tensor("runs", runs, 3, "(_,3,3)")
-        self._run_lengths = lengths
-        self._timestep = timestep
-
-    @property
-    def polarizability_ts(self):
-        return self._host()
-
-    @property
-    def _polarizability_ts(self):  # what the host paths read
-        return self._host()
-
-    def _segments_at_on_device(self, weights, width, starts, tau, average, device: int):
-        source, stream = self._source(device)
-        return _md_segments_at_on_device(source, self._timestep, weights, width, starts, tau, average, device,
-                                         stream=stream)
+    def __init__(self, runs, timestep: float, run_lengths=None):
+        super().__init__(_Series.of_tensor_runs("runs", runs, run_lengths, (None, 3, 3)), timestep)
 
 
 # ----------------------------------------------------------------------------- atom-group (partial) spectra
@@ -918,9 +1005,7 @@ def _md_partial_host(increments: NDArray[np.float64], timestep: float, weights: 
     dropped (``include/rn_potgnn.h``, ``rn_md_raman_partial``)."""
     d = _symmetric_components(np.asarray(increments, dtype=np.float64))  # (N, G, 6)
     n, num_groups = d.shape[:2]
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    keep = np.flatnonzero(wavenumbers >= 0)[1:]
-    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    wavenumbers, keep, length = _lag_axis(n, timestep)
     spectra = np.fft.rfft(d, n=length, axis=0)  # (length / 2 + 1, G, 6)
     forms = _weight_forms(weights)
     out = np.empty((weights.shape[0], num_groups, num_groups, len(keep)))
@@ -928,9 +1013,8 @@ def _md_partial_host(increments: NDArray[np.float64], timestep: float, weights: 
         for h in range(g, num_groups):
             cross = np.real(spectra[:, g, :, None] * np.conj(spectra[:, h, None, :]))
             power = np.einsum("kce,fce->kf", forms, cross)
-            lags = np.fft.irfft(power, n=length, axis=-1)[:, :n]
-            out[:, g, h] = out[:, h, g] = np.real(scipy.fftpack.fft(lags, axis=-1))[:, keep]
-    return wavenumbers[keep], out
+            out[:, g, h] = out[:, h, g] = _lag_spectrum(power, n, length, keep)
+    return wavenumbers, out
 
 
 def _md_partial_on_device(increments, timestep: float, weights, device: int, stream=None, workspace_limit: int = 0):
@@ -954,16 +1038,10 @@ def _md_partial_segments_host(increments, timestep: float, weights, width: int, 
     num_groups = d.shape[1]
     n = width - 1
     starts = np.asarray(starts, dtype=np.int64)
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    keep = np.flatnonzero(wavenumbers >= 0)[1:]
-    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    wavenumbers, keep, length = _lag_axis(n, timestep)
     forms = _weight_forms(weights)
     count = weights.shape[0]
     rows, cols = np.triu_indices(num_groups)
-
-    def finish(power):  # (..., length / 2 + 1) -> (..., bins)
-        lags = np.fft.irfft(power, n=length, axis=-1)[..., :n]
-        return np.real(scipy.fftpack.fft(lags, axis=-1))[..., keep]
 
     out = None if average else np.empty((len(starts), count, len(rows), len(keep)))
     mean = np.zeros((count, len(rows), length // 2 + 1))
@@ -978,11 +1056,11 @@ def _md_partial_segments_host(increments, timestep: float, weights, width: int, 
             if average:
                 mean[:, pair] += power.sum(axis=0)
             else:
-                out[first:first + chunk, :, pair] = finish(power)
+                out[first:first + chunk, :, pair] = _lag_spectrum(power, n, length, keep)
     if average:
-        return wavenumbers[keep], _unpack_pairs(finish(mean / len(starts)), num_groups)
+        return wavenumbers, _unpack_pairs(_lag_spectrum(mean / len(starts), n, length, keep), num_groups)
     unpacked = _unpack_pairs(out.reshape(len(starts) * count, len(rows), len(keep)), num_groups)
-    return wavenumbers[keep], unpacked.reshape(len(starts), count, num_groups, num_groups, len(keep))
+    return wavenumbers, unpacked.reshape(len(starts), count, num_groups, num_groups, len(keep))
 
 
 def _md_partial_segments_on_device(increments, timestep: float, weights, width: int, starts, tau, average: bool,
@@ -1007,40 +1085,19 @@ def _md_partial_segments_on_device(increments, timestep: float, weights, width: 
     return wavenumbers, unpacked
 
 
-class _PartialSpectrum:
-    """``measure`` / ``measure_polarized`` of the partial spectra: ``_partial(weights, device)`` returns the uncorrected
-    ``(wavenumbers, I[K,G,G,bins])``; the corrections apply to every ``(g, h)`` row."""
-
-    def _partial(self, weights, device):
-        raise NotImplementedError
-
-    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
-                bose_einstein_correction=False, temperature=300, device=None):
-        """``(wavenumbers, I[G,G,bins])``: ``I[g,h]`` is the symmetric bilinear form of ``measure()``'s
-        ``45 a^2 + 7 gamma^2`` between groups g and h, so ``I.sum((0, 1))`` is the whole spectrum and ``I[g,g]`` the
-        spectrum of group g alone."""
-        _require_polycrystalline(orientation)
-        wavenumbers, intensities = self._partial(_measure_weights(), device)
-        intensities = _apply_corrections(wavenumbers, intensities[0], laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities
-
-    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False, laser_wavelength=522,
-                          bose_einstein_correction=False, temperature=300, device=None):
-        """``(wavenumbers, I[K,G,G,bins])`` for the configurations of ``polarized_weights``; ``[G,G,bins]`` when no
-        argument has a ``K`` axis, as ``measure_polarized`` squeezes."""
-        weights, squeeze = polarized_weights(incident, scattered, orientation)
-        wavenumbers, intensities = self._partial(weights, device)
-        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities[0] if squeeze else intensities
-
-
-class PartialPhononRamanSpectrum(_PartialSpectrum):
+class PartialPhononRamanSpectrum(_ContractedSpectrum):
     """Atom-group decomposition of a phonon spectrum: wavenumbers ``(M,)`` and partial Raman tensors ``(M,G,3,3)``
     (``R[m,g] = 2 sum_{i in g} J_i . d_{m,i}``, ``PotGNN.calc_partial_raman_tensors``).  ``I[g,h](m)`` is the bilinear
     form of the chosen intensity between ``R[m,g]`` and ``R[m,h]``: ``sum_{g,h}`` is the spectrum of ``sum_g R[m,g]``, and
-    ``I[g,g]`` that of group g's tensors alone (the reference's masking of the other atoms' displacements)."""
+    ``I[g,g]`` that of group g's tensors alone (the reference's masking of the other atoms' displacements).
+
+    ``measure`` returns ``(wavenumbers, I[G,G,M])``: ``I[g,h]`` is the symmetric bilinear form of ``measure()``'s
+    ``45 a^2 + 7 gamma^2`` between groups g and h, so ``I.sum((0, 1))`` is the whole spectrum and ``I[g,g]`` the
+    spectrum of group g alone.  ``measure_polarized`` returns ``(wavenumbers, I[K,G,G,M])`` for the configurations of
+    ``polarized_weights``; ``[G,G,M]`` when no argument has a ``K`` axis, as ``measure_polarized`` squeezes.  The
+    corrections apply to every ``(g, h)`` row."""
+
+    _row_axes = 2
 
     def __init__(self, phonon_wavenumbers, partial_raman_tensors) -> None:
         verify_ndarray_shape("phonon_wavenumbers", phonon_wavenumbers, (None,))
@@ -1056,7 +1113,7 @@ class PartialPhononRamanSpectrum(_PartialSpectrum):
     def partial_raman_tensors(self):
         return self._partial_raman_tensors.copy()
 
-    def _partial(self, weights, device):
+    def _whole(self, weights, device):
         del device  # (at most 3N modes: always the host)
         d = _symmetric_components(np.asarray(self._partial_raman_tensors, dtype=np.float64))  # (M, G, 6)
         intensities = np.einsum("kce,mgc,mhe->kghm", _weight_forms(weights), d, d)
@@ -1065,179 +1122,90 @@ class PartialPhononRamanSpectrum(_PartialSpectrum):
         return self._phonon_wavenumbers, intensities
 
 
-class PartialMDRamanSpectrum(_PartialSpectrum):
+class PartialMDRamanSpectrum(_ContractedMDSpectrum):
     """Atom-group decomposition of an MD spectrum: per-group polarizability increments ``(S-1,G,3,3)``
     (``PotGNN.calc_group_increments``) and a timestep in fs.  ``I[g,h]`` is the transform of the symmetrised
     cross-correlation of groups g and h, so ``I[g,g]`` is ``MDRamanSpectrum(cumsum of group g's increments).measure()`` and
-    ``sum_{g,h} I`` that of the summed increments.  ``device`` (an int) reduces on that GPU (``rn_md_raman_partial``)."""
+    ``sum_{g,h} I`` that of the summed increments.  ``device`` (an int) reduces on that GPU (``rn_md_raman_partial``).
+
+    ``measure`` returns ``(wavenumbers, I[G,G,bins])``: ``I[g,h]`` is the symmetric bilinear form of ``measure()``'s
+    ``45 a^2 + 7 gamma^2`` between groups g and h, so ``I.sum((0, 1))`` is the whole spectrum and ``I[g,g]`` the
+    spectrum of group g alone.  ``measure_polarized`` returns ``(wavenumbers, I[K,G,G,bins])`` for the configurations of
+    ``polarized_weights``; ``[G,G,bins]`` when no argument has a ``K`` axis, as ``measure_polarized`` squeezes.  The
+    corrections apply to every ``(g, h)`` row.
+
+    ``measure_segments``: segment-averaged (Welch) or time-resolved partial spectra over
+    ``MDRamanSpectrum.measure_segments``' segments of ``segment_steps`` frames (``segment_steps - 1`` increments each),
+    with ``I[g,h]`` of ``measure()`` per segment.  ``average=True`` returns ``(wavenumbers, I[G,G,bins])``, the mean over
+    the segments, whose variance falls with their number; ``average=False`` the rows ``(wavenumbers, I[Q,G,G,bins])``.
+    With ``taper="boxcar"`` row q is ``PartialMDRamanSpectrum(increments[a:a + segment_steps - 1], timestep).measure()``
+    for ``a = segment_starts(...)[q]``, the first frame of the segment (frame t is where increment t begins).
+    ``device`` (an int) reduces on that GPU (``rn_md_raman_partial_segments``).  ``measure_segments_polarized`` returns
+    ``I[K,G,G,bins]``, or ``I[Q,K,G,G,bins]`` with ``average=False``; the ``K`` axis is squeezed when no argument has
+    one."""
+
+    _row_axes = 2
 
     def __init__(self, increments, timestep: float):
-        verify_ndarray_shape("increments", increments, (None, None, 3, 3))
-        self._increments = increments
-        self._timestep = timestep
+        super().__init__(_held("increments", increments, (None, None, 3, 3), increments=True), timestep)
 
     @property
     def increments(self):
-        return self._increments
+        return self._series.host()
 
-    @property
-    def timestep(self) -> float:
-        return self._timestep
+    def _whole(self, weights, device):
+        """A single run has an entry of its own (``rn_md_raman_partial``)."""
+        if device is None:
+            return _md_partial_host(self._series.host(), self._timestep, weights)
+        source, stream = self._series.source(int(device))
+        return _md_partial_on_device(source, self._timestep, weights, int(device), stream=stream)
 
-    def _partial(self, weights, device):
-        if device is not None:
-            return _md_partial_on_device(self.increments, self._timestep, weights, int(device))
-        return _md_partial_host(self.increments, self._timestep, weights)
-
-    def _num_increments(self) -> int:
-        return self.increments.shape[0]
-
-    def _segment_table(self, segment_steps, hop, taper):
-        """``(W, tau, starts)``: the segments of the ``S = N + 1`` frames that the ``N`` increments join."""
-        steps = self._num_increments() + 1
-        width, hop, tau = segment_plan(steps, segment_steps, hop, taper)
-        return width, tau, _segment_starts(steps, width, hop)
-
-    def _partial_segments_on_device(self, weights, width, starts, tau, average, device: int):
-        return _md_partial_segments_on_device(self.increments, self._timestep, weights, width, starts, tau, average,
-                                              device)
-
-    def _partial_segments(self, weights, segment_steps, hop, taper, average, device):
-        """The uncorrected ``(wavenumbers, I[K,G,G,bins] or I[Q,K,G,G,bins])`` of both segment measurements."""
-        width, tau, starts = self._segment_table(segment_steps, hop, taper)
-        if device is not None:
-            return self._partial_segments_on_device(weights, width, starts, tau, bool(average), int(device))
-        return _md_partial_segments_host(self.increments, self._timestep, weights, width, starts, tau, bool(average))
-
-    def segment_starts(self, segment_steps, hop=None) -> NDArray[np.int64]:
-        """The first frame of each segment of ``measure_segments`` (frame t is where increment t begins)."""
-        return self._segment_table(segment_steps, hop, "boxcar")[2]
-
-    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
-                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
-                         device=None):
-        """Segment-averaged (Welch) or time-resolved partial spectra: ``MDRamanSpectrum.measure_segments``' segments of
-        ``segment_steps`` frames (``segment_steps - 1`` increments each), with ``I[g,h]`` of ``measure()`` per segment.
-        ``average=True`` returns ``(wavenumbers, I[G,G,bins])``, the mean over the segments, whose variance falls with
-        their number; ``average=False`` the rows ``(wavenumbers, I[Q,G,G,bins])``.  With ``taper="boxcar"`` row q is
-        ``PartialMDRamanSpectrum(increments[a:a + segment_steps - 1], timestep).measure()`` for
-        ``a = segment_starts(...)[q]``.  ``device`` (an int) reduces on that GPU (``rn_md_raman_partial_segments``)."""
-        _require_polycrystalline(orientation)
-        wavenumbers, intensities = self._partial_segments(_measure_weights(), segment_steps, hop, taper, average, device)
-        intensities = _apply_corrections(wavenumbers, intensities[..., 0, :, :, :], laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities
-
-    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
-                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
-                                   bose_einstein_correction=False, temperature=300, device=None):
-        """``measure_segments`` for the configurations of ``polarized_weights``: ``I[K,G,G,bins]``, or
-        ``I[Q,K,G,G,bins]`` with ``average=False``; the ``K`` axis is squeezed when no argument has one."""
-        weights, squeeze = polarized_weights(incident, scattered, orientation)
-        wavenumbers, intensities = self._partial_segments(weights, segment_steps, hop, taper, average, device)
-        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities[..., 0, :, :, :] if squeeze else intensities
+    def _reduce(self, weights, table, average: bool, device):
+        width, tau, starts = table
+        if device is None:
+            return _md_partial_segments_host(self._series.host(), self._timestep, weights, width, starts, tau,
+                                             bool(average))
+        source, stream = self._series.source(int(device))
+        return _md_partial_segments_on_device(source, self._timestep, weights, width, starts, tau, bool(average),
+                                              int(device), stream=stream)
 
 
-class DevicePartialMDRamanSpectrum(_DeviceResident, PartialMDRamanSpectrum):
+class DevicePartialMDRamanSpectrum(_OnDevice, PartialMDRamanSpectrum):
     """``PartialMDRamanSpectrum`` whose increments stay in HBM (a contiguous float64 CUDA tensor ``(S-1,G,3,3)``):
     ``measure`` / ``measure_polarized`` and the segment measurements reduce them on that GPU
     (``rn_md_raman_partial_device``, ``rn_md_raman_partial_segments_device``, ordered after torch's current stream)
     unless ``host=True``; ``increments`` copies them to the host on first use."""
 
-    def __init__(self, increments_device, timestep: float):  # pylint: disable=super-init-not-called
-        self._set_tensor("increments", increments_device, 4, "(_,_,3,3)")
-        self._timestep = timestep
-
-    @property
-    def increments(self):
-        return self._host()
-
-    def _partial(self, weights, device):
-        if device is None:
-            return super()._partial(weights, None)
-        source, stream = self._source(int(device))
-        return _md_partial_on_device(source, self._timestep, weights, int(device), stream=stream)
-
-    def _num_increments(self) -> int:
-        return self._tensor.shape[0]
-
-    def _partial_segments_on_device(self, weights, width, starts, tau, average, device: int):
-        source, stream = self._source(device)
-        return _md_partial_segments_on_device(source, self._timestep, weights, width, starts, tau, average, device,
-                                              stream=stream)
+    def __init__(self, increments_device, timestep: float):
+        super().__init__(_Series.of_tensor("increments", increments_device, (None, None, 3, 3), increments=True),
+                         timestep)
 
 
-class PartialMDRamanEnsemble(PartialMDRamanSpectrum):
+class PartialMDRamanEnsemble(_Ensemble, PartialMDRamanSpectrum):
     """Atom-group spectra averaged over several runs: ``runs`` is a sequence of per-group increments ``(S_r-1,G,3,3)``
     sharing ``G`` and ``timestep``.  The runs are joined with one zero row between them, so that increment t still
     belongs to frame t of the joined frames; no segment reads that row.  ``measure_segments`` /
     ``measure_segments_polarized`` take the segments of every run (``ensemble_segment_starts`` of the runs' ``S_r``
     frames; rows in run order, ``average=True`` the mean over all of them), ``measure`` / ``measure_polarized`` the mean
-    of the runs' whole spectra when the runs have one length.  ``device`` (an int) reduces all runs in one call
-    (``rn_md_raman_partial_segments``)."""
+    of the runs' whole spectra when the runs have one length: one boxcar segment per run.  ``device`` (an int) reduces
+    all runs in one call (``rn_md_raman_partial_segments``)."""
 
-    def __init__(self, runs, timestep: float):  # pylint: disable=super-init-not-called
-        runs = list(runs)
-        if not runs:
-            raise ValueError("an ensemble needs at least one run")
-        for index, run in enumerate(runs):
-            verify_ndarray_shape(f"runs[{index}]", run, (None, runs[0].shape[1], 3, 3))
-        self._run_lengths = [int(run.shape[0]) + 1 for run in runs]  # frames
-        gap = np.zeros((1, *runs[0].shape[1:]))
-        parts = [part for run in runs for part in (np.asarray(run, dtype=np.float64), gap)][:-1]
-        self._increments = np.concatenate(parts, axis=0)
-        self._timestep = timestep
+    _whole = _ContractedMDSpectrum._whole  # runs have no entry of a single series
 
-    @property
-    def run_lengths(self) -> list[int]:
-        """Frames per run (one more than its increments)."""
-        return list(self._run_lengths)
-
-    def _segment_table(self, segment_steps, hop, taper):
-        width, hop, tau = segment_plan(min(self._run_lengths), segment_steps, hop, taper)
-        return width, tau, ensemble_segment_starts(self._run_lengths, width, hop)[0]
-
-    def segment_starts(self, segment_steps, hop=None) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
-        """``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
-        starts, run_index = ensemble_segment_starts(self._run_lengths, segment_steps, hop)
-        return run_index, starts - _run_offsets(self._run_lengths)[run_index]
-
-    def _partial(self, weights, device):
-        """The mean over the runs of each run's whole partial spectra: one boxcar segment per run."""
-        steps = _equal_run_length(self._run_lengths)
-        return self._partial_segments(weights, steps, steps, "boxcar", True, device)
+    def __init__(self, runs, timestep: float):
+        super().__init__(runs if isinstance(runs, _Series) else _Series.of_runs(runs, (3, 3), True, increments=True),
+                         timestep)
 
 
-class DevicePartialMDRamanEnsemble(_DeviceResident, PartialMDRamanEnsemble):
+class DevicePartialMDRamanEnsemble(_OnDevice, PartialMDRamanEnsemble):
     """``PartialMDRamanEnsemble`` whose increments stay in HBM: a sequence of contiguous float64 CUDA tensors
     ``(S_r-1,G,3,3)`` (joined here, on the GPU, with a zero row between them), or one tensor ``(sum(S_r)-1,G,3,3)``
     plus ``run_lengths`` (frames per run), as one batched evaluation of the joined frames writes it: its rows across
     the run boundaries stand where the zero rows would and are never read."""
 
-    def __init__(self, runs, timestep: float, run_lengths=None):  # pylint: disable=super-init-not-called
-        import torch
-        runs, lengths = _joined_tensor("runs", runs, run_lengths, 1)
-        if lengths is None:
-            lengths = [int(run.shape[0]) + 1 for run in runs]
-            gap = runs[0].new_zeros((1, *runs[0].shape[1:]))
-            runs = torch.cat([part for run in runs for part in (run, gap)][:-1], dim=0)
-        self._set_tensor("runs", runs, 4, "(_,_,3,3)")
-        self._run_lengths = lengths
-        self._timestep = timestep
-
-    @property
-    def increments(self):
-        return self._host()
-
-    def _num_increments(self) -> int:
-        return self._tensor.shape[0]
-
-    def _partial_segments_on_device(self, weights, width, starts, tau, average, device: int):
-        source, stream = self._source(device)
-        return _md_partial_segments_on_device(source, self._timestep, weights, width, starts, tau, average, device,
-                                              stream=stream)
+    def __init__(self, runs, timestep: float, run_lengths=None):
+        super().__init__(_Series.of_tensor_runs("runs", runs, run_lengths, (None, None, 3, 3), increments=True),
+                         timestep)
 
 
 # ----------------------------------------------------------------------------- vibrational density of states
@@ -1304,13 +1272,6 @@ def _vdos_steps(positions: NDArray[np.float64], lattices: NDArray[np.float64]) -
     return np.einsum("tik,tkc->tic", steps, 0.5 * (lattices[:-1] + lattices[1:]))
 
 
-def _lag_spectrum(power, n: int, length: int, keep):
-    """The back half of the VDOS paths: power spectra on the padded length ``(..., length / 2 + 1)`` -> the positive lags
-    of the autocorrelation, their length-``n`` transform, the real bins ``keep``: ``(..., bins)``."""
-    lags = np.fft.irfft(power, n=length, axis=-1)[..., :n]
-    return np.real(scipy.fftpack.fft(lags, axis=-1))[..., keep]
-
-
 def _vdos_host(positions, lattices, masses, labels, num_groups: int, timestep: float, width: int, starts, tau,
                average: bool):
     """(wavenumbers, ``D[G][bins]`` or ``D[Q][G][bins]``) on the host, from the definition (``include/rn_potgnn.h``,
@@ -1320,14 +1281,9 @@ def _vdos_host(positions, lattices, masses, labels, num_groups: int, timestep: f
     u = _vdos_steps(np.asarray(positions, dtype=np.float64), lattices) * np.sqrt(masses)[None, :, None]
     n = width - 1
     starts = np.asarray(starts, dtype=np.int64)
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    keep = np.flatnonzero(wavenumbers >= 0)[1:]
-    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    wavenumbers, keep, length = _lag_axis(n, timestep)
     atoms = u.shape[1]
     members = [np.flatnonzero(labels == g) for g in range(num_groups)]
-
-    def finish(power):  # (..., length / 2 + 1) -> (..., bins)
-        return _lag_spectrum(power, n, length, keep)
 
     rows = None if average else np.empty((len(starts), num_groups, len(keep)))
     mean = np.zeros((num_groups, length // 2 + 1))
@@ -1342,8 +1298,8 @@ def _vdos_host(positions, lattices, masses, labels, num_groups: int, timestep: f
         if average:
             mean += power
         else:
-            rows[q] = finish(power)
-    return wavenumbers[keep], finish(mean / len(starts)) if average else rows
+            rows[q] = _lag_spectrum(power, n, length, keep)
+    return wavenumbers, _lag_spectrum(mean / len(starts), n, length, keep) if average else rows
 
 
 def _step_reducer_on_device(entry: str, positions, lattices, masses, rows, count: int, timestep: float, width: int,
@@ -1378,6 +1334,20 @@ def _vdos_on_device(positions, lattices, masses, labels, num_groups: int, timest
                                    starts, tau, average, device, stream, workspace_limit)
 
 
+def _lattice_on_device(lattice, positions):
+    """``(lattice for _vdos_lattices, lattice CUDA tensor or None)`` of positions in HBM: a lattice per frame that is a
+    CUDA tensor is reduced from where it is; any other is made from the validated host lattices on first use."""
+    import torch
+    if not isinstance(lattice, torch.Tensor):
+        return lattice, None
+    host_lattice = lattice.detach().cpu().numpy()
+    if not (lattice.is_cuda and lattice.ndim == 3):
+        return host_lattice, None
+    if not (lattice.is_contiguous() and lattice.dtype == torch.float64 and lattice.device == positions.device):
+        raise ValueError("lattice must be a contiguous float64 CUDA tensor on the positions' GPU")
+    return host_lattice, lattice
+
+
 class VibrationalDensityOfStates:
     """Vibrational density of states (VDOS) of an MD run, whole and by atom group (an addition): which vibrations exist
     at all, on the wavenumber axis of ``MDRamanSpectrum`` for the same number of frames and timestep, so that the two
@@ -1396,19 +1366,23 @@ class VibrationalDensityOfStates:
     that GPU (``rn_md_vdos``); ``None`` is the host path."""
 
     def __init__(self, positions_ts, timestep: float, lattice, masses=None, labels=None, num_groups=1):
-        verify_ndarray_shape("positions_ts", positions_ts, (None, None, 3))
-        self._positions_ts = np.ascontiguousarray(positions_ts, dtype=np.float64)
-        self._set_parameters(self._positions_ts.shape, timestep, lattice, masses, labels, num_groups)
-
-    def _set_parameters(self, shape, timestep, lattice, masses, labels, num_groups) -> None:
+        if isinstance(positions_ts, _Series):  # (a subclass's holder)
+            self._series = positions_ts
+        else:
+            verify_ndarray_shape("positions_ts", positions_ts, (None, None, 3))
+            self._series = _Series(np.ascontiguousarray(positions_ts, dtype=np.float64))
+        self._lattice_tensor = None  # the lattices beside a series in HBM
+        if self._series.gpu is not None:
+            lattice, self._lattice_tensor = _lattice_on_device(lattice, self._series.data)
+        steps, atoms = (int(size) for size in self._series.shape[:2])
         self._timestep = timestep
-        self._lattices = _vdos_lattices(lattice, int(shape[0]))
-        self._masses = _vdos_masses(masses, int(shape[1]))
-        self._labels, self._num_groups = _vdos_labels(labels, num_groups, int(shape[1]))
+        self._lattices = _vdos_lattices(lattice, steps)
+        self._masses = _vdos_masses(masses, atoms)
+        self._labels, self._num_groups = _vdos_labels(labels, num_groups, atoms)
 
     @property
     def positions_ts(self):
-        return self._positions_ts
+        return self._series.host()
 
     @property
     def timestep(self) -> float:
@@ -1417,9 +1391,6 @@ class VibrationalDensityOfStates:
     @property
     def num_groups(self) -> int:
         return self._num_groups
-
-    def _num_steps(self) -> int:
-        return self._positions_ts.shape[0]
 
     def _reducer_call(self, positions, lattices, width, starts, tau, average, device: int, **keywords):
         """The device reduction of ``positions`` and ``lattices`` (host arrays, or CUDA tensors with ``stream=``): what
@@ -1432,109 +1403,61 @@ class VibrationalDensityOfStates:
         return _vdos_host(self.positions_ts, self._lattices, self._masses, self._labels, self._num_groups,
                           self._timestep, width, starts, tau, average)
 
-    def _on_device(self, width, starts, tau, average, device: int, workspace_limit: int = 0):
-        return self._reducer_call(self._positions_ts, self._lattices, width, starts, tau, average, device,
-                                  workspace_limit=workspace_limit)
-
-    def _reduce(self, width, starts, tau, average, device):
-        if device is not None:
-            return self._on_device(width, starts, tau, bool(average), int(device))
-        return self._host_call(width, starts, tau, bool(average))
-
-    def _segment_table(self, segment_steps, hop, taper):
-        """``(W, tau, starts)`` of ``measure_segments``."""
-        width, hop, tau = segment_plan(self._num_steps(), segment_steps, hop, taper)
-        return width, tau, _segment_starts(self._num_steps(), width, hop)
+    def _reduce(self, table, average, device):
+        width, tau, starts = table
+        if device is None:
+            return self._host_call(width, starts, tau, bool(average))
+        positions, stream = self._series.source(int(device))
+        lattices = self._lattices
+        if stream is not None:
+            if self._lattice_tensor is None:
+                import torch
+                self._lattice_tensor = torch.tensor(self._lattices, dtype=torch.float64, device=positions.device)
+            lattices = self._lattice_tensor
+        return self._reducer_call(positions, lattices, width, starts, tau, bool(average), int(device), stream=stream)
 
     def segment_starts(self, segment_steps, hop=None):
-        """The first frame of each of the ``Q = (S - segment_steps) // hop + 1`` segments of ``measure_segments``."""
-        return self._segment_table(segment_steps, hop, "boxcar")[2]
+        """The first frame of each of the ``Q = (S - segment_steps) // hop + 1`` segments of ``measure_segments``; for
+        an ensemble, ``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
+        return self._series.segment_starts(segment_steps, hop)
 
     def measure(self, device=None):
-        """``(wavenumbers, D[G, bins])`` of the whole run: the one boxcar segment of all ``S`` frames."""
-        steps = self._num_steps()
-        width, _, tau = segment_plan(steps, steps, steps, "boxcar")
-        return self._reduce(width, np.zeros(1, dtype=np.int64), tau, True, device)
+        """``(wavenumbers, D[G, bins])`` of the whole run: the one boxcar segment of all ``S`` frames.  An ensemble: the
+        mean of the runs' ``VibrationalDensityOfStates.measure()``, one boxcar segment per run; a ``ValueError`` unless
+        the runs have one length (their wavenumbers differ otherwise)."""
+        return self._reduce(self._series.whole_table(), True, device)
 
     def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, device=None):
         """Segment-averaged (Welch) or time-resolved VDOS on ``MDRamanSpectrum.measure_segments``' segments and axis:
         ``(wavenumbers, D[G, bins])``, the mean over the segments (taken on the power spectra), or with
         ``average=False`` the rows ``(wavenumbers, D[Q, G, bins])``.  Arguments as ``spectrum.segment_plan``."""
-        width, tau, starts = self._segment_table(segment_steps, hop, taper)
-        return self._reduce(width, starts, tau, average, device)
+        return self._reduce(self._series.segment_table(segment_steps, hop, taper), average, device)
 
 
-class _DeviceResidentSteps:
-    """Mixin for a VDOS whose positions (and lattices, if per frame) stay in HBM as contiguous float64 CUDA tensors, on
-    the pattern of ``_DeviceResident``: the measurements reduce on the tensors' GPU unless ``host=True``; another
+class _StepsOnDevice:
+    """Mixin for a VDOS whose positions (and lattices, if per frame) stay in HBM as contiguous float64 CUDA tensors, as
+    ``_OnDevice`` is for the Raman classes: the measurements reduce on the tensors' GPU unless ``host=True``; another
     ``device`` gets the host copy, which is made on first use."""
-
-    def _set_tensors(self, positions, lattice) -> None:
-        import torch
-        shape = tuple(positions.shape)
-        if len(shape) != 3 or shape[-1] != 3:
-            raise ValueError(f"positions_ts has wrong shape: {shape} != (_,_,3)")
-        if not (positions.is_cuda and positions.is_contiguous() and positions.dtype == torch.float64):
-            raise ValueError("positions_ts must be a contiguous float64 CUDA tensor")
-        self._tensor = positions
-        self._host_copy = None
-        host_lattice = lattice.detach().cpu().numpy() if isinstance(lattice, torch.Tensor) else lattice
-        self._lattice_argument = host_lattice
-        if isinstance(lattice, torch.Tensor) and lattice.is_cuda and lattice.ndim == 3:
-            if not (lattice.is_contiguous() and lattice.dtype == torch.float64 and lattice.device == positions.device):
-                raise ValueError("lattice must be a contiguous float64 CUDA tensor on the positions' GPU")
-            self._lattice_tensor = lattice
-        else:
-            self._lattice_tensor = None  # made from the validated host lattices on first use
-
-    @property
-    def positions_ts(self):
-        if self._host_copy is None:
-            self._host_copy = self._tensor.cpu().numpy()
-        return self._host_copy
-
-    def _num_steps(self) -> int:
-        return self._tensor.shape[0]
-
-    def _device_index(self) -> int:
-        return self._tensor.device.index or 0
-
-    def _on_device(self, width, starts, tau, average, device: int, workspace_limit: int = 0):
-        import torch
-        if device != self._device_index():
-            return self._reducer_call(self.positions_ts, self._lattices, width, starts, tau, average, device,
-                                      workspace_limit=workspace_limit)
-        if self._lattice_tensor is None:
-            self._lattice_tensor = torch.tensor(self._lattices, dtype=torch.float64, device=self._tensor.device)
-        stream = torch.cuda.current_stream(self._tensor.device).cuda_stream
-        return self._reducer_call(self._tensor, self._lattice_tensor, width, starts, tau, average, device,
-                                  stream=stream, workspace_limit=workspace_limit)
-
-    def _device_or_host(self, device, host: bool):
-        if host:
-            return None
-        return self._device_index() if device is None else device
 
     def measure(self, device=None, host=False):
         """As the base class's ``measure``; reduces on the tensors' GPU unless ``host=True``."""
-        return super().measure(device=self._device_or_host(device, host))
+        return super().measure(device=self._series.device_or_host(device, host))
 
     def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, device=None, host=False):
         """As the base class's ``measure_segments``; reduces on the tensors' GPU unless ``host=True``."""
-        return super().measure_segments(segment_steps, hop, taper, average, device=self._device_or_host(device, host))
+        return super().measure_segments(segment_steps, hop, taper, average,
+                                        device=self._series.device_or_host(device, host))
 
 
-class DeviceVibrationalDensityOfStates(_DeviceResidentSteps, VibrationalDensityOfStates):
+class DeviceVibrationalDensityOfStates(_StepsOnDevice, VibrationalDensityOfStates):
     """``VibrationalDensityOfStates`` of positions that already sit in HBM for the polarizability evaluation: a
     contiguous float64 CUDA tensor ``(S,N,3)``, and ``lattice`` as an array or a CUDA tensor ``(3,3)`` / ``(S,3,3)``.
     The measurements reduce on that GPU (``rn_md_vdos_device``, ordered after torch's current stream) and only the
     densities travel to the host; ``positions_ts`` copies the positions to the host on first use."""
 
-    def __init__(self, positions_ts_device, timestep: float, lattice, masses=None, labels=None,
-                 num_groups=1):  # pylint: disable=super-init-not-called
-        self._set_tensors(positions_ts_device, lattice)
-        self._set_parameters(tuple(positions_ts_device.shape), timestep, self._lattice_argument, masses, labels,
-                             num_groups)
+    def __init__(self, positions_ts_device, timestep: float, lattice, masses=None, labels=None, num_groups=1):
+        super().__init__(_Series.of_tensor("positions_ts", positions_ts_device, (None, None, 3)), timestep, lattice,
+                         masses, labels, num_groups)
 
 
 def _joined_lattices(lattice, run_lengths):
@@ -1557,54 +1480,25 @@ class VibrationalDensityOfStatesEnsemble(VibrationalDensityOfStates):
     in run order, ``average=True`` the mean over all of them), ``measure`` the mean of the runs' whole VDOS, defined when
     the runs have one length."""
 
-    def __init__(self, runs, timestep: float, lattice, masses=None, labels=None,
-                 num_groups=1):  # pylint: disable=super-init-not-called
-        runs = list(runs)
-        if not runs:
-            raise ValueError("an ensemble needs at least one run")
-        for index, run in enumerate(runs):
-            verify_ndarray_shape(f"runs[{index}]", run, (None, runs[0].shape[1], 3))
-        self._run_lengths = [int(run.shape[0]) for run in runs]
-        self._positions_ts = np.ascontiguousarray(np.concatenate(runs, axis=0), dtype=np.float64)
-        self._set_parameters(self._positions_ts.shape, timestep, _joined_lattices(lattice, self._run_lengths), masses,
-                             labels, num_groups)
+    def __init__(self, runs, timestep: float, lattice, masses=None, labels=None, num_groups=1):
+        if not isinstance(runs, _Series):
+            runs = _Series.of_runs(runs, (3,), True)
+            lattice = _joined_lattices(lattice, runs.run_lengths)
+        super().__init__(runs, timestep, lattice, masses, labels, num_groups)
 
     @property
     def run_lengths(self) -> list[int]:
-        return list(self._run_lengths)
-
-    def _segment_table(self, segment_steps, hop, taper):
-        width, hop, tau = segment_plan(min(self._run_lengths), segment_steps, hop, taper)
-        return width, tau, ensemble_segment_starts(self._run_lengths, width, hop)[0]
-
-    def segment_starts(self, segment_steps, hop=None):
-        """``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
-        starts, run_index = ensemble_segment_starts(self._run_lengths, segment_steps, hop)
-        return run_index, starts - _run_offsets(self._run_lengths)[run_index]
-
-    def measure(self, device=None):
-        """The mean of the runs' ``VibrationalDensityOfStates.measure()``: one boxcar segment per run; a ``ValueError``
-        unless the runs have one length (their wavenumbers differ otherwise)."""
-        steps = _equal_run_length(self._run_lengths)
-        width, tau, starts = self._segment_table(steps, steps, "boxcar")
-        return self._reduce(width, starts, tau, True, device)
+        return list(self._series.run_lengths)
 
 
-class DeviceVibrationalDensityOfStatesEnsemble(_DeviceResidentSteps, VibrationalDensityOfStatesEnsemble):
+class DeviceVibrationalDensityOfStatesEnsemble(_StepsOnDevice, VibrationalDensityOfStatesEnsemble):
     """``VibrationalDensityOfStatesEnsemble`` whose runs stay in HBM: a sequence of contiguous float64 CUDA tensors
     ``(S_r,N,3)`` (joined here, on the GPU), or one tensor holding them end to end plus ``run_lengths``.  ``lattice``:
     ``(3,3)``, or the joined ``(sum S_r,3,3)`` as an array or a CUDA tensor."""
 
-    def __init__(self, runs, timestep: float, lattice, masses=None, labels=None, num_groups=1,
-                 run_lengths=None):  # pylint: disable=super-init-not-called
-        import torch
-        runs, lengths = _joined_tensor("runs", runs, run_lengths, 0)
-        if lengths is None:
-            lengths = [int(run.shape[0]) for run in runs]
-            runs = runs[0] if len(runs) == 1 else torch.cat(runs, dim=0)
-        self._run_lengths = lengths
-        self._set_tensors(runs, lattice)
-        self._set_parameters(tuple(runs.shape), timestep, self._lattice_argument, masses, labels, num_groups)
+    def __init__(self, runs, timestep: float, lattice, masses=None, labels=None, num_groups=1, run_lengths=None):
+        super().__init__(_Series.of_tensor_runs("positions_ts", runs, run_lengths, (None, None, 3)), timestep, lattice,
+                         masses, labels, num_groups)
 
 
 # ----------------------------------------------------------------------------- mode-projected VDOS
@@ -1659,9 +1553,7 @@ def _mode_vdos_host(positions, lattices, masses, vectors, timestep: float, width
     weights = vectors.reshape(vectors.shape[0], -1)
     n = width - 1
     starts = np.asarray(starts, dtype=np.int64)
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    keep = np.flatnonzero(wavenumbers >= 0)[1:]
-    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    wavenumbers, keep, length = _lag_axis(n, timestep)
     modes = weights.shape[0]
     rows = None if average else np.empty((len(starts), modes, len(keep)))
     mean = np.zeros((modes, length // 2 + 1))
@@ -1676,7 +1568,7 @@ def _mode_vdos_host(positions, lattices, masses, vectors, timestep: float, width
             mean += power
         else:
             rows[q] = _lag_spectrum(power, n, length, keep)
-    return wavenumbers[keep], _lag_spectrum(mean / len(starts), n, length, keep) if average else rows
+    return wavenumbers, _lag_spectrum(mean / len(starts), n, length, keep) if average else rows
 
 
 def _mode_vdos_on_device(positions, lattices, masses, vectors, timestep: float, width: int, starts, tau, average: bool,
@@ -1728,8 +1620,8 @@ class _ModeProjection:
             wavenumbers, rows = self.measure(**measure_keywords)
         else:
             wavenumbers, rows = self.measure_segments(segment_steps, hop, taper, average, **measure_keywords)
-        if fit_device is None and isinstance(self, _DeviceResidentSteps) and not measure_keywords.get("host", False):
-            fit_device = self._device_index()
+        if fit_device is None and not measure_keywords.get("host", False):
+            fit_device = self._series.gpu
         return fit_lorentzians(wavenumbers, rows, np.broadcast_to(windows, rows.shape[:-1] + (2,)), device=fit_device)
 
 
@@ -1751,15 +1643,14 @@ class ModeVibrationalDensityOfStates(_ModeProjection, VibrationalDensityOfStates
         self._set_vectors(vectors)
 
 
-class DeviceModeVibrationalDensityOfStates(_DeviceResidentSteps, _ModeProjection, VibrationalDensityOfStates):
+class DeviceModeVibrationalDensityOfStates(_StepsOnDevice, _ModeProjection, VibrationalDensityOfStates):
     """``ModeVibrationalDensityOfStates`` of positions that already sit in HBM (``DeviceVibrationalDensityOfStates``'
     arguments): reduces on that GPU (``rn_md_mode_vdos_device``, ordered after torch's current stream) unless
     ``host=True``; the mode series never leave the device."""
 
-    def __init__(self, positions_ts_device, timestep: float, lattice, vectors,
-                 masses=None):  # pylint: disable=super-init-not-called
-        self._set_tensors(positions_ts_device, lattice)
-        self._set_parameters(tuple(positions_ts_device.shape), timestep, self._lattice_argument, masses, None, 1)
+    def __init__(self, positions_ts_device, timestep: float, lattice, vectors, masses=None):
+        super().__init__(_Series.of_tensor("positions_ts", positions_ts_device, (None, None, 3)), timestep, lattice,
+                         masses)
         self._set_vectors(vectors)
 
 
@@ -1773,14 +1664,14 @@ class ModeVibrationalDensityOfStatesEnsemble(_ModeProjection, VibrationalDensity
         self._set_vectors(vectors)
 
 
-class DeviceModeVibrationalDensityOfStatesEnsemble(_DeviceResidentSteps, _ModeProjection,
+class DeviceModeVibrationalDensityOfStatesEnsemble(_StepsOnDevice, _ModeProjection,
                                                    VibrationalDensityOfStatesEnsemble):
     """``ModeVibrationalDensityOfStatesEnsemble`` whose runs stay in HBM (``DeviceVibrationalDensityOfStatesEnsemble``'s
     arguments)."""
 
-    def __init__(self, runs, timestep: float, lattice, vectors, masses=None,
-                 run_lengths=None):  # pylint: disable=super-init-not-called
-        DeviceVibrationalDensityOfStatesEnsemble.__init__(self, runs, timestep, lattice, masses, run_lengths=run_lengths)
+    def __init__(self, runs, timestep: float, lattice, vectors, masses=None, run_lengths=None):
+        super().__init__(_Series.of_tensor_runs("positions_ts", runs, run_lengths, (None, None, 3)), timestep, lattice,
+                         masses)
         self._set_vectors(vectors)
 
 
@@ -1815,9 +1706,7 @@ def _md_modes_host(increments, timestep: float, weights, width: int, starts, tau
     channels = d.shape[1]
     n = width - 1
     starts = np.asarray(starts, dtype=np.int64)
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    keep = np.flatnonzero(wavenumbers >= 0)[1:]
-    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    wavenumbers, keep, length = _lag_axis(n, timestep)
     forms = _weight_forms(weights)
     count = weights.shape[0]
     out = None if average else np.empty((len(starts), count, channels, len(keep)))
@@ -1834,7 +1723,7 @@ def _md_modes_host(increments, timestep: float, weights, width: int, starts, tau
                 out[q, :, first:first + chunk] = _lag_spectrum(power, n, length, keep)
     if average:
         out = _lag_spectrum(mean / len(starts), n, length, keep)
-    return wavenumbers[keep], out
+    return wavenumbers, out
 
 
 def _md_modes_on_device(increments, timestep: float, weights, width: int, starts, tau, average: bool, device: int,
@@ -1894,9 +1783,7 @@ def _md_mode_matrix_host(increments, timestep: float, weights, width: int, start
     channels = d.shape[1]
     n = width - 1
     starts = np.asarray(starts, dtype=np.int64)
-    wavenumbers = scipy.fftpack.fftfreq(n, timestep) * _PER_FS_TO_CM1
-    keep = np.flatnonzero(wavenumbers >= 0)[1:]
-    length = 1 << int(np.ceil(np.log2(max(2 * n - 1, 1))))
+    wavenumbers, keep, length = _lag_axis(n, timestep)
     forms = _weight_forms(weights)
     count = weights.shape[0]
     power = np.zeros((count, channels, channels, length // 2 + 1))  # rows m, columns n >= m
@@ -1935,7 +1822,7 @@ def _md_mode_matrix_on_device(increments, timestep: float, weights, width: int, 
 MAX_SELECTED = MAX_GROUPS - 1  # channels of ModeMDRamanSpectrum.select, beside the channel of all others
 
 
-class ModeMDRamanSpectrum:
+class ModeMDRamanSpectrum(_ContractedMDSpectrum):
     """Phonon-mode decomposition of an MD spectrum: per-channel polarizability increments ``(S-1,C,3,3)``
     (``PotGNN.calc_mode_increments``: the modes, then the rest and the cell where present) and a timestep in fs.  Every
     measurement returns ``(wavenumbers, I[..., C+1, bins])``: row ``c < C`` is the self-spectrum of channel c, what
@@ -1944,117 +1831,58 @@ class ModeMDRamanSpectrum:
     which of them interfere under a peak comes from ``measure_interference``, the matrix of all pair spectra summed
     over a band, and the pair spectra of a few channels bin by bin from ``select``.  ``device`` (an int) reduces on
     that GPU (``rn_md_raman_modes``, ``rn_md_raman_mode_matrix``); arguments and corrections are those of
-    ``PartialMDRamanSpectrum``."""
+    ``PartialMDRamanSpectrum``.
+
+    ``measure`` returns ``(wavenumbers, I[C+1,bins])`` of ``measure()``'s ``45 a^2 + 7 gamma^2`` over the whole run,
+    ``measure_polarized`` ``(wavenumbers, I[K,C+1,bins])`` for the configurations of ``polarized_weights``;
+    ``[C+1,bins]`` when no argument has a ``K`` axis.  ``measure_segments``: segment-averaged (Welch) or time-resolved
+    spectra over ``PartialMDRamanSpectrum.measure_segments``' segments: ``(wavenumbers, I[C+1,bins])``, or
+    ``I[Q,C+1,bins]`` with ``average=False``; ``measure_segments_polarized`` ``I[K,C+1,bins]``, or ``I[Q,K,C+1,bins]``
+    with ``average=False``; the ``K`` axis is squeezed when no argument has one."""
+
+    _row_axes = 1
 
     def __init__(self, increments, timestep: float):
-        verify_ndarray_shape("increments", increments, (None, None, 3, 3))
-        if increments.shape[1] < 1:
+        super().__init__(_held("increments", increments, (None, None, 3, 3), increments=True), timestep)
+        if self._series.shape[1] < 1:
             raise ValueError("increments has no channel")
-        self._increments = increments
-        self._timestep = timestep
 
     @property
     def increments(self):
-        return self._increments
-
-    @property
-    def timestep(self) -> float:
-        return self._timestep
+        return self._series.host()
 
     @property
     def num_channels(self) -> int:
-        return self._shape()[1]
-
-    def _shape(self):
-        return self.increments.shape
-
-    def _segment_table(self, segment_steps, hop, taper):
-        """``(W, tau, starts)``: the segments of the ``S = N + 1`` frames that the ``N`` increments join."""
-        steps = self._shape()[0] + 1
-        width, hop, tau = segment_plan(steps, segment_steps, hop, taper)
-        return width, tau, _segment_starts(steps, width, hop)
+        return self._series.shape[1]
 
     def _whole_table(self):
-        """The whole run as one boxcar segment."""
-        steps = self._shape()[0]
-        if steps < 2:
-            raise ValueError(_TOO_FEW_STEPS)
-        return steps + 1, np.ones(steps), np.zeros(1, dtype=np.int64)
+        return self._series.whole_table(_TOO_FEW_STEPS)
 
-    def _on_device(self, weights, width, starts, tau, average, device: int):
-        return _md_modes_on_device(self.increments, self._timestep, weights, width, starts, tau, average, device)
-
-    def _reduce(self, weights, table, average, device):
-        """The uncorrected ``(wavenumbers, I[K,C+1,bins] or I[Q,K,C+1,bins])`` of every measurement."""
+    def _reduce(self, weights, table, average: bool, device):
         width, tau, starts = table
-        if device is not None:
-            return self._on_device(weights, width, starts, tau, bool(average), int(device))
-        return _md_modes_host(self.increments, self._timestep, weights, width, starts, tau, bool(average))
-
-    def segment_starts(self, segment_steps, hop=None) -> NDArray[np.int64]:
-        """The first frame of each segment of ``measure_segments`` (frame t is where increment t begins)."""
-        return self._segment_table(segment_steps, hop, "boxcar")[2]
-
-    def measure(self, orientation="polycrystalline", laser_correction=False, laser_wavelength=522,
-                bose_einstein_correction=False, temperature=300, device=None):
-        """``(wavenumbers, I[C+1,bins])`` of ``measure()``'s ``45 a^2 + 7 gamma^2`` over the whole run."""
-        _require_polycrystalline(orientation)
-        wavenumbers, intensities = self._reduce(_measure_weights(), self._whole_table(), True, device)
-        return wavenumbers, _apply_corrections(wavenumbers, intensities[0], laser_correction, laser_wavelength,
-                                               bose_einstein_correction, temperature)
-
-    def measure_polarized(self, incident, scattered, orientation=None, laser_correction=False, laser_wavelength=522,
-                          bose_einstein_correction=False, temperature=300, device=None):
-        """``(wavenumbers, I[K,C+1,bins])`` for the configurations of ``polarized_weights``; ``[C+1,bins]`` when no
-        argument has a ``K`` axis."""
-        weights, squeeze = polarized_weights(incident, scattered, orientation)
-        wavenumbers, intensities = self._reduce(weights, self._whole_table(), True, device)
-        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities[0] if squeeze else intensities
-
-    def measure_segments(self, segment_steps, hop=None, taper="hann", average=True, orientation="polycrystalline",
-                         laser_correction=False, laser_wavelength=522, bose_einstein_correction=False, temperature=300,
-                         device=None):
-        """Segment-averaged (Welch) or time-resolved spectra over ``PartialMDRamanSpectrum.measure_segments``' segments:
-        ``(wavenumbers, I[C+1,bins])``, or ``I[Q,C+1,bins]`` with ``average=False``."""
-        _require_polycrystalline(orientation)
-        table = self._segment_table(segment_steps, hop, taper)
-        wavenumbers, intensities = self._reduce(_measure_weights(), table, average, device)
-        return wavenumbers, _apply_corrections(wavenumbers, intensities[..., 0, :, :], laser_correction,
-                                               laser_wavelength, bose_einstein_correction, temperature)
-
-    def measure_segments_polarized(self, incident, scattered, orientation=None, *, segment_steps, hop=None,
-                                   taper="hann", average=True, laser_correction=False, laser_wavelength=522,
-                                   bose_einstein_correction=False, temperature=300, device=None):
-        """``measure_segments`` for the configurations of ``polarized_weights``: ``I[K,C+1,bins]``, or
-        ``I[Q,K,C+1,bins]`` with ``average=False``; the ``K`` axis is squeezed when no argument has one."""
-        weights, squeeze = polarized_weights(incident, scattered, orientation)
-        table = self._segment_table(segment_steps, hop, taper)
-        wavenumbers, intensities = self._reduce(weights, table, average, device)
-        intensities = _apply_corrections(wavenumbers, intensities, laser_correction, laser_wavelength,
-                                         bose_einstein_correction, temperature)
-        return wavenumbers, intensities[..., 0, :, :] if squeeze else intensities
-
-    def _matrix_on_device(self, weights, width, starts, tau, bin_weights, device: int):
-        return _md_mode_matrix_on_device(self.increments, self._timestep, weights, width, starts, tau, bin_weights,
-                                         device)
+        if device is None:
+            return _md_modes_host(self._series.host(), self._timestep, weights, width, starts, tau, bool(average))
+        source, stream = self._series.source(int(device))
+        return _md_modes_on_device(source, self._timestep, weights, width, starts, tau, bool(average), int(device),
+                                   stream=stream)
 
     def _interference(self, weights, bands, segment_steps, hop, taper, corrections, device):
         """``(bands, A[B,K,C,C])`` of both interference measurements; ``corrections``: the four correction arguments."""
         if segment_steps is None:
             width, tau, starts = self._whole_table()
         else:
-            width, tau, starts = self._segment_table(segment_steps, hop, taper)
+            width, tau, starts = self._series.segment_table(segment_steps, hop, taper)
         n = width - 1
         wavenumbers = (scipy.fftpack.fftfreq(n, self._timestep) * _PER_FS_TO_CM1)[1:(n + 1) // 2]
         if len(wavenumbers) == 0:
             raise ValueError(f"segments of {width} frames have no bin to sum over")
         weights_of_bins = band_weights(wavenumbers, bands, *corrections)
         if device is not None:
-            matrices = self._matrix_on_device(weights, width, starts, tau, weights_of_bins, int(device))
+            source, stream = self._series.source(int(device))
+            matrices = _md_mode_matrix_on_device(source, self._timestep, weights, width, starts, tau, weights_of_bins,
+                                                 int(device), stream=stream)
         else:
-            matrices = _md_mode_matrix_host(self.increments, self._timestep, weights, width, starts, tau,
+            matrices = _md_mode_matrix_host(self._series.host(), self._timestep, weights, width, starts, tau,
                                             weights_of_bins)
         return np.array(bands, dtype=np.float64), matrices
 
@@ -2087,7 +1915,8 @@ class ModeMDRamanSpectrum:
         matrices = np.ascontiguousarray(np.swapaxes(matrices, 0, 1))
         return bands, matrices[0] if squeeze else matrices
 
-    def _selection(self, channels) -> NDArray[np.int64]:
+    def _selection(self, channels) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
+        """``(channels, all others)`` of ``select``."""
         index = np.asarray(channels)
         if index.dtype.kind not in "iu" or index.ndim != 1:
             raise ValueError("channels must be a one-dimensional integer array")
@@ -2097,38 +1926,30 @@ class ModeMDRamanSpectrum:
             raise ValueError(f"channels must lie in [0, {self.num_channels})")
         if len(np.unique(index)) != index.size:
             raise ValueError("channels names a channel twice")
-        return index.astype(np.int64)
+        return index.astype(np.int64), np.setdiff1d(np.arange(self.num_channels), index)
+
+    def _selected(self, channels):
+        """The increments of ``select``, where the series lives: the chosen channels, then the sum of all others."""
+        index, others = self._selection(channels)
+        if self._series.gpu is None:
+            increments = np.asarray(self._series.host())
+            chosen = np.concatenate([increments[:, index], increments[:, others].sum(axis=1, keepdims=True)], axis=1)
+            return np.ascontiguousarray(chosen)
+        import torch
+        tensor = self._series.data
+        chosen = torch.cat([tensor[:, torch.as_tensor(index, device=tensor.device)],
+                            tensor[:, torch.as_tensor(others, device=tensor.device)].sum(dim=1, keepdim=True)], dim=1)
+        return chosen.contiguous()
 
     def select(self, channels):
         """A ``PartialMDRamanSpectrum`` of the chosen ``channels`` (1 to 15 distinct indices, in the order given) plus
         one last channel holding the sum of all others: its ``I[g,h]`` are the pair spectra of the chosen modes, cross
         terms included, and its sum over all pairs is the whole spectrum."""
-        index = self._selection(channels)
-        others = np.setdiff1d(np.arange(self.num_channels), index)
-        increments = np.asarray(self.increments)
-        chosen = np.concatenate([increments[:, index], increments[:, others].sum(axis=1, keepdims=True)], axis=1)
-        return PartialMDRamanSpectrum(np.ascontiguousarray(chosen), self._timestep)
+        return PartialMDRamanSpectrum(self._selected(channels), self._timestep)
 
 
-class _DeviceModeChannels(_DeviceResident):
-    """What the device-resident mode spectra share: the increments stay in HBM as a contiguous float64 CUDA tensor
-    ``(_,C,3,3)`` and every measurement reduces them there, ordered after torch's current stream."""
-
-    @property
-    def increments(self):
-        return self._host()
-
-    def _shape(self):
-        return tuple(self._tensor.shape)
-
-    def _on_device(self, weights, width, starts, tau, average, device: int):
-        source, stream = self._source(device)
-        return _md_modes_on_device(source, self._timestep, weights, width, starts, tau, average, device, stream=stream)
-
-    def _matrix_on_device(self, weights, width, starts, tau, bin_weights, device: int):
-        source, stream = self._source(device)
-        return _md_mode_matrix_on_device(source, self._timestep, weights, width, starts, tau, bin_weights, device,
-                                         stream=stream)
+class _InterferenceOnDevice(_OnDevice):
+    """``_OnDevice`` for the mode spectra, which have the two interference measurements as well."""
 
     def measure_interference(self, bands, segment_steps=None, hop=None, taper="hann", orientation="polycrystalline",
                              laser_correction=False, laser_wavelength=522, bose_einstein_correction=False,
@@ -2136,7 +1957,7 @@ class _DeviceModeChannels(_DeviceResident):
         """As the base class's ``measure_interference``; reduces on the tensor's GPU unless ``host=True``."""
         return super().measure_interference(bands, segment_steps, hop, taper, orientation, laser_correction,
                                             laser_wavelength, bose_einstein_correction, temperature,
-                                            device=self._device_or_host(device, host))
+                                            device=self._series.device_or_host(device, host))
 
     def measure_interference_polarized(self, incident, scattered, orientation=None, *, bands, segment_steps=None,
                                        hop=None, taper="hann", laser_correction=False, laser_wavelength=522,
@@ -2146,35 +1967,24 @@ class _DeviceModeChannels(_DeviceResident):
             incident, scattered, orientation, bands=bands, segment_steps=segment_steps, hop=hop, taper=taper,
             laser_correction=laser_correction, laser_wavelength=laser_wavelength,
             bose_einstein_correction=bose_einstein_correction, temperature=temperature,
-            device=self._device_or_host(device, host))
-
-    def _selected_tensor(self, channels):
-        import torch
-        index = self._selection(channels)
-        others = np.setdiff1d(np.arange(self.num_channels), index)
-        device = self._tensor.device
-        chosen = torch.cat([self._tensor[:, torch.as_tensor(index, device=device)],
-                            self._tensor[:, torch.as_tensor(others, device=device)].sum(dim=1, keepdim=True)], dim=1)
-        return chosen.contiguous()
+            device=self._series.device_or_host(device, host))
 
 
-class DeviceModeMDRamanSpectrum(_DeviceModeChannels, ModeMDRamanSpectrum):
+class DeviceModeMDRamanSpectrum(_InterferenceOnDevice, ModeMDRamanSpectrum):
     """``ModeMDRamanSpectrum`` whose increments stay in HBM (a contiguous float64 CUDA tensor ``(S-1,C,3,3)``): the
     measurements reduce them on that GPU (``rn_md_raman_modes_device``, ``rn_md_raman_mode_matrix_device``, ordered
     after torch's current stream) unless ``host=True``; ``increments`` copies them to the host on first use.
     ``select`` returns a ``DevicePartialMDRamanSpectrum``."""
 
-    def __init__(self, increments_device, timestep: float):  # pylint: disable=super-init-not-called
-        self._set_tensor("increments", increments_device, 4, "(_,_,3,3)")
-        if increments_device.shape[1] < 1:
-            raise ValueError("increments has no channel")
-        self._timestep = timestep
+    def __init__(self, increments_device, timestep: float):
+        super().__init__(_Series.of_tensor("increments", increments_device, (None, None, 3, 3), increments=True),
+                         timestep)
 
     def select(self, channels):
-        return DevicePartialMDRamanSpectrum(self._selected_tensor(channels), self._timestep)
+        return DevicePartialMDRamanSpectrum(self._selected(channels), self._timestep)
 
 
-class ModeMDRamanEnsemble(ModeMDRamanSpectrum):
+class ModeMDRamanEnsemble(_Ensemble, ModeMDRamanSpectrum):
     """Phonon-mode spectra averaged over several runs: ``runs`` is a sequence of per-channel increments
     ``(S_r-1,C,3,3)`` sharing ``C`` and ``timestep``.  The runs are joined with one zero row between them, so that
     increment t still belongs to frame t of the joined frames; no segment reads that row.  Every measurement of
@@ -2185,72 +1995,28 @@ class ModeMDRamanEnsemble(ModeMDRamanSpectrum):
     the runs have one length.  ``device`` (an int) reduces all runs in one call.  ``select`` returns a
     ``PartialMDRamanEnsemble``."""
 
-    def __init__(self, runs, timestep: float):  # pylint: disable=super-init-not-called
-        runs = list(runs)
-        if not runs:
-            raise ValueError("an ensemble needs at least one run")
-        for index, run in enumerate(runs):
-            verify_ndarray_shape(f"runs[{index}]", run, (None, runs[0].shape[1], 3, 3))
-        if runs[0].shape[1] < 1:
-            raise ValueError("increments has no channel")
-        self._run_lengths = [int(run.shape[0]) + 1 for run in runs]  # frames
-        gap = np.zeros((1, *runs[0].shape[1:]))
-        parts = [part for run in runs for part in (np.asarray(run, dtype=np.float64), gap)][:-1]
-        self._increments = np.concatenate(parts, axis=0)
-        self._timestep = timestep
-
-    @property
-    def run_lengths(self) -> list[int]:
-        """Frames per run (one more than its increments)."""
-        return list(self._run_lengths)
-
-    def _segment_table(self, segment_steps, hop, taper):
-        width, hop, tau = segment_plan(min(self._run_lengths), segment_steps, hop, taper)
-        return width, tau, ensemble_segment_starts(self._run_lengths, width, hop)[0]
-
-    def _whole_table(self):
-        """Each run as one boxcar segment."""
-        steps = _equal_run_length(self._run_lengths)
-        if steps < 3:
-            raise ValueError(_TOO_FEW_STEPS)
-        return self._segment_table(steps, steps, "boxcar")
-
-    def segment_starts(self, segment_steps, hop=None) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
-        """``(run_index, start_within_run)`` of each row of ``measure_segments(..., average=False)``."""
-        starts, run_index = ensemble_segment_starts(self._run_lengths, segment_steps, hop)
-        return run_index, starts - _run_offsets(self._run_lengths)[run_index]
+    def __init__(self, runs, timestep: float):
+        super().__init__(runs if isinstance(runs, _Series) else _Series.of_runs(runs, (3, 3), True, increments=True),
+                         timestep)
 
     def select(self, channels):
-        index = self._selection(channels)
-        others = np.setdiff1d(np.arange(self.num_channels), index)
-        increments = np.asarray(self.increments)
-        chosen = np.concatenate([increments[:, index], increments[:, others].sum(axis=1, keepdims=True)], axis=1)
-        bounds = np.cumsum(self._run_lengths)
-        return PartialMDRamanEnsemble([chosen[end - length:end - 1] for length, end in zip(self._run_lengths, bounds)],
+        chosen = self._selected(channels)
+        lengths = self._series.run_lengths
+        return PartialMDRamanEnsemble([chosen[end - length:end - 1] for length, end in zip(lengths, np.cumsum(lengths))],
                                       self._timestep)
 
 
-class DeviceModeMDRamanEnsemble(_DeviceModeChannels, ModeMDRamanEnsemble):
+class DeviceModeMDRamanEnsemble(_InterferenceOnDevice, ModeMDRamanEnsemble):
     """``ModeMDRamanEnsemble`` whose increments stay in HBM: a sequence of contiguous float64 CUDA tensors
     ``(S_r-1,C,3,3)`` (joined here, on the GPU, with a zero row between them), or one tensor ``(sum(S_r)-1,C,3,3)``
     plus ``run_lengths`` (frames per run), as one batched evaluation of the joined frames writes it: its rows across
     the run boundaries stand where the zero rows would and are never read.  ``select`` returns a
     ``DevicePartialMDRamanEnsemble``."""
 
-    def __init__(self, runs, timestep: float, run_lengths=None):  # pylint: disable=super-init-not-called
-        import torch
-        runs, lengths = _joined_tensor("runs", runs, run_lengths, 1)
-        if lengths is None:
-            if not all(isinstance(run, torch.Tensor) for run in runs):
-                raise ValueError("runs must be contiguous float64 CUDA tensors")
-            lengths = [int(run.shape[0]) + 1 for run in runs]
-            gap = runs[0].new_zeros((1, *runs[0].shape[1:]))
-            runs = torch.cat([part for run in runs for part in (run, gap)][:-1], dim=0)
-        self._set_tensor("runs", runs, 4, "(_,_,3,3)")
-        if runs.shape[1] < 1:
-            raise ValueError("increments has no channel")
-        self._run_lengths = lengths
-        self._timestep = timestep
+    def __init__(self, runs, timestep: float, run_lengths=None):
+        super().__init__(_Series.of_tensor_runs("runs", runs, run_lengths, (None, None, 3, 3), increments=True,
+                                                tensors_only=True), timestep)
 
     def select(self, channels):
-        return DevicePartialMDRamanEnsemble(self._selected_tensor(channels), self._timestep, self._run_lengths)
+        return DevicePartialMDRamanEnsemble(self._selected(channels), self._timestep, self._series.run_lengths)
+
