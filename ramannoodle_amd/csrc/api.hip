@@ -17,6 +17,9 @@
 // gradients, atom groups, training); then the C entries.  The entries share their argument checks (check_batch,
 // check_train_batch, check_pending, check_types), their staging (stage, stage_lattices, stage_types, lazy_stream,
 // lazy_event) and the ordering bracket around work done for a caller's stream (behind_caller / hand_back).
+// The error types, DeviceBuf, set_error and guarded() -- the lock and the try block every entry runs in -- are
+// host_runtime.hpp's; the group table, the mode upload, the chunk walk and the checks of the increment entries are
+// increments.hpp's, shared with the interpolation model (api_interp.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +38,8 @@
 
 #include "../../include/rn_potgnn.h"
 #include "graph_plan.hpp"
+#include "host_runtime.hpp"
+#include "increments.hpp"
 #include "kernels.hpp"
 #include "weight_layout.hpp"
 
@@ -43,36 +48,6 @@ using namespace rn;
 namespace {
 
 std::string g_create_error;
-
-struct HipError {
-  hipError_t code;
-  const char *what;
-};
-
-#define HIP_TRY(expr)                                  \
-  do {                                                 \
-    hipError_t _e = (expr);                            \
-    if (_e != hipSuccess) throw HipError{_e, #expr};   \
-  } while (0)
-
-struct DeviceBuf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  ~DeviceBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  void ensure(size_t n) {
-    if (n <= bytes) return;
-    release();
-    HIP_TRY(hipMalloc(&p, n));
-    bytes = n;
-  }
-  template <typename T>
-  T *as() const { return reinterpret_cast<T *>(p); }
-};
 
 enum KernelId {
   K_GEOM = 0, K_NODE_INIT, K_PROJ_NODE, K_PROJ_EDGE_C1, K_NODE_AGG, K_PROJ_EDGE_C3, K_PROJ_C2,
@@ -204,30 +179,17 @@ struct rn_potgnn {
   hipEvent_t ev_g[2] = {nullptr, nullptr};  // "projection stage done" per lane (run_pair)
   bool interleave = true;
   // atom-group contractions: the CSR permutation of the last labels (perm [N] | gptr [G+1]), Jacobian rows, staging
-  std::vector<int32_t> grp_labels;
-  int grp_G = 0;
-  DeviceBuf grp_csr, grp_jac, grp_disp, grp_out;
+  GroupTable groups;
+  DeviceBuf grp_jac, grp_disp, grp_out;
   DeviceBuf mode_vectors;  // rn_potgnn_mode_increments_device: D [M][N][3] | P [M][N][3]
   // variable-cell calls: the lattice rows of the Jacobian [frames][6][9], a trajectory's lattices in the arithmetic of a
   // float32 run (group increments), the float32 lattices of rn_potgnn_forward_cells_device
   DeviceBuf grp_jl, grp_lat, cells_lat;
+  int device_index() const { return cfg.device; }
+  static std::string &create_error() { return g_create_error; }
 };
 
 namespace {
-
-void set_error(rn_potgnn *h, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  if (h) {  // (entry points report argument errors before they enter guarded(): the error text is handle state too)
-    std::lock_guard<std::recursive_mutex> hold(h->lock);
-    h->error = buf;
-  } else {
-    g_create_error = buf;
-  }
-}
 
 // Frames per device work chunk in precision T.  The workspace budget is counted in bytes, so
 // the float64 lanes (created on first use, next to the float32 ones) take half the frames.
@@ -1214,20 +1176,9 @@ void forward_vjp(rn_potgnn *h, const double *d_lat /* [S][9] or null */, const i
 
 // ---- atom-group contractions (rn_potgnn_group_increments_device, rn_potgnn_partial_raman_tensors); G <= kMaxGroups (kernels.hpp)
 
-// labels host int32[N] in [0, G), every group used: the atoms bucketed by group (ascending atom index within a group) as a
-// CSR permutation in h->grp_csr; rebuilt only when the labels change.  false on a label out of range or an empty group.
-bool set_group_labels(rn_potgnn *h, const int32_t *labels, int G) {
-  const int N = h->g.N;
-  std::vector<int32_t> csr;
-  if (!group_csr(labels, N, G, csr)) return false;  // (kernels.hpp: shared with the interpolation model's entries)
-  if (h->grp_G == G && h->grp_labels.size() == (size_t)N && std::equal(labels, labels + N, h->grp_labels.begin()))
-    return true;
-  h->grp_csr.ensure(csr.size() * sizeof(int32_t));
-  HIP_TRY(hipMemcpy(h->grp_csr.p, csr.data(), csr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  h->grp_labels.assign(labels, labels + N);
-  h->grp_G = G;
-  return true;
-}
+// The group table h->groups (increments.hpp) is updated with nothing to wait for: every increments call returns
+// synchronised through hand_back(..., true), and partial_raman_tensors synchronises lane 0 before it stages, so no work
+// enqueued earlier still reads the old permutation.
 
 // Frames per taped chunk of the group entries in precision T: the tape, lane 0's buffers and the reverse pass of six
 // cotangent rows per frame (their per-edge Cartesian cotangents and Jacobian rows included) of F frames, plus one frame of
@@ -1268,11 +1219,10 @@ void jacobian_rows(rn_potgnn *h, const double *d_pos, int s, double *d_jac, cons
   reverse_pass<T>(h, c, rv);
 }
 
-// The loop every increment entry shares: the S frames d_pos (device float64 [S][N][3]) go through in chunks of F steps
-// whose Jacobian rows overlap by one frame (the last frame's rows are carried into the next chunk), and
-// contract(jac, pos, f, out, st) launches the contraction of a chunk's f steps (jac [f+1][6][N][3], pos the chunk's first
-// frame, out its first step's row of d_out [S-1][out_channels][9]) on lane 0's stream.  Ordered after `user`; `user` waits
-// for the work and is synchronised once at the end.
+// The chunk walk of every increment entry (increments.hpp: walk_chunks): the S frames d_pos (device float64 [S][N][3]) go
+// through in chunks of F = group_frames steps, and contract(jac, pos, f, out, st) launches the contraction of a chunk's f
+// steps (jac [f+1][6][N][3], pos the chunk's first frame, out its first step's row of d_out [S-1][out_channels][9]) on
+// lane 0's stream.  Ordered after `user`; `user` waits for the work and is synchronised once at the end.
 // d_lat (device float64 [S][9], or null): a lattice per frame.  The Jacobian rows are then taken at each frame's own
 // lattice (cast to T, as the forward casts it), their lattice rows J_L [6][9] are carried over chunk boundaries with them,
 // and channel `cell_channel` of d_out is the cell's share 1/2 (J_L(t) + J_L(t+1)) : (L_{t+1} - L_t).
@@ -1304,18 +1254,16 @@ void chunked_increments(rn_potgnn *h, const double *d_pos, int64_t S, size_t lim
       lat = h->grp_lat.as<T>();
     }
   }
-  jacobian_rows<T>(h, d_pos, 1, jac, lat, jl);
-  for (int64_t t0 = 0; t0 < S - 1; t0 += F) {
-    const int f = (int)std::min<int64_t>(F, S - 1 - t0);
-    if (t0 > 0) {
-      HIP_TRY(hipMemcpyAsync(jac, jac + (int64_t)F * rows, rows * sizeof(double), hipMemcpyDeviceToDevice, st));
-      if (jl) HIP_TRY(hipMemcpyAsync(jl, jl + (int64_t)F * 54, 54 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    jacobian_rows<T>(h, d_pos + (t0 + 1) * N * 3, f, jac + rows, lat ? lat + (t0 + 1) * 9 : nullptr, jl ? jl + 54 : nullptr);
-    contract(jac, d_pos + t0 * N * 3, f, d_out + t0 * out_channels * 9, st);
-    if (jl) launch_cell_increments(jl, d_lat + t0 * 9, f, cell_channel, out_channels, sigma, d_out + t0 * out_channels * 9, st);
-    HIP_TRY(hipGetLastError());
-  }
+  walk_chunks(
+      S, F, rows, jac, st,
+      [&](int64_t first, int64_t count, double *to, double *to_jl) {
+        jacobian_rows<T>(h, d_pos + first * N * 3, (int)count, to, lat ? lat + first * 9 : nullptr, to_jl);
+      },
+      [&](int64_t t0, int64_t f) {
+        contract(jac, d_pos + t0 * N * 3, (int)f, d_out + t0 * out_channels * 9, st);
+        if (jl) launch_cell_increments(jl, d_lat + t0 * 9, f, cell_channel, out_channels, sigma, d_out + t0 * out_channels * 9, st);
+      },
+      jl, 54);
   hand_back(h, user, P.lanes, 1, true);
 }
 
@@ -1325,7 +1273,7 @@ template <typename T>
 void group_increments(rn_potgnn *h, const double *d_pos, int64_t S, int G, size_t limit, double *d_out,
                       hipStream_t user, const double *d_lat = nullptr) {
   const int N = h->g.N;
-  const int *perm = h->grp_csr.as<int>(), *gptr = perm + N;
+  const int *perm = h->groups.perm(), *gptr = perm + N;
   const double *sigma = h->d_mean_std.as<double>() + 9;
   const int out_groups = d_lat ? G + 1 : G;
   chunked_increments<T>(h, d_pos, S, limit, out_groups, G, d_out, user, d_lat,
@@ -1350,21 +1298,15 @@ template <typename T>
 void mode_increments(rn_potgnn *h, const double *d_pos, int64_t S, const double *disp, const double *proj, int M,
                      bool rest, size_t limit, double *d_out, hipStream_t user, const double *d_lat) {
   const int N = h->g.N;
-  const size_t bytes = (size_t)M * N * 3 * sizeof(double);
-  if (limit <= 2 * bytes) throw HipError{hipErrorOutOfMemory, "mode_increments: the modes do not fit the workspace limit"};
   ensure_precision<T>(h);
-  HIP_TRY(hipStreamSynchronize(prec<T>(h).lanes[0].stream));  // (an earlier call may still read the old modes)
-  h->mode_vectors.ensure(2 * bytes);
-  double *d_disp = h->mode_vectors.as<double>(), *d_proj = d_disp + (size_t)M * N * 3;
-  HIP_TRY(hipMemcpy(d_disp, disp, bytes, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_proj, proj, bytes, hipMemcpyHostToDevice));
+  const ModeVectors modes = upload_modes(h->mode_vectors, disp, proj, M, N, limit, prec<T>(h).lanes[0].stream);
   const double *sigma = h->d_mean_std.as<double>() + 9;
   const int channels = M + (rest ? 1 : 0);
   const int out_channels = channels + (d_lat ? 1 : 0);
-  chunked_increments<T>(h, d_pos, S, limit - 2 * bytes, out_channels, channels, d_out, user, d_lat,
+  chunked_increments<T>(h, d_pos, S, limit - modes.bytes, out_channels, channels, d_out, user, d_lat,
                         "mode_increments: one step does not fit the workspace limit",
                         [&](const double *jac, const double *pos, int f, double *out, hipStream_t st2) {
-                          mode_contract(jac, (int64_t)f + 1, pos, N, d_disp, d_proj, M, sigma, rest, out_channels, out, st2);
+                          mode_contract(jac, (int64_t)f + 1, pos, N, modes.disp, modes.proj, M, sigma, rest, out_channels, out, st2);
                         });
 }
 
@@ -1604,35 +1546,6 @@ inline void train_backward_device(rn_potgnn *h, const float *d_dvec6, hipStream_
   h->grads_on_device = true;
 }
 
-// Every entry point that touches a handle runs inside guarded(): calls on ONE handle are serialised by the handle's own
-// lock (they share its workspaces, streams and tape), so a handle may be used from several threads; distinct handles are
-// independent.  No exception leaves the C ABI.
-struct RnInvalid {};  // an argument found invalid inside guarded() (the error text is already set)
-
-int guarded(rn_potgnn *h, const std::function<void()> &fn) {
-  std::unique_lock<std::recursive_mutex> lock;
-  if (h) lock = std::unique_lock<std::recursive_mutex>(h->lock);
-  try {
-    if (h) HIP_TRY(hipSetDevice(h->cfg.device));
-    fn();
-    return RN_OK;
-  } catch (const RnInvalid &) {
-    return RN_ERR_INVALID_ARGUMENT;
-  } catch (const HipError &e) {
-    set_error(h, "HIP error %d (%s) in %s", (int)e.code, hipGetErrorString(e.code), e.what);
-    return e.code == hipErrorOutOfMemory ? RN_ERR_OUT_OF_MEMORY : RN_ERR_HIP;
-  } catch (const std::bad_alloc &) {
-    set_error(h, "host allocation failed");
-    return RN_ERR_OUT_OF_MEMORY;
-  } catch (const std::exception &e) {
-    set_error(h, "internal error: %s", e.what());
-    return RN_ERR_HIP;
-  } catch (...) {
-    set_error(h, "internal error: unknown exception");
-    return RN_ERR_HIP;
-  }
-}
-
 // ---- what the entries share: argument checks (each returns kGo, or the status the entry returns at once) and lazily
 // created streams / events
 
@@ -1848,14 +1761,14 @@ int rn_potgnn_create(const rn_potgnn_config *cfg, const int32_t *edge_a, const i
   std::string invalid;
   int rc = validate_create_args(cfg, edge_a, edge_b, atom_types, !lattice || !weights || !mean || !stddev, &num_weights, invalid);
   if (rc != RN_OK) {
-    set_error(nullptr, "%s", invalid.c_str());
+    set_error<rn_potgnn>(nullptr, "%s", invalid.c_str());
     return rc;
   }
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 ||
       cfg->device >= ndev) {
-    set_error(nullptr, "no usable HIP device (count=%d, requested=%d)", ndev, cfg->device);
+    set_error<rn_potgnn>(nullptr, "no usable HIP device (count=%d, requested=%d)", ndev, cfg->device);
     return RN_ERR_NO_DEVICE;
   }
   int cus = 256;
@@ -1886,7 +1799,7 @@ int rn_potgnn_create(const rn_potgnn_config *cfg, const int32_t *edge_a, const i
   h->plan = plan_graph(*cfg, h->d, edge_a, edge_b, atom_types, cus, knobs);
 
   rn_potgnn *hp = h.get();
-  rc = guarded(nullptr, [&]() {
+  rc = guarded<rn_potgnn>(nullptr, [&]() {
     HIP_TRY(hipSetDevice(cfg->device));
     HIP_TRY(hipEventCreateWithFlags(&hp->ev_start, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&hp->ev_g[0], hipEventDisableTiming));
@@ -1917,7 +1830,7 @@ int rn_potgnn_debug_plan(const rn_potgnn_config *cfg, const int32_t *edge_a, con
   std::string invalid;
   const int rc = validate_create_args(cfg, edge_a, edge_b, atom_types, false, nullptr, invalid);
   if (rc != RN_OK) {
-    set_error(nullptr, "%s", invalid.c_str());
+    set_error<rn_potgnn>(nullptr, "%s", invalid.c_str());
     return rc;
   }
   try {
@@ -1925,13 +1838,13 @@ int rn_potgnn_debug_plan(const rn_potgnn_config *cfg, const int32_t *edge_a, con
     const std::vector<int32_t> flat = plan_graph(*cfg, plan_dims(*cfg, knobs), edge_a, edge_b, atom_types, num_cus, knobs).flat();
     *count = flat.size();
     if (!out || capacity < flat.size()) {
-      set_error(nullptr, "out holds %zu values, the plan has %zu", out ? capacity : (size_t)0, flat.size());
+      set_error<rn_potgnn>(nullptr, "out holds %zu values, the plan has %zu", out ? capacity : (size_t)0, flat.size());
       return RN_ERR_INVALID_ARGUMENT;
     }
     std::memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
     return RN_OK;
   } catch (const std::bad_alloc &) {
-    set_error(nullptr, "host allocation failed");
+    set_error<rn_potgnn>(nullptr, "host allocation failed");
     return RN_ERR_OUT_OF_MEMORY;
   }
 }
@@ -1943,7 +1856,7 @@ int rn_potgnn_debug_plan_pairs(const rn_potgnn_config *cfg, const int32_t *edge_
   std::string invalid;
   const int rc = validate_create_args(cfg, edge_a, edge_b, atom_types, false, nullptr, invalid);
   if (rc != RN_OK) {
-    set_error(nullptr, "%s", invalid.c_str());
+    set_error<rn_potgnn>(nullptr, "%s", invalid.c_str());
     return rc;
   }
   try {
@@ -1951,13 +1864,13 @@ int rn_potgnn_debug_plan_pairs(const rn_potgnn_config *cfg, const int32_t *edge_
     const std::vector<int32_t> flat = plan_graph(*cfg, plan_dims(*cfg, knobs), edge_a, edge_b, atom_types, num_cus, knobs).flat_pairs();
     *count = flat.size();
     if (!out || capacity < flat.size()) {
-      set_error(nullptr, "out holds %zu values, the pair table has %zu", out ? capacity : (size_t)0, flat.size());
+      set_error<rn_potgnn>(nullptr, "out holds %zu values, the pair table has %zu", out ? capacity : (size_t)0, flat.size());
       return RN_ERR_INVALID_ARGUMENT;
     }
     std::memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
     return RN_OK;
   } catch (const std::bad_alloc &) {
-    set_error(nullptr, "host allocation failed");
+    set_error<rn_potgnn>(nullptr, "host allocation failed");
     return RN_ERR_OUT_OF_MEMORY;
   }
 }
@@ -1969,7 +1882,7 @@ int rn_potgnn_debug_plan_lds(const rn_potgnn_config *cfg, const int32_t *edge_a,
   std::string invalid;
   const int rc = validate_create_args(cfg, edge_a, edge_b, atom_types, false, nullptr, invalid);
   if (rc != RN_OK) {
-    set_error(nullptr, "%s", invalid.c_str());
+    set_error<rn_potgnn>(nullptr, "%s", invalid.c_str());
     return rc;
   }
   try {
@@ -1977,13 +1890,13 @@ int rn_potgnn_debug_plan_lds(const rn_potgnn_config *cfg, const int32_t *edge_a,
     const std::vector<int64_t> lds = plan_graph(*cfg, plan_dims(*cfg, knobs), edge_a, edge_b, atom_types, num_cus, knobs).lds_requests();
     *count = lds.size();
     if (!out || capacity < lds.size()) {
-      set_error(nullptr, "out holds %zu values, the table has %zu", out ? capacity : (size_t)0, lds.size());
+      set_error<rn_potgnn>(nullptr, "out holds %zu values, the table has %zu", out ? capacity : (size_t)0, lds.size());
       return RN_ERR_INVALID_ARGUMENT;
     }
     std::memcpy(out, lds.data(), lds.size() * sizeof(int64_t));
     return RN_OK;
   } catch (const std::bad_alloc &) {
-    set_error(nullptr, "host allocation failed");
+    set_error<rn_potgnn>(nullptr, "host allocation failed");
     return RN_ERR_OUT_OF_MEMORY;
   }
 }
@@ -1993,7 +1906,7 @@ static int debug_layout(const rn_potgnn_config *cfg, bool others_null, const siz
   std::string invalid;
   const int rc = validate_config(cfg, others_null, num_weights, invalid);
   if (rc != RN_OK) {
-    set_error(nullptr, "%s", invalid.c_str());
+    set_error<rn_potgnn>(nullptr, "%s", invalid.c_str());
     return rc;
   }
   L = layout_weights(*cfg, plan_dims(*cfg, read_plan_knobs()));
@@ -2001,7 +1914,7 @@ static int debug_layout(const rn_potgnn_config *cfg, bool others_null, const siz
 }
 static int debug_failed(const std::exception &e) {
   const bool memory = dynamic_cast<const std::bad_alloc *>(&e) != nullptr;
-  set_error(nullptr, memory ? "host allocation failed" : "internal error: %s", e.what());
+  set_error<rn_potgnn>(nullptr, memory ? "host allocation failed" : "internal error: %s", e.what());
   return memory ? RN_ERR_OUT_OF_MEMORY : RN_ERR_HIP;
 }
 
@@ -2014,7 +1927,7 @@ int rn_potgnn_debug_pack_weights(const rn_potgnn_config *cfg, const float *weigh
     if (const int rc = debug_layout(cfg, !weights, &num_weights, L); rc != RN_OK) return rc;
     *count = L.total;
     if (!packed || !mask || !flags || capacity < L.total) {
-      set_error(nullptr, "out holds %zu values, the packed blob has %zu", packed && mask && flags ? capacity : (size_t)0, L.total);
+      set_error<rn_potgnn>(nullptr, "out holds %zu values, the packed blob has %zu", packed && mask && flags ? capacity : (size_t)0, L.total);
       return RN_ERR_INVALID_ARGUMENT;
     }
     std::vector<float> o;
@@ -2047,11 +1960,11 @@ int rn_potgnn_debug_unpack_weights(const rn_potgnn_config *cfg, const float *pac
     if (const int rc = debug_layout(cfg, !packed, nullptr, L); rc != RN_OK) return rc;
     *count = L.weight_count();
     if (num_packed != L.total) {
-      set_error(nullptr, "packed has %zu floats, expected %zu", num_packed, L.total);
+      set_error<rn_potgnn>(nullptr, "packed has %zu floats, expected %zu", num_packed, L.total);
       return RN_ERR_INVALID_ARGUMENT;
     }
     if (!out || capacity < L.weight_count()) {
-      set_error(nullptr, "out holds %zu values, the state dict has %zu", out ? capacity : (size_t)0, L.weight_count());
+      set_error<rn_potgnn>(nullptr, "out holds %zu values, the state dict has %zu", out ? capacity : (size_t)0, L.weight_count());
       return RN_ERR_INVALID_ARGUMENT;
     }
     unpack_weights<float>(L, packed, out, buffers != 0);
@@ -2419,10 +2332,10 @@ int rn_host_buffer_alloc(size_t bytes, int device, void **out) {
   *out = nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_error(nullptr, "no usable HIP device (count=%d, requested=%d)", ndev, device);
+    set_error<rn_potgnn>(nullptr, "no usable HIP device (count=%d, requested=%d)", ndev, device);
     return RN_ERR_NO_DEVICE;
   }
-  return guarded(nullptr, [&]() {
+  return guarded<rn_potgnn>(nullptr, [&]() {
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipHostMalloc(out, bytes, hipHostMallocPortable));
   });
@@ -2637,16 +2550,9 @@ int rn_potgnn_forward_vjp_device(rn_potgnn *h, const double *d_lattices, const i
 
 int rn_potgnn_group_increments_device(rn_potgnn *h, const double *d_positions, int64_t S, const int32_t *labels, int G,
                                       int use_float64, size_t workspace_limit, double *d_out, void *stream) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 2 || !d_positions || !labels || !d_out || G < 1 || G > kMaxGroups) {
-    set_error(h, "invalid arguments to group_increments_device (S < 2, G outside 1..%d or a null pointer)", kMaxGroups);
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  if (const int rc = check_group_entry(h, S, d_positions, labels, d_out, G)) return rc;
   return guarded(h, [&]() {
-    if (!set_group_labels(h, labels, G)) {
-      set_error(h, "group_increments_device: a label outside [0, G) or an empty group");
-      throw RnInvalid{};
-    }
+    h->groups.set(h, "group_increments_device", labels, h->g.N, G, nullptr);
     const size_t limit = workspace_limit ? workspace_limit : kTapeBudget;
     with_precision(h, use_float64, [&](auto t) {
       group_increments<decltype(t)>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream);
@@ -2665,10 +2571,7 @@ int rn_potgnn_group_increments_cells_device(rn_potgnn *h, const double *d_positi
     return RN_ERR_INVALID_ARGUMENT;
   }
   return guarded(h, [&]() {
-    if (!set_group_labels(h, labels, G)) {
-      set_error(h, "group_increments_cells_device: a label outside [0, G) or an empty group");
-      throw RnInvalid{};
-    }
+    h->groups.set(h, "group_increments_cells_device", labels, h->g.N, G, nullptr);
     const size_t limit = workspace_limit ? workspace_limit : kTapeBudget;
     with_precision(h, use_float64, [&](auto t) {
       group_increments<decltype(t)>(h, d_positions, S, G, limit, d_out, (hipStream_t)stream, d_lattices);
@@ -2682,7 +2585,7 @@ int rn_potgnn_mode_contract_device(const double *d_jac, int64_t frames, const do
   if (!d_jac || !d_positions || !d_disp || !d_proj || !sigma || !d_out) return RN_ERR_INVALID_ARGUMENT;
   if (frames < 2 || N < 1 || M < 1 || M > kMaxModes || (rest != 0 && rest != 1)) return RN_ERR_INVALID_ARGUMENT;
   if ((int64_t)out_channels < (int64_t)M + rest) return RN_ERR_INVALID_ARGUMENT;
-  return guarded(nullptr, [&]() {
+  return guarded<rn_potgnn>(nullptr, [&]() {
     hipStream_t st = (hipStream_t)stream;
     DeviceBuf d_sigma;
     d_sigma.ensure(9 * sizeof(double));
@@ -2696,18 +2599,8 @@ int rn_potgnn_mode_contract_device(const double *d_jac, int64_t frames, const do
 int rn_potgnn_mode_increments_device(rn_potgnn *h, const double *d_positions, const double *d_lattices, int64_t S,
                                      const double *disp, const double *proj, int32_t M, int rest, int use_float64,
                                      size_t workspace_limit, double *d_out, void *stream) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 2 || !d_positions || !disp || !proj || !d_out || M < 1 || M > kMaxModes || (rest != 0 && rest != 1)) {
-    set_error(h, "invalid arguments to mode_increments_device (S < 2, M outside 1..%d, rest not 0 or 1 or a null pointer)",
-              kMaxModes);
-    return RN_ERR_INVALID_ARGUMENT;
-  }
-  const size_t entries = (size_t)M * h->g.N * 3;
-  for (size_t j = 0; j < entries; ++j)
-    if (!std::isfinite(disp[j]) || !std::isfinite(proj[j])) {
-      set_error(h, "mode_increments_device: a non-finite entry in disp or proj");
-      return RN_ERR_INVALID_ARGUMENT;
-    }
+  if (const int rc = check_mode_entry(h, S, d_positions, disp, proj, d_out, M, rest)) return rc;
+  if (const int rc = check_mode_vectors(h, disp, proj, M, h->g.N)) return rc;
   return guarded(h, [&]() {
     const size_t limit = workspace_limit ? workspace_limit : kTapeBudget;
     with_precision(h, use_float64, [&](auto t) {
@@ -2718,16 +2611,9 @@ int rn_potgnn_mode_increments_device(rn_potgnn *h, const double *d_positions, co
 
 int rn_potgnn_partial_raman_tensors(rn_potgnn *h, const double *ref_positions, const double *displacements, int64_t M,
                                     const int32_t *labels, int G, double *raman) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (M < 0 || !ref_positions || !labels || G < 1 || G > kMaxGroups || (M > 0 && (!displacements || !raman))) {
-    set_error(h, "invalid arguments to partial_raman_tensors (G outside 1..%d or a null pointer)", kMaxGroups);
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  if (const int rc = check_partial_raman_entry(h, ref_positions, displacements, M, labels, G, raman)) return rc;
   return guarded(h, [&]() {
-    if (!set_group_labels(h, labels, G)) {
-      set_error(h, "partial_raman_tensors: a label outside [0, G) or an empty group");
-      throw RnInvalid{};
-    }
+    h->groups.set(h, "partial_raman_tensors", labels, h->g.N, G, nullptr);
     if (M == 0) return;
     sync_host(h);  // (device-resident training may have moved the weights ahead of the float64 copy)
     ensure_precision<double>(h);
@@ -2742,7 +2628,7 @@ int rn_potgnn_partial_raman_tensors(rn_potgnn *h, const double *ref_positions, c
     stage<double>(h->grp_disp, displacements, (size_t)M * n3 * sizeof(double));
     jacobian_rows<double>(h, d_ref, 1, h->grp_jac.as<double>());
     // R[m][g] = 2 sigma (.) sum_{i in g} J_i . d_{m,i}: the kernel's 1/2 (J + J) . (2 d)
-    const int *perm = h->grp_csr.as<int>();
+    const int *perm = h->groups.perm();
     launch_group_increments(h->grp_jac.as<double>(), 0, nullptr, h->grp_disp.as<double>(), 2.0, M, N, perm, perm + N, G,
                             h->d_mean_std.as<double>() + 9, h->grp_out.as<double>(), st);
     HIP_TRY(hipGetLastError());
@@ -2929,15 +2815,15 @@ int rn_potgnn_train_backward(rn_potgnn *h, const float *dvec6, float *grads) {
 int rn_potgnn_radius_graph(const double *lattice, const double *positions, int32_t num_atoms,
                            double cutoff, int device, uint8_t *adjacency) {
   if (!lattice || !positions || !adjacency || num_atoms <= 0 || !(cutoff > 0)) {
-    set_error(nullptr, "invalid arguments to radius_graph");
+    set_error<rn_potgnn>(nullptr, "invalid arguments to radius_graph");
     return RN_ERR_INVALID_ARGUMENT;
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_error(nullptr, "no usable HIP device (count=%d, requested=%d)", ndev, device);
+    set_error<rn_potgnn>(nullptr, "no usable HIP device (count=%d, requested=%d)", ndev, device);
     return RN_ERR_NO_DEVICE;
   }
-  return guarded(nullptr, [&]() {
+  return guarded<rn_potgnn>(nullptr, [&]() {
     HIP_TRY(hipSetDevice(device));
     const size_t n = (size_t)num_atoms;
     DeviceBuf lat, pos, adj;

@@ -3,23 +3,23 @@
 // A handle owns the model as the kernels read it (kernels.hpp: InterpModel; the tables padded to one Horner trip
 // count) and the workspaces of its entries.  The evaluation is one launch per call; the Jacobian is two (the spline
 // derivatives, then their product with the basis); the increment entries walk the frames in chunks whose Jacobian rows
-// overlap by one frame, as the PotGNN entries of api.hip do, and hand the rows to the same contractions
-// (launch_group_increments, launch_mode_increments, launch_mode_rest) with sigma = 1.  All device work of an entry is
-// enqueued on the caller's stream, in order.
+// overlap by one frame, with the loop, group table, mode upload and argument checks the PotGNN entries of api.hip use
+// (increments.hpp), and hand the rows to the same contractions (launch_group_increments, launch_mode_increments,
+// launch_mode_rest) with sigma = 1.  All device work of an entry is enqueued on the caller's stream, in order.  The guard
+// every entry runs in, the error types and the device buffer are host_runtime.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/rn_interp.h"
 #include "../../include/rn_potgnn.h"
+#include "host_runtime.hpp"
+#include "increments.hpp"
 #include "kernels.hpp"
 
 using namespace rn;
@@ -27,41 +27,6 @@ using namespace rn;
 namespace {
 
 std::string g_interp_create_error;
-
-struct HipFail {
-  hipError_t code;
-  const char *what;
-};
-struct Invalid {};  // an argument found invalid inside guarded() (the error text is already set)
-
-#define HIP_TRY(expr)                                \
-  do {                                               \
-    hipError_t _e = (expr);                          \
-    if (_e != hipSuccess) throw HipFail{_e, #expr};  \
-  } while (0)
-
-struct Buf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  ~Buf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  void ensure(size_t n) {
-    if (n <= bytes) return;
-    release();
-    HIP_TRY(hipMalloc(&p, n));
-    bytes = n;
-  }
-  void upload(const void *src, size_t n) {
-    ensure(n);
-    HIP_TRY(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
-  }
-  template <typename T>
-  T *as() const { return reinterpret_cast<T *>(p); }
-};
 
 constexpr size_t kDefaultWorkspace = (size_t)1 << 30;
 constexpr int64_t kHostChunk = 1 << 15;  // frames per staged chunk of the host entry
@@ -73,11 +38,12 @@ struct rn_interp {
   int device = 0;
   int N = 0, J = 0, order = 0, Pmax = 0;
   bool symmetric = false;
-  Buf F, FT, ref, alpha_ref, poff, xs, coef, scale, ones;
-  Buf g, jac, modes, csr, io_pos, io_out, disp;
-  std::vector<int32_t> labels;
-  int G = 0;
+  DeviceBuf F, FT, ref, alpha_ref, poff, xs, coef, scale, ones;
+  DeviceBuf g, jac, modes, io_pos, io_out, disp;
+  GroupTable groups;
   std::string error;
+  int device_index() const { return device; }
+  static std::string &create_error() { return g_interp_create_error; }
   InterpModel model() const {
     return InterpModel{F.as<double>(),   FT.as<double>(),    ref.as<double>(), alpha_ref.as<double>(), xs.as<double>(),
                        coef.as<double>(), scale.as<double>(), poff.as<int>(),   (int64_t)3 * N,         J,
@@ -86,50 +52,6 @@ struct rn_interp {
 };
 
 namespace {
-
-void set_error(rn_interp *h, const char *fmt, ...) {
-  char text[512];
-  va_list args;
-  va_start(args, fmt);
-  vsnprintf(text, sizeof text, fmt, args);
-  va_end(args);
-  if (h) {
-    std::lock_guard<std::recursive_mutex> lock(h->lock);
-    h->error = text;
-  } else {
-    g_interp_create_error = text;
-  }
-}
-
-int guarded(rn_interp *h, const std::function<void()> &fn) {
-  std::unique_lock<std::recursive_mutex> lock;
-  if (h) lock = std::unique_lock<std::recursive_mutex>(h->lock);
-  try {
-    if (h) HIP_TRY(hipSetDevice(h->device));
-    fn();
-    return RN_OK;
-  } catch (const Invalid &) {
-    return RN_ERR_INVALID_ARGUMENT;
-  } catch (const HipFail &e) {
-    set_error(h, "HIP error %d (%s) in %s", (int)e.code, hipGetErrorString(e.code), e.what);
-    return e.code == hipErrorOutOfMemory ? RN_ERR_OUT_OF_MEMORY : RN_ERR_HIP;
-  } catch (const std::bad_alloc &) {
-    set_error(h, "host allocation failed");
-    return RN_ERR_OUT_OF_MEMORY;
-  } catch (const std::exception &e) {
-    set_error(h, "internal error: %s", e.what());
-    return RN_ERR_HIP;
-  } catch (...) {
-    set_error(h, "internal error: unknown exception");
-    return RN_ERR_HIP;
-  }
-}
-
-bool all_finite(const double *v, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
 
 // The create arguments, checked on the host; the text of the first violation in `why`.
 bool check_model(int32_t N, const double *lattice, const double *ref_positions, const double *alpha_ref, int32_t J,
@@ -239,39 +161,23 @@ bool needs_symmetry(rn_interp *h, const char *entry) {
   return false;
 }
 
-// The loop both increment entries share: chunks of F steps whose Jacobian rows overlap by one frame (the last frame's
-// rows are carried into the next chunk); contract(jac, pos, f, out) launches the contraction of a chunk's f steps on st.
+// The chunk walk of both increment entries (increments.hpp: walk_chunks) with as many steps F per chunk as `limit` bytes
+// hold; contract(jac, pos, f, out) launches the contraction of a chunk's f steps on st, the caller's stream.
 template <class Contract>
 void chunked_increments(rn_interp *h, const double *d_pos, int64_t S, size_t limit, int out_channels, double *d_out,
                         hipStream_t st, Contract contract) {
   const size_t rows = (size_t)6 * 3 * h->N, grow = (size_t)6 * h->J;
   const size_t per = (rows + grow) * sizeof(double), carry = rows * sizeof(double);
-  if (limit < per + carry) throw HipFail{hipErrorOutOfMemory, "increments: one step does not fit the workspace limit"};
+  if (limit < per + carry) throw HipError{hipErrorOutOfMemory, "increments: one step does not fit the workspace limit"};
   const int64_t F = (int64_t)std::min<size_t>((limit - carry) / per, (size_t)(S - 1));
   h->g.ensure((size_t)F * grow * sizeof(double));
   h->jac.ensure((size_t)(F + 1) * rows * sizeof(double));
   double *jac = h->jac.as<double>();
   const int64_t n3 = (int64_t)3 * h->N;
-  jacobian_rows(h, d_pos, 1, F, jac, st);
-  for (int64_t t0 = 0; t0 < S - 1; t0 += F) {
-    const int64_t f = std::min<int64_t>(F, S - 1 - t0);
-    if (t0 > 0) HIP_TRY(hipMemcpyAsync(jac, jac + F * rows, rows * sizeof(double), hipMemcpyDeviceToDevice, st));
-    jacobian_rows(h, d_pos + (t0 + 1) * n3, f, F, jac + rows, st);
-    contract(jac, d_pos + t0 * n3, f, d_out + t0 * out_channels * 9);
-    HIP_TRY(hipGetLastError());
-  }
-}
-
-// labels -> h->csr (perm | gptr), uploaded only when they change; false on a bad label or an empty group.
-bool set_labels(rn_interp *h, const int32_t *labels, int G, hipStream_t st) {
-  std::vector<int32_t> csr;
-  if (!group_csr(labels, h->N, G, csr)) return false;
-  if (h->G == G && h->labels.size() == (size_t)h->N && std::equal(labels, labels + h->N, h->labels.begin())) return true;
-  HIP_TRY(hipStreamSynchronize(st));  // (an earlier call may still read the old permutation)
-  h->csr.upload(csr.data(), csr.size() * sizeof(int32_t));
-  h->labels.assign(labels, labels + h->N);
-  h->G = G;
-  return true;
+  walk_chunks(
+      S, F, (int64_t)rows, jac, st,
+      [&](int64_t first, int64_t count, double *to, double *) { jacobian_rows(h, d_pos + first * n3, count, F, to, st); },
+      [&](int64_t t0, int64_t f) { contract(jac, d_pos + t0 * n3, f, d_out + t0 * out_channels * 9); });
 }
 
 }  // namespace
@@ -286,12 +192,12 @@ int rn_interp_create(int32_t N, const double *lattice, const double *ref_positio
   std::string why;
   if (!check_model(N, lattice, ref_positions, alpha_ref, J, basis_cart, piece_offsets, breakpoints, orders, coefficients,
                    why)) {
-    set_error(nullptr, "invalid arguments to rn_interp_create: %s", why.c_str());
+    set_error<rn_interp>(nullptr, "invalid arguments to rn_interp_create: %s", why.c_str());
     return RN_ERR_INVALID_ARGUMENT;
   }
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-    set_error(nullptr, "rn_interp_create: no device %d", device);
+    set_error<rn_interp>(nullptr, "rn_interp_create: no device %d", device);
     return RN_ERR_NO_DEVICE;
   }
   rn_interp *h = nullptr;
@@ -396,20 +302,13 @@ int rn_interp_jacobian_device(rn_interp *h, const double *d_positions, int64_t S
 
 int rn_interp_group_increments_device(rn_interp *h, const double *d_positions, int64_t S, const int32_t *labels, int G,
                                       size_t workspace_limit, double *d_out, void *stream) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 2 || !d_positions || !labels || !d_out || G < 1 || G > kMaxGroups) {
-    set_error(h, "invalid arguments to group_increments_device (S < 2, G outside 1..%d or a null pointer)", kMaxGroups);
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  if (const int rc = check_group_entry(h, S, d_positions, labels, d_out, G)) return rc;
   if (!needs_symmetry(h, "group_increments_device")) return RN_ERR_INVALID_ARGUMENT;
   return guarded(h, [&]() {
     hipStream_t st = (hipStream_t)stream;
-    if (!set_labels(h, labels, G, st)) {
-      set_error(h, "group_increments_device: a label outside [0, G) or an empty group");
-      throw Invalid{};
-    }
     const int N = h->N;
-    const int *perm = h->csr.as<int>(), *gptr = perm + N;
+    h->groups.set(h, "group_increments_device", labels, N, G, &st);
+    const int *perm = h->groups.perm(), *gptr = perm + N;
     const double *sigma = h->ones.as<double>();
     chunked_increments(h, d_positions, S, workspace_limit ? workspace_limit : kDefaultWorkspace, G, d_out, st,
                        [&](const double *jac, const double *pos, int64_t f, double *out) {
@@ -422,32 +321,18 @@ int rn_interp_group_increments_device(rn_interp *h, const double *d_positions, i
 int rn_interp_mode_increments_device(rn_interp *h, const double *d_positions, int64_t S, const double *disp,
                                      const double *proj, int32_t M, int rest, size_t workspace_limit, double *d_out,
                                      void *stream) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (S < 2 || !d_positions || !disp || !proj || !d_out || M < 1 || M > kMaxModes || (rest != 0 && rest != 1)) {
-    set_error(h, "invalid arguments to mode_increments_device (S < 2, M outside 1..%d, rest not 0 or 1 or a null pointer)",
-              kMaxModes);
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  if (const int rc = check_mode_entry(h, S, d_positions, disp, proj, d_out, M, rest)) return rc;
   if (!needs_symmetry(h, "mode_increments_device")) return RN_ERR_INVALID_ARGUMENT;
-  const size_t entries = (size_t)M * h->N * 3;
-  if (!all_finite(disp, entries) || !all_finite(proj, entries)) {
-    set_error(h, "mode_increments_device: a non-finite entry in disp or proj");
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  if (const int rc = check_mode_vectors(h, disp, proj, M, h->N)) return rc;
   return guarded(h, [&]() {
     hipStream_t st = (hipStream_t)stream;
-    const size_t limit = workspace_limit ? workspace_limit : kDefaultWorkspace, bytes = entries * sizeof(double);
-    if (limit <= 2 * bytes) throw HipFail{hipErrorOutOfMemory, "mode_increments: the modes do not fit the workspace limit"};
-    HIP_TRY(hipStreamSynchronize(st));  // (an earlier call may still read the old modes)
-    h->modes.ensure(2 * bytes);
-    double *d_disp = h->modes.as<double>(), *d_proj = d_disp + entries;
-    HIP_TRY(hipMemcpy(d_disp, disp, bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_proj, proj, bytes, hipMemcpyHostToDevice));
+    const size_t limit = workspace_limit ? workspace_limit : kDefaultWorkspace;
     const int N = h->N, channels = M + rest;
+    const ModeVectors modes = upload_modes(h->modes, disp, proj, M, N, limit, st);
     const double *sigma = h->ones.as<double>();
-    chunked_increments(h, d_positions, S, limit - 2 * bytes, channels, d_out, st,
+    chunked_increments(h, d_positions, S, limit - modes.bytes, channels, d_out, st,
                        [&](const double *jac, const double *pos, int64_t f, double *out) {
-                         launch_mode_increments(jac, pos, f, N, d_disp, d_proj, M, sigma, channels, out, st);
+                         launch_mode_increments(jac, pos, f, N, modes.disp, modes.proj, M, sigma, channels, out, st);
                          if (rest) launch_mode_rest(jac, pos, f, N, M, sigma, channels, out, st);
                        });
   });
@@ -455,19 +340,13 @@ int rn_interp_mode_increments_device(rn_interp *h, const double *d_positions, in
 
 int rn_interp_partial_raman_tensors(rn_interp *h, const double *ref_positions, const double *displacements, int64_t M,
                                     const int32_t *labels, int G, double *raman) {
-  if (!h) return RN_ERR_INVALID_ARGUMENT;
-  if (M < 0 || !ref_positions || !labels || G < 1 || G > kMaxGroups || (M > 0 && (!displacements || !raman))) {
-    set_error(h, "invalid arguments to partial_raman_tensors (G outside 1..%d or a null pointer)", kMaxGroups);
-    return RN_ERR_INVALID_ARGUMENT;
-  }
+  if (const int rc = check_partial_raman_entry(h, ref_positions, displacements, M, labels, G, raman)) return rc;
   if (!needs_symmetry(h, "partial_raman_tensors")) return RN_ERR_INVALID_ARGUMENT;
   return guarded(h, [&]() {
-    if (!set_labels(h, labels, G, nullptr)) {
-      set_error(h, "partial_raman_tensors: a label outside [0, G) or an empty group");
-      throw Invalid{};
-    }
-    if (M == 0) return;
     const int N = h->N;
+    const hipStream_t null_stream = nullptr;
+    h->groups.set(h, "partial_raman_tensors", labels, N, G, &null_stream);
+    if (M == 0) return;
     const size_t n3 = (size_t)N * 3;
     HIP_TRY(hipDeviceSynchronize());  // (the staging buffers are filled from the null stream)
     h->io_pos.upload(ref_positions, n3 * sizeof(double));
@@ -477,7 +356,7 @@ int rn_interp_partial_raman_tensors(rn_interp *h, const double *ref_positions, c
     h->jac.ensure(6 * n3 * sizeof(double));
     jacobian_rows(h, h->io_pos.as<double>(), 1, 1, h->jac.as<double>(), nullptr);
     // R[m][g] = 2 sum_{i in g} J_i . d_{m,i}: the kernel's 1/2 (J + J) . (2 d)
-    const int *perm = h->csr.as<int>();
+    const int *perm = h->groups.perm();
     launch_group_increments(h->jac.as<double>(), 0, nullptr, h->disp.as<double>(), 2.0, M, N, perm, perm + N, G,
                             h->ones.as<double>(), h->io_out.as<double>(), nullptr);
     HIP_TRY(hipGetLastError());

@@ -21,6 +21,7 @@ for f in $hip_srcs; do
      [ "$here/graph_plan.hpp" -nt "$o" ] || [ "$here/weight_layout.hpp" -nt "$o" ] || \
      [ "$here/spectrum_common.hpp" -nt "$o" ] || [ "$here/spectrum_segment_core.hpp" -nt "$o" ] || \
      [ "$here/spectrum_steps.hpp" -nt "$o" ] || \
+     [ "$here/host_runtime.hpp" -nt "$o" ] || [ "$here/increments.hpp" -nt "$o" ] || \
      [ "$here/../../include/rn_potgnn.h" -nt "$o" ] || [ "$here/../../include/rn_interp.h" -nt "$o" ] || \
      [ "$here/../../include/rn_lineshape.h" -nt "$o" ] || [ "$here/../../include/rn_quasiharmonic.h" -nt "$o" ]; then
     extra=""

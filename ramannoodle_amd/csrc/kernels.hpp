@@ -346,24 +346,6 @@ void launch_interp_alpha(const double *pos, int64_t S, const InterpModel &m, dou
 // Jacobian rows jac float64 [S][6][K3] (component order of launch_group_increments) of the frames pos; g: workspace
 // of S * 6 * J doubles (the scaled spline derivatives).  Two launches on `st`, no atomics.
 void launch_interp_jacobian(const double *pos, int64_t S, const InterpModel &m, double *g, double *jac, hipStream_t st);
-// The atoms bucketed by group for launch_group_increments: csr = perm [N] (ascending atom index within a group) followed
-// by gptr [G+1].  false on a label outside [0, G) or an empty group.  Host only.
-inline bool group_csr(const int32_t *labels, int N, int G, std::vector<int32_t> &csr) {
-  std::vector<int32_t> ptr(G + 1, 0);
-  for (int i = 0; i < N; ++i) {
-    if (labels[i] < 0 || labels[i] >= G) return false;
-    ++ptr[labels[i] + 1];
-  }
-  for (int g = 0; g < G; ++g) {
-    if (ptr[g + 1] == 0) return false;
-    ptr[g + 1] += ptr[g];
-  }
-  csr.assign((size_t)N + G + 1, 0);
-  std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-  for (int i = 0; i < N; ++i) csr[fill[labels[i]]++] = i;
-  std::copy(ptr.begin(), ptr.end(), csr.begin() + N);
-  return true;
-}
 
 // Fused EdgeBlock (kernels_fused.hip): projections + triplet aggregation in one launch.
 // Fused EdgeBlock (kernels_fused.hip): float32, FnP == FeP == 64.  Two workgroups per CU

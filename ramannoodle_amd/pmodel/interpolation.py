@@ -32,6 +32,8 @@ from ramannoodle_amd import _lib
 from ramannoodle_amd.abstract import PolarizabilityModel
 from ramannoodle_amd.constants import RAMAN_TENSOR_CENTRAL_DIFFERENCE
 from ramannoodle_amd.exceptions import verify_ndarray_shape
+from ramannoodle_amd.pmodel._device import (DeviceIncrements, _ptr, device_frames, device_out, mode_arrays,
+                                            raman_arguments)
 
 MAX_ORDER = 5  # RN_INTERP_MAX_ORDER of include/rn_interp.h
 SYMMETRY_TOLERANCE = 1e-12  # asymmetry of the tables, relative to the largest coefficient
@@ -155,11 +157,7 @@ def tables_asymmetry(tables: PiecewiseTables) -> float:
     return float(np.abs(c - c.transpose(0, 2, 1)).max()) / largest if largest > 0 else 0.0
 
 
-def _ptr(array) -> C.c_void_p:
-    return C.c_void_p(array.ctypes.data)
-
-
-class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-instance-attributes
+class InterpolationModel(DeviceIncrements, PolarizabilityModel):  # pylint: disable=too-many-instance-attributes
     """A finished interpolation model on GPU ``device``.
 
     ``ref_structure``: any object with ``lattice``, ``positions``, ``atomic_numbers`` and ``num_atoms``
@@ -326,49 +324,13 @@ class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-insta
             raise ValueError(f"{what} uses the Jacobian's six components and needs symmetric tables; this model's "
                              f"asymmetry is {tables_asymmetry(self._tables):.3e} of the largest coefficient")
 
-    def _device_positions(self, positions, least: int, what: str) -> int:
-        import torch
-        if not (isinstance(positions, torch.Tensor) and positions.is_cuda and positions.dtype == torch.float64
-                and positions.is_contiguous()):
-            raise ValueError("positions must be a contiguous float64 device tensor")
-        if positions.device.index != self._device:
-            raise ValueError(f"positions live on {positions.device}, the model on cuda:{self._device}")
-        if positions.dim() != 3 or tuple(positions.shape[1:]) != (self.num_atoms, 3):
-            raise ValueError(f"positions has wrong shape: {tuple(positions.shape)} != (_,{self.num_atoms},3)")
-        if positions.shape[0] < least:
-            raise ValueError(f"{what} needs at least {least} frame(s), not {positions.shape[0]}")
-        return positions.shape[0]
-
-    @staticmethod
-    def _device_out(out, positions, shape):
-        import torch
-        if out is None:
-            return torch.empty(shape, dtype=torch.float64, device=positions.device)
-        if not isinstance(out, torch.Tensor):
-            raise ValueError(f"out must be a torch.Tensor, not {type(out).__name__}")
-        if not out.is_cuda or out.device.index != positions.device.index:
-            raise ValueError(f"out lives on {out.device}, the result is written on {positions.device}")
-        if out.dtype != torch.float64:
-            raise ValueError(f"out must be float64, not {out.dtype}")
-        if tuple(out.shape) != tuple(shape):
-            raise ValueError(f"out has shape {tuple(out.shape)}, the result is {tuple(shape)}")
-        if not out.is_contiguous():
-            raise ValueError("out must be contiguous")
-        return out
-
     @staticmethod
     def _stream(positions) -> C.c_void_p:
         import torch
         return C.c_void_p(torch.cuda.current_stream(positions.device).cuda_stream)
 
-    def _host_to_device(self, name: str, positions_ts):
-        import torch
-        verify_ndarray_shape(name, positions_ts, (None, self.num_atoms, 3))
-        return torch.tensor(np.asarray(positions_ts, dtype=np.float64), device=f"cuda:{self._device}")
-
-    def _group_labels(self, groups):
-        from ramannoodle_amd.spectrum import group_labels
-        return group_labels(groups, self._ref_structure.atomic_numbers)
+    _partial_raman_entry = "rn_interp_partial_raman_tensors"
+    _check_status = staticmethod(_lib.check_interp)
 
     # ------------------------------------------------------------------ evaluation
     def calc_polarizabilities(self, positions_batch, lattices=None) -> NDArray[np.float64]:
@@ -386,8 +348,8 @@ class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-insta
         """A contiguous CUDA float64 ``(S,N,3)`` tensor in, a CUDA float64 ``(S,3,3)`` tensor out
         (``rn_interp_forward_device``), enqueued on torch's current stream."""
         self._no_lattices(lattices)
-        s = self._device_positions(positions, 1, "the evaluation")
-        out = self._device_out(out, positions, (s, 3, 3))
+        s = device_frames(positions, self.num_atoms, 1, "the evaluation", self._device)
+        out = device_out(out, positions, (s, 3, 3))
         handle = self._ensure_handle()
         rc = _lib.load().rn_interp_forward_device(handle, C.c_void_p(positions.data_ptr()), s,
                                                   C.c_void_p(out.data_ptr()), self._stream(positions))
@@ -397,8 +359,8 @@ class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-insta
     def calc_jacobian_device(self, positions, out=None):
         """``d vec6 / d x`` of every frame: a CUDA float64 ``(S,6,N,3)`` tensor (``rn_interp_jacobian_device``)."""
         self._need_symmetric("the Jacobian")
-        s = self._device_positions(positions, 1, "the Jacobian")
-        out = self._device_out(out, positions, (s, 6, self.num_atoms, 3))
+        s = device_frames(positions, self.num_atoms, 1, "the Jacobian", self._device)
+        out = device_out(out, positions, (s, 6, self.num_atoms, 3))
         handle = self._ensure_handle()
         rc = _lib.load().rn_interp_jacobian_device(handle, C.c_void_p(positions.data_ptr()), s,
                                                    C.c_void_p(out.data_ptr()), self._stream(positions))
@@ -407,12 +369,7 @@ class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-insta
 
     # ------------------------------------------------------------------ phonons
     def _check_raman_arguments(self, ref_positions, displacements, delta, method) -> None:
-        verify_ndarray_shape("ref_positions", ref_positions, (self.num_atoms, 3))
-        verify_ndarray_shape("displacements", displacements, (None, self.num_atoms, 3))
-        if method not in ("finite-difference", "analytic"):
-            raise ValueError(f"unsupported method: {method}")
-        if method == "finite-difference" and not (np.isfinite(delta) and float(delta) != 0.0):
-            raise ValueError(f"delta must be finite and non-zero, not {delta}")
+        raman_arguments(ref_positions, displacements, delta, method, self.num_atoms)
 
     def calc_raman_tensors(self, ref_positions, displacements, delta: float = RAMAN_TENSOR_CENTRAL_DIFFERENCE,
                            method: str = "finite-difference") -> NDArray[np.float64]:
@@ -433,15 +390,7 @@ class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-insta
         (``rn_interp_partial_raman_tensors``)."""
         self._check_raman_arguments(ref_positions, displacements, 1.0, "analytic")
         self._need_symmetric("calc_partial_raman_tensors")
-        labels, num_groups = self._group_labels(groups)
-        ref = np.ascontiguousarray(ref_positions, dtype=np.float64)
-        disp = np.ascontiguousarray(displacements, dtype=np.float64)
-        out = np.empty((disp.shape[0], num_groups, 3, 3), dtype=np.float64)
-        handle = self._ensure_handle()
-        rc = _lib.load().rn_interp_partial_raman_tensors(handle, _ptr(ref), _ptr(disp), disp.shape[0], _ptr(labels),
-                                                         num_groups, _ptr(out))
-        _lib.check_interp(rc, handle, "rn_interp_partial_raman_tensors")
-        return out
+        return self._partial_raman_tensors(ref_positions, displacements, groups)
 
     # ------------------------------------------------------------------ increments along a trajectory
     def calc_group_increments_device(self, positions, groups, out=None, workspace_limit: int = 0, lattices=None):
@@ -449,9 +398,9 @@ class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-insta
         ``(S,N,3)`` in, ``(S-1,G,3,3)`` out, as ``PotGNN.calc_group_increments_device`` for a fixed cell."""
         self._no_lattices(lattices)
         self._need_symmetric("calc_group_increments_device")
-        s = self._device_positions(positions, 2, "group increments")
+        s = device_frames(positions, self.num_atoms, 2, "group increments", self._device)
         labels, num_groups = self._group_labels(groups)
-        out = self._device_out(out, positions, (s - 1, num_groups, 3, 3))
+        out = device_out(out, positions, (s - 1, num_groups, 3, 3))
         handle = self._ensure_handle()
         rc = _lib.load().rn_interp_group_increments_device(
             handle, C.c_void_p(positions.data_ptr()), s, _ptr(labels), num_groups, int(workspace_limit),
@@ -462,26 +411,7 @@ class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-insta
     def calc_group_increments(self, positions_ts, groups, lattices=None) -> NDArray[np.float64]:
         """``calc_group_increments_device`` for host arrays."""
         self._no_lattices(lattices)
-        positions = self._host_to_device("positions_ts", positions_ts)
-        return self.calc_group_increments_device(positions, groups).cpu().numpy()
-
-    def _mode_arrays(self, displacements, projectors):
-        arrays = []
-        for name, value in (("displacements", displacements), ("projectors", projectors)):
-            if value is None or isinstance(value, (str, bytes)) or not isinstance(value, (np.ndarray, list, tuple)):
-                raise ValueError(f"{name} must be a host array (M,{self.num_atoms},3)")
-            array = np.asarray(value)
-            if array.dtype.kind not in "iuf":
-                raise ValueError(f"{name} must hold real numbers, not {array.dtype}")
-            if array.ndim != 3 or array.shape[0] < 1 or tuple(array.shape[1:]) != (self.num_atoms, 3):
-                raise ValueError(f"{name} has wrong shape: {tuple(array.shape)} != (_,{self.num_atoms},3)")
-            array = np.ascontiguousarray(array, dtype=np.float64)
-            if not np.all(np.isfinite(array)):
-                raise ValueError(f"{name} has a non-finite entry")
-            arrays.append(array)
-        if arrays[0].shape != arrays[1].shape:
-            raise ValueError(f"displacements {arrays[0].shape} and projectors {arrays[1].shape} differ in shape")
-        return arrays
+        return self._increments_from_host(self.calc_group_increments_device, positions_ts, None, groups)
 
     def calc_mode_increments_device(self, positions, displacements, projectors, rest: bool = True, out=None,
                                     workspace_limit: int = 0, lattices=None):
@@ -489,9 +419,9 @@ class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-insta
         ``(S,N,3)`` in, ``(S-1,M+rest,3,3)`` out, as ``PotGNN.calc_mode_increments_device`` for a fixed cell."""
         self._no_lattices(lattices)
         self._need_symmetric("calc_mode_increments_device")
-        s = self._device_positions(positions, 2, "mode increments")
-        disp, proj = self._mode_arrays(displacements, projectors)
-        out = self._device_out(out, positions, (s - 1, disp.shape[0] + bool(rest), 3, 3))
+        s = device_frames(positions, self.num_atoms, 2, "mode increments", self._device)
+        disp, proj = mode_arrays(displacements, projectors, self.num_atoms)
+        out = device_out(out, positions, (s - 1, disp.shape[0] + bool(rest), 3, 3))
         handle = self._ensure_handle()
         rc = _lib.load().rn_interp_mode_increments_device(
             handle, C.c_void_p(positions.data_ptr()), s, _ptr(disp), _ptr(proj), disp.shape[0], int(bool(rest)),
@@ -503,5 +433,5 @@ class InterpolationModel(PolarizabilityModel):  # pylint: disable=too-many-insta
                              lattices=None) -> NDArray[np.float64]:
         """``calc_mode_increments_device`` for host arrays."""
         self._no_lattices(lattices)
-        positions = self._host_to_device("positions_ts", positions_ts)
-        return self.calc_mode_increments_device(positions, displacements, projectors, rest=rest).cpu().numpy()
+        return self._increments_from_host(self.calc_mode_increments_device, positions_ts, None, displacements,
+                                          projectors, rest=rest)

@@ -22,6 +22,8 @@ from ramannoodle_amd.abstract import PolarizabilityModel
 from ramannoodle_amd.constants import RAMAN_TENSOR_CENTRAL_DIFFERENCE
 from ramannoodle_amd.exceptions import verify_ndarray_shape
 from ramannoodle_amd.pmodel import graph as graph_utils
+from ramannoodle_amd.pmodel._device import (DeviceIncrements, _ptr, check_out as _check_out, device_frames, device_out,
+                                            mode_arrays, raman_arguments)
 
 _VEC_TO_TENSOR = np.array([[0, 3, 4], [3, 1, 5], [4, 5, 2]])  # dataset/torch/utils.py:30-37
 
@@ -52,25 +54,6 @@ def _wants_float64(dtype) -> bool:
 
 
 _REDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_void_p)
-
-
-def _ptr(array) -> C.c_void_p:
-    return C.c_void_p(array.ctypes.data)
-
-
-def _check_out(out, s: int, device_index: int) -> None:
-    """A caller's result tensor for the device entries, which write ``s * 9`` float64 values through its pointer: checked
-    before anything reaches the library (a leading slice ``out[:s]`` of a larger tensor is contiguous and passes)."""
-    if not isinstance(out, torch.Tensor):
-        raise ValueError(f"out must be a torch.Tensor, not {type(out).__name__}")
-    if not out.is_cuda or out.device.index != device_index:
-        raise ValueError(f"out lives on {out.device}, the evaluation writes on cuda:{device_index}")
-    if out.dtype != torch.float64:
-        raise ValueError(f"out must be float64, not {out.dtype}")
-    if tuple(out.shape) != (s, 3, 3):
-        raise ValueError(f"out has shape {tuple(out.shape)}, the evaluation writes ({s}, 3, 3)")
-    if not out.is_contiguous():
-        raise ValueError("out must be contiguous")
 
 
 class _Activation(torch.nn.Module):
@@ -113,7 +96,7 @@ class _EdgeBlockParams(torch.nn.Module):
         self.c3_norm_2 = torch.nn.LayerNorm(fe)
 
 
-class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-instance-attributes
+class PotGNN(torch.nn.Module, DeviceIncrements, PolarizabilityModel):  # pylint: disable=too-many-instance-attributes
     """POlarizability Tensor Graph Neural Network, device evaluation.
 
     A ``torch.nn.Module`` like the reference's (``_gnn.py:418-421``): its children are the reference's containers
@@ -985,12 +968,7 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         rank before it branches, so that all ranks raise together)."""
         if unknown:
             raise TypeError(f"calc_raman_tensors() got unexpected keyword arguments: {sorted(unknown)}")
-        verify_ndarray_shape("ref_positions", ref_positions, (self.num_atoms, 3))
-        verify_ndarray_shape("displacements", displacements, (None, self.num_atoms, 3))
-        if method not in ("finite-difference", "analytic"):
-            raise ValueError(f"unsupported method: {method}")
-        if method == "finite-difference" and not (np.isfinite(delta) and float(delta) != 0.0):
-            raise ValueError(f"delta must be finite and non-zero, not {delta}")
+        raman_arguments(ref_positions, displacements, delta, method, self.num_atoms)
 
     def alpha_jacobian(self, positions, float64: bool = True) -> NDArray[np.float64]:
         """``d vec6_k / d x_{n,c}`` of the standardised 6-vector at one structure,
@@ -1004,37 +982,8 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         return out
 
     # ------------------------------------------------------------------ atom-group decomposition
-    def _group_labels(self, groups):
-        from ramannoodle_amd.spectrum import group_labels
-        return group_labels(groups, self._ref_structure.atomic_numbers)
-
-    def _increments_frames(self, positions, what: str) -> int:
-        """The frame count of the device positions of an increments entry, after their checks."""
-        if not (isinstance(positions, torch.Tensor) and positions.is_cuda and positions.dtype == torch.float64
-                and positions.is_contiguous()):
-            raise ValueError("positions must be a contiguous float64 device tensor")
-        if positions.dim() != 3 or tuple(positions.shape[1:]) != (self.num_atoms, 3):
-            raise ValueError(f"positions has wrong shape: {tuple(positions.shape)} != (_,{self.num_atoms},3)")
-        if positions.shape[0] < 2:
-            raise ValueError(f"{what} increments need at least two frames, not {positions.shape[0]}")
-        return positions.shape[0]
-
-    @staticmethod
-    def _increments_out(out, positions: torch.Tensor, shape) -> torch.Tensor:
-        """``out`` of an increments entry after its checks, or a new tensor of ``shape`` on the positions' device."""
-        if out is None:
-            return torch.empty(shape, dtype=torch.float64, device=positions.device)
-        if not isinstance(out, torch.Tensor):
-            raise ValueError(f"out must be a torch.Tensor, not {type(out).__name__}")
-        if not out.is_cuda or out.device.index != positions.device.index:
-            raise ValueError(f"out lives on {out.device}, the increments are written on {positions.device}")
-        if out.dtype != torch.float64:
-            raise ValueError(f"out must be float64, not {out.dtype}")
-        if tuple(out.shape) != shape:
-            raise ValueError(f"out has shape {tuple(out.shape)}, the increments are {shape}")
-        if not out.is_contiguous():
-            raise ValueError("out must be contiguous")
-        return out
+    _partial_raman_entry = "rn_potgnn_partial_raman_tensors"  # (what DeviceIncrements asks of a model)
+    _check_status = staticmethod(_lib.check)
 
     def calc_group_increments_device(self, positions: torch.Tensor, groups, float64: bool = True,
                                      out: torch.Tensor | None = None, workspace_limit: int = 0,
@@ -1055,7 +1004,8 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         polarizability because the cell deforms at fixed fractional positions.  The sum over all ``G+1`` channels is
         ``alpha(t+1) - alpha(t)`` up to the trapezoid error; without the cell channel it is not.  The cell counts as a
         group: more than 15 atom groups together with lattices raise ``ValueError``."""
-        s = self._increments_frames(positions, "group")
+        # (no device_index: the positions' device is not compared with the model's, here and for the modes)
+        s = device_frames(positions, self.num_atoms, 2, "group increments")
         labels, num_groups = self._group_labels(groups)
         if lattices is not None:
             lattices = self._check_device_lattices(lattices, positions)
@@ -1063,7 +1013,7 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
             if num_groups + 1 > MAX_GROUPS:
                 raise ValueError(f"{num_groups} atom groups and the cell are more than {MAX_GROUPS} channels: with lattices "
                                  f"at most {MAX_GROUPS - 1} atom groups")
-        out = self._increments_out(out, positions, (s - 1, num_groups + (lattices is not None), 3, 3))
+        out = device_out(out, positions, (s - 1, num_groups + (lattices is not None), 3, 3))
         self.eval()
         handle = self._ensure_handle()
         stream = torch.cuda.current_stream(positions.device).cuda_stream
@@ -1083,50 +1033,18 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         """``calc_group_increments_device`` for host arrays: fractional positions ``(S,N,3)`` in, float64
         ``(S-1,G,3,3)`` out.  ``lattices``: host ``(S,3,3)``, one lattice per frame; the result is then
         ``(S-1,G+1,3,3)`` and the last group is the cell.  Non-finite or singular lattices raise ``ValueError``."""
-        verify_ndarray_shape("positions_ts", positions_ts, (None, self.num_atoms, 3))
-        device = f"cuda:{self.device_index}"
-        if lattices is not None:
-            from ramannoodle_amd.dynamics import verify_lattices
-            lattices = torch.tensor(verify_lattices(lattices, len(positions_ts)), device=device)
-        positions = torch.tensor(np.asarray(positions_ts, dtype=np.float64), device=device)
-        return self.calc_group_increments_device(positions, groups, float64=float64, lattices=lattices).cpu().numpy()
+        return self._increments_from_host(self.calc_group_increments_device, positions_ts, lattices, groups,
+                                          float64=float64)
 
     def calc_partial_raman_tensors(self, ref_positions, displacements, groups) -> NDArray[np.float64]:
         """Raman tensors split by atom group, ``(M,G,3,3)``: ``R[m,g] = 2 sum_{i in g} J_i(ref) . d_{m,i}``
         (``rn_potgnn_partial_raman_tensors``: one float64 Jacobian, then the device contraction), so that
         ``sum_g R[m,g]`` is ``calc_raman_tensors(method="analytic")``."""
         self._check_raman_arguments(ref_positions, displacements, method="analytic")
-        labels, num_groups = self._group_labels(groups)
-        ref = np.ascontiguousarray(ref_positions, dtype=np.float64)
-        disp = np.ascontiguousarray(displacements, dtype=np.float64)
-        out = np.empty((disp.shape[0], num_groups, 3, 3), dtype=np.float64)
         self.eval()
-        handle = self._ensure_handle()
-        rc = _lib.load().rn_potgnn_partial_raman_tensors(handle, _ptr(ref), _ptr(disp), disp.shape[0], _ptr(labels),
-                                                         num_groups, _ptr(out))
-        _lib.check(rc, handle, "rn_potgnn_partial_raman_tensors")
-        return out
+        return self._partial_raman_tensors(ref_positions, displacements, groups)
 
     # ------------------------------------------------------------------ phonon-mode decomposition
-    def _mode_arrays(self, displacements, projectors):
-        """``displacements`` and ``projectors`` ``(M,N,3)``, finite, as contiguous float64 (``spectrum.mode_projectors``)."""
-        arrays = []
-        for name, value in (("displacements", displacements), ("projectors", projectors)):
-            if value is None or isinstance(value, (str, bytes, torch.Tensor)):
-                raise ValueError(f"{name} must be a host array (M,{self.num_atoms},3)")
-            array = np.asarray(value)
-            if array.dtype.kind not in "iuf":
-                raise ValueError(f"{name} must hold real numbers, not {array.dtype}")
-            if array.ndim != 3 or array.shape[0] < 1 or tuple(array.shape[1:]) != (self.num_atoms, 3):
-                raise ValueError(f"{name} has wrong shape: {tuple(array.shape)} != (_,{self.num_atoms},3)")
-            array = np.ascontiguousarray(array, dtype=np.float64)
-            if not np.all(np.isfinite(array)):
-                raise ValueError(f"{name} has a non-finite entry")
-            arrays.append(array)
-        if arrays[0].shape != arrays[1].shape:
-            raise ValueError(f"displacements {arrays[0].shape} and projectors {arrays[1].shape} differ in shape")
-        return arrays
-
     def calc_mode_increments_device(self, positions: torch.Tensor, displacements, projectors, rest: bool = True,
                                     float64: bool = True, out: torch.Tensor | None = None, workspace_limit: int = 0,
                                     lattices=None) -> torch.Tensor:
@@ -1140,12 +1058,12 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
         otherwise); ``lattices`` (as for ``calc_group_increments_device``) adds the cell channel, the last.  The
         channels, ``[modes..., rest?, cell?]``, sum to what the atom groups sum to.  Ordered on torch's current stream;
         ``out`` as for ``calc_group_increments_device``."""
-        s = self._increments_frames(positions, "mode")
-        disp, proj = self._mode_arrays(displacements, projectors)
+        s = device_frames(positions, self.num_atoms, 2, "mode increments")
+        disp, proj = mode_arrays(displacements, projectors, self.num_atoms)
         if lattices is not None:
             lattices = self._check_device_lattices(lattices, positions)
         channels = disp.shape[0] + bool(rest) + (lattices is not None)
-        out = self._increments_out(out, positions, (s - 1, channels, 3, 3))
+        out = device_out(out, positions, (s - 1, channels, 3, 3))
         self.eval()
         handle = self._ensure_handle()
         stream = torch.cuda.current_stream(positions.device).cuda_stream
@@ -1160,14 +1078,8 @@ class PotGNN(torch.nn.Module, PolarizabilityModel):  # pylint: disable=too-many-
                              lattices=None) -> NDArray[np.float64]:
         """``calc_mode_increments_device`` for host arrays: fractional positions ``(S,N,3)`` in, float64
         ``(S-1,C,3,3)`` out; ``lattices``: host ``(S,3,3)`` (non-finite or singular lattices raise ``ValueError``)."""
-        verify_ndarray_shape("positions_ts", positions_ts, (None, self.num_atoms, 3))
-        device = f"cuda:{self.device_index}"
-        if lattices is not None:
-            from ramannoodle_amd.dynamics import verify_lattices
-            lattices = torch.tensor(verify_lattices(lattices, len(positions_ts)), device=device)
-        positions = torch.tensor(np.asarray(positions_ts, dtype=np.float64), device=device)
-        return self.calc_mode_increments_device(positions, displacements, projectors, rest=rest, float64=float64,
-                                                lattices=lattices).cpu().numpy()
+        return self._increments_from_host(self.calc_mode_increments_device, positions_ts, lattices, displacements,
+                                          projectors, rest=rest, float64=float64)
 
     # ------------------------------------------------------------------ introspection
     @property
