@@ -944,7 +944,9 @@ int rn_potgnn_debug_triplets(rn_potgnn *h, int32_t *idx_i, int32_t *idx_j,
  * `index` (0 = initial) [S_c*N,Fn], 2 = edge embedding after pass `index` [S_c*E,Fe]
  * (only the most recent pass and pass 0... see DESIGN.md: intermediates are kept only
  * when the handle was created with RN_POTGNN_KEEP_STAGES=1 in the environment),
- * 3 = readout embedding [S_c*E,12].  Returns rows written via *rows.
+ * 3 = readout embedding [S_c*E,12], 4 = the snapshot stage 2 reads exactly as it lies in memory, padded columns included
+ * [S_c*E,FeP] 32-bit words (rows in the kernels' own order; where the rows are split-f16 pairs, bit 10 of
+ * rn_potgnn_config_flags, the words hold per eight columns 8 x f16 hi | 8 x f16 lo).  Returns rows written via *rows.
  * RN_POTGNN_KEEP_STAGES=1 puts the run on float32 edge rows and the readout on the layout stage 3 reads.
  * RN_POTGNN_KEEP_STAGES=2 keeps stages 1 and 2 only and leaves the run on the kernels it would take without
  * snapshots (frames are not spread over two lanes, nothing else changes): where its edge rows are split-f16

@@ -2917,6 +2917,10 @@ int rn_potgnn_debug_stage(rn_potgnn *h, int stage, int index, float *out, size_t
       else { src = P.snap_edge[index].as<float>(); r = ME; c = h->d.Fe; ld = h->d.FeP; }
     } else if (stage == 3) {
       src = P.lanes[0].bufA.as<float>(); r = ME; c = 12; ld = 32;
+    } else if (stage == 4) {  // stage 2's snapshot as it lies in memory: padded columns included, pair rows not decoded
+      if ((!h->keep_stages && !h->snap_pairs) || index < 0 || index > h->cfg.num_message_passes)
+        throw HipError{hipErrorInvalidValue, "stage snapshots need RN_POTGNN_KEEP_STAGES=1 or 2"};
+      src = P.snap_edge[index].as<float>(); r = ME; c = h->d.FeP; ld = h->d.FeP;
     } else {
       throw HipError{hipErrorInvalidValue, "unknown stage"};
     }
@@ -2935,7 +2939,7 @@ int rn_potgnn_debug_stage(rn_potgnn *h, int stage, int index, float *out, size_t
     }
     HIP_TRY(hipMemcpy2D(out, c * sizeof(float), src, ld * sizeof(float), c * sizeof(float), r,
                         hipMemcpyDeviceToHost));
-    if (h->last_in_order && r == ME && stage != 1) {  // per-edge rows of a narrow run: back to edge-id order
+    if (h->last_in_order && r == ME && stage != 1 && stage != 4) {  // per-edge rows of a narrow run: back to edge-id order
       std::vector<float> tmp(out, out + r * c);
       const int E = h->g.E;
       for (int64_t s = 0; s < S; ++s)

@@ -175,6 +175,12 @@ __global__ __launch_bounds__(256) void geom_rbf_pairs_kernel(const PT *__restric
   const int64_t total = (int64_t)S * g.E;
   const int64_t r0 = (int64_t)blockIdx.x * 256;
   const int64_t row = r0 + threadIdx.x;
+  // This lane's eight Gaussian centres, read once: its column group m is the same in every step of the second phase (read
+  // at their use, the compiler left eight dependent loads, each behind a full wait that covers the stores too, in every step)
+  const int lane = threadIdx.x & 63, m = lane & 7;
+  float mu[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) mu[j] = offs[8 * m + j];
   float dist = 0;
   if (row < total) {
     const int s = (int)(row / g.E), e = (int)(row % g.E);
@@ -182,12 +188,19 @@ __global__ __launch_bounds__(256) void geom_rbf_pairs_kernel(const PT *__restric
     const float *lat = lat_base + (int64_t)s * lat_stride;
     const PT *pa = pos + ((int64_t)s * g.N + a) * 3;
     const PT *pb = pos + ((int64_t)s * g.N + b) * 3;
+    // (all fifteen loads requested before the first wrap: fmod is a loop, and behind it each coordinate's pair of loads
+    //  and then the lattice's would wait out a memory latency of their own)
+    float xa[3], xb[3], lt[9];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) xa[k] = (float)pa[k], xb[k] = (float)pb[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) lt[k] = lat[k];
     float f[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) f[k] = wrap_min_image((float)pb[k] - (float)pa[k]);
+    for (int k = 0; k < 3; ++k) f[k] = wrap_min_image(xb[k] - xa[k]);
     float c[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) c[k] = f[0] * lat[k] + f[1] * lat[3 + k] + f[2] * lat[6 + k];
+    for (int k = 0; k < 3; ++k) c[k] = f[0] * lt[k] + f[1] * lt[3 + k] + f[2] * lt[6 + k];
     dist = sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
     float *u = unit4 + row * 4;
     u[0] = c[0] / dist;
@@ -198,14 +211,14 @@ __global__ __launch_bounds__(256) void geom_rbf_pairs_kernel(const PT *__restric
   sdist[threadIdx.x] = dist;
   __syncthreads();
   for (int i = threadIdx.x; i < 256 * 8; i += 256) {  // (row, group m of eight columns)
-    const int r = i >> 3, m = i & 7;
+    const int r = i >> 3;
     if (r0 + r >= total) break;
     const float dd = sdist[r];
     h8 hi, lo;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int col = 8 * m + j;
-      const float x = dd - offs[col];
+      const float x = dd - mu[j];
       // (hardware exp2: 1 ulp, and the value is rounded to hi + lo = 2^-25 absolute right below anyway)
       const float v = (col < d.Fe) ? __builtin_amdgcn_exp2f((coef * 1.4426950408889634f) * (x * x)) : 0.0f;
       hi[j] = (_Float16)v;

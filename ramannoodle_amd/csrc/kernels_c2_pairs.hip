@@ -138,8 +138,10 @@ __global__ __launch_bounds__(C2P_THREADS, 2) void c2_pairs_kernel(C2PairArgs a) 
           qq = fmaf(gv[p][t][i], gv[p][t][i], qq);
         }
     const float rstd = fast_rsq(sum_xor32(sum_xor16(qq)) * invn + 1e-5f);
-    const int64_t row = tile * 16 + l15;
-    if (row < a.M) {
+    // A row beyond the last was fetched as the last row again and is stored as such, the same bits to the same place: behind
+    // a conditional store the wait for the next tile's rows, requested before these stores, has to wait for the stores too
+    const int64_t row = tile * 16 + l15 < a.M ? tile * 16 + l15 : a.M - 1;
+    {
 #pragma unroll
       for (int p = 0; p < 2; ++p)
 #pragma unroll

@@ -382,6 +382,11 @@ __global__ __launch_bounds__(256, 2) void rowgemm_split_kernel(GemmArgs a) {
   // A tile of 16 rows as MFMA-ready fragments: [buffer][kb][slice s][hi | lo][row * 4 + quad] x 16 bytes
   __shared__ __attribute__((aligned(16))) gf16x8 atile[2][KB][2][2][64];
   __shared__ float s_inv[2][16];
+  // The evaluation path's node projections (K = 64, 128 columns per workgroup, Y = ...): the 16 x 128 output tile crosses
+  // LDS, so that a store instruction writes two whole 512-byte row segments instead of 16 rows x 64 bytes of the accumulator
+  // layout (rows padded by 16 bytes: the accumulator-shaped writes then spread over all banks).
+  constexpr bool ROWOUT = KB == 1 && NTW == 2 && AMODE == 0;
+  __shared__ __attribute__((aligned(16))) float otile[ROWOUT ? 16 : 1][132];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, quad = lane >> 4;
   const int col0 = blockIdx.y * (64 * NTW) + wave * (16 * NTW);
@@ -464,6 +469,12 @@ __global__ __launch_bounds__(256, 2) void rowgemm_split_kernel(GemmArgs a) {
       *dl = lo;
     }
   };
+  // the bias of this lane's columns, read once: a load inside the loop is issued behind the next tile's rows, and waiting
+  // for it waits for them too
+  float4 bias[NTW];
+#pragma unroll
+  for (int t = 0; t < NTW; ++t)
+    bias[t] = a.shift ? *reinterpret_cast<const float4 *>(a.shift + col0 + 16 * t + 4 * quad) : make_float4(0.f, 0.f, 0.f, 0.f);
   if ((int64_t)blockIdx.x < ntiles) fetch(blockIdx.x);
   int b = 0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, b ^= 1) {
@@ -494,14 +505,35 @@ __global__ __launch_bounds__(256, 2) void rowgemm_split_kernel(GemmArgs a) {
         tot[t] += acc * scale;
       }
     }
-    if (live) {
+    bool stored = false;
+    if constexpr (ROWOUT) if (!a.accum) {
+      stored = true;
+#pragma unroll
+      for (int t = 0; t < NTW; ++t) {
+        const int c = wave * (16 * NTW) + 16 * t + 4 * quad;
+        float4 v = make_float4(tot[t][0], tot[t][1], tot[t][2], tot[t][3]);
+        if (a.shift) {
+          v.x += bias[t].x; v.y += bias[t].y; v.z += bias[t].z; v.w += bias[t].w;
+        }
+        *reinterpret_cast<float4 *>(&otile[l15][c]) = v;
+      }
+      __syncthreads();  // (read here before the next tile's barrier, written again only behind it)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {  // wave w: rows 4w .. 4w+3 whole, 32 lanes x 16 bytes each
+        const int rowl = 4 * wave + 2 * i + (lane >> 5), c = 4 * (lane & 31);
+        const int64_t orow = tile * 16 + rowl;
+        if (orow < a.M)
+          *reinterpret_cast<float4 *>(a.Y + orow * a.NOUT + blockIdx.y * (64 * NTW) + c) =
+              *reinterpret_cast<const float4 *>(&otile[rowl][c]);
+      }
+    }
+    if (live && !stored) {
 #pragma unroll
       for (int t = 0; t < NTW; ++t) {
         const int col = col0 + 16 * t + 4 * quad;
         float4 v = make_float4(tot[t][0], tot[t][1], tot[t][2], tot[t][3]);
         if (a.shift) {
-          const float4 bb = *reinterpret_cast<const float4 *>(a.shift + col);
-          v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
+          v.x += bias[t].x; v.y += bias[t].y; v.z += bias[t].z; v.w += bias[t].w;
         }
         if (a.accum) {
           v.x += old[t].x; v.y += old[t].y; v.z += old[t].z; v.w += old[t].w;
