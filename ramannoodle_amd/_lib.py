@@ -206,6 +206,16 @@ QH_SIGNATURES = {
     "rn_qh_last_error": (C.c_char_p, []),
 }
 
+# include/rn_harmonic.h (the harmonic trajectories of ramannoodle_amd/harmonic.py; a table of its own as well)
+HT_SIGNATURES = {
+    "rn_ht_synthesize": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P]),
+    "rn_ht_synthesize_device": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                          C.c_int64, _P, _P]),
+    "rn_ht_set_profiling": (C.c_int, [C.c_int]),
+    "rn_ht_phase_times": (C.c_int, [_P]),
+    "rn_ht_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 
 
@@ -228,7 +238,8 @@ def load() -> C.CDLL:
     except OSError as exc:
         raise DeviceError(f"cannot load {_LIB_PATH}: {exc}") from exc
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items())
-                                      + list(LINESHAPE_SIGNATURES.items()) + list(QH_SIGNATURES.items())):
+                                      + list(LINESHAPE_SIGNATURES.items()) + list(QH_SIGNATURES.items())
+                                      + list(HT_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes

@@ -330,6 +330,14 @@ void launch_covariance_chunks(const double *pos, int64_t K, const double *anchor
 void launch_covariance_reduce(const double *ws, const double *first_ws, int64_t K, const int64_t *block_chunks, int64_t B,
                               double *first, double *second, hipStream_t st);
 
+// Harmonic trajectories (kernels_harmonic.hip; include/rn_harmonic.h states them): ref float64 [K], D float64 [M][K],
+// omega_dt float64 [M], amp / phase float64 [R][M] -> out float64 [R][T][K], frame t of a call being the absolute frame
+// t0 + t.  All device pointers; harmonic_workgroups is the grid of the launch, -1 when it exceeds 2^31 - 1 workgroups.
+int64_t harmonic_workgroups(int64_t K, int64_t R, int64_t T);
+void launch_harmonic_synthesis(const double *ref, const double *D, const double *omega_dt, const double *amp,
+                               const double *phase, int64_t K, int M, int64_t R, int64_t T, int64_t t0, double *out,
+                               hipStream_t st);
+
 // The interpolation model on the device (kernels_interp.hip; api_interp.hip owns the arrays).  Everything float64:
 // F [J][K3] the basis with the lattice folded in and FT [K3][J] its transpose, ref [K3] the reference positions,
 // alpha_ref [9], poff [J+1] the piece offsets, xs the breakpoints (DOF j's P_j + 1 values start at poff[j] + j),
