@@ -630,6 +630,49 @@ int rn_md_raman_segments_at_device(const double *d_alpha, int64_t S, int64_t seg
                                    void *stream);
 
 /*
+ * Replicate spectra of rn_md_raman_segments_at's segment mean, for error bars: R linear combinations of the Q segments'
+ * spectra, formed on the power spectra before the back half, which is linear, exactly as average = 1 forms the mean.
+ * alpha, S, segment_steps = W (n = W - 1), starts, Q, taper, weights, K and num_bins as for rn_md_raman_segments_at;
+ * replicate_weights: host float64[R][Q], R >= 1, any finite values (zero and negative ones included), applied as given
+ * with no normalisation: a bootstrap draw of blocks of segments, a delete-one-block jackknife mean, a block mean.
+ *   intensities[r][k] = back half of  sum_q replicate_weights[r][q] P_qk(f),   P_qk the contracted power spectrum of
+ *                       segment q and configuration k (row (q, k) of average = 0 is the back half of P_qk alone)
+ * host float64[R][K][num_bins]; it equals replicate_weights @ (the rows of average = 0) up to rounding, at 6 Q forward
+ * FFTs and 2 R K more instead of Q (6 + 2 K), and only the R K rows are copied.  A row of 1/Q is the mean of average = 1
+ * up to rounding; a row of zeros gives rows that are exactly zero.  The sum over q is a float64 matrix product on the
+ * matrix pipe whose right operand (the 21 pair powers of each segment at each frequency) is generated in registers
+ * (csrc/spectrum_replicates.hip).  Every (r, k, f) is summed by one lane, segments in table order, without atomics:
+ * repeated calls with the same arguments are bit-identical.  Blocks of segments are multiples of four, so the products
+ * group the same segments whatever the block size, but each block's sum is contracted with the weights before it is
+ * added to the stored partial result: calls whose workspace_limit gives a different number of segment blocks agree to
+ * rounding error, not bit for bit.  Checks, before any device work: a null pointer, K < 1, R < 1, segment_steps < 3 or
+ * > S, Q < 1, a wrong num_bins, a start out of range, a replicate weight that is not finite (RN_ERR_INVALID_ARGUMENT
+ * each); then hipFFT (RN_ERR_UNSUPPORTED) and the device (RN_ERR_NO_DEVICE).  workspace_limit (bytes, 0 = 4 GiB) bounds
+ * the device memory besides the staged copy of alpha: the taper, the weights, the table, the replicate weights
+ * (8 R Q bytes, R and Q rounded up to multiples of 16 and 4), the segments' series and the accumulator rows with their
+ * bins.  The segments go through in blocks of a multiple of four, the rows in blocks of whole 16-replicate tiles with
+ * all K configurations or, when those do not fit, one tile with some of the configurations; a limit that four
+ * segments (or all Q) and one row of each replicate of a tile do not fit in returns RN_ERR_OUT_OF_MEMORY.  Plans and
+ * work buffers are cached in a cache of their own.  Work runs on the null stream; the call returns when the intensities
+ * are on the host.
+ */
+int rn_md_raman_segment_replicates(const double *alpha, int64_t S, int64_t segment_steps, const int64_t *starts,
+                                   int64_t Q, const double *taper, const double *weights, int64_t K,
+                                   const double *replicate_weights, int64_t R, int device, size_t workspace_limit,
+                                   double *intensities, int64_t num_bins);
+/* The same for a time series already in HBM (d_alpha: device float64[S][3][3], produced on `stream`): the call
+ * synchronises `stream` before it reads d_alpha; starts, taper, weights and replicate_weights stay host arrays. */
+int rn_md_raman_segment_replicates_device(const double *d_alpha, int64_t S, int64_t segment_steps,
+                                          const int64_t *starts, int64_t Q, const double *taper, const double *weights,
+                                          int64_t K, const double *replicate_weights, int64_t R, int device,
+                                          size_t workspace_limit, double *intensities, int64_t num_bins, void *stream);
+/* Device time of the phases of the most recent rn_md_raman_segment_replicates(_device) call (HIP events on the null
+ * stream): millis[4] = segment builder, forward FFTs, product kernel, back half with its copies to the host.  Measured
+ * only while enabled with rn_md_raman_segment_replicates_set_profiling(1). */
+int rn_md_raman_segment_replicates_set_profiling(int enabled);
+int rn_md_raman_segment_replicates_phase_times(double *millis);
+
+/*
  * Segment-averaged (Welch) and time-resolved partial (atom-group) MD Raman spectra: rn_md_raman_partial per segment of a
  * start table.  increments: host float64[N][G][9], 1 <= G <= 16; increment t belongs to the step from frame t to frame
  * t + 1 of the N + 1 frames, so frame indices mean what they mean in rn_md_raman_segments_at: a segment of

@@ -124,6 +124,12 @@ SIGNATURES = {
                                           C.c_size_t, _P, C.c_int64]),
     "rn_md_raman_segments_at_device": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int,
                                                  C.c_int, C.c_size_t, _P, C.c_int64, _P]),
+    "rn_md_raman_segment_replicates": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P,
+                                                 C.c_int64, C.c_int, C.c_size_t, _P, C.c_int64]),
+    "rn_md_raman_segment_replicates_device": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P,
+                                                        C.c_int64, C.c_int, C.c_size_t, _P, C.c_int64, _P]),
+    "rn_md_raman_segment_replicates_set_profiling": (C.c_int, [C.c_int]),
+    "rn_md_raman_segment_replicates_phase_times": (C.c_int, [_P]),
     "rn_md_raman_partial_segments": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64,
                                                C.c_int, C.c_int, C.c_size_t, _P, C.c_int64]),
     "rn_md_raman_partial_segments_device": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64, _P, _P,

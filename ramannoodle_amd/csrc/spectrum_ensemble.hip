@@ -34,26 +34,6 @@ using rn::kMaxGroups;
 
 constexpr int kPairTile = 8;  // rows per thread of the atom-group power kernels (blockIdx.y)
 
-// build_segments_kernel of spectrum_segments.hip with the segment's first step read from starts[q0 + b]
-__global__ void build_segments_at_kernel(const double *__restrict__ alpha, const double *__restrict__ tau, int64_t n,
-                                         int64_t L, const int64_t *__restrict__ starts, int64_t q0, int count,
-                                         hipfftDoubleComplex *__restrict__ x) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int b = blockIdx.y;
-  if (t >= L) return;
-  double s[kComponents] = {0, 0, 0, 0, 0, 0};
-  if (t < n && b < count) {
-    const double *a0 = alpha + (starts[q0 + b] + t) * 9, *a1 = a0 + 9;
-    const double w = tau[t];
-    double d[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) d[i] = w * (a1[i] - a0[i]);
-    symmetric_components(d, s);
-  }
-#pragma unroll
-  for (int c = 0; c < kComponents; ++c) x[((int64_t)b * kComponents + c) * L + t] = make_double2(s[c], 0.0);
-}
-
 // segment b of the block, group g = blockIdx.z: x[b][g][c][t] = tau[t] * component c of the symmetric part of
 // incr[starts[q0+b] + t][g] for t < n; zero for n <= t < L and for b >= count
 __global__ void build_group_segments_kernel(const double *__restrict__ incr, const double *__restrict__ tau, int64_t n,

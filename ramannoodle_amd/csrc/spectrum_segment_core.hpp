@@ -5,9 +5,10 @@
 // check, the upload helper and the phase timer): the two power kernels of the whole spectra, the plans and work buffers of one (device, n, series per segment, segments per block, rows per block), the workspace arithmetic
 // that chooses the two block sizes, the loop that fits plans of those sizes into a workspace limit (get_segment_plans,
 // for any block chooser), and the pipeline from the transformed segments to the host rows; for the start-table reducers
-// also the check of the table, the upload helper and the phase timer.  A reducer brings its segment builder (and, but
-// for the whole spectra, its own power kernels) and its own PlanCache, so the caches stay apart.  What only the two
-// reducers that read positions share is in spectrum_steps.hpp.
+// also the check of the table, the upload helper and the phase timer, and the table builder of the whole spectra, which
+// spectrum_replicates.hip (replicate combinations of the segments' spectra) takes with the plans and the back half.
+// A reducer brings its segment builder (and, but for the whole spectra, its own power kernels) and its own PlanCache,
+// so the caches stay apart.  What only the two reducers that read positions share is in spectrum_steps.hpp.
 //
 // A segment is `series` zero-padded real series of length L (6 components; 6 G for G atom groups) and yields `rows` rows
 // (K configurations; K G(G+1)/2 for the atom-group form).  Per block of B segments:
@@ -110,6 +111,27 @@ static __global__ void __launch_bounds__(kPowerThreads)
 #pragma unroll
   for (int i = 0; i < kRowTile; ++i)
     if (i0 + i < slots) pbar[(int64_t)(i0 + i) * L + f] = make_double2(acc[i], 0.0);
+}
+
+// The builder of the whole spectra from a start table (spectrum_ensemble.hip, spectrum_replicates.hip):
+// build_segments_kernel of spectrum_segments.hip with the segment's first step read from starts[q0 + b]
+static __global__ void build_segments_at_kernel(const double *__restrict__ alpha, const double *__restrict__ tau,
+                                                int64_t n, int64_t L, const int64_t *__restrict__ starts, int64_t q0,
+                                                int count, hipfftDoubleComplex *__restrict__ x) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y;
+  if (t >= L) return;
+  double s[kComponents] = {0, 0, 0, 0, 0, 0};
+  if (t < n && b < count) {
+    const double *a0 = alpha + (starts[q0 + b] + t) * 9, *a1 = a0 + 9;
+    const double w = tau[t];
+    double d[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) d[i] = w * (a1[i] - a0[i]);
+    symmetric_components(d, s);
+  }
+#pragma unroll
+  for (int c = 0; c < kComponents; ++c) x[((int64_t)b * kComponents + c) * L + t] = make_double2(s[c], 0.0);
 }
 
 constexpr int kFormSize = kComponents * kComponents;

@@ -338,3 +338,63 @@ def fit_lorentzians(wavenumbers, rows, windows, device=None, max_iterations: int
                                      C.c_void_p(iterations.ctypes.data), *tail)
     _check_lineshape(rc, entry)
     return _results(w, spacing, first, leading, out, status, iterations)
+
+
+# ----------------------------------------------------------------------------- error bars from replicate spectra
+@dataclass(frozen=True)
+class LorentzianErrors:
+    """The error bars of ``replicate_errors``, each array of the fits' shape without the replicate axis: the standard
+    errors of ``position`` and ``hwhm`` (cm^-1), ``lifetime_ps`` and ``area``, and ``used``, the number of replicates
+    whose fit converged and went into them (fewer than two: NaN)."""
+
+    position_error: NDArray[np.float64]
+    hwhm_error: NDArray[np.float64]
+    lifetime_ps_error: NDArray[np.float64]
+    area_error: NDArray[np.float64]
+    used: NDArray[np.int64]
+
+
+REPLICATE_METHODS = ("bootstrap", "jackknife", "blocks")
+
+
+def check_replicate_method(method) -> None:
+    if method not in REPLICATE_METHODS:
+        raise ValueError(f"unknown method: {method!r} (one of {', '.join(REPLICATE_METHODS)})")
+
+
+def replicate_standard_error(replicates, method, valid=None, blocks_count=None):
+    """The standard error over the replicate axis (the first) of ``replicates`` ``(R, ...)``.  ``"bootstrap"``:
+    ``std(ddof=1)``; ``"jackknife"``: ``sqrt((G - 1) / G sum_r (rep_r - mean_r rep)^2)``; ``"blocks"``:
+    ``std(ddof=1) / sqrt(G)``.  ``valid`` (bool, the shape of ``replicates``) leaves replicates out, entry by entry;
+    ``G`` is ``blocks_count``, or the number of replicates used.  Fewer than two used: NaN.  Returns ``(error, used)``."""
+    check_replicate_method(method)
+    values = np.asarray(replicates, dtype=np.float64)
+    valid = np.ones(values.shape, dtype=bool) if valid is None else np.asarray(valid, dtype=bool)
+    used = valid.sum(axis=0)
+    with np.errstate(all="ignore"):
+        mean = np.where(valid, values, 0.0).sum(axis=0) / used
+        squares = np.where(valid, (values - mean) ** 2, 0.0).sum(axis=0)
+        groups = used if blocks_count is None else blocks_count
+        if method == "jackknife":
+            error = np.sqrt((groups - 1) / groups * squares)
+        else:
+            error = np.sqrt(squares / (used - 1))
+            if method == "blocks":
+                error = error / np.sqrt(groups)
+    return np.where(used >= 2, error, np.nan), used
+
+
+def replicate_errors(fits: LorentzianFits, method: str, blocks_count=None) -> LorentzianErrors:
+    """Error bars of fitted peaks from the fits of replicate spectra: ``fits`` is
+    ``fit_lorentzians(w, rows[R, ...], windows)`` on the rows of ``replicates.measure_segment_replicates`` (replicates along the
+    first axis), ``method`` the one that made the replicates.  Each error is
+    ``replicate_standard_error`` over the replicate axis: ``"bootstrap"`` ``std(ddof=1)``, ``"jackknife"``
+    ``sqrt((G - 1) / G sum_r (x_r - mean x)^2)``, ``"blocks"`` ``std(ddof=1) / sqrt(G)``.  Replicates whose status is
+    not 0 are left out, window by window; ``G`` is ``blocks_count`` or, by default, the number of replicates used."""
+    status = np.asarray(fits.status)
+    if status.ndim < 1:
+        raise ValueError("fits has no replicate axis")
+    valid = status == STATUS_CONVERGED
+    errors = [replicate_standard_error(values, method, valid, blocks_count)[0]
+              for values in (fits.position, fits.hwhm, fits.lifetime_ps, fits.area)]
+    return LorentzianErrors(*errors, used=valid.sum(axis=0).astype(np.int64))
