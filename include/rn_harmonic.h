@@ -31,6 +31,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+#pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden: this is what it exports */
 
 /* ref host float64 [3N]; D host float64 [M][3N]; omega_dt host float64 [M]; amp, phase host float64 [R][M]; out host
  * float64 [R][T][3N].  Returns when out is filled. */
@@ -50,6 +51,7 @@ int rn_ht_set_profiling(int enabled);
 int rn_ht_phase_times(double *millis);
 const char *rn_ht_last_error(void);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

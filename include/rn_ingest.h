@@ -35,6 +35,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+#pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden: this is what it exports */
 
 typedef struct rn_xdatcar rn_xdatcar; /* opaque */
 
@@ -142,6 +143,7 @@ int rn_vasprun_initial_structure(rn_vasprun *h, int32_t *num_atoms, double *latt
 
 const char *rn_vasprun_last_error(const rn_vasprun *h);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+#pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden: this is what it exports */
 
 typedef struct rn_interp rn_interp;
 
@@ -70,6 +71,7 @@ int rn_interp_mode_increments_device(rn_interp *h, const double *d_positions, in
 int rn_interp_partial_raman_tensors(rn_interp *h, const double *ref_positions, const double *displacements, int64_t M,
                                     const int32_t *labels, int G, double *raman);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

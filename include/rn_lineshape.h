@@ -27,6 +27,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+#pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden: this is what it exports */
 
 #define RN_LINESHAPE_OUTPUTS 8
 #define RN_LINESHAPE_MIN_BINS 5
@@ -47,6 +48,7 @@ int rn_lineshape_fit_device(int device, const double *d_rows, int64_t num_rows, 
 int rn_lineshape_window_capacity(void);
 const char *rn_lineshape_last_error(void);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+#pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden: this is what it exports */
 
 typedef enum rn_status {
   RN_OK = 0,
@@ -1008,6 +1009,7 @@ int rn_potgnn_kernel_times(rn_potgnn *h, const char **names, double *millis,
 const char *rn_potgnn_last_error(const rn_potgnn *h);
 const char *rn_potgnn_version(void);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+#pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden: this is what it exports */
 
 /* pos host float64 [T][3N]; anchor host float64 [3N]; bounds host int64 [B+1]; joined host int32 [B]; first host
  * float64 [B][3N]; second host float64 [B][2][3N][3N]; counts host int64 [B][2].  Returns when the results are in the
@@ -56,6 +57,7 @@ int rn_qh_set_profiling(int enabled);
 int rn_qh_phase_times(double *millis);
 const char *rn_qh_last_error(void);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -7,24 +7,22 @@ here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 tag="${RN_BUILD_TAG:-}"
 out="$here/../librn_potgnn${tag:+_$tag}.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function ${RN_EXTRA_FLAGS:-}"
+FLAGS="-O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -Wall -Wno-unused-function ${RN_EXTRA_FLAGS:-}"
 bdir="build${tag:+_$tag}"
 mkdir -p "$here/$bdir"
 pids=()
-hip_srcs="api api_interp graph_plan weight_layout kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_c2_pairs kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group kernels_mode kernels_covariance kernels_harmonic kernels_interp spectrum spectrum_polarized spectrum_partial spectrum_segments spectrum_ensemble spectrum_replicates spectrum_vdos spectrum_mode_vdos spectrum_modes spectrum_mode_matrix spectrum_covariance spectrum_harmonic lineshape"
+hip_srcs="api forward reverse training api_interp graph_plan weight_layout kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_c2_pairs kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group kernels_mode kernels_covariance kernels_harmonic kernels_interp spectrum spectrum_polarized spectrum_partial spectrum_segments spectrum_ensemble spectrum_replicates spectrum_vdos spectrum_mode_vdos spectrum_modes spectrum_mode_matrix spectrum_covariance spectrum_harmonic lineshape"
 objs=()
 for f in $hip_srcs; do
   o="$here/$bdir/$(basename "$f").o"
   objs+=("$o")
-  if [ ! -f "$o" ] || [ "$here/$f.hip" -nt "$o" ] || [ "$here/fused_common.hpp" -nt "$o" ] || \
-     [ "$here/kernels.hpp" -nt "$o" ] || [ "$here/device_utils.hpp" -nt "$o" ] || \
-     [ "$here/graph_plan.hpp" -nt "$o" ] || [ "$here/weight_layout.hpp" -nt "$o" ] || \
-     [ "$here/spectrum_common.hpp" -nt "$o" ] || [ "$here/spectrum_segment_core.hpp" -nt "$o" ] || \
-     [ "$here/spectrum_steps.hpp" -nt "$o" ] || \
-     [ "$here/host_runtime.hpp" -nt "$o" ] || [ "$here/increments.hpp" -nt "$o" ] || \
-     [ "$here/../../include/rn_potgnn.h" -nt "$o" ] || [ "$here/../../include/rn_interp.h" -nt "$o" ] || \
-     [ "$here/../../include/rn_lineshape.h" -nt "$o" ] || [ "$here/../../include/rn_quasiharmonic.h" -nt "$o" ] || \
-     [ "$here/../../include/rn_harmonic.h" -nt "$o" ]; then
+  stale=0
+  if [ ! -f "$o" ] || [ "$here/$f.hip" -nt "$o" ]; then stale=1; fi
+  # (every header counts for every object: a new header needs no entry here)
+  for hdr in "$here"/*.hpp "$here"/../../include/*.h; do
+    if [ "$stale" = 0 ] && [ "$hdr" -nt "$o" ]; then stale=1; fi
+  done
+  if [ "$stale" = 1 ]; then
     extra=""
     # (the two kernels with hand-counted vmcnt waits keep their assembly listing for tools/check_ps_isa.py, below)
     case "$f" in kernels_edge_ps|kernels_node_atom) extra="-save-temps=obj";; esac
@@ -36,7 +34,7 @@ for f in ingest ingest_vasprun; do
   if [ ! -f "$here/$bdir/$f.o" ] || [ "$here/$f.cpp" -nt "$here/$bdir/$f.o" ] || \
      [ "$here/ingest_common.hpp" -nt "$here/$bdir/$f.o" ] || [ "$here/ingest_internal.hpp" -nt "$here/$bdir/$f.o" ] || \
      [ "$here/../../include/rn_ingest.h" -nt "$here/$bdir/$f.o" ]; then
-    g++ -O3 -std=c++17 -fPIC -Wall -pthread -c "$here/$f.cpp" -o "$here/$bdir/$f.o" &
+    g++ -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -pthread -c "$here/$f.cpp" -o "$here/$bdir/$f.o" &
     pids+=($!)
   fi
 done
@@ -62,5 +60,5 @@ case " ${RN_EXTRA_FLAGS:-} " in
      tail -n 1 "$here/$bdir/check_ps_isa.log" ;;
 esac
 rm -f "$here/$bdir"/*.hipi "$here/$bdir"/*.bc "$here/$bdir"/*.out "$here/$bdir"/*.resolution.txt "$here/$bdir"/*-host-*.s "$here/$bdir"/*.hipfb
-$HIPCC -shared -fPIC --offload-arch=gfx950 -o "$out" "${objs[@]}" "$here/$bdir/ingest.o" "$here/$bdir/ingest_vasprun.o" -lpthread -ldl
+$HIPCC -shared -fPIC --offload-arch=gfx950 -Wl,--version-script="$here/exports.map" -o "$out" "${objs[@]}" "$here/$bdir/ingest.o" "$here/$bdir/ingest_vasprun.o" -lpthread -ldl
 echo "built $out"

@@ -1,5 +1,5 @@
-// What a translation unit that owns device handles needs on the host: the error types thrown below the C ABI, a device
-// buffer, and the guard every entry runs in.  Host only.
+// What a translation unit that owns device handles needs on the host: the error types thrown below the C ABI, the owners
+// of device memory, streams, events and page-locked memory, and the guard every entry runs in.  Host only.
 //
 // A handle type H gives set_error() and guarded(): `lock` (a std::recursive_mutex), `error` (a std::string),
 // `int device_index() const` (the device the handle lives on) and `static std::string &create_error()` (the text kept for
@@ -16,6 +16,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 
 #include "../../include/rn_potgnn.h"
 
@@ -51,6 +52,52 @@ struct DeviceBuf {
   void upload(const void *src, size_t n) {
     ensure(n);
     HIP_TRY(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
+  }
+  template <typename T>
+  T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// Owners of a stream, an event (no timing) and a page-locked host buffer: created on first get() / ensure(), released by
+// the destructor, move-only.  `s` / `e` / `p` read what there is without creating it (null before the first use).
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+  Stream &operator=(Stream &&o) noexcept { std::swap(s, o.s); return *this; }
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  hipStream_t get() {  // non-blocking with respect to the null stream
+    if (!s) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return s;
+  }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+  Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  hipEvent_t get() {
+    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return e;
+  }
+};
+struct PinnedBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+  PinnedBuf &operator=(PinnedBuf &&o) noexcept { std::swap(p, o.p), std::swap(bytes, o.bytes); return *this; }
+  ~PinnedBuf() { release(); }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  void ensure(size_t n) {  // grow-only; the contents do not survive growing
+    if (n <= bytes) return;
+    release();
+    HIP_TRY(hipHostMalloc(&p, n, hipHostMallocDefault));
+    bytes = n;
   }
   template <typename T>
   T *as() const { return reinterpret_cast<T *>(p); }

@@ -2,7 +2,7 @@
 // kernels read (transposed, [filter | core] halves padded to the planned widths), which entries are derived from others
 // (transposed and centred copies, folded gate constants, split-f16 prescale pairs), and the decisions the host takes from the
 // packed values.  Nothing here calls the HIP runtime or needs a device: rn_potgnn_debug_pack_weights /
-// rn_potgnn_debug_unpack_weights run it on any machine.  api.hip uploads the result.
+// rn_potgnn_debug_unpack_weights run it on any machine.  forward.hip uploads the result.
 #pragma once
 
 #include <cstdint>
@@ -87,7 +87,7 @@ bool mfma_f16_range_ok(const PackedLayout &L, const float *packed, bool host_sta
 // May pass p's triplet loop fold c3_norm_1's scale into its operands and drop the gate's overflow clamp?
 bool folded_gate_ok(const PackedLayout &L, const float *packed, int p);
 
-// The kernels' views of a packed blob in precision T at `w` (c3_fast is left 0: api.hip's refresh_pass_flags decides it).
+// The kernels' views of a packed blob in precision T at `w` (c3_fast is left 0: forward.hip's refresh_pass_flags decides it).
 template <typename T>
 struct WeightViews {
   std::vector<PassW<T>> pass;

@@ -881,7 +881,7 @@ def test_ring_refused_passes_run_the_unfused_edge_block_in_several_blocks(monkey
     """A pass of the fused pipeline that the role-specialised EdgeBlock does not serve -- a graph its ring refuses (forced
     here on TiO2 at 5 A, 47 neighbours per atom, by allowing no ring lookahead at all; the real ring refuses ``blob_ring`` of
     tests/test_dense_graphs_gpu.py, a 66-atom ball, with no knob set), the kernel switched off, a pass without the folded gate scale -- takes the unfused EdgeBlock
-    block of frames by block of frames (``api.hip: edge_unfused_in_blocks``).  With the block forced to 3 frames a 7-frame batch
+    block of frames by block of frames (``forward.hip: edge_unfused_in_blocks``).  With the block forced to 3 frames a 7-frame batch
     walks the multi-block branch (offsets into the node projections, the node rows and the edge rows): against the oracle,
     and bit-equal to the same batch in one block."""
     from oracle import potgnn_oracle as O

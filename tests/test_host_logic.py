@@ -3,6 +3,7 @@ C-ABI symbol table."""
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -159,6 +160,22 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert b"gfx950" in _lib.load().rn_potgnn_version()
+    # ... and nothing else of the library's own: the dynamic symbols named rn_* are exactly what include/ declares (every
+    # header, the entries without a ctypes signature too), and no C++ internal -- namespace rn, or anything that takes a
+    # handle -- is exported next to them
+    every = set()
+    for name in sorted(os.listdir(os.path.join(ROOT, "include"))):
+        header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+        every |= set(re.findall(r"\b(rn_\w+)\s*\(", header))
+    every -= {"rn_potgnn_reduce_fn"}
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.library_path()], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    assert {s for s in exported if s.startswith("rn_")} == every, {s for s in exported if s.startswith("rn_")} ^ every
+    mangled = sorted(s for s in exported if s.startswith("_Z"))
+    demangled = subprocess.run(["c++filt"], input="\n".join(mangled), check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(demangled) == len(mangled)
+    internal = [d for d in demangled if re.search(r"\brn::", d) or "rn_potgnn" in d]
+    assert not internal, internal[:10]
 
 
 def test_create_rejects_bad_arguments_without_touching_the_gpu():
@@ -1088,7 +1105,7 @@ def _digest(packed):
 def test_packed_weights_match_the_parent_commit():
     """The host-only packer (csrc/weight_layout.hip) writes, bit for bit, the packed blob, the trainable mask and the flags
     (split-f16 range guard; folded gate per pass) that ``pack_weights``, ``trainable_mask``, ``mfma_f16_range_ok`` and the
-    loop of ``refresh_pass_flags`` in csrc/api.hip produced before they moved out of it.  tests/golden/packed_weights.npz was
+    loop of ``refresh_pass_flags`` in what was then csrc/api.hip (now csrc/forward.hip) produced before they moved out of it.  tests/golden/packed_weights.npz was
     recorded from that parent commit (b687cbc), not from this code: a throw-away harness (not committed) compiled the
     parent's function text, unchanged, around a minimal handle and ran it on a CPU over tests/helpers.py
     ``weight_layout_cases`` (profiles/weight_layout_ab.txt: the commit, the harness, the cases, the file size).  A packed
