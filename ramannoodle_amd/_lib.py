@@ -222,6 +222,17 @@ HT_SIGNATURES = {
     "rn_ht_last_error": (C.c_char_p, []),
 }
 
+# include/rn_bandmodes.h (the band moments of ramannoodle_amd/bandmodes.py; a table of its own as well)
+BM_SIGNATURES = {
+    "rn_bm_moments": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64,
+                                C.c_int64, C.c_size_t, _P]),
+    "rn_bm_moments_device": (C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int64, _P, _P,
+                                       C.c_int64, C.c_int64, C.c_size_t, _P, _P]),
+    "rn_bm_set_profiling": (C.c_int, [C.c_int]),
+    "rn_bm_phase_times": (C.c_int, [_P]),
+    "rn_bm_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 
 
@@ -245,7 +256,7 @@ def load() -> C.CDLL:
         raise DeviceError(f"cannot load {_LIB_PATH}: {exc}") from exc
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items())
                                       + list(LINESHAPE_SIGNATURES.items()) + list(QH_SIGNATURES.items())
-                                      + list(HT_SIGNATURES.items())):
+                                      + list(HT_SIGNATURES.items()) + list(BM_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes

@@ -1,0 +1,318 @@
+"""Band modes of MD runs (an addition): the atomic motion, and its Raman tensor, under one peak of an MD spectrum, from
+the run alone.
+
+The cross-spectral matrix of the mass-weighted atomic velocities, summed over the bins of one peak, is the band-limited
+(frequency-resolved) covariance; its eigenvectors are the effective normal modes at that peak at the run's temperature.
+With six more columns, the polarizability differences, the same matrix also holds each mode's effective Raman tensor,
+with no derivative of the model.
+
+Definition.  All float64.  ``f[t]``: fractional positions ``(S,N,3)``; one ``lattice`` ``(3,3)``, rows = lattice
+vectors; ``m``: masses ``(N,)``; ``alpha``: polarizabilities ``(S,3,3)`` or ``None``.  ``K = 3N`` columns and ``K' = K +
+6`` when ``alpha`` is given, else ``K' = K``.
+
+* steps ``u[t] = ((f[t+1] - f[t]) - rint(f[t+1] - f[t])) @ lattice`` (``spectrum._vdos_steps``);
+* series: column ``j = 3 i + r`` is ``x[t][j] = sqrt(m_i) u[t][i][r]``; column ``K + c`` is component ``c`` of
+  ``_symmetric_components(alpha[t+1] - alpha[t])``, in the order xx, yy, zz, xy, yz, xz;
+* segments ``(W, starts[Q], taper[n])`` with ``n = W - 1``: the start table of ``rn_md_vdos``;
+* bins: ``bins = (n + 1) // 2 - 1``; bin ``m = 1..bins`` lies on the axis ``fftfreq(n, timestep)[1:bins + 1]``, the axis
+  of ``VibrationalDensityOfStates.measure``; weights ``bw[B][bins]``, finite and applied as given
+  (``spectrum.band_weights`` makes them);
+* transform ``X_q[m][j] = sum_{t<n} taper[t] x[starts[q] + t][j] exp(-2 pi i m t / n)``: the plain length-``n`` DFT, no
+  zero padding;
+* result ``moments[b][j][l] = 1/Q sum_q sum_m bw[b][m] Re(X_q[m][j] conj(X_q[m][l]))``: ``[B][K'][K']``, symmetric.
+
+Relation to the VDOS.  The project's spectra are ``1/2 periodogram + 1/2 zero lag`` because they transform the positive
+lags only, so for the one-group VDOS ``D`` of the same table
+
+``trace(moments[b][:K,:K]) = 2 sum_m bw[b][m] D[m] - (sum_m bw[b][m]) mean_q sum_{t,j} (taper[t] x[starts[q]+t][j])^2``.
+
+``band_moments_host`` states the moments in numpy; ``band_moments_device`` computes them on the GPU
+(``include/rn_bandmodes.h``), differing by the order of the sums only.  ``modes_from_band_moments`` turns moments into
+modes on the host.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+from numpy.typing import NDArray
+
+from ramannoodle_amd.quasiharmonic import _quotients, _symmetric
+
+
+def _moments_arguments(frames: int, atoms: int, lattice, masses, width, starts, taper, bin_weights):
+    """The host arrays of a moments call, contiguous and typed; ``ValueError`` where they do not belong together."""
+    lattice = np.ascontiguousarray(lattice, dtype=np.float64)
+    masses = np.ascontiguousarray(masses, dtype=np.float64)
+    starts = np.ascontiguousarray(starts, dtype=np.int64)
+    taper = np.ascontiguousarray(taper, dtype=np.float64)
+    bin_weights = np.ascontiguousarray(bin_weights, dtype=np.float64)
+    width = int(width)
+    if lattice.shape != (3, 3) or not np.all(np.isfinite(lattice)):
+        raise ValueError("lattice must be a finite (3,3) array")
+    if masses.shape != (atoms,) or not (np.all(np.isfinite(masses)) and np.all(masses > 0)):
+        raise ValueError(f"masses must be ({atoms},), finite and positive")
+    if width < 3 or width > frames:
+        raise ValueError(f"W = {width} frames per segment is not in [3, {frames}]")
+    if starts.ndim != 1 or starts.size < 1 or starts.min() < 0 or starts.max() > frames - width:
+        raise ValueError(f"starts must hold Q >= 1 values in [0, {frames - width}]")
+    steps = width - 1
+    bins = (steps + 1) // 2 - 1
+    if taper.shape != (steps,):
+        raise ValueError(f"taper has wrong shape: {taper.shape} != ({steps},)")
+    if bin_weights.ndim != 2 or bin_weights.shape[0] < 1 or bin_weights.shape[1] != bins:
+        raise ValueError(f"bin_weights has wrong shape: {bin_weights.shape} != (B >= 1, {bins})")
+    if not np.all(np.isfinite(bin_weights)):
+        raise ValueError("bin_weights has a non-finite entry")
+    return lattice, masses, width, starts, taper, bin_weights
+
+
+def band_series(positions, lattice, masses, alpha=None) -> NDArray[np.float64]:
+    """The series ``x[S-1][K']`` of the module's definition."""
+    from ramannoodle_amd.spectrum import _symmetric_components, _vdos_steps
+    positions = np.asarray(positions, dtype=np.float64)
+    steps = _vdos_steps(positions, np.asarray(lattice, dtype=np.float64)[None]) * np.sqrt(masses)[None, :, None]
+    series = steps.reshape(len(steps), -1)
+    if alpha is not None:
+        alpha = np.asarray(alpha, dtype=np.float64)
+        series = np.concatenate([series, _symmetric_components(alpha[1:] - alpha[:-1])], axis=1)
+    return series
+
+
+def band_moments_host(positions, lattice, masses, alpha, width, starts, taper, bin_weights) -> NDArray[np.float64]:
+    """``moments[B][K'][K']`` of the module's definition, in numpy: the statement the device path is tested against.
+    ``positions``: ``(S,N,3)``; ``alpha``: ``(S,3,3)`` or ``None``."""
+    positions = np.asarray(positions, dtype=np.float64)
+    if positions.ndim != 3 or positions.shape[2] != 3 or positions.shape[1] < 1:
+        raise ValueError("positions must be (S,N,3) with N >= 1")
+    frames, atoms = positions.shape[:2]
+    if alpha is not None and np.shape(alpha) != (frames, 3, 3):
+        raise ValueError(f"alpha has wrong shape: {np.shape(alpha)} != ({frames}, 3, 3)")
+    lattice, masses, width, starts, taper, bin_weights = _moments_arguments(frames, atoms, lattice, masses, width, starts,
+                                                                            taper, bin_weights)
+    series = band_series(positions, lattice, masses, alpha)
+    steps, columns = width - 1, series.shape[1]
+    active = np.flatnonzero((bin_weights != 0).any(axis=0))  # (bins without a weight add nothing)
+    moments = np.zeros((len(bin_weights), columns, columns))
+    for start in starts:
+        spectra = np.fft.fft(taper[:, None] * series[start:start + steps], axis=0)[1 + active]  # X_q[m][j]
+        for b, weights in enumerate(bin_weights[:, active]):
+            moments[b] += (spectra.real.T * weights) @ spectra.real + (spectra.imag.T * weights) @ spectra.imag
+    moments /= len(starts)
+    return np.stack([_symmetric(matrix) for matrix in moments])
+
+
+def _is_tensor(value) -> bool:
+    return type(value).__module__.split(".")[0] == "torch"
+
+
+def band_moments_device(positions, lattice, masses, alpha, width, starts, taper, bin_weights, device: int = 0,
+                        workspace_limit: int = 0) -> NDArray[np.float64]:
+    """The same moments on GPU ``device`` (``rn_bm_moments``).  ``positions``: a host array as for
+    ``band_moments_host``, or a contiguous float64 CUDA tensor ``(S,N,3)``, which is read where it is, on its GPU,
+    ordered after torch's current stream (``rn_bm_moments_device``); ``alpha`` is then ``None`` or a contiguous float64
+    CUDA tensor ``(S,3,3)`` on the same GPU.  ``moments`` comes back as a host array."""
+    from ramannoodle_amd import _lib
+    stream = None
+    if _is_tensor(positions):
+        import torch
+        tensors = [positions] if alpha is None else [positions, alpha]
+        if not all(_is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 for t in tensors):
+            raise ValueError("positions and alpha must both be contiguous float64 CUDA tensors")
+        if positions.dim() != 3 or positions.shape[2] != 3 or positions.shape[1] < 1:
+            raise ValueError("positions must be (S,N,3) with N >= 1")
+        if alpha is not None and (tuple(alpha.shape) != (positions.shape[0], 3, 3) or alpha.device != positions.device):
+            raise ValueError(f"alpha must be ({positions.shape[0]}, 3, 3) on the positions' GPU")
+        frames, atoms = int(positions.shape[0]), int(positions.shape[1])
+        device = positions.device.index or 0
+        stream = torch.cuda.current_stream(positions.device).cuda_stream
+        pointer, alpha_pointer = positions.data_ptr(), None if alpha is None else alpha.data_ptr()
+    else:
+        host = np.ascontiguousarray(positions, dtype=np.float64)
+        if host.ndim != 3 or host.shape[2] != 3 or host.shape[1] < 1:
+            raise ValueError("positions must be (S,N,3) with N >= 1")
+        frames, atoms = host.shape[:2]
+        pointer, alpha_pointer = host.ctypes.data, None
+        if alpha is not None:
+            host_alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+            if host_alpha.shape != (frames, 3, 3):
+                raise ValueError(f"alpha has wrong shape: {host_alpha.shape} != ({frames}, 3, 3)")
+            alpha_pointer = host_alpha.ctypes.data
+    lattice, masses, width, starts, taper, bin_weights = _moments_arguments(frames, atoms, lattice, masses, width, starts,
+                                                                            taper, bin_weights)
+    columns = 3 * atoms + (0 if alpha is None else 6)
+    moments = np.zeros((len(bin_weights), columns, columns))
+    lib = _lib.load()
+    entry = lib.rn_bm_moments if stream is None else lib.rn_bm_moments_device
+    tail = () if stream is None else (C.c_void_p(stream),)
+    rc = entry(int(device), C.c_void_p(pointer), C.c_void_p(lattice.ctypes.data), frames, atoms,
+               C.c_void_p(masses.ctypes.data), C.c_void_p(alpha_pointer), width, C.c_void_p(starts.ctypes.data),
+               len(starts), C.c_void_p(taper.ctypes.data), C.c_void_p(bin_weights.ctypes.data), len(bin_weights),
+               bin_weights.shape[1], int(workspace_limit), C.c_void_p(moments.ctypes.data), *tail)
+    if rc != _lib.RN_OK:
+        from ramannoodle_amd.exceptions import DeviceError
+        text = (lib.rn_bm_last_error() or b"").decode()
+        if rc == _lib.RN_ERR_INVALID_ARGUMENT:
+            raise ValueError(f"rn_bm_moments: {text}")
+        if rc == _lib.RN_ERR_OUT_OF_MEMORY:
+            raise MemoryError(f"rn_bm_moments: {text}")
+        raise DeviceError(f"rn_bm_moments failed ({rc}): {text}")
+    return moments
+
+
+@dataclass(frozen=True)
+class BandModes:
+    """The result of ``get_band_modes`` / ``modes_from_band_moments``.
+
+    ``bands`` ``(B,2)``: the half-open intervals in 1/cm; ``wavenumber_axis`` ``(bins,)``; ``bin_counts`` ``(B,)``: the
+    bins inside each band; ``moments`` ``(B,K',K')``.  Per band ``b``, lists of ``B`` arrays from the eigen-decomposition
+    of the ``[K x K]`` block (after the three mass-weighted rigid translations are projected out, when asked for),
+    eigenvalues descending, the ``r_b`` eigenvalues above ``rank_tolerance`` times the largest kept: ``eigenvalues[b]``
+    ``(r_b,)``; ``vectors[b]`` ``(r_b,N,3)``, orthonormal and mass-weighted; ``shares[b] = eigenvalues / trace`` of the
+    block; ``wavenumbers[b]`` ``(r_b,)`` in 1/cm, the ratio of the Rayleigh quotients of the wavenumber-weighted and the
+    plain block.  When ``alpha`` was given (else ``None``): ``alpha_moments`` ``(B,6,6)``, rows and columns
+    ``K..K+5`` of the moments; ``raman_patterns`` ``(B,6,N,3)``, rows ``K..K+5`` against the atoms; ``mode_raman_tensors[b]``
+    ``(r_b,3,3)``: ``R_k = (G e_k) / lambda_k``, the symmetric ``d alpha / d Q_k`` per unit mass-weighted amplitude of
+    mode ``k``.  ``lattice`` and ``masses`` are those of the call."""
+    bands: NDArray[np.float64]
+    wavenumber_axis: NDArray[np.float64]
+    bin_counts: NDArray[np.int64]
+    moments: NDArray[np.float64]
+    eigenvalues: list
+    vectors: list
+    shares: list
+    wavenumbers: list
+    alpha_moments: NDArray[np.float64] | None
+    raman_patterns: NDArray[np.float64] | None
+    mode_raman_tensors: list | None
+    lattice: NDArray[np.float64]
+    masses: NDArray[np.float64]
+
+    def phonons(self, band: int, ref_positions):
+        """The modes of ``band`` as a ``Phonons`` about ``ref_positions`` ``(N,3)``, in the displacement convention of
+        ``QuasiHarmonicModes.phonons``: ``D[k,i] = (e_k[i] / sqrt(m_i)) @ inv(lattice)``, so that
+        ``spectrum.mode_vectors`` gives back ``vectors[band]``; the modes keep the order of ``vectors[band]``.  For
+        ``get_mode_vdos``, ``get_mode_raman_spectrum`` and ``fit_peaks``."""
+        from ramannoodle_amd.dynamics import Phonons
+        band = int(band)
+        if not 0 <= band < len(self.vectors):
+            raise ValueError(f"band = {band} is not one of the {len(self.vectors)} bands")
+        atoms = len(self.masses)
+        reference = np.asarray(ref_positions)
+        if reference.shape != (atoms, 3) or reference.dtype.kind not in "iuf":
+            raise ValueError(f"ref_positions has wrong shape or type: {reference.shape} != ({atoms}, 3) reals")
+        unit = self.vectors[band]
+        displacements = np.ascontiguousarray((unit / np.sqrt(self.masses)[None, :, None]) @ np.linalg.inv(self.lattice))
+        return Phonons(np.ascontiguousarray(reference, dtype=np.float64), np.ascontiguousarray(self.wavenumbers[band]),
+                       displacements)
+
+
+_TENSOR_INDEX = np.array([[0, 3, 5], [3, 1, 4], [5, 4, 2]])  # component (xx, yy, zz, xy, yz, xz) of entry (a, b)
+
+
+def modes_from_band_moments(moments, weighted_moments, lattice, masses, bands, wavenumber_axis, bin_counts,
+                            remove_translations: bool = True, rank_tolerance: float = 1e-10) -> BandModes:
+    """Modes from ``moments[B][K'][K']`` and ``weighted_moments[B][K'][K']``, the moments of the weights ``bw`` and of
+    ``bw * wavenumber_axis`` (``band_moments_host``, ``band_moments_device``).  Per band, with ``C`` and ``C_nu`` the
+    ``[K x K]`` blocks of the two: with ``remove_translations`` both become ``P . P``, ``P = 1 - sum_r t_r t_r^T``,
+    ``t_r[3i+s] = sqrt(m_i / sum m) delta_rs``.  ``numpy.linalg.eigh`` of ``C``, sorted descending, keeps ``lambda_k >
+    rank_tolerance lambda_max`` (``ValueError`` when none is positive); ``shares = lambda / trace(C)``; ``wavenumbers_k
+    = (e_k^T C_nu e_k) / (e_k^T C e_k)``.  With ``K' = K + 6``: ``G`` = rows ``K..K+5`` of ``moments[b]`` against the
+    first ``K`` columns and ``R_k = (G e_k) / lambda_k``."""
+    moments = np.asarray(moments, dtype=np.float64)
+    weighted = np.asarray(weighted_moments, dtype=np.float64)
+    lattice = np.asarray(lattice, dtype=np.float64)
+    masses = np.asarray(masses, dtype=np.float64)
+    atoms = len(masses)
+    columns = 3 * atoms
+    if moments.ndim != 3 or moments.shape[1] != moments.shape[2] or moments.shape[1] not in (columns, columns + 6):
+        raise ValueError("moments and masses do not belong together")
+    if weighted.shape != moments.shape:
+        raise ValueError("moments and weighted_moments do not belong together")
+    with_alpha = moments.shape[1] == columns + 6
+    projector = np.eye(columns)
+    if remove_translations:
+        translations = (np.sqrt(masses / masses.sum())[:, None, None] * np.eye(3)[None]).reshape(columns, 3)
+        projector = projector - translations @ translations.T
+    eigenvalues, vectors, shares, wavenumbers, tensors = [], [], [], [], []
+    for b in range(len(moments)):
+        block = projector @ moments[b, :columns, :columns] @ projector
+        block = 0.5 * (block + block.T)
+        values, basis = np.linalg.eigh(block)
+        values, basis = values[::-1], basis[:, ::-1]
+        keep = values > rank_tolerance * values[0] if values[0] > 0 else np.zeros(columns, dtype=bool)
+        if not keep.any():
+            raise ValueError(f"bands[{b}]: the band moments have rank 0: nothing moves in this band")
+        values, basis = values[keep], basis[:, keep]
+        eigenvalues.append(values)
+        vectors.append(np.ascontiguousarray(basis.T.reshape(-1, atoms, 3)))
+        shares.append(values / np.trace(block))
+        wavenumbers.append(_quotients(projector @ weighted[b, :columns, :columns] @ projector, basis)
+                           / _quotients(block, basis))
+        if with_alpha:
+            responses = (moments[b, columns:, :columns] @ basis) / values[None, :]  # (6, r)
+            tensors.append(np.ascontiguousarray(responses.T[:, _TENSOR_INDEX]))
+    return BandModes(
+        bands=np.array(bands, dtype=np.float64), wavenumber_axis=np.array(wavenumber_axis, dtype=np.float64),
+        bin_counts=np.array(bin_counts, dtype=np.int64), moments=moments, eigenvalues=eigenvalues, vectors=vectors,
+        shares=shares, wavenumbers=wavenumbers,
+        alpha_moments=np.ascontiguousarray(moments[:, columns:, columns:]) if with_alpha else None,
+        raman_patterns=(np.ascontiguousarray(moments[:, columns:, :columns]).reshape(len(moments), 6, atoms, 3)
+                        if with_alpha else None),
+        mode_raman_tensors=tensors if with_alpha else None, lattice=lattice, masses=masses)
+
+
+def band_modes(positions_ts, run_lengths, timestep: float, bands, lattice, masses=None, polarizability_model=None,
+               segment_steps=None, hop=None, taper="hann", remove_translations: bool = True, on_device: bool = False,
+               device: int = 0) -> BandModes:
+    """What ``Trajectory.get_band_modes`` and ``TrajectoryEnsemble.get_band_modes`` share: ``positions_ts`` ``(S,N,3)``
+    are the joined frames of runs of ``run_lengths`` frames (``None``: one run).  Every ``ValueError`` comes before any
+    device work."""
+    import scipy.fftpack
+
+    from ramannoodle_amd.dynamics import verify_lattices
+    from ramannoodle_amd.exceptions import verify_ndarray_shape
+    from ramannoodle_amd.spectrum import _PER_FS_TO_CM1, _Series, _vdos_masses, band_weights
+    frames, atoms = positions_ts.shape[0], positions_ts.shape[1]
+    if min(run_lengths or [frames]) < 3:
+        raise ValueError("band modes need at least three frames of every run")
+    if lattice is None:
+        raise ValueError("get_band_modes needs lattice (3,3)")
+    verify_ndarray_shape("lattice", np.asarray(lattice), (3, 3))
+    lattice = verify_lattices(np.asarray(lattice)[None], 1)[0]
+    masses = _vdos_masses(masses, atoms)
+    if polarizability_model is not None and int(polarizability_model.num_atoms) != atoms:
+        raise ValueError(f"polarizability_model and trajectory are incompatible: the model has "
+                         f"{int(polarizability_model.num_atoms)} atoms, the frames have {atoms}")
+    series = _Series(positions_ts, None if run_lengths is None else list(run_lengths))
+    if segment_steps is None:
+        width, tau, starts = series.whole_table("band modes need at least three frames of every run")
+    else:
+        width, tau, starts = series.segment_table(segment_steps, hop, taper)
+    steps = width - 1
+    bins = (steps + 1) // 2 - 1
+    if bins < 1:
+        raise ValueError(f"segments of {width} frames have no bin: band modes need at least 4 frames per segment")
+    axis = (scipy.fftpack.fftfreq(steps, timestep) * _PER_FS_TO_CM1)[1:bins + 1]
+    weights = band_weights(axis, bands)
+    bin_counts = (weights != 0).sum(axis=1)
+    rows = np.concatenate([weights, weights * axis[None, :]], axis=0)  # [bw; bw nu]
+
+    if on_device:
+        import torch
+        evaluate = None
+        if polarizability_model is not None:
+            evaluate = getattr(polarizability_model, "calc_polarizabilities_device", None)
+            if evaluate is None:
+                raise TypeError("on_device=True needs a model with calc_polarizabilities_device")
+            device = polarizability_model.device_index
+        positions = torch.tensor(positions_ts, dtype=torch.float64, device=f"cuda:{int(device)}")
+        alpha = None if evaluate is None else evaluate(positions)
+        both = band_moments_device(positions, lattice, masses, alpha, width, starts, tau, rows)
+    else:
+        alpha = None if polarizability_model is None else polarizability_model.calc_polarizabilities(positions_ts)
+        both = band_moments_host(positions_ts, lattice, masses, alpha, width, starts, tau, rows)
+    count = len(weights)
+    return modes_from_band_moments(both[:count], both[count:], lattice, masses, np.asarray(bands, dtype=np.float64), axis,
+                                   bin_counts, remove_translations)

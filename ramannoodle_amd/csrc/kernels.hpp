@@ -323,6 +323,12 @@ void launch_mode_rest(const double *jac, const double *pos, int64_t steps, int N
 // -> first float64 [B][K], second float64 [B][2][K][K].  All device pointers; B <= 65535 and num_chunks
 // covariance_pairs(K) < 2^31 (the grid).
 constexpr int kCovarianceChunkFrames = 512;  // the frames of a chunk: a multiple of the kernel's k-tile of 16
+// pair p of the lower triangle of a matrix of tiles, row-major: (0,0) (1,0) (1,1) (2,0) ..  (also kernels_band.hip)
+__device__ inline void lower_pair(int p, int &I, int &J) {
+  I = 0;
+  while ((I + 1) * (I + 2) / 2 <= p) ++I;
+  J = p - I * (I + 1) / 2;
+}
 int covariance_pairs(int64_t K);
 size_t covariance_workspace_doubles(int64_t K, int64_t num_chunks);
 void launch_covariance_chunks(const double *pos, int64_t K, const double *anchor, const int64_t *chunks,
@@ -337,6 +343,27 @@ int64_t harmonic_workgroups(int64_t K, int64_t R, int64_t T);
 void launch_harmonic_synthesis(const double *ref, const double *D, const double *omega_dt, const double *amp,
                                const double *phase, int64_t K, int M, int64_t R, int64_t T, int64_t t0, double *out,
                                hipStream_t st);
+
+// Band moments (kernels_band.hip; include/rn_bandmodes.h states them).  All device pointers but `lattice` (host, [9]).
+// pos float64 [.][K], alpha float64 [.][9] or null (then Kc == K, else Kc == K + 6), sqrt_mass float64 [K / 3], starts
+// int64, taper float64 [n], table float64 [n][2] (launch_band_phases), row_bins int32 [Rp]: the bin of row 2 i + part,
+// -1 for the padding; Rp = band_padded(2 U).  V float64 [count][Rp][band_padded(Kc)]: the transforms of segments q0 ..
+// q0 + count - 1.  launch_band_update: rows = count * Rp rows of V, weights float64 [B][Rp], ws float64
+// [band_partial_doubles(Kc, B, rows)] -> moments float64 [B][Kc][Kc] (accumulate = 1: added to what is there).
+// B <= 65535, band_chunks(rows) * band_pairs(Kc) and band_transform_workgroups (-1 when too many) < 2^31: the grids.
+constexpr int kBandChunkRows = 512;  // the rows of V per chunk of the update: a multiple of its k-tile of 16
+int64_t band_padded(int64_t count);
+int band_pairs(int64_t Kc);
+int64_t band_chunks(int64_t rows);
+size_t band_partial_doubles(int64_t Kc, int64_t B, int64_t rows);
+int64_t band_transform_workgroups(int64_t Kc, int64_t Rp, int64_t count);
+void launch_band_phases(int64_t n, double *table, hipStream_t st);
+void launch_band_transform(const double *pos, const double *alpha, const double *lattice, const double *sqrt_mass,
+                           int64_t K, int64_t Kc, int64_t n, const int64_t *starts, int64_t q0, int64_t count,
+                           const double *taper, const double *table, const int *row_bins, int64_t Rp, double *V,
+                           hipStream_t st);
+void launch_band_update(const double *V, int64_t rows, int64_t Rp, int64_t Kc, const double *weights, int64_t B,
+                        int accumulate, double *ws, double *moments, hipStream_t st);
 
 // The interpolation model on the device (kernels_interp.hip; api_interp.hip owns the arrays).  Everything float64:
 // F [J][K3] the basis with the lattice folded in and FT [K3][J] its transpose, ref [K3] the reference positions,

@@ -51,13 +51,6 @@ constexpr int kMirrorStride = kTile + 1;
 
 typedef double f64x4_t __attribute__((ext_vector_type(4)));
 
-// pair p of the lower triangle, row-major: (0,0) (1,0) (1,1) (2,0) ..
-__device__ inline void lower_pair(int p, int &I, int &J) {
-  I = 0;
-  while ((I + 1) * (I + 2) / 2 <= p) ++I;
-  J = p - I * (I + 1) / 2;
-}
-
 // chunks: int64 [chunk][3] = (first frame f0, frames nf, steps ns <= nf); the chunk reads frames f0 .. f0 + max(nf - 1, ns)
 __global__ void __launch_bounds__(kThreads)
     covariance_chunk_kernel(const double *__restrict__ pos, int64_t K, const double *__restrict__ anchor,

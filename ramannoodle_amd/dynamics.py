@@ -383,6 +383,27 @@ class Trajectory(Dynamics, Sequence):
         return quasiharmonic_modes(self._positions_ts, [len(self._positions_ts)], self._timestep, lattice, masses,
                                    temperature, ref_positions, blocks, remove_translations, on_device, device)
 
+    def get_band_modes(self, bands, lattice, masses=None, polarizability_model=None, segment_steps=None, hop=None,
+                       taper="hann", remove_translations: bool = True, on_device: bool = False, device: int = 0):
+        """The atomic motion, and its Raman tensor, under peaks of the run's spectra (an addition): ``BandModes`` from
+        the band-limited covariance of the mass-weighted velocities (``ramannoodle_amd.bandmodes`` states the
+        definition).  ``bands`` ``(B,2)``: half-open intervals ``[lo, hi)`` in 1/cm on the axis of
+        ``get_vdos(...).measure()`` (``spectrum.band_weights``); ``lattice`` ``(3,3)``: the fixed cell; ``masses``
+        ``(N,)`` (``None``: unit masses); ``polarizability_model``: when given, every frame is evaluated and the moments
+        gain the six polarizability columns, so that every mode has its effective Raman tensor; ``segment_steps``,
+        ``hop``, ``taper`` as ``spectrum.segment_plan`` (``segment_steps=None``: the whole run as one boxcar segment);
+        ``remove_translations``: project the three rigid translations out.  ``on_device=True``: the positions go to
+        the HBM of GPU ``device`` (with a model: of the model's GPU, where ``calc_polarizabilities_device`` evaluates
+        them) and the moments are summed there.  ``ValueError``, before any device work: a trajectory with
+        ``lattice_ts``, a bad ``lattice`` or ``masses``, what ``band_weights`` refuses, fewer than three frames, a
+        model of another atom count."""
+        from ramannoodle_amd.bandmodes import band_modes
+        if self._lattice_ts is not None:
+            raise ValueError("band modes and a trajectory with a lattice per frame are incompatible: a fluctuating cell "
+                             "has no single mass-weighted metric")
+        return band_modes(self._positions_ts, None, self._timestep, bands, lattice, masses, polarizability_model,
+                          segment_steps, hop, taper, remove_translations, on_device, device)
+
     def __len__(self) -> int:
         return len(self._positions_ts)
 
@@ -558,3 +579,16 @@ class TrajectoryEnsemble:
                              "fluctuating cell has no single mass-weighted metric")
         return quasiharmonic_modes(self._positions_ts, self._run_lengths, self._timestep, lattice, masses, temperature,
                                    ref_positions, blocks, remove_translations, on_device, device)
+
+    def get_band_modes(self, bands, lattice, masses=None, polarizability_model=None, segment_steps=None, hop=None,
+                       taper="hann", remove_translations: bool = True, on_device: bool = False, device: int = 0):
+        """``BandModes`` of the joined runs (arguments as ``Trajectory.get_band_modes``): the moments are the mean over
+        the segments of every run, none of which crosses a run boundary (``spectrum.ensemble_segment_starts``);
+        ``segment_steps=None`` takes each run whole and needs runs of one length, as the ensemble VDOS does.  With a
+        model, all frames are evaluated in one call."""
+        from ramannoodle_amd.bandmodes import band_modes
+        if self._lattice_ts is not None:
+            raise ValueError("band modes and trajectories with a lattice per frame are incompatible: a fluctuating cell "
+                             "has no single mass-weighted metric")
+        return band_modes(self._positions_ts, self._run_lengths, self._timestep, bands, lattice, masses,
+                          polarizability_model, segment_steps, hop, taper, remove_translations, on_device, device)
