@@ -202,6 +202,17 @@ LINESHAPE_SIGNATURES = {
     "rn_lineshape_last_error": (C.c_char_p, []),
 }
 
+# include/rn_peakfit.h (the multi-peak fits of ramannoodle_amd/peakfit.py; a table of its own as well): the arguments of the
+# two lineshape entries with (shape, linear, P, origin, centres, widths) after F
+PEAKFIT_SIGNATURES = {
+    "rn_peakfit_fit": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P,
+                                 _P, _P, C.c_int, _P, _P, _P]),
+    "rn_peakfit_fit_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, C.c_int, C.c_int,
+                                        C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "rn_peakfit_window_capacity": (C.c_int, []),
+    "rn_peakfit_last_error": (C.c_char_p, []),
+}
+
 # include/rn_quasiharmonic.h (the covariance moments of ramannoodle_amd/quasiharmonic.py; a table of its own as well)
 QH_SIGNATURES = {
     "rn_qh_moments": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P]),
@@ -255,7 +266,8 @@ def load() -> C.CDLL:
     except OSError as exc:
         raise DeviceError(f"cannot load {_LIB_PATH}: {exc}") from exc
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items())
-                                      + list(LINESHAPE_SIGNATURES.items()) + list(QH_SIGNATURES.items())
+                                      + list(LINESHAPE_SIGNATURES.items()) + list(PEAKFIT_SIGNATURES.items())
+                                      + list(QH_SIGNATURES.items())
                                       + list(HT_SIGNATURES.items()) + list(BM_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = restype

@@ -196,8 +196,9 @@ def _axis(wavenumbers) -> tuple[NDArray[np.float64], float]:
     return w, spacing
 
 
-def _fit_table(w, spacing: float, rows_shape, windows):
-    """``(row_index, first_bin, num_bins, leading shape)`` of the fits of ``windows`` on rows of shape ``rows_shape``."""
+def _fit_table(w, spacing: float, rows_shape, windows, min_bins: int = MIN_BINS, needs: str = str(MIN_BINS)):
+    """``(row_index, first_bin, num_bins, leading shape)`` of the fits of ``windows`` on rows of shape ``rows_shape``;
+    a window must hold ``min_bins`` bins, which the message spells as ``needs``."""
     windows = np.asarray(windows, dtype=np.float64)
     leading = tuple(rows_shape[:-1])
     count = int(np.prod(leading, dtype=np.int64))
@@ -221,10 +222,10 @@ def _fit_table(w, spacing: float, rows_shape, windows):
         raise ValueError(f"window [{bad[0]:g}, {bad[1]:g}) is empty: lo >= hi")
     first = np.searchsorted(w, edges[:, 0], side="left").astype(np.int64)
     bins = np.searchsorted(w, edges[:, 1], side="left").astype(np.int64) - first
-    if np.any(bins < MIN_BINS):
-        index = int(np.flatnonzero(bins < MIN_BINS)[0])
+    if np.any(bins < min_bins):
+        index = int(np.flatnonzero(bins < min_bins)[0])
         raise ValueError(f"window [{edges[index, 0]:g}, {edges[index, 1]:g}) holds {int(bins[index])} bins of the axis "
-                         f"(spacing {spacing:g} cm^-1): a fit needs at least {MIN_BINS}")
+                         f"(spacing {spacing:g} cm^-1): a fit needs at least {needs}")
     return row_index, first, np.ascontiguousarray(bins), leading
 
 
@@ -384,17 +385,28 @@ def replicate_standard_error(replicates, method, valid=None, blocks_count=None):
     return np.where(used >= 2, error, np.nan), used
 
 
-def replicate_errors(fits: LorentzianFits, method: str, blocks_count=None) -> LorentzianErrors:
+def replicate_errors(fits, method: str, blocks_count=None):
     """Error bars of fitted peaks from the fits of replicate spectra: ``fits`` is
     ``fit_lorentzians(w, rows[R, ...], windows)`` on the rows of ``replicates.measure_segment_replicates`` (replicates along the
     first axis), ``method`` the one that made the replicates.  Each error is
     ``replicate_standard_error`` over the replicate axis: ``"bootstrap"`` ``std(ddof=1)``, ``"jackknife"``
     ``sqrt((G - 1) / G sum_r (x_r - mean x)^2)``, ``"blocks"`` ``std(ddof=1) / sqrt(G)``.  Replicates whose status is
-    not 0 are left out, window by window; ``G`` is ``blocks_count`` or, by default, the number of replicates used."""
+    not 0 are left out, window by window; ``G`` is ``blocks_count`` or, by default, the number of replicates used.
+
+    ``fits`` may also be the ``peakfit.PeakFits`` of ``peakfit.fit_peaks_multi`` on such rows: the result is then a
+    ``peakfit.PeakErrors``, the errors of ``position``, ``hwhm``, ``height`` and ``lifetime_ps`` per peak (a replicate
+    is left out of all the peaks of a window together)."""
+    from ramannoodle_amd import peakfit
     status = np.asarray(fits.status)
     if status.ndim < 1:
         raise ValueError("fits has no replicate axis")
     valid = status == STATUS_CONVERGED
+    used = valid.sum(axis=0).astype(np.int64)
+    if isinstance(fits, peakfit.PeakFits):
+        per_peak = np.broadcast_to(valid[..., None], fits.position.shape)
+        errors = [replicate_standard_error(values, method, per_peak, blocks_count)[0]
+                  for values in (fits.position, fits.hwhm, fits.height, fits.lifetime_ps)]
+        return peakfit.PeakErrors(*errors, used=used)
     errors = [replicate_standard_error(values, method, valid, blocks_count)[0]
               for values in (fits.position, fits.hwhm, fits.lifetime_ps, fits.area)]
-    return LorentzianErrors(*errors, used=valid.sum(axis=0).astype(np.int64))
+    return LorentzianErrors(*errors, used=used)
