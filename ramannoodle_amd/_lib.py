@@ -281,6 +281,19 @@ def check_interp(rc: int, handle=None, what: str = "device call") -> None:
     check(rc, handle, what, last_error="rn_interp_last_error")
 
 
+def check_status(rc: int, what: str, last_error: str) -> None:
+    """``check`` for the modules whose entries take no handle (the fits, the covariance moments, the harmonic
+    trajectories, the band moments): ``last_error`` names the module's ``rn_*_last_error``, which takes no argument."""
+    if rc == RN_OK:
+        return
+    text = (getattr(load(), last_error)() or b"").decode()
+    if rc == RN_ERR_INVALID_ARGUMENT:
+        raise ValueError(f"{what}: {text}")
+    if rc == RN_ERR_OUT_OF_MEMORY:
+        raise MemoryError(f"{what}: {text}")
+    raise DeviceError(f"{what} failed ({rc}): {text}")
+
+
 def check(rc: int, handle=None, what: str = "device call", last_error: str = "rn_potgnn_last_error") -> None:
     """Map a status code to the exception the reference API contract expects."""
     if rc == RN_OK:

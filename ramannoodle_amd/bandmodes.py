@@ -38,6 +38,7 @@ from dataclasses import dataclass
 import numpy as np
 from numpy.typing import NDArray
 
+from ramannoodle_amd._source import is_tensor, source
 from ramannoodle_amd.quasiharmonic import _quotients, _symmetric
 
 
@@ -103,10 +104,6 @@ def band_moments_host(positions, lattice, masses, alpha, width, starts, taper, b
     return np.stack([_symmetric(matrix) for matrix in moments])
 
 
-def _is_tensor(value) -> bool:
-    return type(value).__module__.split(".")[0] == "torch"
-
-
 def band_moments_device(positions, lattice, masses, alpha, width, starts, taper, bin_weights, device: int = 0,
                         workspace_limit: int = 0) -> NDArray[np.float64]:
     """The same moments on GPU ``device`` (``rn_bm_moments``).  ``positions``: a host array as for
@@ -114,26 +111,22 @@ def band_moments_device(positions, lattice, masses, alpha, width, starts, taper,
     ordered after torch's current stream (``rn_bm_moments_device``); ``alpha`` is then ``None`` or a contiguous float64
     CUDA tensor ``(S,3,3)`` on the same GPU.  ``moments`` comes back as a host array."""
     from ramannoodle_amd import _lib
-    stream = None
-    if _is_tensor(positions):
-        import torch
-        tensors = [positions] if alpha is None else [positions, alpha]
-        if not all(_is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 for t in tensors):
-            raise ValueError("positions and alpha must both be contiguous float64 CUDA tensors")
+    refusal = "positions and alpha must both be contiguous float64 CUDA tensors"
+    pointer, index, stream, positions = source(positions, refusal)
+    if stream is not None:
+        if alpha is not None and not is_tensor(alpha):
+            raise ValueError(refusal)
+        device, alpha_pointer = index, None if alpha is None else source(alpha, refusal)[0]
         if positions.dim() != 3 or positions.shape[2] != 3 or positions.shape[1] < 1:
             raise ValueError("positions must be (S,N,3) with N >= 1")
         if alpha is not None and (tuple(alpha.shape) != (positions.shape[0], 3, 3) or alpha.device != positions.device):
             raise ValueError(f"alpha must be ({positions.shape[0]}, 3, 3) on the positions' GPU")
         frames, atoms = int(positions.shape[0]), int(positions.shape[1])
-        device = positions.device.index or 0
-        stream = torch.cuda.current_stream(positions.device).cuda_stream
-        pointer, alpha_pointer = positions.data_ptr(), None if alpha is None else alpha.data_ptr()
     else:
-        host = np.ascontiguousarray(positions, dtype=np.float64)
-        if host.ndim != 3 or host.shape[2] != 3 or host.shape[1] < 1:
+        if positions.ndim != 3 or positions.shape[2] != 3 or positions.shape[1] < 1:
             raise ValueError("positions must be (S,N,3) with N >= 1")
-        frames, atoms = host.shape[:2]
-        pointer, alpha_pointer = host.ctypes.data, None
+        frames, atoms = positions.shape[:2]
+        alpha_pointer = None
         if alpha is not None:
             host_alpha = np.ascontiguousarray(alpha, dtype=np.float64)
             if host_alpha.shape != (frames, 3, 3):
@@ -150,14 +143,7 @@ def band_moments_device(positions, lattice, masses, alpha, width, starts, taper,
                C.c_void_p(masses.ctypes.data), C.c_void_p(alpha_pointer), width, C.c_void_p(starts.ctypes.data),
                len(starts), C.c_void_p(taper.ctypes.data), C.c_void_p(bin_weights.ctypes.data), len(bin_weights),
                bin_weights.shape[1], int(workspace_limit), C.c_void_p(moments.ctypes.data), *tail)
-    if rc != _lib.RN_OK:
-        from ramannoodle_amd.exceptions import DeviceError
-        text = (lib.rn_bm_last_error() or b"").decode()
-        if rc == _lib.RN_ERR_INVALID_ARGUMENT:
-            raise ValueError(f"rn_bm_moments: {text}")
-        if rc == _lib.RN_ERR_OUT_OF_MEMORY:
-            raise MemoryError(f"rn_bm_moments: {text}")
-        raise DeviceError(f"rn_bm_moments failed ({rc}): {text}")
+    _lib.check_status(rc, "rn_bm_moments", "rn_bm_last_error")
     return moments
 
 

@@ -15,18 +15,13 @@
 // The work is latency-bound float64 VALU arithmetic (one division per bin and evaluation) and six shuffle stages per
 // sum; a call launches one wave per fit and leaves the overlap to the number of waves.
 //
-// Entries.  The table and the results are host arrays; they and (for the host entry) the rows pass through one
-// grow-only device workspace per process, under one lock.  Copies and the kernel are enqueued on the caller's stream
-// (the host entry: the null stream) and the entry returns after synchronising it.
+// Entries: fit_entry.hpp, with nothing of their own but the least number of bins and the launch.
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <mutex>
-#include <string>
 
 #include "../../include/rn_lineshape.h"
-#include "spectrum_common.hpp"
+#include "fit_entry.hpp"
 
 namespace {
 
@@ -280,102 +275,35 @@ __global__ void __launch_bounds__(kWaves *kLanes)
 }
 
 // ----------------------------------------------------------------------------- entries
-thread_local std::string g_error;
+using rn_fit::FitArgs;
+thread_local rn_spectrum::ErrorText g_error;
+rn_fit::FitWorkspace g_fits(kOutputs);
 
-int fail(int rc, const char *format, ...) {
-  char text[512];
-  va_list args;
-  va_start(args, format);
-  vsnprintf(text, sizeof text, format, args);
-  va_end(args);
-  g_error = text;
-  return rc;
-}
-
-// the process's device workspace: grow-only buffers (spectrum_common.hpp) on one device at a time, under g_mutex for
-// the whole call
-using rn_spectrum::DeviceBuffer;
-using rn_spectrum::Fit;
-std::mutex g_mutex;
-int g_device = -1;
-DeviceBuffer g_rows, g_table, g_out, g_flags;
-
-int lineshape_fit(int device, const double *rows, bool rows_on_host, int64_t num_rows, int64_t bins,
-                  const int64_t *row_index, const int64_t *first_bin, const int64_t *num_bins, int64_t F,
-                  int max_iterations, double *out, int32_t *status, int32_t *iterations, hipStream_t stream) {
-  if (F < 0) return fail(RN_ERR_INVALID_ARGUMENT, "F = %lld is negative", (long long)F);
-  if (max_iterations < 1) return fail(RN_ERR_INVALID_ARGUMENT, "max_iterations = %d is not positive", max_iterations);
-  if (num_rows < 1 || bins < 1 || bins > INT32_MAX || F > ((int64_t)1 << 30))
-    return fail(RN_ERR_INVALID_ARGUMENT, "num_rows = %lld, bins = %lld or F = %lld is out of range", (long long)num_rows,
-                (long long)bins, (long long)F);
-  if (F == 0) return RN_OK;
-  if (!rows || !row_index || !first_bin || !num_bins || !out || !status || !iterations)
-    return fail(RN_ERR_INVALID_ARGUMENT, "a null pointer");
-  for (int64_t f = 0; f < F; ++f) {
-    if (row_index[f] < 0 || row_index[f] >= num_rows)
-      return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: row %lld is outside [0, %lld)", (long long)f,
-                  (long long)row_index[f], (long long)num_rows);
-    if (num_bins[f] < RN_LINESHAPE_MIN_BINS)
-      return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: %lld bins, a fit needs at least %d", (long long)f,
-                  (long long)num_bins[f], RN_LINESHAPE_MIN_BINS);
-    if (first_bin[f] < 0 || first_bin[f] > bins || num_bins[f] > bins - first_bin[f])
-      return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: bins [%lld, %lld + %lld) are outside [0, %lld)", (long long)f,
-                  (long long)first_bin[f], (long long)first_bin[f], (long long)num_bins[f], (long long)bins);
+int lineshape_fit(int device, const FitArgs &a) {
+  if (int rc = rn_fit::check_sizes(a, g_error)) return rc;
+  if (a.F == 0) return RN_OK;
+  if (a.any_null()) return g_error.fail(RN_ERR_INVALID_ARGUMENT, "a null pointer");
+  for (int64_t f = 0; f < a.F; ++f) {
+    if (int rc = rn_fit::check_row(a, f, g_error)) return rc;
+    if (a.num_bins[f] < RN_LINESHAPE_MIN_BINS)
+      return g_error.fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: %lld bins, a fit needs at least %d", (long long)f,
+                          (long long)a.num_bins[f], RN_LINESHAPE_MIN_BINS);
+    if (int rc = rn_fit::check_window(a, f, g_error)) return rc;
   }
-  int devices = 0;
-  if (hipGetDeviceCount(&devices) != hipSuccess || device < 0 || device >= devices)
-    return fail(RN_ERR_NO_DEVICE, "device %d is not one of the %d GPUs", device, devices);
-  if (hipSetDevice(device) != hipSuccess) return fail(RN_ERR_HIP, "hipSetDevice(%d) failed", device);
+  if (int rc = rn_spectrum::select_device(device, g_error)) return rc;
 
-  std::lock_guard<std::mutex> lock(g_mutex);
-  if (g_device != device) {  // (buffers belong to the device they were allocated on)
-    if (g_device >= 0 && hipSetDevice(g_device) == hipSuccess) {
-      g_rows.release();
-      g_table.release();
-      g_out.release();
-      g_flags.release();
-      (void)hipSetDevice(device);
-    }
-    g_device = device;
-  }
-  const size_t count = (size_t)F;
-  const size_t row_bytes = (size_t)num_rows * (size_t)bins * sizeof(double);
-  if ((rows_on_host && g_rows.ensure(row_bytes, Fit::kGrowOnly) != RN_OK) ||
-      g_table.ensure(3 * count * sizeof(int64_t), Fit::kGrowOnly) != RN_OK ||
-      g_out.ensure(count * kOutputs * sizeof(double), Fit::kGrowOnly) != RN_OK ||
-      g_flags.ensure(2 * count * sizeof(int32_t), Fit::kGrowOnly) != RN_OK)
-    return fail(RN_ERR_OUT_OF_MEMORY, "no device memory for %lld fits of %lld rows of %lld bins", (long long)F,
-                (long long)num_rows, (long long)bins);
-  auto *d_table = static_cast<int64_t *>(g_table.ptr);
-  auto *d_out = static_cast<double *>(g_out.ptr);
-  auto *d_flags = static_cast<int32_t *>(g_flags.ptr);
-  const double *d_rows = rows;
-  hipError_t e = hipSuccess;
-  auto ok = [&](hipError_t status_of_call) {
-    if (e == hipSuccess) e = status_of_call;
-    return e == hipSuccess;
-  };
-  if (rows_on_host) {
-    ok(hipMemcpyAsync(g_rows.ptr, rows, row_bytes, hipMemcpyHostToDevice, stream));
-    d_rows = static_cast<const double *>(g_rows.ptr);
-  }
-  ok(hipMemcpyAsync(d_table, row_index, count * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-  ok(hipMemcpyAsync(d_table + count, first_bin, count * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-  ok(hipMemcpyAsync(d_table + 2 * count, num_bins, count * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-  if (e == hipSuccess) {
-    const unsigned blocks = (unsigned)((F + kWaves - 1) / kWaves);
-    lineshape_fit_kernel<<<blocks, kWaves * kLanes, 0, stream>>>(d_rows, bins, d_table, d_table + count,
-                                                                 d_table + 2 * count, F, max_iterations, d_out, d_flags,
-                                                                 d_flags + count);
+  std::lock_guard<std::mutex> lock(g_fits.mutex);
+  g_fits.bind(device);
+  if (g_fits.ensure(a) != RN_OK) return g_fits.no_memory(a, g_error);
+  rn_spectrum::FirstError ok;
+  const double *d_rows = g_fits.stage(a, ok);
+  if (ok.first == hipSuccess) {
+    lineshape_fit_kernel<<<rn_fit::fit_blocks(a.F, kWaves), kWaves * kLanes, 0, a.stream>>>(
+        d_rows, a.bins, g_fits.column(a, 0), g_fits.column(a, 1), g_fits.column(a, 2), a.F, a.max_iterations,
+        g_fits.d_out(), g_fits.d_status(), g_fits.d_iterations(a));
     ok(hipGetLastError());
   }
-  ok(hipMemcpyAsync(out, d_out, count * kOutputs * sizeof(double), hipMemcpyDeviceToHost, stream));
-  ok(hipMemcpyAsync(status, d_flags, count * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  ok(hipMemcpyAsync(iterations, d_flags + count, count * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failure: the buffers may be in use)
-  ok(waited);
-  if (e != hipSuccess) return fail(RN_ERR_HIP, "%s", hipGetErrorString(e));
-  return RN_OK;
+  return g_fits.finish(a, ok, g_error);
 }
 
 }  // namespace
@@ -383,18 +311,18 @@ int lineshape_fit(int device, const double *rows, bool rows_on_host, int64_t num
 extern "C" int rn_lineshape_fit(int device, const double *rows, int64_t num_rows, int64_t bins,
                                 const int64_t *row_index, const int64_t *first_bin, const int64_t *num_bins, int64_t F,
                                 int max_iterations, double *out, int32_t *status, int32_t *iterations) {
-  return lineshape_fit(device, rows, true, num_rows, bins, row_index, first_bin, num_bins, F, max_iterations, out, status,
-                       iterations, nullptr);
+  return lineshape_fit(device, {rows, true, num_rows, bins, row_index, first_bin, num_bins, F, max_iterations, out, status,
+                                iterations, nullptr});
 }
 
 extern "C" int rn_lineshape_fit_device(int device, const double *d_rows, int64_t num_rows, int64_t bins,
                                        const int64_t *row_index, const int64_t *first_bin, const int64_t *num_bins,
                                        int64_t F, int max_iterations, double *out, int32_t *status, int32_t *iterations,
                                        void *stream) {
-  return lineshape_fit(device, d_rows, false, num_rows, bins, row_index, first_bin, num_bins, F, max_iterations, out,
-                       status, iterations, static_cast<hipStream_t>(stream));
+  return lineshape_fit(device, {d_rows, false, num_rows, bins, row_index, first_bin, num_bins, F, max_iterations, out,
+                                status, iterations, static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int rn_lineshape_window_capacity(void) { return kCapacity; }
 
-extern "C" const char *rn_lineshape_last_error(void) { return g_error.c_str(); }
+extern "C" const char *rn_lineshape_last_error(void) { return g_error.text.c_str(); }

@@ -25,16 +25,14 @@
 // way.  delta is lane p's solution and (N^-1)_ii is entry i of lane 16 + i's.  Every value that steers the fit (delta,
 // S, the pivots) is read into scalar registers, so the control flow is wave-uniform.  No atomics, no scratch.
 //
-// Entries: those of lineshape.hip, with the three real columns (origin, centres, widths) next to the integer table.
+// Entries: fit_entry.hpp, with the model's scalars, the three real columns (origin, centres, widths: one more grow-only
+// buffer, staged on the same stream) and their checks next to the integer table.
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <mutex>
-#include <string>
 
 #include "../../include/rn_peakfit.h"
-#include "spectrum_common.hpp"
+#include "fit_entry.hpp"
 
 namespace {
 
@@ -370,18 +368,6 @@ __global__ void __launch_bounds__(kWaves *kLanes)
 }
 
 // ----------------------------------------------------------------------------- entries
-thread_local std::string g_error;
-
-int fail(int rc, const char *format, ...) {
-  char text[512];
-  va_list args;
-  va_start(args, format);
-  vsnprintf(text, sizeof text, format, args);
-  va_end(args);
-  g_error = text;
-  return rc;
-}
-
 using Kernel = void (*)(const double *, int64_t, const int64_t *, const int64_t *, const int64_t *, const double *,
                         const double *, const double *, int64_t, int, double *, int32_t *, int32_t *);
 
@@ -400,116 +386,64 @@ Kernel kernel_of(int P, bool linear, bool dho) {
   }
 }
 
-// the process's device workspace: grow-only buffers (spectrum_common.hpp) on one device at a time, under g_mutex for
-// the whole call
-using rn_spectrum::DeviceBuffer;
+using rn_fit::FitArgs;
 using rn_spectrum::Fit;
-std::mutex g_mutex;
-int g_device = -1;
-DeviceBuffer g_rows, g_table, g_real, g_out, g_flags;
+thread_local rn_spectrum::ErrorText g_error;
+rn_spectrum::DeviceBuffer g_real;  // origin [F], centres [F][P], widths [F][P]
+rn_fit::FitWorkspace g_fits(kOutputs, {&g_real});
 
-int peakfit_fit(int device, const double *rows, bool rows_on_host, int64_t num_rows, int64_t bins,
-                const int64_t *row_index, const int64_t *first_bin, const int64_t *num_bins, int64_t F, int shape,
-                int linear, int P, const double *origin, const double *centres, const double *widths,
-                int max_iterations, double *out, int32_t *status, int32_t *iterations, hipStream_t stream) {
-  if (F < 0) return fail(RN_ERR_INVALID_ARGUMENT, "F = %lld is negative", (long long)F);
-  if (max_iterations < 1) return fail(RN_ERR_INVALID_ARGUMENT, "max_iterations = %d is not positive", max_iterations);
-  if (num_rows < 1 || bins < 1 || bins > INT32_MAX || F > ((int64_t)1 << 30))
-    return fail(RN_ERR_INVALID_ARGUMENT, "num_rows = %lld, bins = %lld or F = %lld is out of range", (long long)num_rows,
-                (long long)bins, (long long)F);
+int peakfit_fit(int device, const FitArgs &a, int shape, int linear, int P, const double *origin, const double *centres,
+                const double *widths) {
+  if (int rc = rn_fit::check_sizes(a, g_error)) return rc;
   if (P < 1 || P > RN_PEAKFIT_MAX_PEAKS)
-    return fail(RN_ERR_INVALID_ARGUMENT, "P = %d peaks is outside 1 .. %d", P, RN_PEAKFIT_MAX_PEAKS);
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT, "P = %d peaks is outside 1 .. %d", P, RN_PEAKFIT_MAX_PEAKS);
   if (shape != RN_PEAKFIT_LORENTZIAN && shape != RN_PEAKFIT_DHO)
-    return fail(RN_ERR_INVALID_ARGUMENT, "shape = %d is neither RN_PEAKFIT_LORENTZIAN nor RN_PEAKFIT_DHO", shape);
-  if (linear != 0 && linear != 1) return fail(RN_ERR_INVALID_ARGUMENT, "linear = %d is neither 0 nor 1", linear);
-  if (F == 0) return RN_OK;
-  if (!rows || !row_index || !first_bin || !num_bins || !origin || !centres || !widths || !out || !status || !iterations)
-    return fail(RN_ERR_INVALID_ARGUMENT, "a null pointer");
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT, "shape = %d is neither RN_PEAKFIT_LORENTZIAN nor RN_PEAKFIT_DHO", shape);
+  if (linear != 0 && linear != 1) return g_error.fail(RN_ERR_INVALID_ARGUMENT, "linear = %d is neither 0 nor 1", linear);
+  if (a.F == 0) return RN_OK;
+  if (a.any_null() || !origin || !centres || !widths) return g_error.fail(RN_ERR_INVALID_ARGUMENT, "a null pointer");
   const int parameters = 3 * P + 1 + linear;
-  for (int64_t f = 0; f < F; ++f) {
-    if (row_index[f] < 0 || row_index[f] >= num_rows)
-      return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: row %lld is outside [0, %lld)", (long long)f,
-                  (long long)row_index[f], (long long)num_rows);
-    if (num_bins[f] < parameters + 2)
-      return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: %lld bins, a fit of %d parameters needs at least p + 2 = %d",
-                  (long long)f, (long long)num_bins[f], parameters, parameters + 2);
-    if (first_bin[f] < 0 || first_bin[f] > bins || num_bins[f] > bins - first_bin[f])
-      return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: bins [%lld, %lld + %lld) are outside [0, %lld)", (long long)f,
-                  (long long)first_bin[f], (long long)first_bin[f], (long long)num_bins[f], (long long)bins);
-    if (!std::isfinite(origin[f])) return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: the origin is not finite", (long long)f);
+  for (int64_t f = 0; f < a.F; ++f) {
+    if (int rc = rn_fit::check_row(a, f, g_error)) return rc;
+    if (a.num_bins[f] < parameters + 2)
+      return g_error.fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: %lld bins, a fit of %d parameters needs at least p + 2 = %d",
+                          (long long)f, (long long)a.num_bins[f], parameters, parameters + 2);
+    if (int rc = rn_fit::check_window(a, f, g_error)) return rc;
+    if (!std::isfinite(origin[f]))
+      return g_error.fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: the origin is not finite", (long long)f);
     if (shape == RN_PEAKFIT_DHO && !(origin[f] > 0.0))
-      return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: origin %g is not positive, as RN_PEAKFIT_DHO needs", (long long)f,
-                  origin[f]);
+      return g_error.fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: origin %g is not positive, as RN_PEAKFIT_DHO needs",
+                          (long long)f, origin[f]);
     for (int k = 0; k < P; ++k) {
       const double centre = centres[f * P + k], width = widths[f * P + k];
-      if (!(centre >= 0.0 && centre <= (double)(num_bins[f] - 1)))  // (not so for NaN)
-        return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: centre %d = %g is outside [0, %lld]", (long long)f, k, centre,
-                    (long long)(num_bins[f] - 1));
+      if (!(centre >= 0.0 && centre <= (double)(a.num_bins[f] - 1)))  // (not so for NaN)
+        return g_error.fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: centre %d = %g is outside [0, %lld]", (long long)f, k,
+                            centre, (long long)(a.num_bins[f] - 1));
       if (!std::isfinite(width) || !(width > 0.0))
-        return fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: width %d = %g is not positive and finite", (long long)f, k, width);
+        return g_error.fail(RN_ERR_INVALID_ARGUMENT, "fit %lld: width %d = %g is not positive and finite", (long long)f, k,
+                            width);
     }
   }
-  int devices = 0;
-  if (hipGetDeviceCount(&devices) != hipSuccess || device < 0 || device >= devices)
-    return fail(RN_ERR_NO_DEVICE, "device %d is not one of the %d GPUs", device, devices);
-  if (hipSetDevice(device) != hipSuccess) return fail(RN_ERR_HIP, "hipSetDevice(%d) failed", device);
+  if (int rc = rn_spectrum::select_device(device, g_error)) return rc;
 
-  std::lock_guard<std::mutex> lock(g_mutex);
-  if (g_device != device) {  // (buffers belong to the device they were allocated on)
-    if (g_device >= 0 && hipSetDevice(g_device) == hipSuccess) {
-      g_rows.release();
-      g_table.release();
-      g_real.release();
-      g_out.release();
-      g_flags.release();
-      (void)hipSetDevice(device);
-    }
-    g_device = device;
-  }
-  const size_t count = (size_t)F;
-  const size_t row_bytes = (size_t)num_rows * (size_t)bins * sizeof(double);
-  if ((rows_on_host && g_rows.ensure(row_bytes, Fit::kGrowOnly) != RN_OK) ||
-      g_table.ensure(3 * count * sizeof(int64_t), Fit::kGrowOnly) != RN_OK ||
-      g_real.ensure((1 + 2 * (size_t)P) * count * sizeof(double), Fit::kGrowOnly) != RN_OK ||
-      g_out.ensure(count * kOutputs * sizeof(double), Fit::kGrowOnly) != RN_OK ||
-      g_flags.ensure(2 * count * sizeof(int32_t), Fit::kGrowOnly) != RN_OK)
-    return fail(RN_ERR_OUT_OF_MEMORY, "no device memory for %lld fits of %lld rows of %lld bins", (long long)F,
-                (long long)num_rows, (long long)bins);
-  auto *d_table = static_cast<int64_t *>(g_table.ptr);
-  auto *d_real = static_cast<double *>(g_real.ptr);
-  auto *d_out = static_cast<double *>(g_out.ptr);
-  auto *d_flags = static_cast<int32_t *>(g_flags.ptr);
-  double *d_centres = d_real + count, *d_widths = d_real + (1 + (size_t)P) * count;
-  const double *d_rows = rows;
-  hipError_t e = hipSuccess;
-  auto ok = [&](hipError_t status_of_call) {
-    if (e == hipSuccess) e = status_of_call;
-    return e == hipSuccess;
-  };
-  if (rows_on_host) {
-    ok(hipMemcpyAsync(g_rows.ptr, rows, row_bytes, hipMemcpyHostToDevice, stream));
-    d_rows = static_cast<const double *>(g_rows.ptr);
-  }
-  ok(hipMemcpyAsync(d_table, row_index, count * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-  ok(hipMemcpyAsync(d_table + count, first_bin, count * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-  ok(hipMemcpyAsync(d_table + 2 * count, num_bins, count * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-  ok(hipMemcpyAsync(d_real, origin, count * sizeof(double), hipMemcpyHostToDevice, stream));
-  ok(hipMemcpyAsync(d_centres, centres, (size_t)P * count * sizeof(double), hipMemcpyHostToDevice, stream));
-  ok(hipMemcpyAsync(d_widths, widths, (size_t)P * count * sizeof(double), hipMemcpyHostToDevice, stream));
-  if (e == hipSuccess) {
-    const unsigned blocks = (unsigned)((F + kWaves - 1) / kWaves);
-    kernel_of(P, linear != 0, shape == RN_PEAKFIT_DHO)<<<blocks, kWaves * kLanes, 0, stream>>>(
-        d_rows, bins, d_table, d_table + count, d_table + 2 * count, d_real, d_centres, d_widths, F, max_iterations,
-        d_out, d_flags, d_flags + count);
+  std::lock_guard<std::mutex> lock(g_fits.mutex);
+  g_fits.bind(device);
+  const size_t count = (size_t)a.F;
+  if (g_fits.ensure(a) != RN_OK || g_real.ensure((1 + 2 * (size_t)P) * count * sizeof(double), Fit::kGrowOnly) != RN_OK)
+    return g_fits.no_memory(a, g_error);
+  double *d_origin = g_real.as<double>(), *d_centres = d_origin + count, *d_widths = d_centres + (size_t)P * count;
+  rn_spectrum::FirstError ok;
+  const double *d_rows = g_fits.stage(a, ok);
+  ok(hipMemcpyAsync(d_origin, origin, count * sizeof(double), hipMemcpyHostToDevice, a.stream));
+  ok(hipMemcpyAsync(d_centres, centres, (size_t)P * count * sizeof(double), hipMemcpyHostToDevice, a.stream));
+  ok(hipMemcpyAsync(d_widths, widths, (size_t)P * count * sizeof(double), hipMemcpyHostToDevice, a.stream));
+  if (ok.first == hipSuccess) {
+    kernel_of(P, linear != 0, shape == RN_PEAKFIT_DHO)<<<rn_fit::fit_blocks(a.F, kWaves), kWaves * kLanes, 0, a.stream>>>(
+        d_rows, a.bins, g_fits.column(a, 0), g_fits.column(a, 1), g_fits.column(a, 2), d_origin, d_centres, d_widths, a.F,
+        a.max_iterations, g_fits.d_out(), g_fits.d_status(), g_fits.d_iterations(a));
     ok(hipGetLastError());
   }
-  ok(hipMemcpyAsync(out, d_out, count * kOutputs * sizeof(double), hipMemcpyDeviceToHost, stream));
-  ok(hipMemcpyAsync(status, d_flags, count * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  ok(hipMemcpyAsync(iterations, d_flags + count, count * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failure: the buffers may be in use)
-  ok(waited);
-  if (e != hipSuccess) return fail(RN_ERR_HIP, "%s", hipGetErrorString(e));
-  return RN_OK;
+  return g_fits.finish(a, ok, g_error);
 }
 
 }  // namespace
@@ -518,8 +452,8 @@ extern "C" int rn_peakfit_fit(int device, const double *rows, int64_t num_rows, 
                               const int64_t *first_bin, const int64_t *num_bins, int64_t F, int shape, int linear, int P,
                               const double *origin, const double *centres, const double *widths, int max_iterations,
                               double *out, int32_t *status, int32_t *iterations) {
-  return peakfit_fit(device, rows, true, num_rows, bins, row_index, first_bin, num_bins, F, shape, linear, P, origin,
-                     centres, widths, max_iterations, out, status, iterations, nullptr);
+  return peakfit_fit(device, {rows, true, num_rows, bins, row_index, first_bin, num_bins, F, max_iterations, out, status,
+                              iterations, nullptr}, shape, linear, P, origin, centres, widths);
 }
 
 extern "C" int rn_peakfit_fit_device(int device, const double *d_rows, int64_t num_rows, int64_t bins,
@@ -527,10 +461,10 @@ extern "C" int rn_peakfit_fit_device(int device, const double *d_rows, int64_t n
                                      int64_t F, int shape, int linear, int P, const double *origin, const double *centres,
                                      const double *widths, int max_iterations, double *out, int32_t *status,
                                      int32_t *iterations, void *stream) {
-  return peakfit_fit(device, d_rows, false, num_rows, bins, row_index, first_bin, num_bins, F, shape, linear, P, origin,
-                     centres, widths, max_iterations, out, status, iterations, static_cast<hipStream_t>(stream));
+  return peakfit_fit(device, {d_rows, false, num_rows, bins, row_index, first_bin, num_bins, F, max_iterations, out, status,
+                              iterations, static_cast<hipStream_t>(stream)}, shape, linear, P, origin, centres, widths);
 }
 
 extern "C" int rn_peakfit_window_capacity(void) { return kCapacity; }
 
-extern "C" const char *rn_peakfit_last_error(void) { return g_error.c_str(); }
+extern "C" const char *rn_peakfit_last_error(void) { return g_error.text.c_str(); }

@@ -3,18 +3,15 @@
 // The host finds the U bins with a nonzero weight in some row and lays out the rows of the transform, row 2 i + part of
 // active bin i padded with -1 to Rp = a multiple of 64, and the weights of those rows, [B][Rp], divided by Q and zero
 // in the padding.  Positions and alpha are staged on the device (host entry) or read where they are (device entry)
-// through the Source front end of the MD reducers (spectrum_common.hpp): the producer's stream is synchronised first
-// and all work runs on the null stream.  The segments go through in equal blocks, the largest whose V and chunk
-// partials fit workspace_limit beside the phase table, the weights and the result: per block one transform launch and
-// one update, which adds to the result of the blocks before it.  All device arrays live in one workspace per process,
-// under one lock; the entry returns when moments is in the host array.  hipFFT is not used.
+// through Source (entry_runtime.hpp): the producer's stream is synchronised before the lock is taken, all work runs on
+// the null stream, and the entry waits for the device before it returns, when moments is in the host array.  The
+// segments go through in equal blocks, the largest whose V and chunk partials fit workspace_limit beside the phase
+// table, the weights and the result: per block one transform launch and one update, which adds to the result of the
+// blocks before it.  hipFFT is not used (spectrum_segment_core.hpp is here for num_bins, check_table and balanced).
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <string>
 #include <vector>
 
 #include "../../include/rn_bandmodes.h"
@@ -24,54 +21,45 @@
 namespace {
 
 using rn_spectrum::DeviceBuffer;
+using rn_spectrum::first_non_finite;
 using rn_spectrum::Fit;
 using rn_spectrum::PhaseTimer;
 using rn_spectrum::Source;
 
-thread_local std::string g_error;
-
-int fail(int rc, const char *format, ...) {
-  char text[512];
-  va_list args;
-  va_start(args, format);
-  vsnprintf(text, sizeof text, format, args);
-  va_end(args);
-  g_error = text;
-  return rc;
-}
-
-std::mutex g_mutex;
-int g_device = -1;
+thread_local rn_spectrum::ErrorText g_error;
 DeviceBuffer g_pos, g_alpha, g_sqrt_mass, g_starts, g_taper, g_table, g_row_bins, g_weights, g_transforms, g_partials,
     g_moments;
-PhaseTimer g_timer;  // copies to the device and the phase table, transforms, rank updates, the copy to the host; under g_mutex
+rn_spectrum::Workspace g_workspace{&g_pos,      &g_alpha,   &g_sqrt_mass,  &g_starts,   &g_taper,  &g_table,
+                                   &g_row_bins, &g_weights, &g_transforms, &g_partials, &g_moments};
+// copies to the device and the phase table, transforms, rank updates, the copy to the host; under the workspace's mutex
+PhaseTimer g_timer;
 
 int bm_moments(int device, Source pos, const double *lattice, int64_t S, int32_t N, const double *masses, Source alpha,
                int64_t W, const int64_t *starts, int64_t Q, const double *taper, const double *bin_weights, int64_t B,
                int64_t bins, size_t workspace_limit, double *moments) {
   if (!pos.data || !lattice || !masses || !starts || !taper || !bin_weights || !moments)
-    return fail(RN_ERR_INVALID_ARGUMENT, "a null pointer");
-  if (N < 1) return fail(RN_ERR_INVALID_ARGUMENT, "N = %d atoms is not positive", (int)N);
-  if (B < 1 || B > 65535) return fail(RN_ERR_INVALID_ARGUMENT, "B = %lld weight rows is not in [1, 65535]", (long long)B);
-  if (W < 3) return fail(RN_ERR_INVALID_ARGUMENT, "W = %lld frames per segment is less than 3", (long long)W);
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT, "a null pointer");
+  if (N < 1) return g_error.fail(RN_ERR_INVALID_ARGUMENT, "N = %d atoms is not positive", (int)N);
+  if (B < 1 || B > 65535)
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT, "B = %lld weight rows is not in [1, 65535]", (long long)B);
+  if (W < 3) return g_error.fail(RN_ERR_INVALID_ARGUMENT, "W = %lld frames per segment is less than 3", (long long)W);
   if (W - 1 > (int64_t)1 << 28)
-    return fail(RN_ERR_INVALID_ARGUMENT, "W = %lld frames per segment is more than 2^28 + 1", (long long)W);
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT, "W = %lld frames per segment is more than 2^28 + 1", (long long)W);
   if (bins != rn_spectrum::num_bins(W - 1))
-    return fail(RN_ERR_INVALID_ARGUMENT, "bins = %lld is not (W - 1 + 1) / 2 - 1 = %lld", (long long)bins,
-                (long long)rn_spectrum::num_bins(W - 1));
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT, "bins = %lld is not (W - 1 + 1) / 2 - 1 = %lld", (long long)bins,
+                        (long long)rn_spectrum::num_bins(W - 1));
   if (S < 1 || S > ((int64_t)1 << 40) || rn_spectrum::check_table(S, W, starts, Q, 1, bins) != RN_OK)
-    return fail(RN_ERR_INVALID_ARGUMENT,
-                "the start table is refused: Q = %lld segments of W = %lld frames, each start in [0, S - W], S = %lld",
-                (long long)Q, (long long)W, (long long)S);
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT,
+                        "the start table is refused: Q = %lld segments of W = %lld frames, each start in [0, S - W], S = %lld",
+                        (long long)Q, (long long)W, (long long)S);
   for (int32_t i = 0; i < N; ++i)
     if (!(std::isfinite(masses[i]) && masses[i] > 0.0))
-      return fail(RN_ERR_INVALID_ARGUMENT, "masses[%d] = %g is not finite and positive", (int)i, masses[i]);
-  for (int i = 0; i < 9; ++i)
-    if (!std::isfinite(lattice[i])) return fail(RN_ERR_INVALID_ARGUMENT, "lattice[%d] is not finite", i);
-  for (int64_t i = 0; i < B * bins; ++i)
-    if (!std::isfinite(bin_weights[i]))
-      return fail(RN_ERR_INVALID_ARGUMENT, "bin_weights[%lld][%lld] is not finite", (long long)(i / bins),
-                  (long long)(i % bins));
+      return g_error.fail(RN_ERR_INVALID_ARGUMENT, "masses[%d] = %g is not finite and positive", (int)i, masses[i]);
+  if (const int64_t i = first_non_finite(lattice, 9); i >= 0)
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT, "lattice[%d] is not finite", (int)i);
+  if (const int64_t i = first_non_finite(bin_weights, B * bins); i >= 0)
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT, "bin_weights[%lld][%lld] is not finite", (long long)(i / bins),
+                        (long long)(i % bins));
 
   // the rows of the transform and their weights
   const int64_t n = W - 1, K = (int64_t)3 * N, Kc = K + (alpha.data ? 6 : 0);
@@ -111,30 +99,19 @@ int bm_moments(int device, Source pos, const double *lattice, int64_t S, int32_t
     per_block = (per_block + 1) / 2;
   per_block = rn_spectrum::balanced(Q, per_block);
   if (fixed_bytes + block_bytes(per_block) > limit)
-    return fail(RN_ERR_OUT_OF_MEMORY,
-                "workspace_limit = %zu bytes: one segment of %lld rows x %lld columns needs %zu bytes beside the %zu of "
-                "the tables and the result", limit, (long long)Rp, (long long)Kp, block_bytes(1), fixed_bytes);
+    return g_error.fail(RN_ERR_OUT_OF_MEMORY,
+                        "workspace_limit = %zu bytes: one segment of %lld rows x %lld columns needs %zu bytes beside the %zu of "
+                        "the tables and the result", limit, (long long)Rp, (long long)Kp, block_bytes(1), fixed_bytes);
   if (rn::band_transform_workgroups(Kc, Rp, per_block) < 0 ||
       rn::band_chunks(per_block * Rp) * rn::band_pairs(Kc) > INT32_MAX)
-    return fail(RN_ERR_INVALID_ARGUMENT, "%lld rows x %lld columns exceed the grid (2^31 - 1 workgroups)", (long long)Rp,
-                (long long)Kp);
+    return g_error.fail(RN_ERR_INVALID_ARGUMENT, "%lld rows x %lld columns exceed the grid (2^31 - 1 workgroups)",
+                        (long long)Rp, (long long)Kp);
 
-  int devices = 0;
-  if (hipGetDeviceCount(&devices) != hipSuccess || device < 0 || device >= devices)
-    return fail(RN_ERR_NO_DEVICE, "device %d is not one of the %d GPUs", device, devices);
-  if (hipSetDevice(device) != hipSuccess) return fail(RN_ERR_HIP, "hipSetDevice(%d) failed", device);
-  if (pos.wait() != RN_OK) return fail(RN_ERR_HIP, "the producer's stream could not be synchronised");
+  if (int rc = rn_spectrum::select_device(device, g_error)) return rc;
+  if (pos.wait() != RN_OK) return g_error.fail(RN_ERR_HIP, "the producer's stream could not be synchronised");
 
-  std::lock_guard<std::mutex> lock(g_mutex);
-  DeviceBuffer *const buffers[] = {&g_pos, &g_alpha, &g_sqrt_mass, &g_starts, &g_taper, &g_table, &g_row_bins, &g_weights,
-                                   &g_transforms, &g_partials, &g_moments};
-  if (g_device != device) {  // (buffers belong to the device they were allocated on)
-    if (g_device >= 0 && hipSetDevice(g_device) == hipSuccess) {
-      for (DeviceBuffer *buffer : buffers) buffer->release();
-      (void)hipSetDevice(device);
-    }
-    g_device = device;
-  }
+  std::lock_guard<std::mutex> lock(g_workspace.mutex);
+  g_workspace.bind(device);
   const double *d_pos = nullptr, *d_alpha = nullptr;
   g_timer.reset();
   g_timer.mark(0);
@@ -152,21 +129,17 @@ int bm_moments(int device, Source pos, const double *lattice, int64_t S, int32_t
   if (rc == RN_OK) rc = g_moments.ensure(result_bytes);
   if (rc != RN_OK) {
     g_timer.collect();
-    return fail(rc, "%s for %lld frames of %d atoms, %lld segments (%lld per block) of %lld rows x %lld columns",
-                rc == RN_ERR_OUT_OF_MEMORY ? "no device memory" : "the copy of the positions or of alpha failed",
-                (long long)S, (int)N, (long long)Q, (long long)per_block, (long long)Rp, (long long)Kp);
+    return g_error.fail(rc, "%s for %lld frames of %d atoms, %lld segments (%lld per block) of %lld rows x %lld columns",
+                        rc == RN_ERR_OUT_OF_MEMORY ? "no device memory" : "the copy of the positions or of alpha failed",
+                        (long long)S, (int)N, (long long)Q, (long long)per_block, (long long)Rp, (long long)Kp);
   }
-  hipError_t e = hipSuccess;
-  auto ok = [&](hipError_t status_of_call) {
-    if (e == hipSuccess) e = status_of_call;
-    return e == hipSuccess;
-  };
+  rn_spectrum::FirstError ok;
   ok(hipMemcpy(g_sqrt_mass.ptr, sqrt_mass.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
   ok(hipMemcpy(g_starts.ptr, starts, (size_t)Q * sizeof(int64_t), hipMemcpyHostToDevice));
   ok(hipMemcpy(g_taper.ptr, taper, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
   ok(hipMemcpy(g_row_bins.ptr, row_bins.data(), (size_t)Rp * sizeof(int), hipMemcpyHostToDevice));
   ok(hipMemcpy(g_weights.ptr, weights.data(), weights.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (e == hipSuccess) {
+  if (ok.first == hipSuccess) {
     rn::launch_band_phases(n, g_table.as<double>(), nullptr);
     for (int64_t q0 = 0; q0 < Q; q0 += per_block) {
       const int64_t count = std::min(per_block, Q - q0);
@@ -186,7 +159,7 @@ int bm_moments(int device, Source pos, const double *lattice, int64_t S, int32_t
   g_timer.collect();
   const hipError_t waited = hipDeviceSynchronize();  // (also after a failure: the buffers may be in use)
   ok(waited);
-  if (e != hipSuccess) return fail(RN_ERR_HIP, "%s", hipGetErrorString(e));
+  if (ok.first != hipSuccess) return g_error.fail(RN_ERR_HIP, "%s", hipGetErrorString(ok.first));
   return RN_OK;
 }
 
@@ -208,8 +181,8 @@ extern "C" int rn_bm_moments_device(int device, const double *d_pos, const doubl
                     starts, Q, taper, bin_weights, B, bins, workspace_limit, moments);
 }
 
-extern "C" int rn_bm_set_profiling(int enabled) { return g_timer.set_profiling(g_mutex, enabled); }
+extern "C" int rn_bm_set_profiling(int enabled) { return g_timer.set_profiling(g_workspace.mutex, enabled); }
 
-extern "C" int rn_bm_phase_times(double *millis) { return g_timer.phase_times(g_mutex, millis); }
+extern "C" int rn_bm_phase_times(double *millis) { return g_timer.phase_times(g_workspace.mutex, millis); }
 
-extern "C" const char *rn_bm_last_error(void) { return g_error.c_str(); }
+extern "C" const char *rn_bm_last_error(void) { return g_error.text.c_str(); }

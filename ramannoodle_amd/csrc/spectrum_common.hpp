@@ -1,16 +1,17 @@
 // What the on-device MD spectrum reducers share (spectrum.hip, spectrum_polarized.hip, spectrum_partial.hip,
 // spectrum_segments.hip, spectrum_ensemble.hip, spectrum_vdos.hip, spectrum_mode_vdos.hip, spectrum_modes.hip): the hipFFT loader, the
-// series-length arithmetic, RAII holders for plans and device buffers, the most-recently-used plan cache, the argument /
-// device check, the host-or-HBM source of a call and the two per-slot kernels of the polarized, partial and segment
-// pipelines.  The three whole-run reducers each keep their own signal builder, power / contraction kernel, plans struct,
-// workspace arithmetic and pipeline; the segment reducers (the last five files) share those through
-// spectrum_segment_core.hpp, and the two that read positions share their front end through spectrum_steps.hpp.
+// series-length arithmetic, the RAII holder for plans, the most-recently-used plan cache, the argument / device check
+// and the two per-slot kernels of the polarized, partial and segment pipelines; the holder for device buffers and the
+// host-or-HBM source of a call come from entry_runtime.hpp.  The three whole-run reducers each keep their own signal
+// builder, power / contraction kernel, plans struct, workspace arithmetic and pipeline; the segment reducers (the last
+// five files) share those through spectrum_segment_core.hpp, and the two that read positions share their front end
+// through spectrum_steps.hpp.
 //
 // Two decisions that hold for every reducer:
-//  * Buffer sizing.  A buffer that `workspace_limit` counts (the weights, the taper, the polarized output block, and the fixed
-//    x / p / c / out buffers of an entry) is sized with Fit::kExact: it is reallocated whenever the size differs, so a
-//    cached entry never holds more than the limit of the call that uses it.  The staged copies of a host input
-//    (`alpha`, `incr`) are outside the accounting by rn_potgnn.h's own words and use Fit::kGrowOnly.
+//  * Buffer sizing.  The rule is at the head of entry_runtime.hpp (Fit::kExact for what `workspace_limit` counts,
+//    Fit::kGrowOnly for the rest).  Here the limit counts the weights, the taper, the polarized output block and the
+//    fixed x / p / c / out buffers of an entry; the staged copies of a host input (`alpha`, `incr`) are outside the
+//    accounting by rn_potgnn.h's own words.
 //  * Shrink and retry.  The polarized reducer shrinks G (pairs per group, then balanced over ceil(21/G) groups), the
 //    partial reducer shrinks B (rows per block, capped by the row count) and the segment reducers shrink B and R
 //    (segments and rows per block) together.  The three differ in the key, the balancing, the per-slot cost and what
@@ -29,6 +30,7 @@
 #include <mutex>
 
 #include "../../include/rn_potgnn.h"
+#include "entry_runtime.hpp"
 
 namespace rn_spectrum {
 
@@ -144,37 +146,6 @@ struct FftPlan {
   }
 };
 
-enum class Fit { kExact, kGrowOnly };  // which rule applies to which buffer: see the head of this file
-
-// a device allocation, freed with its holder
-struct DeviceBuffer {
-  void *ptr = nullptr;
-  size_t bytes = 0;
-  DeviceBuffer() = default;
-  DeviceBuffer(const DeviceBuffer &) = delete;
-  DeviceBuffer &operator=(const DeviceBuffer &) = delete;
-  ~DeviceBuffer() { release(); }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    bytes = 0;
-  }
-  int ensure(size_t want, Fit fit = Fit::kExact) {
-    if (ptr && (fit == Fit::kExact ? bytes == want : bytes >= want)) return RN_OK;
-    release();
-    if (hipMalloc(&ptr, want) != hipSuccess) {
-      ptr = nullptr;
-      return RN_ERR_OUT_OF_MEMORY;
-    }
-    bytes = want;
-    return RN_OK;
-  }
-  template <class T>
-  T *as() const {
-    return static_cast<T *>(ptr);
-  }
-};
-
 // Most-recently-used cache of one reducer's plans (front = most recent), instantiated once per reducer so that the
 // caches stay apart and each keeps kCacheEntries entries.  The caller holds `mutex` for the whole call.
 template <class Entry>
@@ -212,26 +183,5 @@ inline int check_call(std::initializer_list<const void *> pointers, int64_t N, i
   if (hipSetDevice(device) != hipSuccess) return RN_ERR_HIP;
   return RN_OK;
 }
-
-// Where a call's time series is: a host array (staged into the entry's buffer, outside the workspace accounting), or
-// HBM, written by work on `stream`.  All reduction work runs on the null stream, so the producer's stream is
-// synchronised first.
-struct Source {
-  const double *data;
-  bool on_host;
-  void *stream;
-  static Source host(const double *data) { return {data, true, nullptr}; }
-  static Source device(const double *data, void *stream) { return {data, false, stream}; }
-  int wait() const {
-    return !on_host && stream && hipStreamSynchronize((hipStream_t)stream) != hipSuccess ? RN_ERR_HIP : RN_OK;
-  }
-  int on_device(DeviceBuffer &staging, size_t bytes, const double **d_data) const {
-    *d_data = data;
-    if (!on_host) return RN_OK;
-    if (int rc = staging.ensure(bytes, Fit::kGrowOnly)) return rc;
-    *d_data = staging.as<const double>();
-    return hipMemcpy(staging.ptr, data, bytes, hipMemcpyHostToDevice) == hipSuccess ? RN_OK : RN_ERR_HIP;
-  }
-};
 
 }  // namespace rn_spectrum

@@ -2,10 +2,10 @@
 // start table, whole and by atom group; spectrum_vdos.hip: the density of states, which takes the plans and the back
 // half; spectrum_mode_vdos.hip: the density of states by mode; spectrum_modes.hip: the self-spectra of many channels of
 // increments; spectrum_mode_matrix.hip: their band-summed pair spectra, which takes the channel builder, the table
-// check, the upload helper and the phase timer): the two power kernels of the whole spectra, the plans and work buffers of one (device, n, series per segment, segments per block, rows per block), the workspace arithmetic
+// check and the upload helper): the two power kernels of the whole spectra, the plans and work buffers of one (device, n, series per segment, segments per block, rows per block), the workspace arithmetic
 // that chooses the two block sizes, the loop that fits plans of those sizes into a workspace limit (get_segment_plans,
 // for any block chooser), and the pipeline from the transformed segments to the host rows; for the start-table reducers
-// also the check of the table, the upload helper and the phase timer, and the table builder of the whole spectra, which
+// also the check of the table and the upload helper, and the table builder of the whole spectra, which
 // spectrum_replicates.hip (replicate combinations of the segments' spectra) takes with the plans and the back half.
 // A reducer brings its segment builder (and, but for the whole spectra, its own power kernels) and its own PlanCache,
 // so the caches stay apart.  What only the two reducers that read positions share is in spectrum_steps.hpp.
@@ -344,63 +344,6 @@ inline int check_table(int64_t frames, int64_t W, const int64_t *starts, int64_t
     if (starts[q] < 0 || starts[q] > frames - W) return RN_ERR_INVALID_ARGUMENT;
   return RN_OK;
 }
-
-// HIP-event times of the four phases of a reducer's most recent call (builder, forward FFTs, power kernel, back half),
-// kept only while profiling is on; one per reducer, under its cache's mutex.  A phase lasts from its mark to the next
-// mark or close, because run_segments launches the transforms and the back half itself.  A reducer that launches
-// everything itself (the VDOS) marks all the same: on the null stream, with nothing between the end of a phase and the
-// next mark, that is the span of a begin / end pair plus one event.
-struct PhaseTimer {
-  bool enabled = false;
-  double millis[4] = {0, 0, 0, 0};
-  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> spans;
-  bool open = false;
-  void close() {
-    if (enabled && open) (void)hipEventRecord(spans.back().second.second, nullptr);
-    open = false;
-  }
-  void mark(int phase) {
-    if (!enabled) return;
-    close();
-    hipEvent_t a, b;
-    if (hipEventCreate(&a) != hipSuccess) return;
-    if (hipEventCreate(&b) != hipSuccess) {
-      (void)hipEventDestroy(a);
-      return;
-    }
-    (void)hipEventRecord(a, nullptr);
-    spans.push_back({phase, {a, b}});
-    open = true;
-  }
-  void reset() {
-    for (double &v : millis) v = 0.0;
-  }
-  void collect() {  // after the call's last copy to the host
-    if (!enabled) return;
-    close();
-    (void)hipDeviceSynchronize();
-    for (auto &s : spans) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, s.second.first, s.second.second) == hipSuccess) millis[s.first] += ms;
-      (void)hipEventDestroy(s.second.first);
-      (void)hipEventDestroy(s.second.second);
-    }
-    spans.clear();
-  }
-  // the bodies of a reducer's two extern "C" profiling entries
-  int set_profiling(std::mutex &mutex, int on) {
-    std::lock_guard<std::mutex> lock(mutex);
-    enabled = on != 0;
-    reset();
-    return RN_OK;
-  }
-  int phase_times(std::mutex &mutex, double *out) {
-    if (!out) return RN_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(mutex);
-    std::copy_n(millis, 4, out);
-    return RN_OK;
-  }
-};
 
 // slots of s.p (powers, `count` of them real) -> out: host float64[count][bins]
 inline int segment_rows_to_host(SegmentPlans &s, int count, double *out) {

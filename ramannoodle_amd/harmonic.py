@@ -184,7 +184,7 @@ def synthesize_device(ref, D, omega_dt, amp, phase, frames: int, first_frame: in
                                          C.c_void_p(omega_dt.ctypes.data), C.c_void_p(amp.ctypes.data),
                                          C.c_void_p(phase.ctypes.data), atoms, modes, runs, int(frames), int(first_frame),
                                          C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-    _check(lib, rc, "rn_ht_synthesize_device")
+    _lib.check_status(rc, "rn_ht_synthesize_device", "rn_ht_last_error")
     return out
 
 
@@ -199,21 +199,8 @@ def synthesize_download(ref, D, omega_dt, amp, phase, frames: int, first_frame: 
     rc = lib.rn_ht_synthesize(int(device), C.c_void_p(ref.ctypes.data), C.c_void_p(D.ctypes.data),
                               C.c_void_p(omega_dt.ctypes.data), C.c_void_p(amp.ctypes.data), C.c_void_p(phase.ctypes.data),
                               atoms, modes, runs, int(frames), int(first_frame), C.c_void_p(out.ctypes.data))
-    _check(lib, rc, "rn_ht_synthesize")
+    _lib.check_status(rc, "rn_ht_synthesize", "rn_ht_last_error")
     return out
-
-
-def _check(lib, rc: int, what: str) -> None:
-    from ramannoodle_amd import _lib
-    if rc == _lib.RN_OK:
-        return
-    from ramannoodle_amd.exceptions import DeviceError
-    text = (lib.rn_ht_last_error() or b"").decode()
-    if rc == _lib.RN_ERR_INVALID_ARGUMENT:
-        raise ValueError(f"{what}: {text}")
-    if rc == _lib.RN_ERR_OUT_OF_MEMORY:
-        raise MemoryError(f"{what}: {text}")
-    raise DeviceError(f"{what} failed ({rc}): {text}")
 
 
 def phonon_arguments(phonons, lattice, timestep, masses=None, modes=None, min_wavenumber: float = 1.0):

@@ -34,6 +34,8 @@ from dataclasses import dataclass
 import numpy as np
 from numpy.typing import NDArray
 
+from ramannoodle_amd._source import is_tensor, source
+
 STATUS_CONVERGED = 0
 STATUS_MAX_ITERATIONS = 1
 STATUS_DEGENERATE = 2
@@ -274,21 +276,13 @@ def window_capacity() -> int:
     return int(_lib.load().rn_lineshape_window_capacity())
 
 
-def _check_lineshape(rc: int, what: str) -> None:
-    from ramannoodle_amd import _lib
-    from ramannoodle_amd.exceptions import DeviceError
-    if rc == _lib.RN_OK:
-        return
-    text = (_lib.load().rn_lineshape_last_error() or b"").decode()
-    if rc == _lib.RN_ERR_INVALID_ARGUMENT:
-        raise ValueError(f"{what}: {text}")
-    if rc == _lib.RN_ERR_OUT_OF_MEMORY:
-        raise MemoryError(f"{what}: {text}")
-    raise DeviceError(f"{what} failed ({rc}): {text}")
-
-
-def _is_tensor(rows) -> bool:
-    return type(rows).__module__.split(".")[0] == "torch"
+def _rows_source(rows, device):
+    """``source`` of the rows of a fit, with the device of the call: the tensor's GPU, which ``device`` may only
+    confirm, or ``device`` for a host array."""
+    pointer, index, stream, rows = source(rows, "rows must be a contiguous float64 CUDA tensor (or a host array)")
+    if index is not None and device is not None and int(device) != index:
+        raise ValueError(f"rows are on GPU {index}, not on device {device}")
+    return pointer, int(device if index is None else index), stream, rows
 
 
 def fit_lorentzians(wavenumbers, rows, windows, device=None, max_iterations: int = 400) -> LorentzianFits:
@@ -304,25 +298,11 @@ def fit_lorentzians(wavenumbers, rows, windows, device=None, max_iterations: int
     current stream (``rn_lineshape_fit_device``); only the results travel to the host.  ``ValueError``, before any
     device work, for an axis that is not uniform, a window with fewer than 5 bins, ``lo >= hi``, a non-finite edge and
     a shape that fits none of the three forms."""
-    tensor = _is_tensor(rows)
-    if device is None and not tensor:
+    if device is None and not is_tensor(rows):
         return fit_lorentzians_host(wavenumbers, rows, windows, max_iterations)
     from ramannoodle_amd import _lib
     w, spacing = _axis(wavenumbers)
-    stream = None
-    if tensor:
-        import torch
-        if not (rows.is_cuda and rows.is_contiguous() and rows.dtype == torch.float64):
-            raise ValueError("rows must be a contiguous float64 CUDA tensor (or a host array)")
-        index = rows.device.index or 0
-        if device is not None and int(device) != index:
-            raise ValueError(f"rows are on GPU {index}, not on device {device}")
-        device = index
-        stream = torch.cuda.current_stream(rows.device).cuda_stream
-        pointer = rows.data_ptr()
-    else:
-        rows = np.ascontiguousarray(rows, dtype=np.float64)
-        pointer = rows.ctypes.data
+    pointer, device, stream, rows = _rows_source(rows, device)
     shape = tuple(rows.shape)
     _check_rows(shape, w)
     max_iterations = _check_iterations(max_iterations)
@@ -333,11 +313,11 @@ def fit_lorentzians(wavenumbers, rows, windows, device=None, max_iterations: int
     num_rows = int(np.prod(shape[:-1], dtype=np.int64))
     entry = "rn_lineshape_fit" if stream is None else "rn_lineshape_fit_device"
     tail = () if stream is None else (C.c_void_p(stream),)
-    rc = getattr(_lib.load(), entry)(int(device), C.c_void_p(pointer), num_rows, len(w), C.c_void_p(row_index.ctypes.data),
+    rc = getattr(_lib.load(), entry)(device, C.c_void_p(pointer), num_rows, len(w), C.c_void_p(row_index.ctypes.data),
                                      C.c_void_p(first.ctypes.data), C.c_void_p(bins.ctypes.data), count, max_iterations,
                                      C.c_void_p(out.ctypes.data), C.c_void_p(status.ctypes.data),
                                      C.c_void_p(iterations.ctypes.data), *tail)
-    _check_lineshape(rc, entry)
+    _lib.check_status(rc, entry, "rn_lineshape_last_error")
     return _results(w, spacing, first, leading, out, status, iterations)
 
 

@@ -51,9 +51,10 @@ from dataclasses import dataclass
 import numpy as np
 from numpy.typing import NDArray
 
+from ramannoodle_amd._source import is_tensor
 from ramannoodle_amd.lineshape import (_SPEED_OF_LIGHT, _STEP_TOLERANCE, STATUS_CONVERGED, STATUS_DEGENERATE,
                                        STATUS_MAX_ITERATIONS, STATUS_STALLED, _axis, _check_iterations, _check_rows,
-                                       _fit_table, _is_tensor)
+                                       _fit_table, _rows_source)
 
 MAX_PEAKS = 4       # RN_PEAKFIT_MAX_PEAKS
 OUTPUTS = 32        # RN_PEAKFIT_OUTPUTS
@@ -356,19 +357,6 @@ def window_capacity() -> int:
     return int(_lib.load().rn_peakfit_window_capacity())
 
 
-def _check_peakfit(rc: int, what: str) -> None:
-    from ramannoodle_amd import _lib
-    from ramannoodle_amd.exceptions import DeviceError
-    if rc == _lib.RN_OK:
-        return
-    text = (_lib.load().rn_peakfit_last_error() or b"").decode()
-    if rc == _lib.RN_ERR_INVALID_ARGUMENT:
-        raise ValueError(f"{what}: {text}")
-    if rc == _lib.RN_ERR_OUT_OF_MEMORY:
-        raise MemoryError(f"{what}: {text}")
-    raise DeviceError(f"{what} failed ({rc}): {text}")
-
-
 def fit_peaks_multi(wavenumbers, rows, windows, centres, hwhm=None, shape: str = "lorentzian",
                     baseline: str = "constant", device=None, max_iterations: int = 400) -> PeakFits:
     """Fit ``P`` peaks on a constant or linear baseline to each window of ``rows`` ``(..., bins)`` on the uniform axis
@@ -386,25 +374,11 @@ def fit_peaks_multi(wavenumbers, rows, windows, centres, hwhm=None, shape: str =
     (``rn_peakfit_fit_device``); only the results travel to the host.  ``ValueError``, before any device work, for what
     ``fit_lorentzians`` refuses, a centre outside its window, more than 4 peaks, fewer than ``p + 2`` bins, an unknown
     shape or baseline, and ``"dho"`` on a window whose first bin is at or below 0 cm^-1."""
-    tensor = _is_tensor(rows)
-    if device is None and not tensor:
+    if device is None and not is_tensor(rows):
         return fit_peaks_host(wavenumbers, rows, windows, centres, hwhm, shape, baseline, max_iterations)
     from ramannoodle_amd import _lib
     w, spacing = _axis(wavenumbers)
-    stream = None
-    if tensor:
-        import torch
-        if not (rows.is_cuda and rows.is_contiguous() and rows.dtype == torch.float64):
-            raise ValueError("rows must be a contiguous float64 CUDA tensor (or a host array)")
-        index = rows.device.index or 0
-        if device is not None and int(device) != index:
-            raise ValueError(f"rows are on GPU {index}, not on device {device}")
-        device = index
-        stream = torch.cuda.current_stream(rows.device).cuda_stream
-        pointer = rows.data_ptr()
-    else:
-        rows = np.ascontiguousarray(rows, dtype=np.float64)
-        pointer = rows.ctypes.data
+    pointer, device, stream, rows = _rows_source(rows, device)
     shape_of_rows = tuple(rows.shape)
     _check_rows(shape_of_rows, w)
     max_iterations = _check_iterations(max_iterations)
@@ -416,10 +390,10 @@ def fit_peaks_multi(wavenumbers, rows, windows, centres, hwhm=None, shape: str =
     num_rows = int(np.prod(shape_of_rows[:-1], dtype=np.int64))
     entry = "rn_peakfit_fit" if stream is None else "rn_peakfit_fit_device"
     tail = () if stream is None else (C.c_void_p(stream),)
-    rc = getattr(_lib.load(), entry)(int(device), C.c_void_p(pointer), num_rows, len(w), C.c_void_p(row_index.ctypes.data),
+    rc = getattr(_lib.load(), entry)(device, C.c_void_p(pointer), num_rows, len(w), C.c_void_p(row_index.ctypes.data),
                                      C.c_void_p(first.ctypes.data), C.c_void_p(bins.ctypes.data), count, int(dho),
                                      int(linear), peaks, C.c_void_p(origin.ctypes.data), C.c_void_p(centres.ctypes.data),
                                      C.c_void_p(widths.ctypes.data), max_iterations, C.c_void_p(out.ctypes.data),
                                      C.c_void_p(status.ctypes.data), C.c_void_p(iterations.ctypes.data), *tail)
-    _check_peakfit(rc, entry)
+    _lib.check_status(rc, entry, "rn_peakfit_last_error")
     return _results(w, spacing, first, bins, leading, peaks, linear, out, status, iterations)
