@@ -220,6 +220,26 @@ int rn_potgnn_forward_cells_device(rn_potgnn *h, const double *d_positions, cons
                                    int use_float64, double *d_alpha, void *stream, int synchronize);
 
 /*
+ * Structure descriptors (an addition): desc[s][c] = (1 / E) sum_e edge_P[s][e][c], the mean over a frame's edges of the
+ * size_edge_embedding real columns of the edge embedding after the last message pass -- the rows the readout consumes,
+ * read once more before it in whatever layout the run keeps them (float32, split-f16 pairs, the narrow pipeline's
+ * destination order, float64), summed in float64 in an order that depends on the graph and the widths alone: a frame's
+ * descriptor has the same bits whatever S, chunk or lane it was evaluated with.  desc is f64[S * size_edge_embedding].
+ * One evaluation yields both outputs: with `alpha` (f64[S*9]) not NULL the polarizabilities of the same frames come
+ * with it, bit for bit those of rn_potgnn_calc_polarizabilities / _cells (rn_potgnn_forward_cells_device).  lattices NULL:
+ * the fixed cell; otherwise [S*9] as for the _cells entries, checked in the same way by the host entry.  S = 0 is a
+ * no-op.  Without descriptors asked for, no entry launches the pooling kernel.
+ * rn_potgnn_device_descriptors: everything in HBM; the work starts behind what `stream` holds at the call and `stream`
+ * continues behind it (rn_potgnn_forward_device with synchronize = 0).  The pooling kernel touches the caller's pointers
+ * one element at a time (d_desc[s * Fe + c], one thread each); tests/test_model_domain.py hands the entry views inside
+ * guarded buffers.
+ */
+int rn_potgnn_descriptors(rn_potgnn *h, const double *positions, const double *lattices, int64_t S, int use_float64,
+                          double *desc, double *alpha);
+int rn_potgnn_device_descriptors(rn_potgnn *h, const double *d_positions, const double *d_lattices, int64_t S,
+                                 int use_float64, double *d_desc, double *d_alpha, void *stream);
+
+/*
  * Replaces PotGNN.forward for host callers (_gnn.py:617-665, eval mode):
  * host f64 positions -> host f32[S*6] standardised 6-vectors.
  */

@@ -54,6 +54,8 @@ SIGNATURES = {
     "rn_potgnn_calc_polarizabilities_cells": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P]),
     "rn_potgnn_calc_polarizabilities_cells_to_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
     "rn_potgnn_forward_cells_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, C.c_int]),
+    "rn_potgnn_descriptors": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P]),
+    "rn_potgnn_device_descriptors": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "rn_potgnn_forward_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int]),
     "rn_potgnn_forward_device_f64": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int]),
     "rn_potgnn_calc_polarizabilities_async": (C.c_int, [_P, _P, C.c_int64, _P]),
@@ -244,6 +246,22 @@ BM_SIGNATURES = {
     "rn_bm_last_error": (C.c_char_p, []),
 }
 
+# include/rn_select.h (the nearest-reference distance and farthest-point selection of ramannoodle_amd/selection.py; a
+# table of its own as well)
+SELECT_SIGNATURES = {
+    "rn_select_nearest": (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P]),
+    "rn_select_nearest_device": (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P, _P]),
+    "rn_select_farthest": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P,
+                                     _P]),
+    "rn_select_farthest_device": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64,
+                                            C.c_int64, _P, _P, _P]),
+    "rn_select_tile_rows": (C.c_int, []),
+    "rn_select_reference_splits": (C.c_int64, [C.c_int64, C.c_int64]),
+    "rn_select_set_profiling": (C.c_int, [C.c_int]),
+    "rn_select_phase_times": (C.c_int, [_P]),
+    "rn_select_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 
 
@@ -268,7 +286,8 @@ def load() -> C.CDLL:
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items())
                                       + list(LINESHAPE_SIGNATURES.items()) + list(PEAKFIT_SIGNATURES.items())
                                       + list(QH_SIGNATURES.items())
-                                      + list(HT_SIGNATURES.items()) + list(BM_SIGNATURES.items())):
+                                      + list(HT_SIGNATURES.items()) + list(BM_SIGNATURES.items())
+                                      + list(SELECT_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes

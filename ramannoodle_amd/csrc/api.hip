@@ -489,6 +489,44 @@ int rn_potgnn_forward_cells_device(rn_potgnn *h, const double *d_positions, cons
   });
 }
 
+int rn_potgnn_descriptors(rn_potgnn *h, const double *positions, const double *lattices, int64_t S, int use_float64,
+                          double *desc, double *alpha) {
+  if (const int rc = check_batch(h, S, {positions, desc}, "invalid positions / desc / S"); rc != kGo) return rc;
+  if (const int rc = check_lattices(h, lattices, S); rc != kGo) return rc;
+  return guarded(h, [&]() {
+    with_precision(h, use_float64 != 0, [&](auto t) {
+      host_descriptors<decltype(t)>(h, lattices, positions, S, desc, alpha);
+    });
+  });
+}
+
+int rn_potgnn_device_descriptors(rn_potgnn *h, const double *d_positions, const double *d_lattices, int64_t S, int use_float64,
+                                 double *d_desc, double *d_alpha, void *stream) {
+  if (const int rc = check_batch(h, S, {d_positions, d_desc}, "invalid positions / desc / S"); rc != kGo) return rc;
+  return guarded(h, [&]() {
+    hipStream_t user = (hipStream_t)stream;
+    if (use_float64) {
+      sync_host(h);  // the float64 copy of the weights is made from the host master copy
+      ForwardIO<double> io = device_io<double>(d_positions, d_lattices, nullptr, d_alpha, nullptr);
+      io.desc = d_desc;
+      forward_device<double>(h, io, S, user, false);
+      return;
+    }
+    const float *lat32 = nullptr;
+    if (d_lattices) {  // cast on the caller's stream into the handle's buffer, as rn_potgnn_forward_cells_device does
+      ensure_precision<float>(h);
+      for (auto &ln : h->f32.lanes)
+        if (ln.done.e) HIP_TRY(hipStreamWaitEvent(user, ln.done.e, 0));
+      h->cells_lat.ensure((size_t)S * 9 * sizeof(float));
+      launch_cast_from_f64<float>(d_lattices, h->cells_lat.as<float>(), S * 9, user);
+      lat32 = h->cells_lat.as<float>();
+    }
+    ForwardIO<float> io = device_io<float>(d_positions, lat32, nullptr, d_alpha, nullptr);
+    io.desc = d_desc;
+    forward_device<float>(h, io, S, user, false);
+  });
+}
+
 int rn_potgnn_calc_polarizabilities_f64(rn_potgnn *h, const double *positions, int64_t S, double *alpha) {
   if (const int rc = check_batch(h, S, {positions, alpha}, "invalid positions / alpha / S"); rc != kGo) return rc;
   return host_polarizabilities_f64(h, positions, nullptr, S, alpha);

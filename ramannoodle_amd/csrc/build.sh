@@ -11,7 +11,7 @@ FLAGS="-O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -Wall -Wno
 bdir="build${tag:+_$tag}"
 mkdir -p "$here/$bdir"
 pids=()
-hip_srcs="api forward reverse training api_interp graph_plan weight_layout kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_c2_pairs kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group kernels_mode kernels_covariance kernels_harmonic kernels_band kernels_interp spectrum spectrum_polarized spectrum_partial spectrum_segments spectrum_ensemble spectrum_replicates spectrum_vdos spectrum_mode_vdos spectrum_modes spectrum_mode_matrix spectrum_covariance spectrum_harmonic spectrum_band lineshape peakfit"
+hip_srcs="api forward reverse training api_interp graph_plan weight_layout kernels_agg kernels_gemm kernels_fused kernels_edge_ps kernels_c2_pairs kernels_node_atom kernels_narrow kernels_bwd kernels_train kernels_group kernels_mode kernels_covariance kernels_harmonic kernels_band kernels_interp spectrum spectrum_polarized spectrum_partial spectrum_segments spectrum_ensemble spectrum_replicates spectrum_vdos spectrum_mode_vdos spectrum_modes spectrum_mode_matrix spectrum_covariance spectrum_harmonic spectrum_band lineshape peakfit kernels_pool kernels_select select"
 objs=()
 for f in $hip_srcs; do
   o="$here/$bdir/$(basename "$f").o"

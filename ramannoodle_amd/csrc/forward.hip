@@ -394,6 +394,12 @@ void ChunkRun<T>::finish() {
   Precision<T> &P = prec<T>(h);
   const Graph &g = h->g;
   const Dims d = h->d;
+  if (io.desc) {  // the descriptors, from the rows the readout is about to read (nothing has written edge[cur] since the last pass)
+    const EdgeRows rows = sizeof(T) == 8 ? EdgeRows::kFloat64 : ch.pair_rows ? EdgeRows::kPairs : EdgeRows::kFloat32;
+    if (!edge_pool_supported(rows, d.FeP)) throw HipError{hipErrorInvalidValue, "descriptors: unsupported edge row width"};
+    launch_edge_pool(edge[cur], rows, S, g.E, d.Fe, d.FeP, io.desc, st());
+    HIP_TRY(hipGetLastError());
+  }
   if constexpr (sizeof(T) == 4) {
     if (ch.narrow) {  // readout MLP + edge tensors + per-frame mean in one launch
       Timer t(h, st(), K_READOUT_MLP);
@@ -550,7 +556,7 @@ void forward_device(rn_potgnn *h, const ForwardIO<T> &io, int64_t S, hipStream_t
   const int N = h->cfg.num_atoms;
   const int lanes = h->plan.num_lanes;
   behind_caller(h, user, P.lanes, lanes);
-  auto make = [&](int lane, int64_t first, int s) { return ChunkRun<T>(h, P.lanes[lane], io.at(first, N), s); };
+  auto make = [&](int lane, int64_t first, int s) { return ChunkRun<T>(h, P.lanes[lane], io.at(first, N, h->d.Fe), s); };
   int64_t done = 0;
   // Work chunks of EQUAL size: as many as the workspace demands, the frames split evenly among them (10 000 frames at a
   // capacity of 2344: five launches of 2000 instead of four of 2344 and one of 624, whose persistent workgroups idle through
@@ -623,6 +629,25 @@ void host_forward(rn_potgnn *h, const double *lattices, const int32_t *types, co
     HIP_TRY(hipMemcpy(raw.data(), h->io_alpha.p, raw.size() * sizeof(double), hipMemcpyDeviceToHost));
     pick_vec6(raw.data(), S, vec6);
   }
+}
+
+// rn_potgnn_descriptors: host_forward's staging with the descriptors [S][Fe] as the result, and the polarizabilities [S][9]
+// of the same evaluation when `alpha` is given.
+template <typename T>
+void host_descriptors(rn_potgnn *h, const double *lattices, const double *positions, int64_t S, double *desc, double *alpha) {
+  const size_t desc_bytes = (size_t)S * h->d.Fe * sizeof(double), alpha_bytes = (size_t)S * 9 * sizeof(double);
+  ForwardIO<T> io;
+  io.pos = stage<double>(h->io_pos, positions, (size_t)S * h->cfg.num_atoms * 3 * sizeof(double));
+  io.lat = stage_lattices<T>(h, lattices, S);
+  h->io_desc.ensure(desc_bytes);
+  io.desc = h->io_desc.as<double>();
+  if (alpha) {
+    h->io_alpha.ensure(alpha_bytes);
+    io.alpha = h->io_alpha.as<double>();
+  }
+  forward_device<T>(h, io, S, nullptr, true);
+  HIP_TRY(hipMemcpy(desc, h->io_desc.p, desc_bytes, hipMemcpyDeviceToHost));
+  if (alpha) HIP_TRY(hipMemcpy(alpha, h->io_alpha.p, alpha_bytes, hipMemcpyDeviceToHost));
 }
 
 // Chunk size.  Throughput rises monotonically with the frames per launch
@@ -851,7 +876,8 @@ void read_stage(rn_potgnn *h, int stage, int index, float *out, size_t out_capac
   template void behind_caller<T>(rn_potgnn *, hipStream_t, Lane<T> *, int);                                  \
   template void hand_back<T>(rn_potgnn *, hipStream_t, Lane<T> *, int, bool, bool);                          \
   template void forward_device<T>(rn_potgnn *, const ForwardIO<T> &, int64_t, hipStream_t, bool);            \
-  template void host_forward<T>(rn_potgnn *, const double *, const int32_t *, const double *, int64_t, double *, T *);
+  template void host_forward<T>(rn_potgnn *, const double *, const int32_t *, const double *, int64_t, double *, T *); \
+  template void host_descriptors<T>(rn_potgnn *, const double *, const double *, int64_t, double *, double *);
 RN_FORWARD_INSTANCES(float)
 RN_FORWARD_INSTANCES(double)
 

@@ -51,7 +51,8 @@ struct ForwardIO {
   double *alpha_raw = nullptr;     // [S][9] the standardised tensor in float64
   const T *lat = nullptr;          // [S][9] per-frame lattices, or null: the reference structure's
   const int *types = nullptr;      // [S][N] per-frame atom types, or null: the reference structure's
-  ForwardIO at(int64_t first, int N) const {  // the frames from `first` on: the one place that knows the strides
+  double *desc = nullptr;          // [S][Fe] structure descriptors: the mean of the final edge embedding's rows
+  ForwardIO at(int64_t first, int N, int Fe) const {  // the frames from `first` on: the one place that knows the strides
     auto from = [first](auto *p, int64_t stride) { return p ? p + first * stride : nullptr; };
     ForwardIO o;
     o.pos = from(pos, 3 * (int64_t)N);
@@ -61,6 +62,7 @@ struct ForwardIO {
     o.alpha_raw = from(alpha_raw, 9);
     o.lat = from(lat, 9);
     o.types = from(types, N);
+    o.desc = from(desc, Fe);
     return o;
   }
 };
@@ -105,6 +107,8 @@ void forward_device(rn_potgnn *h, const ForwardIO<T> &io, int64_t S, hipStream_t
 template <typename T>
 void host_forward(rn_potgnn *h, const double *lattices, const int32_t *types, const double *positions, int64_t S,
                   double *alpha, T *vec6);
+template <typename T>
+void host_descriptors(rn_potgnn *h, const double *lattices, const double *positions, int64_t S, double *desc, double *alpha);
 void staged_forward(rn_potgnn *h, const double *positions, const double *lattices, int64_t S, double *d_alpha, bool sync);
 void host_polarizabilities(rn_potgnn *h, const double *positions, const double *lattices, int64_t S, double *alpha);
 void read_stage(rn_potgnn *h, int stage, int index, float *out, size_t out_capacity, int64_t *rows, int64_t *cols);

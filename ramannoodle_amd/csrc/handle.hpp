@@ -93,7 +93,7 @@ struct rn_potgnn {
   rn::Precision<float> f32;
   rn::Precision<double> f64;
   // cached I/O staging for the host entry points
-  rn::DeviceBuf io_pos, io_alpha, io_vec6, io_lat, io_types;
+  rn::DeviceBuf io_pos, io_alpha, io_vec6, io_lat, io_types, io_desc;
   // pipelined host entry (rn_potgnn_calc_polarizabilities_async): two staging slots
   struct Slot {
     rn::DeviceBuf pos, alpha;

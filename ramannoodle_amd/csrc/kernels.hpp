@@ -336,6 +336,47 @@ void launch_covariance_chunks(const double *pos, int64_t K, const double *anchor
 void launch_covariance_reduce(const double *ws, const double *first_ws, int64_t K, const int64_t *block_chunks, int64_t B,
                               double *first, double *second, hipStream_t st);
 
+// Structure descriptors (kernels_pool.hip): desc float64 [S][Fe] = the mean over a frame's E edge rows of the Fe real
+// columns of `edge`, [S][E] rows of FeP columns in one of three layouts: float32, split-f16 pairs ([hi x 8][lo x 8] per
+// group of eight columns, the bytes of a float32 row) or float64.  edge_pool_supported: FeP is a whole number of 16-byte
+// (pairs: 32-byte) groups, at most 256 of them.
+enum class EdgeRows { kFloat32, kPairs, kFloat64 };
+bool edge_pool_supported(EdgeRows rows, int FeP);
+void launch_edge_pool(const void *edge, EdgeRows rows, int S, int E, int Fe, int FeP, double *desc, hipStream_t st);
+
+// Nearest reference row and farthest-point selection (kernels_select.hip;include/rn_select.h states them): X float64
+// [S][D], R float64 [M][D], params float64 [2][D] = (center, scale).  All device pointers; the grids need S, M < 2^31.
+constexpr int kSelectTile = 64;       // rows of X and of R per tile of the search
+constexpr int kSelectSliceRows = 128; // rows of X a workgroup of the selection owns
+struct SelectBest {                   // a candidate of a search (key ascending) or of a pick (value descending)
+  double value;
+  int64_t index;
+};
+// the ascending ranges of whole tiles a reference of M rows is split into for S rows of X, and the tiles of a range
+void select_splits(int64_t S, int64_t M, int64_t *splits, int64_t *tiles_per_split);
+// norms[j] = sum_c ((R[j][c] - center[c]) scale[c])^2, ascending c
+void launch_select_norms(const double *R, int64_t M, int64_t D, const double *params, double *norms, hipStream_t st);
+// partials [splits][S]: per row of X the lowest (|r'|^2 - 2 x'.r', j) of the range, (+inf, -1) when it has no candidate
+void launch_select_search(const double *X, int64_t S, const double *R, int64_t M, int64_t D, const double *params,
+                          const double *norms, int exclude_self, SelectBest *partials, hipStream_t st);
+// index[s] = the lowest candidate over the ranges (ascending, the lowest index on equal keys); dist2[s] from differences
+void launch_select_merge(const double *X, int64_t S, const double *R, int64_t M, int64_t D, const double *params,
+                         const SelectBest *partials, double *dist2, int64_t *index, hipStream_t st);
+// mean [D] = the column means of X, in a fixed order; mind[s] = d2(X_s, mean); mind[s] = value
+void launch_select_column_mean(const double *X, int64_t S, int64_t D, double *mean, hipStream_t st);
+void launch_select_distance_to(const double *X, int64_t S, int64_t D, const double *params, const double *point,
+                               double *mind, hipStream_t st);
+void launch_select_fill(double *mind, int64_t S, double value, hipStream_t st);
+// partials [select_slices(S)]: per slice of rows the highest (mind, s), the lowest s on equal values
+int64_t select_slices(int64_t S);
+void launch_select_argmax(const double *mind, int64_t S, SelectBest *partials, hipStream_t st);
+// One pick.  p = forced >= 0 ? forced : the highest of partials_in; picks[step] = p, pick_dist2[step] = first_of_none ?
+// +inf : its value; then, unless `last`, mind[s] = first_of_none ? d2(X_s, X_p) : min(mind[s], d2(X_s, X_p)), mind[p] =
+// -1 (picked: below every distance), and the slices' highest go to partials_out.
+void launch_select_pick(const double *X, int64_t S, int64_t D, const double *params, double *mind,
+                        const SelectBest *partials_in, SelectBest *partials_out, int64_t forced, int first_of_none, int last,
+                        int64_t step, int64_t *picks, double *pick_dist2, hipStream_t st);
+
 // Harmonic trajectories (kernels_harmonic.hip; include/rn_harmonic.h states them): ref float64 [K], D float64 [M][K],
 // omega_dt float64 [M], amp / phase float64 [R][M] -> out float64 [R][T][K], frame t of a call being the absolute frame
 // t0 + t.  All device pointers; harmonic_workgroups is the grid of the launch, -1 when it exceeds 2^31 - 1 workgroups.

@@ -223,6 +223,21 @@ def _mode_increments(polarizability_model, positions_ts, lattice_ts, phonons, la
         raise ValueError(f"polarizability_model and trajectory are incompatible: {exc}") from exc
 
 
+def _descriptors(model, positions_ts, lattice_ts, on_device: bool):
+    """What ``Trajectory.get_descriptors`` and ``TrajectoryEnsemble.get_descriptors`` share."""
+    if getattr(model, "calc_descriptors", None) is None:
+        raise TypeError("descriptors need a model with a latent space (the device PotGNN): calc_descriptors")
+    try:
+        if on_device:
+            import torch
+            verify_ndarray_shape("positions_batch", positions_ts, (None, model.num_atoms, 3))
+            positions = torch.tensor(positions_ts, dtype=torch.float64, device=f"cuda:{model.device_index}")
+            return model.calc_descriptors_device(positions, **_cells(lattice_ts, positions.device))
+        return model.calc_descriptors(positions_ts, **_cells(lattice_ts))
+    except ValueError as exc:
+        raise ValueError("polarizability_model and trajectory are incompatible") from exc
+
+
 class Trajectory(Dynamics, Sequence):
     """MD trajectory: fractional positions ``(S,N,3)`` (wrapped into the cell on
     construction) and a timestep in fs (``dynamics/_trajectory.py:16-109``).
@@ -279,6 +294,12 @@ class Trajectory(Dynamics, Sequence):
         except ValueError as exc:
             raise ValueError("polarizability_model and trajectory are incompatible") from exc
         return MDRamanSpectrum(polarizability_ts, self._timestep)
+
+    def get_descriptors(self, model, on_device: bool = False):
+        """Structure descriptors of every frame (an addition; ``PotGNN.calc_descriptors``): ``(S, columns)`` float64, a
+        host array, or with ``on_device=True`` a CUDA tensor that never leaves HBM (``calc_descriptors_device``).  A
+        trajectory with ``lattice_ts`` is evaluated in each frame's own cell."""
+        return _descriptors(model, self._positions_ts, self._lattice_ts, on_device)
 
     def get_partial_raman_spectrum(self, polarizability_model: PolarizabilityModel, groups, on_device: bool = False):
         """Atom-group decomposition of the spectrum (an addition): ``PartialMDRamanSpectrum`` of the per-group trapezoid
@@ -487,6 +508,11 @@ class TrajectoryEnsemble:
         except ValueError as exc:
             raise ValueError("polarizability_model and trajectory are incompatible") from exc
         return MDRamanEnsemble(self._split(polarizability_ts), self._timestep)
+
+    def get_descriptors(self, model, on_device: bool = False):
+        """Structure descriptors of the frames of every run, joined in the order of the runs (``Trajectory.get_descriptors``):
+        one evaluation."""
+        return _descriptors(model, self._positions_ts, self._lattice_ts, on_device)
 
     def get_partial_raman_spectrum(self, polarizability_model: PolarizabilityModel, groups, on_device: bool = False):
         """``PartialMDRamanEnsemble`` of the runs' per-group increments (``groups`` as for ``Trajectory``), from one

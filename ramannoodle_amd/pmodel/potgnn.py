@@ -544,6 +544,60 @@ class PotGNN(torch.nn.Module, DeviceIncrements, PolarizabilityModel):  # pylint:
         _lib.check(rc, handle, "rn_potgnn_forward_device")
         return out
 
+    @property
+    def num_descriptor_columns(self) -> int:
+        """The columns of a structure descriptor: the size of the edge embedding."""
+        return int(self._fe)
+
+    def calc_descriptors(self, positions_batch, lattices=None, float64: bool = False, with_polarizabilities: bool = False):
+        """Structure descriptors ``(S, num_descriptor_columns)`` float64 of fractional positions ``(S,N,3)`` (an addition;
+        ``rn_potgnn_descriptors``): per frame the mean over the edges of the edge embedding after the last message pass,
+        the rows the readout turns into the polarizability -- the model's own latent space, for
+        ``ramannoodle_amd.selection``.  ``lattices`` as for ``calc_polarizabilities``; ``float64`` runs the kernels
+        instantiated for ``double``.  With ``with_polarizabilities`` the result is ``(descriptors, polarizabilities
+        (S,3,3))`` from one evaluation, the polarizabilities bit for bit those of ``calc_polarizabilities``."""
+        pos = self._check_positions(positions_batch)
+        lat = None if lattices is None else self._check_lattices(lattices, pos.shape[0])
+        if self.training:
+            self.eval()
+        desc = np.empty((pos.shape[0], self.num_descriptor_columns), dtype=np.float64)
+        alpha = np.empty((pos.shape[0], 3, 3), dtype=np.float64) if with_polarizabilities else None
+        handle = self._ensure_handle()
+        rc = _lib.load().rn_potgnn_descriptors(handle, _ptr(pos), None if lat is None else _ptr(lat), pos.shape[0],
+                                               int(bool(float64)), _ptr(desc), None if alpha is None else _ptr(alpha))
+        _lib.check(rc, handle, "rn_potgnn_descriptors")
+        return (desc, alpha) if with_polarizabilities else desc
+
+    def calc_descriptors_device(self, positions: torch.Tensor, lattices=None, out: torch.Tensor | None = None,
+                                alpha_out: torch.Tensor | None = None, float64: bool = False) -> torch.Tensor:
+        """``calc_descriptors`` on a device-resident ``float64[S,N,3]`` tensor (``rn_potgnn_device_descriptors``):
+        returns a device ``float64[S, num_descriptor_columns]`` tensor (``out``, when given).  ``alpha_out``, a contiguous
+        ``float64[S,3,3]`` tensor on the same device, receives the polarizabilities of the same evaluation.  Work is
+        enqueued on torch's current stream; ``lattices`` as for ``calc_polarizabilities_device``."""
+        if not (positions.is_cuda and positions.dtype == torch.float64 and positions.is_contiguous()):
+            raise ValueError("positions must be a contiguous float64 device tensor")
+        if positions.dim() != 3 or tuple(positions.shape[1:]) != (self.num_atoms, 3):
+            raise ValueError(f"positions_batch has wrong shape: {tuple(positions.shape)} != "
+                             f"(_,{self.num_atoms},3)")
+        s, columns = positions.shape[0], self.num_descriptor_columns
+        if out is None:
+            out = torch.empty((s, columns), dtype=torch.float64, device=positions.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+                  and tuple(out.shape) == (s, columns) and out.device == positions.device):
+            raise ValueError(f"out must be a contiguous float64[{s},{columns}] tensor on {positions.device}")
+        if alpha_out is not None:
+            _check_out(alpha_out, s, positions.device.index)
+        if lattices is not None:
+            lattices = self._check_device_lattices(lattices, positions)
+        handle = self._ensure_handle()
+        stream = torch.cuda.current_stream(positions.device).cuda_stream
+        rc = _lib.load().rn_potgnn_device_descriptors(
+            handle, C.c_void_p(positions.data_ptr()), C.c_void_p(None if lattices is None else lattices.data_ptr()), s,
+            int(bool(float64)), C.c_void_p(out.data_ptr()), C.c_void_p(None if alpha_out is None else alpha_out.data_ptr()),
+            C.c_void_p(stream))
+        _lib.check(rc, handle, "rn_potgnn_device_descriptors")
+        return out
+
     def forward(self, lattice, atomic_numbers, positions) -> torch.Tensor:
         """Standardised 6-vectors ``[S,6]`` (``_gnn.py:617-665``).  ``lattice`` ``[S,3,3]`` is
         used per sample in the geometry, as the reference does (``_gnn.py:603-611``), and
